@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — NFP forward+backward throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run times the headline leg only (`value` / `ms_per_step`, below) and prints its line.  `--full` adds every
+other figure: the rotating leg (`cold`, `roofline`, `kernels`), the extras and the baselines.  `--dump-outputs DIR`
+writes what the last timed step returned to its caller, `DIR/out.npy` (the NFP maps) and `DIR/grad_x.npy`, as
+float32 (rank 0's; a fixed seeded sample of each if the two exceed DUMP_LIMIT_BYTES).  The inputs come from a seeded
+generator, so two runs with the same arguments compute on the same data.
 
 `--gpus N` with N > 1 starts N ranks itself (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...` as a
 child process, one rank per GPU over RCCL); under an external launcher (WORLD_SIZE / RANK in the environment) it runs
@@ -13,7 +19,7 @@ Workload at every N: BASELINE.json configs[1], NFP(cosine, k=3) on [B=64, C=512,
 scaling: every rank owns its own batch; the path has no exchange step, so there is no collective in the
 timed region beyond the bracketing barriers).  Prints ONE JSON line on rank 0.
 
-Two legs, both timed over exactly K steps between barriers:
+Two legs (the second with `--full`), both timed over exactly K steps between barriers:
   * `value` / `ms_per_step`: K steps on ONE set of (x, grad_out) — 6.4 MB of x, served by L2 / the 256 MiB Infinity
     Cache after the first step, which is what a training step sees: the backbone has just written the feature map.
     (Round 1's protocol; every step still writes a fresh out / grad_x buffer.)
@@ -21,8 +27,9 @@ Two legs, both timed over exactly K steps between barriers:
     of x alone, a fresh grad_x / out per step, and a 512 MiB fill right before the clock starts: x, grad_out and
     grad_x are HBM traffic (within a step the backward re-reads the x its forward read microseconds before).  The
     HBM roofline fraction is quoted on THIS leg's kernel times, never on the cache-resident ones.
-Beside them (`--no-extras` skips these): the same kernels at a saturating batch, and `large_maps` — the module on the
-maps above 512 pixels MobileNetV3_MultiStageNFP feeds it at B = 256 (row-band kernels), per-kernel event times.
+With `--full`, beside them (`--no-extras` skips these): the same kernels at a saturating batch, and `large_maps` — the
+module on the maps above 512 pixels MobileNetV3_MultiStageNFP feeds it at B = 256 (row-band kernels), per-kernel event
+times.
 The K timed steps are captured once into a HIP graph and replayed (`--launch eager` times plain launches
 instead): a step is ~11 us of GPU work, far below the host cost of two Python->ctypes->hipLaunch round trips.
 """
@@ -41,6 +48,7 @@ import torch
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); 6290 GB/s is the measured-achievable copy rate
 INFINITY_CACHE_BYTES = 256 << 20
+DUMP_LIMIT_BYTES = 48 << 20   # --dump-outputs: all arrays together
 
 
 def parse(argv=None):
@@ -56,15 +64,21 @@ def parse(argv=None):
     ap.add_argument("--measure", default="cosine")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--layout", choices=["nchw", "nhwc"], default="nchw")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline leg, run the rotating leg (cold, roofline, "
+                    "per-kernel times), the extras and the baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's out / grad_x as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU and same-GPU unfold baselines")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the cache-resident, ReLU-input, saturating-batch, large-map and "
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cache-resident, ReLU-input, saturating-batch, large-map and "
                     "live-traffic legs: every NFP launch of the process then belongs to the rotating leg, so a rocprofv3 "
                     "--kernel-trace --stats summary of the run averages exactly the launches `roofline` is quoted on")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # run under rocprofv3 --pmc by bench.py itself
     ap.add_argument("--print-launch", action="store_true", help="with --gpus N > 1 and no launcher: print the "
                     "torch.distributed.run command the N ranks would be started with, and exit")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(B, C, HW, N, e):
@@ -315,6 +329,21 @@ def median(v):
     return v[len(v) // 2]
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy, float32 in logical (NCHW) order.  If the arrays hold more than
+    DUMP_LIMIT_BYTES in all, each keeps its share as a sample: flat indices drawn by a fixed seed from the array's
+    size alone, so every run of the same shape samples the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy())
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, size=k))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class Workload:
     """S rotating sets of (x, grad_out) for one module; `step(i)` = product forward + backward on set i mod S."""
 
@@ -421,8 +450,8 @@ def main():
     from neighbour_feature_pooling_amd import _abi
     L = _abi.load()
     B, C, S, R = args.batch, args.channels, args.size, args.radius
-    rot = Workload(args, dev, rank)               # the timed leg: rotating sets, every byte from HBM
-    hot = Workload(args, dev, rank, sets=1)       # one resident set
+    rot = Workload(args, dev, rank) if args.full else None   # --full's rotating leg: every byte from HBM
+    hot = Workload(args, dev, rank, sets=1)       # the headline leg: one resident set
 
     def barrier():
         if dist is not None:
@@ -430,12 +459,13 @@ def main():
 
     stream = torch.cuda.Stream(device=dev)
 
-    flush_buf = torch.empty(2 * INFINITY_CACHE_BYTES, dtype=torch.uint8, device=dev)
+    flush_buf = torch.empty(2 * INFINITY_CACHE_BYTES, dtype=torch.uint8, device=dev) if args.full else None
 
     def timed(w, cold=True):
-        """K steps of workload `w` on `stream`: elapsed seconds.  cold: a 512 MiB fill runs (untimed) right before the
-        timed region, so that nothing the steps read or write — x, grad_out, and the grad_x / out buffers the graph
-        wrote on its previous replay — is still in the 256 MiB Infinity Cache when the clock starts."""
+        """K steps of workload `w` on `stream`: (elapsed seconds, the (out, grad_x) its last step returned).  cold: a
+        512 MiB fill runs (untimed) right before the timed region, so that nothing the steps read or write — x,
+        grad_out, and the grad_x / out buffers the graph wrote on its previous replay — is still in the 256 MiB
+        Infinity Cache when the clock starts."""
         with torch.cuda.stream(stream):
             for i in range(args.warmup):
                 w.step(i)
@@ -445,6 +475,7 @@ def main():
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
                 keep = [w.step(i) for i in range(args.steps)]
+            last = keep[-1]     # (its buffers are rewritten by every replay: after the timed one, they hold step K-1)
             del keep
             n_graph = L.nfp_launch_count() - n0
             torch.cuda.synchronize()
@@ -467,31 +498,53 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             with torch.cuda.stream(stream):
-                for i in range(args.steps):
+                for i in range(args.steps - 1):
                     w.step(i)
+                last = w.step(args.steps - 1)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             barrier()
             n_graph = L.nfp_launch_count() - n0
         assert n_graph >= 2 * args.steps, "HIP kernels did not run"
-        return t1 - t0
+        return t1 - t0, last
 
     from neighbour_feature_pooling_amd.parallel import max_over_ranks
     red_dev = dev if backend == "nccl" else "cpu"
-    elapsed_cold = max_over_ranks(timed(rot), device=red_dev)
-    elapsed = max_over_ranks(timed(hot, cold=False), device=red_dev)
-    extras = world == 1 and not args.no_extras
-    with torch.cuda.stream(stream):
-        out = hot.m(hot.x[0])
-        fwd_variant = L.nfp_last_variant().decode()
-        torch.autograd.grad(out, hot.x[0], hot.go[0])
-        torch.cuda.synchronize()
-        bwd_variant = L.nfp_last_variant().decode()
+    if args.full:
+        elapsed_cold = max_over_ranks(timed(rot)[0], device=red_dev)
+    elapsed, last = timed(hot, cold=False)
+    elapsed = max_over_ranks(elapsed, device=red_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": last[0], "grad_x": last[1]})
+    del last
     px_per_step = B * S * S
     value = world * px_per_step * args.steps / elapsed / 1e6
+    extras = world == 1 and not args.no_extras
+    if args.full:
+        with torch.cuda.stream(stream):
+            out = hot.m(hot.x[0])
+            fwd_variant = L.nfp_last_variant().decode()
+            torch.autograd.grad(out, hot.x[0], hot.go[0])
+            torch.cuda.synchronize()
+            bwd_variant = L.nfp_last_variant().decode()
 
     res = None
     if rank == 0:
+        res = {
+            "metric": "NFP fwd+bwd Mpixels/s @ [B64,C512,7×7,k3]; 1/2/4/8 GPU + %HBM roofline",
+            "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 6),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": f"NFP({args.measure},k={2 * R + 1},reflect pad {R}) fwd+bwd on "
+                                   f"[{B},{C},{S},{S}] {args.dtype} {args.layout.upper()} per GPU (BASELINE.json configs[1])",
+                       "batch_per_gpu": B, "global_batch": B * world, "launch": args.launch,
+                       "buffers": "value / ms_per_step: one resident set of (x, grad_out) per GPU, a fresh out / grad_x buffer per "
+                                  "step (round 1's protocol: the feature map has just been written by the backbone); "
+                                  "`cold` and `roofline` (--full): rotating sets, every byte from HBM",
+                       "parallelism": f"batch-sharded replicas x{world}, no data-path collective"},
+        }
+    if rank == 0 and args.full:
         timer = KernelTimer(L)
         # Per-kernel durations of the TIMED REGION's launches: HIP events on the launch stream around graph-replayed
         # launches — a graph of forwards, and a graph of steps minus it.  (rocprofv3's kernel trace of a graph replay
@@ -513,19 +566,7 @@ def main():
             traffic_src = ("profiles/traffic_latest.json (same kernel sources)" if traffic is not None
                            else f"none ({why or 'no live pass'}; no committed profile of these sources)")
         e = 4 if args.dtype == "f32" else 2
-        res = {
-            "metric": "NFP fwd+bwd Mpixels/s @ [B64,C512,7×7,k3]; 1/2/4/8 GPU + %HBM roofline",
-            "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 6),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": f"NFP({args.measure},k={2 * R + 1},reflect pad {R}) fwd+bwd on "
-                                   f"[{B},{C},{S},{S}] {args.dtype} {args.layout.upper()} per GPU (BASELINE.json configs[1])",
-                       "batch_per_gpu": B, "global_batch": B * world, "launch": args.launch,
-                       "buffers": "value / ms_per_step: one resident set of (x, grad_out) per GPU, a fresh out / grad_x buffer per "
-                                  "step (round 1's protocol: the feature map has just been written by the backbone); "
-                                  "`cold` and `roofline`: rotating sets, every byte from HBM",
-                       "parallelism": f"batch-sharded replicas x{world}, no data-path collective"},
+        res.update({
             "cold": {"what": f"the same K steps over {rot.sets} rotating sets of (x, grad_out) = "
                              f"{rot.sets * rot.B * C * S * S * e >> 20} MiB of x per GPU (> 256 MiB Infinity Cache), a fresh "
                              f"grad_x / out per step, 512 MiB fill right before the clock: every step reads and writes HBM",
@@ -549,7 +590,7 @@ def main():
                         "forward_variant": fwd_variant, "backward_variant": bwd_variant,
                         "fwd_bytes": rot.fb, "bwd_bytes": rot.bb,
                         "fwd_GBs": round(rot.fb / tf / 1e3, 1), "bwd_GBs": round(rot.bb / tb / 1e3, 1)},
-        }
+        })
         if extras:
             tf_hot, tb_hot = hot.kernel_times(stream, reps=50)
             res["cache_resident"] = {"what": "kernel times of the `value` leg (one buffer set: inputs from L2 / Infinity Cache)",

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   out=gpurun_out/pmc_$c; rm -rf $out; mkdir -p $out
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out -o pmc -- \
-    python3 bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 "$@" > $out/bench.log 2>&1
+    python3 bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 "$@" > $out/bench.log 2>&1
   echo "$c rc=$?"
 done
 python3 - <<'PY'
