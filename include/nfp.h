@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NFP_ABI_VERSION 6
+#define NFP_ABI_VERSION 7
 
 /* error codes */
 #define NFP_OK 0
@@ -172,6 +172,31 @@ int nfp_pool_forward(const nfp_desc* d, const void* x, float* gap, float* nfpm, 
 /* grad_x = d( sum(gap*grad_gap) + sum(nfpm*grad_nfpm) ) / dx;  out_map / saved from nfp_pool_forward. */
 int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, const float* grad_nfpm,
                       const void* out_map, const float* saved, void* grad_x, void* hip_stream);
+
+/*
+ * ABI 7 — NFPPooling(bias=True) (nfp.py:42-58 with bias=True: both depthwise convs carry a TRAINABLE bias, only their
+ * weights are frozen, nfp.py:61,82).  The conv adds the bias after padding: a zero-padded tap reads 0 + bias.  Per pair
+ * (output o, neighbour n) of channel c the measure then sees
+ *   centre      a = x_c + centre_bias[c]
+ *   neighbour   v = x_n + neighbour_bias[c*N + n]            (d->diff_weights: x_c - x_n + neighbour_bias[c*N + n])
+ * Every measure but SCS, every geometry, f32 / bf16, any strides; inner_R must be 0.  centre_bias [C] and
+ * neighbour_bias [C*N] (reshape order of nfp.py:136-139, n in tap order without the centre) and their gradients are f32
+ * DEVICE pointers.  Norm and RMSE never read the centre bias: centre_bias / grad_centre_bias may be NULL there (and
+ * grad_centre_bias is then not written).  The bias gradients are sums over the batch in a fixed order (no atomics).
+ *   nfp_bias_saved_floats(d)     per-call state forward hands to backward: per-pair statistics (2 * stats per pair) or,
+ *                                for Attention, the raw dots (needed also without a backward); -1 for a refused d
+ *   nfp_bias_scratch_floats(d)   scratch of the backward (per-pair coefficients, per-image bias partials)
+ * Both calls take the LENGTH of every caller buffer and return NFP_E_INVALID, launching nothing, when one is short.
+ * `saved` may be NULL in nfp_bias_forward when no backward follows (not for Attention).
+ */
+int64_t nfp_bias_saved_floats(const nfp_desc* d);
+int64_t nfp_bias_scratch_floats(const nfp_desc* d);
+int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias, const float* neighbour_bias, void* out,
+                     float* saved, int64_t saved_floats, void* hip_stream);
+int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias, const float* neighbour_bias,
+                      const void* grad_out, const void* out, const float* saved, int64_t saved_floats, void* grad_x,
+                      float* grad_centre_bias, float* grad_neighbour_bias, float* scratch, int64_t scratch_floats,
+                      void* hip_stream);
 
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnfp_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 MEASURES = ["norm", "cosine", "dot", "rmse", "geman", "attention", "emd", "canberra", "hellinger",
             "chisquared1", "chisquared2", "gfc", "pearson", "jeffrey", "squaredchord", "smith", "scs"]
@@ -20,7 +20,8 @@ TICKET_BYTES = 4096 * 4       # the arrival counters at the head of a workspace 
 
 EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_floats", "nfp_forward",
            "nfp_backward", "nfp_pool_supported", "nfp_pool_saved_floats", "nfp_pool_forward", "nfp_pool_backward", "nfp_launch_count",
-           "nfp_last_variant", "nfp_plan", "nfp_reload_env", "nfp_workspace_bytes", "nfp_workspace_init", "nfp_time_next_launch"]
+           "nfp_last_variant", "nfp_plan", "nfp_reload_env", "nfp_workspace_bytes", "nfp_workspace_init", "nfp_time_next_launch",
+           "nfp_bias_saved_floats", "nfp_bias_scratch_floats", "nfp_bias_forward", "nfp_bias_backward"]
 
 
 class NfpDesc(ctypes.Structure):
@@ -78,6 +79,13 @@ def load():
         L.nfp_pool_saved_floats.restype = ctypes.c_int64
     L.nfp_pool_forward.argtypes = [dp, vp, vp, vp, vp, vp, vp]
     L.nfp_pool_backward.argtypes = [dp, vp, vp, vp, vp, vp, vp, vp]
+    i64 = ctypes.c_int64
+    L.nfp_bias_saved_floats.argtypes = [dp]
+    L.nfp_bias_saved_floats.restype = i64
+    L.nfp_bias_scratch_floats.argtypes = [dp]
+    L.nfp_bias_scratch_floats.restype = i64
+    L.nfp_bias_forward.argtypes = [dp, vp, vp, vp, vp, vp, i64, vp]
+    L.nfp_bias_backward.argtypes = [dp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

@@ -34,10 +34,17 @@ def _taps(x, cfg):
     return centre.unsqueeze(2), neigh  # [B,C,1,Ho,Wo], [B,C,N,Ho,Wo]
 
 
-def nfp_host(x, cfg):
+def nfp_host(x, cfg, centre_bias=None, neighbour_bias=None):
+    """centre_bias [C] / neighbour_bias [C*N] (NFPPooling(bias=True)): the biases of the reference's two convs, added
+    after padding (a zero-padded tap reads 0 + bias); neighbour_bias in the reshape order of nfp.py:136-139."""
     a, b = _taps(x, cfg)
     m, sim, eps = cfg.measure, cfg.similarity, cfg.eps
     v = (a - b) if cfg.diff_weights else b  # what the reference's comp_neighbors conv yields
+    if neighbour_bias is not None:
+        beta = neighbour_bias.to(x.dtype).reshape(1, b.shape[1], b.shape[2], 1, 1)
+        v, b = v + beta, b + beta
+    if centre_bias is not None and m not in ("norm", "rmse"):   # (Norm and RMSE never call center_value: nfp.py:141-148,172-179)
+        a = a + centre_bias.to(x.dtype).reshape(1, a.shape[1], 1, 1, 1)
     if m == "norm":
         r = torch.linalg.norm(v, ord=cfg.p, dim=1)
         return -r if sim else r

@@ -222,3 +222,70 @@ def _pool_bwd(ctx, g_gap, g_nfpm, g_map, g_saved):
 
 
 nfp_pool_op.register_autograd(_pool_bwd, setup_context=_pool_setup)
+
+
+# ---- nfp_biased: (x, centre_bias, neighbour_bias) -> (maps, saved) — NFPPooling(bias=True), include/nfp.h ABI 7 ------------
+def _bias_saved_floats(shape, dtype, cfg):
+    """nfp_bias_saved_floats for this call — a function of the shape and the measure alone."""
+    d = _abi.NfpDesc()
+    d.B, d.C, d.H, d.W = shape
+    d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
+    d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
+    d.measure = _abi.measure_id(cfg.measure)
+    d.similarity, d.diff_weights = int(cfg.similarity), int(cfg.diff_weights)
+    d.dtype = _abi.F32 if dtype == torch.float32 else _abi.BF16
+    d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
+    d.sxB, d.sxC, d.sxH, d.sxW = shape[1] * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1
+    return max(int(_abi.load().nfp_bias_saved_floats(ctypes.byref(d))), 0)
+
+
+@torch.library.custom_op("nfp_amd::nfp_biased", mutates_args=(), device_types="cuda",
+                         schema=f"(Tensor x, Tensor centre_bias, Tensor neighbour_bias, {_CFG_SCHEMA}) -> (Tensor, Tensor)")
+def nfp_biased_op(x, centre_bias, neighbour_bias, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps,
+                  q_scs, diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    from . import functional as F
+    return F.bias_forward_call(x, centre_bias, neighbour_bias, cfg)
+
+
+@nfp_biased_op.register_fake
+def _(x, centre_bias, neighbour_bias, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs,
+      diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    B, _, H, W = x.shape
+    Ho, Wo = _out_hw(H, W, cfg)
+    return (x.new_empty((B, cfg.out_channels, Ho, Wo)),
+            x.new_empty((_bias_saved_floats(tuple(x.shape), x.dtype, cfg),), dtype=torch.float32))
+
+
+@torch.library.custom_op("nfp_amd::nfp_biased_backward", mutates_args=(), device_types="cuda",
+                         schema=f"(Tensor x, Tensor centre_bias, Tensor neighbour_bias, Tensor out, Tensor saved, "
+                                f"Tensor grad_out, {_CFG_SCHEMA}) -> (Tensor, Tensor, Tensor)")
+def nfp_biased_backward_op(x, centre_bias, neighbour_bias, out, saved, grad_out, R, measure, p, stride, padding, dilation,
+                           padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    from . import functional as F
+    gx, gcb, gnb = F.bias_backward_call(x, centre_bias, neighbour_bias, out, saved, grad_out, cfg)
+    if gcb is None:     # (Norm / RMSE: no centre-bias gradient; the autograd formula below returns None for it)
+        gcb = torch.zeros(centre_bias.shape, dtype=torch.float32, device=x.device)
+    return gx, gcb.to(centre_bias.dtype), gnb.to(neighbour_bias.dtype)
+
+
+@nfp_biased_backward_op.register_fake
+def _(x, centre_bias, neighbour_bias, out, saved, grad_out, *cfg_fields):
+    return torch.empty_like(x), torch.empty_like(centre_bias), torch.empty_like(neighbour_bias)
+
+
+def _biased_setup(ctx, inputs, output):
+    ctx.cfg_fields = inputs[3:15]
+    ctx.save_for_backward(inputs[0], inputs[1], inputs[2], output[0], output[1])
+
+
+def _biased_bwd(ctx, g_out, g_saved):
+    x, cb, nb, out, saved = ctx.saved_tensors
+    gx, gcb, gnb = torch.ops.nfp_amd.nfp_biased_backward(x, cb, nb, out, saved, g_out, *ctx.cfg_fields)
+    no_centre = ctx.cfg_fields[1] in ("norm", "rmse")
+    return (gx, None if no_centre else gcb, gnb) + (None,) * 12
+
+
+nfp_biased_op.register_autograd(_biased_bwd, setup_context=_biased_setup)

@@ -1209,4 +1209,97 @@ int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, c
   return finish(rc, "nfp_pool_backward");
 }
 
+// ---- ABI 7: NFPPooling(bias=True) — nfp_bias.hip ---------------------------------------------------------------------
+// The descriptor's own measure: make_kp serves EMD as Norm p = 1 on the difference weights, which a bias on the
+// neighbour side breaks (|(a + bc) - (x_n + beta)| is not |(a - x_n) + beta|).  The difference weights are applied by the
+// kernels (dw); the measures then see g.diff = 0.
+static int bias_kp(const nfp_desc* d, KP* g, int* dw) {
+  if (int rc = make_kp(d, g)) return rc;
+  if (d->inner_R != 0) return fail(NFP_E_UNSUPPORTED, "biased NFP: one radius per call (inner_R = 0)");
+  if (d->measure == NFP_SCS)
+    return fail(NFP_E_UNSUPPORTED, "biased NFP: measure %d (SharpenedCosine mixes batch elements) has no HIP kernel", d->measure);
+  g->measure = d->measure;
+  g->p = d->p;
+  g->diff = 0;
+  *dw = d->diff_weights != 0 ? 1 : 0;
+  return NFP_OK;
+}
+static bool bias_no_centre(const KP& g) { return g.measure == NFP_NORM || g.measure == NFP_RMSE; }
+
+int64_t nfp_bias_saved_floats(const nfp_desc* d) {
+  KP g;
+  int dw;
+  if (bias_kp(d, &g, &dw)) return -1;
+  const int64_t bno = (int64_t)g.B * g.N * g.O;
+  if (g.measure == NFP_ATTENTION) return bno;  // the raw dots (float32), also without a backward
+  return 2LL * stats_of(g.measure) * bno;      // per-pair stats of the centre and the neighbour side
+}
+
+int64_t nfp_bias_scratch_floats(const nfp_desc* d) {
+  KP g;
+  int dw;
+  if (bias_kp(d, &g, &dw)) return -1;
+  const int64_t bno = (int64_t)g.B * g.N * g.O;
+  const bool attn = g.measure == NFP_ATTENTION;
+  return bno * bias_coef_floats(attn ? as_dot(g) : g) + (int64_t)g.B * g.C * (g.N + 1) + (attn ? bno : 0);
+}
+
+int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias, const float* neighbour_bias, void* out,
+                     float* saved, int64_t saved_floats, void* hip_stream) {
+  KP g;
+  int dw;
+  if (int rc = bias_kp(d, &g, &dw)) return rc;
+  if (!x || !out || !neighbour_bias || (!centre_bias && !bias_no_centre(g))) return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = nfp_bias_saved_floats(d);
+  if ((saved != nullptr || g.measure == NFP_ATTENTION) && need > 0 && (saved == nullptr || saved_floats < need))
+    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
+  if (g.B == 0) return NFP_OK;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (g.measure == NFP_ATTENTION) {
+    if (int rc = bias_forward(as_dot(g), dw, x, centre_bias, neighbour_bias, nullptr, nullptr, saved, st)) return rc;
+    const long long n = (long long)g.B * g.O;
+    strncat(g_variant, "+attn_softmax", sizeof(g_variant) - strlen(g_variant) - 1);
+    return finish(launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
+                         (const float*)saved, out), "nfp_bias_forward");
+  }
+  return finish(bias_forward(g, dw, x, centre_bias, neighbour_bias, out, saved, nullptr, st), "nfp_bias_forward");
+}
+
+int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias, const float* neighbour_bias,
+                      const void* grad_out, const void* out, const float* saved, int64_t saved_floats, void* grad_x,
+                      float* grad_centre_bias, float* grad_neighbour_bias, float* scratch, int64_t scratch_floats,
+                      void* hip_stream) {
+  KP g;
+  int dw;
+  if (int rc = bias_kp(d, &g, &dw)) return rc;
+  const bool nc = bias_no_centre(g);
+  if (!x || !grad_out || !out || !grad_x || !neighbour_bias || !grad_neighbour_bias || (!nc && (!centre_bias || !grad_centre_bias)))
+    return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = nfp_bias_saved_floats(d), need_s = nfp_bias_scratch_floats(d);
+  if (need > 0 && (saved == nullptr || saved_floats < need))
+    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
+  if (scratch == nullptr || scratch_floats < need_s)
+    return fail(NFP_E_INVALID, "scratch holds %lld floats, nfp_bias_scratch_floats is %lld", (long long)scratch_floats,
+                (long long)need_s);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (g.measure == NFP_ATTENTION) {
+    // gradient with respect to the dots behind the scratch's coefficient and partial-sum parts, then DotProduct's backward
+    const long long bno = (long long)g.B * g.N * g.O, n = (long long)g.B * g.O;
+    KP gdot = as_dot(g);
+    gdot.godtype = NFP_F32;
+    float* gd = scratch + bno * bias_coef_floats(gdot) + (long long)g.B * g.C * (g.N + 1);
+    if (g.B > 0)
+      if (int rc = launch("attn_softmax_bwd", attn_softmax_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, grad_out,
+                          out, gd))
+        return rc;
+    const int rc = bias_backward(gdot, dw, x, centre_bias, neighbour_bias, gd, saved, nullptr, grad_x, grad_centre_bias,
+                                 grad_neighbour_bias, scratch, st);
+    if (rc == NFP_OK) strncat(g_variant, "+attn_softmax", sizeof(g_variant) - strlen(g_variant) - 1);
+    return finish(rc, "nfp_bias_backward");
+  }
+  return finish(bias_backward(g, dw, x, centre_bias, neighbour_bias, grad_out, out, saved, grad_x, nc ? nullptr : grad_centre_bias,
+                              grad_neighbour_bias, scratch, st),
+                "nfp_bias_backward");
+}
+
 }  // extern "C"

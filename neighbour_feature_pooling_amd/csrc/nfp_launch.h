@@ -1,6 +1,6 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI,
-// table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels).  Two units so that they compile in
-// parallel; everything here is `inline` (one instance per shared library).
+// table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True)).  Separate
+// units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -212,5 +212,15 @@ int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                   bool pool, const float* ggap, const float* gnfpm);
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st);
+
+// ---- NFPPooling(bias=True) (nfp_bias.hip, ABI 7) -------------------------------------------------------------------------
+// g.measure is the descriptor's own measure (Attention: its DotProduct form), g.diff = 0 and dw = the difference weights.
+// bias_forward stores the maps in `out` (g.odtype) and the per-pair stats in `saved`, or — dots != null — the raw sums in
+// `dots` alone.  bias_backward needs bias_coef_floats(g) * B*N*O + B*C*(N + 1) floats of `scratch`.
+int bias_coef_floats(const KP& g);
+int bias_forward(const KP& g, int dw, const void* x, const float* bc, const float* beta, void* out, float* saved,
+                 float* dots, hipStream_t st);
+int bias_backward(const KP& g, int dw, const void* x, const float* bc, const float* beta, const void* go, const void* out,
+                  const float* saved, void* gx, float* gbc, float* gbeta, float* scratch, hipStream_t st);
 
 }  // namespace nfp_host

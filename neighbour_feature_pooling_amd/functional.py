@@ -525,3 +525,107 @@ def nfp(x, cfg):
         return torch.cat([nfp_host(x, dataclasses.replace(cfg, R=cfg.inner_R, padding=cfg.inner_R, inner_R=0)),
                           nfp_host(x, dataclasses.replace(cfg, inner_R=0))], dim=1)
     return nfp_host(x, cfg)
+
+
+# ---- NFPPooling(bias=True) — include/nfp.h, ABI 7 (csrc/nfp_bias.hip) ------------------------------------------------------
+def bias_no_centre(cfg):
+    """Norm and RMSE never call center_value (nfp.py:141-148, 172-179): its bias gets no gradient (None, as in the reference)."""
+    return cfg.measure in ("norm", "rmse")
+
+
+def _bias_plan(x, layout, cfg):
+    """(descriptor, output shape, saved floats, scratch floats) of a biased call — cached with the plans."""
+    key = ("bias", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
+    plan = _plans_get(key)
+    if plan is None:
+        L = _abi.load()
+        d = make_desc(x, cfg, layout)
+        d.ws = None     # (the biased kernels keep no tables)
+        plan = (d, output_shape(d), int(L.nfp_bias_saved_floats(ctypes.byref(d))),
+                int(L.nfp_bias_scratch_floats(ctypes.byref(d))))
+        _plans_put(key, plan)
+    return plan
+
+
+def _bias_f32(t):
+    return t.detach().float().contiguous()
+
+
+def bias_forward_call(x, centre_bias, neighbour_bias, cfg):
+    """(out, saved) from nfp_bias_forward; saved is torch-allocated (graph capture safe)."""
+    L = _abi.load()
+    xd, layout = _dense(x)
+    d, oshape, ns, _ = _bias_plan(xd, layout, cfg)
+    cb, nb = _bias_f32(centre_bias), _bias_f32(neighbour_bias)
+    with _on_device(x.device):
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+        saved = torch.empty(max(ns, 0), dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_bias_forward(ctypes.byref(d), xd.data_ptr(), cb.data_ptr(), nb.data_ptr(), out.data_ptr(),
+                                      saved.data_ptr() if ns > 0 else None, max(ns, 0), _raw_stream(x.device)))
+    return out, saved
+
+
+def bias_backward_call(x, centre_bias, neighbour_bias, out, saved, grad_out, cfg):
+    """(grad_x, grad_centre_bias or None for Norm / RMSE, grad_neighbour_bias) from nfp_bias_backward, the bias gradients
+    float32 in the biases' shapes."""
+    L = _abi.load()
+    xd, layout = _dense(x)
+    d, _, ns, nsc = _bias_plan(xd, layout, cfg)
+    cb, nb = _bias_f32(centre_bias), _bias_f32(neighbour_bias)
+    go = grad_out.contiguous()
+    if go.dtype != x.dtype:
+        go = go.to(x.dtype)
+    with _on_device(x.device):
+        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
+                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
+        gcb = None if bias_no_centre(cfg) else torch.empty(cb.shape, dtype=torch.float32, device=x.device)
+        gnb = torch.empty(nb.shape, dtype=torch.float32, device=x.device)
+        scratch = torch.empty(max(nsc, 0), dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_bias_backward(ctypes.byref(d), xd.data_ptr(), cb.data_ptr(), nb.data_ptr(), go.data_ptr(),
+                                       out.data_ptr(), saved.data_ptr() if saved.numel() else None, saved.numel(),
+                                       gx.data_ptr(), gcb.data_ptr() if gcb is not None else None, gnb.data_ptr(),
+                                       scratch.data_ptr(), scratch.numel(), _raw_stream(x.device)))
+    return gx, gcb, gnb
+
+
+class _NfpBiasHip(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, centre_bias, neighbour_bias, cfg):
+        out, saved = bias_forward_call(x, centre_bias, neighbour_bias, cfg)
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, centre_bias, neighbour_bias, out, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, cb, nb, out, saved = ctx.saved_tensors
+        gx, gcb, gnb = bias_backward_call(x, cb, nb, out, saved, grad_out, ctx.cfg)
+        return (gx, None if gcb is None else gcb.to(cb.dtype), gnb.to(nb.dtype), None)
+
+
+def nfp_biased(x, cfg, centre_bias, neighbour_bias):
+    """NFPPooling(bias=True).forward: `nfp` with the trainable biases of the reference's two convs — centre_bias [C]
+    (center_value.bias) and neighbour_bias [C*N] (comp_neighbors.bias, nfp.py:42-58), added after padding.  CUDA tensors
+    run the biased HIP kernels (include/nfp.h, ABI 7; SCS: torch ops, as `nfp`), CPU tensors `_host.nfp_host`.  Returns
+    gradients for x and both biases (None for the centre bias of Norm / RMSE, which never read it)."""
+    if x.dim() != 4:
+        raise RuntimeError(f"NFP expects a 4-D [B,C,H,W] feature map, got {tuple(x.shape)}")
+    if cfg.inner_R:
+        raise ValueError("nfp_biased: one radius per call (inner_R = 0)")
+    xin, cast = _amp_input(x)
+    if xin is not x:
+        with torch.autocast("cuda", enabled=False):
+            out = nfp_biased(xin, cfg, centre_bias, neighbour_bias)
+        return out if cast is None else out.to(cast)
+    if x.is_cuda and cfg.measure == "scs":
+        import warnings
+        warnings.warn("NFP measure 'scs' (SharpenedCosine) mixes batch elements in the reference; it runs as "
+                      "PyTorch ops on the GPU, not through the HIP kernels", RuntimeWarning, stacklevel=3)
+        return nfp_host(x, cfg, centre_bias, neighbour_bias)
+    if x.is_cuda and torch.compiler.is_compiling():
+        from . import _ops
+        return torch.ops.nfp_amd.nfp_biased(x, centre_bias, neighbour_bias, *_ops.cfg_args(cfg))[0]
+    if x.is_cuda:
+        return _NfpBiasHip.apply(x, centre_bias, neighbour_bias, cfg)
+    return nfp_host(x, cfg, centre_bias, neighbour_bias)

@@ -226,6 +226,8 @@ class MultiStageNFPNet(nn.Module):
         from .functional import nfp_pooled
         feats = self.backbone.forward_stages(x)
         # texture_pooling.py:251-252: F.adaptive_avg_pool2d(nfp(feat), 1) per stage — the pooled maps alone, no GAP(feat)
-        v = torch.cat([nfp_pooled(f, layer.config).to(f.dtype) for f, layer in zip(feats, self.nfps)], dim=1)   # [B, 40]
+        # (a biased layer has no fused pooled form: its own forward, then the mean)
+        v = torch.cat([(F.adaptive_avg_pool2d(layer(f), 1).flatten(1) if layer.bias else nfp_pooled(f, layer.config)).to(f.dtype)
+                       for f, layer in zip(feats, self.nfps)], dim=1)   # [B, 40]
         head = self.conv_head(feats[-1]).mean((2, 3))
         return self.fc(head * self.nfp_proj(v))

@@ -3,16 +3,27 @@
 Same constructor, same forward contract ([B,C,H,W] -> [B, k*k-1, H', W']), same
 public attributes, same error on an unknown measure; the work is done by the
 fused gfx950 kernels behind include/nfp.h instead of two frozen depthwise convs
-and a chain of ATen ops.  The module has no trainable parameters (as in the
-reference, whose two conv weights are frozen: nfp.py:61,82).
+and a chain of ATen ops.  With bias=False (the default) the module has no
+trainable parameters (as in the reference, whose two conv weights are frozen:
+nfp.py:61,82); with bias=True the two convs' biases are trainable parameters
+under the reference's names, comp_neighbors.bias [C*N] and center_value.bias [C].
 """
 import torch
 import torch.nn as nn
 
 from . import _abi
-from .functional import NfpConfig, nfp, nfp_multi_radius
+from .functional import NfpConfig, nfp, nfp_biased, nfp_multi_radius
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
+
+
+class _ConvBias(nn.Module):
+    """comp_neighbors / center_value of the reference with bias=True: only the trainable bias is a parameter here (the
+    frozen one-hot weight is a constant of (C, R, measure), emitted into the state dict by NFPPooling)."""
+
+    def __init__(self, bias):
+        super().__init__()
+        self.bias = nn.Parameter(bias)
 
 
 class NFPPooling(nn.Module):
@@ -20,9 +31,6 @@ class NFPPooling(nn.Module):
                  dilation=1, bias=False, padding_mode='reflect', similarity=True,
                  eps=1e-6, input_size=224, q_scs=1e-6):
         super().__init__()
-        if bias:
-            # nfp.py:46,57 would give both frozen-weight convs TRAINABLE random biases; no caller uses it.
-            raise NotImplementedError("NFPPooling(bias=True) is not supported by the HIP implementation")
         if padding_mode not in _abi.PAD_MODES:
             raise ValueError(f"padding_mode must be one of {_abi.PAD_MODES}, got {padding_mode!r}")
         self.in_size = input_size
@@ -42,6 +50,16 @@ class NFPPooling(nn.Module):
         self.out_channels = int(self.kernel_size ** 2 - 1)  # nfp.py:39
         # nfp.py:74 tests the RAW string, nfp.py:85 the lower-cased one: 'Norm' yields |neighbour|.
         self._diff_weights = measure in ('norm', 'rmse', 'mahalanobis')
+        if bias:
+            # nfp.py:42-58 with bias=True: both depthwise convs get TRAINABLE biases (only the weights are frozen,
+            # nfp.py:61,82).  The two convs are built as the reference builds them, so that nn.Conv2d.reset_parameters
+            # draws from the RNG in the reference's order (comp_neighbors weight, its bias, center_value weight, its
+            # bias): the same seed gives bit-identical biases.
+            k, C = self.kernel_size, int(in_channels)
+            comp = nn.Conv2d(C, self.out_channels * C, k, groups=C, bias=True)
+            centre = nn.Conv2d(C, C, k, groups=C, bias=True)
+            self.comp_neighbors = _ConvBias(comp.bias.data.clone())
+            self.center_value = _ConvBias(centre.bias.data.clone())
         if self.measure not in _DISPATCH:
             raise RuntimeError(f'Similarity measure {self.measure} not implemented')  # nfp.py:120
 
@@ -71,6 +89,8 @@ class NFPPooling(nn.Module):
         if x.dim() == 4 and x.shape[1] != self.in_channels:
             raise RuntimeError(f"NFPPooling expected input with {self.in_channels} channels, "
                                f"got {x.shape[1]} channels instead")
+        if self.bias:
+            return nfp_biased(x, self.config, self.center_value.bias, self.comp_neighbors.bias)
         return nfp(x, self.config)
 
     @property
@@ -81,7 +101,7 @@ class NFPPooling(nn.Module):
     def extra_repr(self):
         return (f"in_channels={self.in_channels}, R={self.R}, measure={self.measure!r}, p={self.p}, "
                 f"stride={self.stride}, padding={self.padding}, dilation={self.dilation}, "
-                f"padding_mode={self.padding_mode!r}, similarity={self.similarity}")
+                f"padding_mode={self.padding_mode!r}, similarity={self.similarity}" + (", bias=True" if self.bias else ""))
 
     # -- checkpoint compatibility ------------------------------------------------------------
     # A reference NFPPooling state-dict holds its two frozen conv weights,
@@ -146,7 +166,7 @@ class MultiRadiusNFPPooling(nn.Module):
 
     def forward(self, x):
         blocks = list(self.nfp_blocks)
-        if len(blocks) == 2 and all(isinstance(b, NFPPooling) for b in blocks):
+        if len(blocks) == 2 and all(isinstance(b, NFPPooling) and not b.bias for b in blocks):   # (no fused form with biases)
             if x.dim() == 4 and x.shape[1] != self.in_channels:
                 raise RuntimeError(f"MultiRadiusNFPPooling expected input with {self.in_channels} channels, "
                                    f"got {x.shape[1]} channels instead")

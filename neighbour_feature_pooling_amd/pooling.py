@@ -41,7 +41,7 @@ class nfp_pooling(nn.Module):
 
     def forward(self, x):
         layer = self.nfp_layer
-        if isinstance(layer, NFPPooling) and x.dim() == 4 and x.shape[1] == layer.in_channels:
+        if isinstance(layer, NFPPooling) and not layer.bias and x.dim() == 4 and x.shape[1] == layer.in_channels:
             pooled_x, pooled_nfp = nfp_pool(x, layer.config)                  # NFP_Pooling.py:27-31, fused
             pooled_x, pooled_nfp = pooled_x.to(x.dtype), pooled_nfp.to(x.dtype)
         else:
