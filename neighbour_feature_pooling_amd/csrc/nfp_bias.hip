@@ -371,7 +371,7 @@ int bias_forward(const KP& g, int dw, const void* x, const float* bc, const floa
   const dim3 grid((unsigned)((g.O + OT - 1) / OT), (unsigned)((g.N + NB - 1) / NB), (unsigned)g.B);
   return bias_switch(g, [&](auto m) {
     constexpr int M = decltype(m)::value;
-    snprintf(g_variant, sizeof(g_variant), "bias_fwd<%d>", M);
+    snprintf(g_variant, sizeof(g_variant), "bias_fwd<%d,%s>x%d", M, cfast ? "nhwc" : "nchw", NB);
     return launch("bias_fwd", bias_fwd<M>, grid, dim3(kBiasT), 0, st, g, dw, OT, cfast, NB, x, bc, beta, out, saved, dots);
   });
 }
@@ -383,7 +383,7 @@ int bias_backward(const KP& g, int dw, const void* x, const float* bc, const flo
   float* part = scratch + BNO * bias_coef_floats(g);
   return bias_switch(g, [&](auto m) {
     constexpr int M = decltype(m)::value;
-    snprintf(g_variant, sizeof(g_variant), "bias_bwd<%d>", M);
+    snprintf(g_variant, sizeof(g_variant), "bias_bwd<%d,%s>", M, g.sC == 1 ? "nhwc" : "nchw");
     if (g.B > 0) {
     if (int rc = launch("bias_coef", bias_coef<M>, dim3(flat_blocks(BNO)), dim3(kBiasT), 0, st, g, go, out, saved, cf)) return rc;
     if (int rc = launch("bias_gx", bias_gx<M>, dim3(flat_blocks((long long)g.B * g.C * g.P)), dim3(kBiasT), 0, st, g, dw, x,

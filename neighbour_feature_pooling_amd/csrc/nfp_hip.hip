@@ -1249,7 +1249,9 @@ int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias,
   KP g;
   int dw;
   if (int rc = bias_kp(d, &g, &dw)) return rc;
-  if (!x || !out || !neighbour_bias || (!centre_bias && !bias_no_centre(g))) return fail(NFP_E_INVALID, "null tensor pointer");
+  // (an empty batch: x and out hold no element, and torch hands such tensors over as NULL)
+  if ((g.B > 0 && (!x || !out)) || !neighbour_bias || (!centre_bias && !bias_no_centre(g)))
+    return fail(NFP_E_INVALID, "null tensor pointer");
   const int64_t need = nfp_bias_saved_floats(d);
   if ((saved != nullptr || g.measure == NFP_ATTENTION) && need > 0 && (saved == nullptr || saved_floats < need))
     return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
@@ -1273,12 +1275,13 @@ int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias
   int dw;
   if (int rc = bias_kp(d, &g, &dw)) return rc;
   const bool nc = bias_no_centre(g);
-  if (!x || !grad_out || !out || !grad_x || !neighbour_bias || !grad_neighbour_bias || (!nc && (!centre_bias || !grad_centre_bias)))
+  if ((g.B > 0 && (!x || !grad_out || !out || !grad_x)) || !neighbour_bias || !grad_neighbour_bias ||
+      (!nc && (!centre_bias || !grad_centre_bias)))
     return fail(NFP_E_INVALID, "null tensor pointer");
   const int64_t need = nfp_bias_saved_floats(d), need_s = nfp_bias_scratch_floats(d);
   if (need > 0 && (saved == nullptr || saved_floats < need))
     return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
-  if (scratch == nullptr || scratch_floats < need_s)
+  if ((need_s > 0 && scratch == nullptr) || scratch_floats < need_s)
     return fail(NFP_E_INVALID, "scratch holds %lld floats, nfp_bias_scratch_floats is %lld", (long long)scratch_floats,
                 (long long)need_s);
   hipStream_t st = (hipStream_t)hip_stream;

@@ -107,17 +107,25 @@ class _nullctx:
         return False
 
 
-@pytest.mark.parametrize("measure", MEASURES + ["Norm"])
-def test_every_measure_bf16(measure, dev):
+# channels-last under the measure's own id (as before), NCHW as <measure>-nchw
+BF16_CASES = ([pytest.param(m, True, id=m) for m in MEASURES + ["Norm"]] +
+              [pytest.param(m, False, id=f"{m}-nchw") for m in MEASURES + ["Norm"]])
+
+
+@pytest.mark.parametrize("measure,channels_last", BF16_CASES)
+def test_every_measure_bf16(measure, channels_last, dev):
     """bf16 storage, f32 arithmetic, against the float64 formulation on the SAME bf16-rounded inputs, at the bf16 bounds
     of the existing bf16 tests: out within 1e-2 and gradients within 2e-2 of the tensor's largest magnitude."""
     g = torch.Generator().manual_seed(3)
-    x = (torch.rand(2, 12, 9, 7, generator=g) + 0.25).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    x = (torch.rand(2, 12, 9, 7, generator=g) + 0.25).to(torch.bfloat16)
+    if channels_last:
+        x = x.contiguous(memory_format=torch.channels_last)
     m = _module(12, dict(R=1, measure=measure, padding=1), seed=4)
     go = torch.randn(2, 8, 9, 7, generator=g).to(torch.bfloat16)
     mg = m.to(dev)
     out, gx, gbc, gnb, _ = _run(mg, x.to(dev), go.to(dev))
     assert _variant().startswith("bias_bwd<"), _variant()
+    assert ("nhwc" if channels_last else "nchw") in _variant(), _variant()
     r_out, r_gx, r_gbc, r_gnb = _host64(m.cpu(), x.float(), go.float())
     assert rel_err(out, r_out) <= 1e-2
     assert rel_err(gx, r_gx) <= 2e-2
