@@ -174,6 +174,29 @@ int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, c
                       const void* out_map, const float* saved, void* grad_x, void* hip_stream);
 
 /*
+ * GAP(x) beside the FULL maps — the first step of every head of models/nfp_heads.py (NFPHead, MultiRadiusNFPHead,
+ * AdaptiveFusionNFP: gap(fmap) and nfp(fmap) of one feature map, the maps then consumed by a trainable 1x1 conv): one
+ * pass over x yields
+ *   gap     [B,C] f32 = AdaptiveAvgPool2d(1)(x)
+ *   out_map [B,N,Ho,Wo] (dtype of x) = NFPPooling(x), exactly what nfp_forward writes
+ * and the backward takes BOTH gradients: grad_x = d( sum(gap*grad_gap) + sum(out_map*grad_out) ) / dx, grad_out a map as
+ * in nfp_backward, grad_gap[b,c] / (H*W) added in the same store.  grad_gap may be NULL (GAP(x) took no part in the
+ * loss): nothing is added and nothing is read.  No atomics: several row bands per image write partial channel sums to
+ * the scratch in `saved` and a second, tiny launch joins them in band order.
+ * Served where nfp_gap_supported(d) != 0 — the set of nfp_pool_supported: cosine / dot / gfc / L2 / rmse on "same" maps,
+ * NCHW or channels-last, f32 or bf16, inner_R = 0; the answer is a host-only dry run of both launchers.  Otherwise compose
+ * nfp_forward with an ordinary mean.  Additive to ABI 7 (nfp_desc is unchanged); the length convention of the bias calls:
+ * `saved` comes with its length in floats, and a buffer shorter than nfp_gap_saved_floats(d) (min 1 float; the backward
+ * reads the per-pixel part alone) returns NFP_E_INVALID and launches nothing.
+ */
+int nfp_gap_supported(const nfp_desc* d);
+int64_t nfp_gap_saved_floats(const nfp_desc* d);
+int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map, float* saved, int64_t saved_floats,
+                    void* hip_stream);
+int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, const void* grad_out, const void* out_map,
+                     const float* saved, int64_t saved_floats, void* grad_x, void* hip_stream);
+
+/*
  * ABI 7 — NFPPooling(bias=True) (nfp.py:42-58 with bias=True: both depthwise convs carry a TRAINABLE bias, only their
  * weights are frozen, nfp.py:61,82).  The conv adds the bias after padding: a zero-padded tap reads 0 + bias.  Per pair
  * (output o, neighbour n) of channel c the measure then sees

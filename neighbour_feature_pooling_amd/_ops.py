@@ -224,6 +224,78 @@ def _pool_bwd(ctx, g_gap, g_nfpm, g_map, g_saved):
 nfp_pool_op.register_autograd(_pool_bwd, setup_context=_pool_setup)
 
 
+# ---- nfp_gap: x -> (gap, maps, saved) — GAP(x) beside the full maps, the first step of an NFP head -------------------------
+def _gap_saved_bound(shape, dtype, cfg):
+    """An upper bound, from the shape alone, of nfp_gap_saved_floats (per-pixel state + at most H row bands of C partial
+    channel sums per image): what the compiled graph allocates."""
+    B, C, H, W = shape
+    return max(_saved_floats(shape, dtype, cfg, True) + B * H * C, 1)
+
+
+@torch.library.custom_op("nfp_amd::nfp_gap", mutates_args=(), device_types="cuda",
+                         schema=f"(Tensor x, {_CFG_SCHEMA}) -> (Tensor, Tensor, Tensor)")
+def nfp_gap_op(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    from . import functional as F
+    ns = _gap_saved_bound(tuple(x.shape), x.dtype, cfg)
+    if not F.nfp_gap_fused_ok(x, cfg):
+        # (functional.nfp_with_gap asked the library at trace time; what only the run shows — a misaligned channels-last
+        # pointer, a geometry first seen inside a graph capture — is served here by the maps' own op and a mean, never an
+        # error.  The state buffer has the size the fake implementation states, the maps' state in front)
+        maps, sv = nfp_op(x, *cfg_args(cfg), True)
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        saved[:sv.numel()] = sv
+        return x.float().mean((2, 3)), maps, saved
+    return F.gap_forward_call(x, cfg, ns)
+
+
+@nfp_gap_op.register_fake
+def _(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    B, C, H, W = x.shape
+    Ho, Wo = _out_hw(H, W, cfg)
+    return (x.new_empty((B, C), dtype=torch.float32), x.new_empty((B, cfg.out_channels, Ho, Wo)),
+            x.new_empty((_gap_saved_bound(tuple(x.shape), x.dtype, cfg),), dtype=torch.float32))
+
+
+@torch.library.custom_op("nfp_amd::nfp_gap_backward", mutates_args=(), device_types="cuda",
+                         schema=f"(Tensor x, Tensor maps, Tensor saved, Tensor? grad_gap, Tensor? grad_maps, {_CFG_SCHEMA}) -> Tensor")
+def nfp_gap_backward_op(x, maps, saved, grad_gap, grad_maps, R, measure, p, stride, padding, dilation, padding_mode,
+                        similarity, eps, q_scs, diff_weights, inner_R):
+    cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
+    from . import functional as F
+    if not F.nfp_gap_fused_ok(x, cfg):
+        go = torch.zeros_like(maps) if grad_maps is None else grad_maps
+        ns = _saved_floats(tuple(x.shape), x.dtype, cfg, True)
+        gx = nfp_backward_op(x, maps, saved[:ns], go, *cfg_args(cfg))
+        if grad_gap is not None:
+            gx = (gx.float() + (grad_gap.float() / (x.shape[2] * x.shape[3]))[:, :, None, None]).to(x.dtype)
+        return gx
+    return F.gap_backward_call(x, cfg, maps, saved, grad_gap, grad_maps)
+
+
+@nfp_gap_backward_op.register_fake
+def _(x, maps, saved, grad_gap, grad_maps, *cfg_fields):
+    return torch.empty_like(x)
+
+
+def _gap_setup(ctx, inputs, output):
+    ctx.cfg_fields = inputs[1:13]
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(inputs[0], output[1], output[2])
+
+
+def _gap_bwd(ctx, g_gap, g_maps, g_saved):
+    x, maps, saved = ctx.saved_tensors
+    if g_gap is None and g_maps is None:
+        return (None,) * 13
+    gx = torch.ops.nfp_amd.nfp_gap_backward(x, maps, saved, g_gap, g_maps, *ctx.cfg_fields)
+    return (gx,) + (None,) * 12
+
+
+nfp_gap_op.register_autograd(_gap_bwd, setup_context=_gap_setup)
+
+
 # ---- nfp_biased: (x, centre_bias, neighbour_bias) -> (maps, saved) — NFPPooling(bias=True), include/nfp.h ABI 7 ------------
 def _bias_saved_floats(shape, dtype, cfg):
     """nfp_bias_saved_floats for this call — a function of the shape and the measure alone."""

@@ -63,13 +63,16 @@ struct FoffQ {
 // VAR: one of the measures that ride on these kernels through KP's run-time constants (DotProduct, GFC, RMSE:
 // nfp_common.h).  Cosine and L2 themselves keep the finalize of round 2, constants folded: the three extra transcendental
 // instructions of the general form sit on the critical path of a 5 us kernel (4.97 vs 4.87 us at the headline shape).
-template <int R, int M, bool BF, bool NHWC, bool POOL = false, bool VAR = false>
+// POOL = kPoolGap: the channel sums alone beside the maps — no map staging, no map sums; scratch rows of C floats.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool VAR = false>
 __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restrict__ x, void* __restrict__ out,
                                                  float* __restrict__ saved, const unsigned char* __restrict__ ws,
                                                  int rb, float* __restrict__ gap, float* __restrict__ nfpm,
                                                  float* __restrict__ part) {
   constexpr int N = Win<R>::N, NF = Win<R>::NF;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool MAPSUM = POOL == kPoolBoth;   // the N pooled map sums (and their staging)
+  constexpr int NP = MAPSUM ? N : 0;            // map sums behind the channel sums of a scratch row
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   float4* slab = lds4;
   const int P = g.P, W = g.W;
@@ -224,7 +227,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
       // pixels p0 + part, p0 + part + 4, ...; joined by a fixed xor tree.  One band per image: the mean goes straight to
       // gap[b][c]; several bands: the band's sum goes to its row of the scratch (pool_fold joins the bands in order).
       const int nbands = gridDim.y;
-      float* gdst = nbands == 1 ? gap + (long long)b * g.C : part + ((long long)b * nbands + band) * (g.C + N);
+      float* gdst = nbands == 1 ? gap + (long long)b * g.C : part + ((long long)b * nbands + band) * (g.C + NP);
       const float gscale = nbands == 1 ? g.invP : 1.f;
       for (int i0 = 0; i0 < ncq * 4; i0 += T) {
         const int i = i0 + t, cq = min(i >> 2, ncq - 1), quarter = i & 3;   // (which quarter of the pixels this lane sums)
@@ -245,7 +248,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
           if (nbands == 1)
             *(float4*)(gdst + c0 + 4 * cq) = gv;
           else   // (a scratch row another workgroup may fold: written through — nfp_common.h::pool_last_band)
-            pool_store4(pool_rsrc(gdst, g.C + N), c0 + 4 * cq, gv);
+            pool_store4(pool_rsrc(gdst, g.C + NP), c0 + 4 * cq, gv);
         }
       }
     }
@@ -342,14 +345,14 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
           }
         }
         if (!POOL || g.pool_map) stx(ob, n * P + pf, v, BF ? NFP_BF16 : NFP_F32);
-        if constexpr (POOL) Tt[NV + n * Ps + lpf] = v;  // vm[n][p], behind the half-stencil table
-      } else if constexpr (POOL) {
+        if constexpr (MAPSUM) Tt[NV + n * Ps + lpf] = v;  // vm[n][p], behind the half-stencil table
+      } else if constexpr (MAPSUM) {
         Tt[NV + n * Ps + lpf] = 0.f;                    // (an output another band writes: not part of this band's sum)
       }
     }
     if (M == NFP_COSINE && !g.unit && saved != nullptr && glf == 0 && pf < po) saved[(long long)b * P + pf] = __builtin_amdgcn_sqrtf(n2p);
   }
-  if constexpr (POOL) {
+  if constexpr (MAPSUM) {
     lds_barrier();   // (not __syncthreads(): the map stores just issued drain under the sums — nfp_common.h)
     // wave w reduces map n = w, w + nwaves, ...: lane-strided partial sums over the outputs THIS band wrote, then a
     // fixed shuffle tree

@@ -57,6 +57,11 @@ struct KP {
   unsigned int* tickets;   // fused pooling tail, several row bands per image: one arrival counter per image (the first
                            // kTicketBytes of the descriptor's workspace, zero between launches) or null — see pool_last_band
 };
+// Fused-tail mode of the hot-path kernels (their template parameter POOL):
+//   kPoolBoth  nfp_pool_*: GAP(x) and the pooled NFP vector; the backward's grad_out is gnfpm[b,n] / P, not a map
+//   kPoolGap   nfp_gap_*: GAP(x) beside the full maps (an NFP head, nfp_heads.py: gap(fmap) and nfp(fmap) of one feature
+//              map) — no pooled map sums; the backward reads grad_out as a map and adds ggap[b,c] / P in the same store
+constexpr int kPoolNone = 0, kPoolBoth = 1, kPoolGap = 2;
 constexpr int kTicketWords = 4096;              // (batches beyond it: no counters — make_kp)
 constexpr int kTicketBytes = kTicketWords * 4;
 

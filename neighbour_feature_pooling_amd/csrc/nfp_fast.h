@@ -627,7 +627,9 @@ struct L_BRQ {
 // ---- backward -------------------------------------------------------------------------------
 // POOL: grad_out is not a map but the gradients of the two pooled outputs: go[b,n,p] = gnfpm[b,n]/P
 // for every p, and every grad_x[b,c,p] also receives ggap[b,c]/P (adjoint of the two means).
-template <int R, int M, bool BF, bool NHWC, bool POOL = false, int GEMM = 0>   // GEMM: 0 vector phase B, 1 / 2 matrix cores
+// POOL = kPoolGap (nfp_common.h): the head's pass — grad_out IS a map, read as the plain backward reads it, and every
+// grad_x[b,c,p] also receives ggap[b,c]/P where the pooled mode adds it.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0>   // GEMM: 0 vector phase B, 1 / 2 matrix cores
 __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g, const void* __restrict__ x,
                                                         const void* __restrict__ go, const void* __restrict__ out,
                                                         const float* __restrict__ saved, void* __restrict__ gx,
@@ -636,6 +638,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
                                                         const unsigned char* __restrict__ ws) {
   static_assert(!GEMM || BF, "matrix-core phase B: bf16 storage only");
   constexpr int K2 = Win<R>::K2, N = Win<R>::N;
+  constexpr bool GO_POOLED = POOL == kPoolBoth, HAS_GAP = POOL != kPoolNone;   // what grad_out is / whether grad(GAP) joins
   // the diagonal is folded by a phase of its own when the weights are consumed as a table (matrix cores) or the
   // window is large; for k = 3 every compute thread folds its own pixel's nine terms while it loads its weights
   constexpr bool FOLD_PHASE = GEMM || Win<R>::RAD != 1;  // (R: radius spec of nfp_tables.h::Win)
@@ -655,7 +658,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   float* dfn = ipn + P;            // [P] -1 / (|x_p| max(|x_p|, eps)), 0 where |x_p| = 0
   float* Wc = dfn + P;             // (GEMM = 2) [P] centre weights before the fold
   const int g3_band = Win<R>::RAD * g.W + Win<R>::RAD, g3_wq = odd_up(2 * gemm_kw(g3_band) + 1);
-  const int g3_fixed4 = (3 * P + (POOL ? (int)(g.Cwg) : 0) + 3) >> 2;   // float4 slots in front of Wd
+  const int g3_fixed4 = (3 * P + (HAS_GAP ? (int)(g.Cwg) : 0) + 3) >> 2;   // float4 slots in front of Wd
   uint4* g3_Wd = (uint4*)(lds4 + g3_fixed4);
   float4* g3_pv4 = (float4*)(g3_Wd + (long long)((P + 31) >> 5) * 64 * g3_wq);
   float4* pv4 = G3 ? g3_pv4 : (GEMM ? lds4 + ((P * K2 + 2 * P + 3) >> 2) + ((P * K2 + 3) >> 2) : lds4 + ((2 * P * K2 + 2 * P + 3) >> 2));
@@ -675,7 +678,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   // (The vector kernel keeps its 16-byte global loads in the channel loop: staged the same way it measured 7.3 vs 6.7 us.)
   float* gg_s = nullptr;
   float ggv0 = 0.f, ggv1 = 0.f;
-  if constexpr (POOL && GEMM) {
+  if constexpr (HAS_GAP && GEMM) {
     const int ncw = cb1 - cb0;
     const int band = Win<R>::RAD * g.W + Win<R>::RAD, KW = gemm_kw(band);
     gg_s = G3 ? Wc + P : (float*)(gemm_Wd + (long long)g.Tc * 2 * 32 * odd_up(2 * KW + 1));
@@ -745,7 +748,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   uint4 gq, oq, gq0, oq0;  // (the first round's piece in registers of its own: a copy made before the x block is
                            // requested would wait for the data there)
   auto pair_load_to = [&](uint4& gd, uint4& od, int o) {  // o: first pair of the piece
-    if constexpr (!POOL) gd = *(const uint4*)((const char*)gob + (long long)o * ES);
+    if constexpr (!GO_POOLED) gd = *(const uint4*)((const char*)gob + (long long)o * ES);
     od = *(const uint4*)((const char*)outb + (long long)o * ES);
   };
   auto pair_load = [&](int o) { pair_load_to(gq, oq, o); };
@@ -817,7 +820,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
     // most two maps when P >= VP: two loads instead of one per pair
     int n0 = 0;
     float gn0 = 0.f, gn1 = 0.f;
-    if constexpr (POOL) {
+    if constexpr (GO_POOLED) {
       n0 = fdivi(o, P);
       gn0 = gnfpm[(long long)b * N + n0] * g.invP;
       gn1 = gnfpm[(long long)b * N + min(n0 + 1, N - 1)] * g.invP;
@@ -825,7 +828,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
 #pragma unroll
     for (int k = 0; k < VP; ++k) {
       const float oc = pair_value(oc4, k);
-      const float gc = !POOL ? pair_value(gc4, k)
+      const float gc = !GO_POOLED ? pair_value(gc4, k)
                        : (P >= VP ? ((o + k) >= (n0 + 1) * P ? gn1 : gn0) : gnfpm[(long long)b * N + fdivi(o + k, P)] * g.invP);
       if (M == NFP_COSINE) {
         const float s = g.osa * (oc - g.osb);   // out = osa * s + osb, osa = +-1
@@ -877,7 +880,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
       if (t < ((2 * P * K2) & 3)) Wt[((2 * P * K2) & ~3) + t] = 0.f;
     }
   }
-  if constexpr (POOL && GEMM) {
+  if constexpr (HAS_GAP && GEMM) {
     const int ncw = cb1 - cb0;
     if (t < ncw) gg_s[t] = ggv0 * g.invP;
     if (t + T < ncw) gg_s[t + T] = ggv1 * g.invP;
@@ -1084,10 +1087,10 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
     // (the pair values behind the tables are dead: their LDS becomes the GEMM's operand images)
     if constexpr (G3)
       bwd_gemm_phase3<Win<R>::RAD, NHWC>(g, gemm_Wd, gemm_Xt, gxr, x16, (uint16_t*)gx + (long long)b * g.gB, cb0, cb1, t, T,
-                                         POOL ? gg_s : nullptr);
+                                         HAS_GAP ? gg_s : nullptr);
     else
       bwd_gemm_phase<R, NHWC>(g, Wt, gemm_Xt, gemm_Wd, gxr, x16, (uint16_t*)gx + (long long)b * g.gB, cb0, cb1, t, T,
-                              POOL ? gg_s : nullptr);
+                              HAS_GAP ? gg_s : nullptr);
     return;
   }
   float w[K2];
@@ -1122,7 +1125,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
       for (int cq = gl; cq < ncq; cq += g.G) {
         const float4* row = slab + cq * Pp + sp;
         float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (POOL && g.pool_gap) {
+        if (HAS_GAP && g.pool_gap) {
           const float4 gg = *(const float4*)(ggap + (long long)b * g.C + c0 + 4 * cq);
           r4 = make_float4(gg.x * g.invP, gg.y * g.invP, gg.z * g.invP, gg.w * g.invP);
         }

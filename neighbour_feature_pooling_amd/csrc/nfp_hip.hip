@@ -386,7 +386,7 @@ int chunk_channels(const KP& g, int total, int T, int G, bool nhwc, int budget) 
 #ifndef NFP_BAND_WGS
 #define NFP_BAND_WGS 256
 #endif
-template <int R, int M, bool BF, bool NHWC, bool POOL = false>
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone>
 int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
                       float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
   constexpr int NF = Win<R>::NF;
@@ -443,11 +443,11 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   // its sums already hide the next chunk's latency behind four times the LDS reads)
   g.pf = (NFP_BAND_PF && nch > 1 && Win<R>::RAD == 1) ? 1 : 0;
   const size_t slab = (size_t)(g.Cc / 4) * ppb * 16;
-  const size_t tail = (size_t)psm * (NF + 1) * 4 + (POOL ? (size_t)Win<R>::N * psm * 4 : 0);   // Tt (+ pooled-map staging)
+  const size_t tail = (size_t)psm * (NF + 1) * 4 + (POOL == kPoolBoth ? (size_t)Win<R>::N * psm * 4 : 0);   // Tt (+ pooled-map staging)
   const size_t lds = slab + tail;
   if (lds > (size_t)kLdsMax) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "fwd_band<R%s,%s,%s,%s%s>x%d", R == 12 ? "1+2" : (R == 1 ? "1" : "2"), hot_name(g),
-           BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", POOL ? ",pool" : "", nb);
+           BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
   if (nb_out) *nb_out = nb;
   // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — pool_forward_rm)
   if constexpr (M != kSymTerm)
@@ -476,7 +476,7 @@ size_t bwd_pair_bytes(const KP& g, int M, int N) {
 }
 constexpr size_t kEarlyBudget = 96 * 1024;  // slab beside the pair values (committed during phase A) up to this much LDS
 
-template <int R, int M, bool BF, bool NHWC, bool POOL = false>
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone>
 int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                       hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
@@ -524,7 +524,7 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
   const size_t lds = g.early ? fixed + pairs + slab : fixed + std::max(pairs, slab);
   if (lds > (size_t)kLdsMax) return kNotApplicable;  // tables + slab do not fit: the generic kernels serve it
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%s,%s,%s,%s%s>", R == 12 ? "1+2" : (R == 1 ? "1" : "2"),
-           hot_name(g), BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", POOL ? ",pool" : "");
+           hot_name(g), BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL));
   return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, g, x, go, out, saved, gx,
                 ggap, gnfpm, g.ws);
 }
@@ -544,10 +544,12 @@ int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStre
   if (tiles > (size_t)kLdsMax) return kNotApplicable;
   if (g.contig && tiles + image > (size_t)kLdsMax) return kNotApplicable;  // NCHW is transposed through LDS only
   if (tiles + (size_t)g.P * 8 > (size_t)kLdsMax) return kNotApplicable;  // (the norm tables reuse the image's words)
-  // the pooled variant takes its sums from the LDS image and stages the map values in it afterwards
+  // the pooled variant takes its sums from the LDS image and stages the map values in it afterwards; GAP(x) alone (gap set,
+  // nfpm null: nfp_gap_forward) needs the LDS image too, and nothing behind it
+  if (gap != nullptr && nfpm == nullptr && tiles + image > (size_t)kLdsMax) return kNotApplicable;
   if (nfpm != nullptr && (tiles + image > (size_t)kLdsMax || image < (size_t)(2 + Win<R>::N) * g.P * 4)) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "fwd_gram<R%d,%s,bf16,%s%s>", R, hot_name(g),
-           g.contig ? "nchw" : "nhwc", nfpm != nullptr ? ",pool" : "");
+           g.contig ? "nchw" : "nhwc", nfpm != nullptr ? ",pool" : (gap != nullptr ? ",gap" : ""));
   if (g.contig)
     return launch("fwd_gram", fwd_gram<R, M, true, true>, dim3(g.B), dim3(1024), tiles + image, st, g, x, out, saved, D, g.ws,
                   gap, nfpm);
@@ -559,7 +561,7 @@ int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStre
 }
 
 // Phase B of the backward on the matrix cores (nfp_fast.h::bwd_gemm_phase): bf16 storage, C a multiple of 32.
-template <int R, int M, bool NHWC, bool POOL = false>
+template <int R, int M, bool NHWC, int POOL = kPoolNone>
 int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                       hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
@@ -576,7 +578,7 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   // table.  At config 5 a third of the workgroup's threads hold a position and walk ~500 instructions each: 13.8 us of
   // phase A against 6.0 us for the table-driven one spread over all 1024 threads (in-kernel stamps, profiles/r04_g_…).
 #ifdef NFP_GEMM2_ARM
-  if constexpr (R != 12) {
+  if constexpr (R != 12 && POOL != kPoolGap) {
     const int npu2 = (g.H + 2 * R) * (g.W + 2 * R);
     if (g_sw.gemm2.load(std::memory_order_relaxed) && !g.gfc && npu2 <= 1024 && !(!NHWC && (g.P & 3) && S < 2)) {
       KP h = g;
@@ -628,7 +630,7 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   // the diagonal is folded — the operand images lie over both
   const size_t xt = (size_t)g.Cwg * xq * 16, wd1 = (size_t)2 * 32 * wq * 16;
   const size_t fixed = ((size_t)(g.P * K2 + 2 * g.P) * 4 + 15) & ~(size_t)15, dtb = ((size_t)g.P * K2 * 4 + 15) & ~(size_t)15;
-  const size_t ggb = POOL ? (size_t)g.Cwg * 4 : 0;   // grad(GAP(x)) of the block, staged behind Wd
+  const size_t ggb = POOL != kPoolNone ? (size_t)g.Cwg * 4 : 0;   // grad(GAP(x)) of the block, staged behind Wd
   int rt = fixed + xt + ggb < (size_t)kLdsMax ? (int)(((size_t)kLdsMax - fixed - xt - ggb) / wd1) : 0;
   rt = std::min(rt, nt);
   // Second form (round 4): Wd of ALL row tiles, written by phase A itself, x in chunks of `ctr` channel tiles (about one output
@@ -640,14 +642,14 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
     int ctr = std::max(1, std::min(nct, nw / nt));
     const int nch = (nct + ctr - 1) / ctr;
     ctr = (nct + nch - 1) / nch;   // even chunks
-    const size_t fixed3 = ((size_t)(3 * g.P + (POOL ? g.Cwg : 0)) * 4 + 15) & ~(size_t)15;
+    const size_t fixed3 = ((size_t)(3 * g.P + (POOL != kPoolNone ? g.Cwg : 0)) * 4 + 15) & ~(size_t)15;
     const size_t xtc = (size_t)32 * ctr * xq * 16;
     const size_t lds3 = fixed3 + (size_t)nt * wd1 + std::max((size_t)(nch > 1 ? 2 : 1) * xtc, bwd_pair_bytes(g, M, N) + dtb);
     if (lds3 <= (size_t)kLdsMax) {
       g.Tc = ctr;
       g.early = 0;
       snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma2%s>", R, hot_name(g), NHWC ? "nhwc" : "nchw",
-               POOL ? ",pool" : "");
+               pool_tag(POOL));
       return launch("bwd_fast_mfma2", bwd_fast<R, M, true, NHWC, POOL, 2>, dim3(g.B, S), dim3(T), lds3, st, g, x, go, out, saved,
                     gx, ggap, gnfpm, g.ws);
     }
@@ -660,7 +662,7 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   g.early = 0;
   if (lds > (size_t)kLdsMax) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma%s>", R, hot_name(g),
-           NHWC ? "nhwc" : "nchw", POOL ? ",pool" : "");
+           NHWC ? "nhwc" : "nchw", pool_tag(POOL));
   return launch("bwd_fast_mfma", bwd_fast<R, M, true, NHWC, POOL, 1>, dim3(g.B, S), dim3(T), lds, st, g, x, go, out,
                 saved, gx, ggap, gnfpm, g.ws);
 }
@@ -1005,6 +1007,68 @@ int pool_backward_rm(const KP& g, const void* x, const void* out_map, const floa
   return tile_backward(g, x, nullptr, out_map, saved, gx, st, true, ggap, gnfpm);
 }
 
+// ---- GAP(x) beside the maps (nfp_gap_*): the pass of an NFP head (nfp_heads.py: gap(fmap) and nfp(fmap) of one feature map) ----
+// Forward: the pooled kernels' channel sums without their map sums (kPoolGap); several bands per image write rows of C
+// partial sums to the scratch behind the norms, joined in band order by pool_fold — never by the arrival counters (no
+// atomics on this path).  Backward: grad_out read as a map, ggap[b,c] / P added in the same store.
+// bf16: fwd_gram (its channel sums are a run-time option) and the matrix-core backwards serve this mode as well.
+template <int R, int M>
+int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
+  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  t_pool_scratch = 0;
+  g.tickets = nullptr;
+  g.pool_gap = g.pool_map = 1;
+  if (saved == nullptr) return fail(NFP_E_INVALID, "GAP beside the maps needs the scratch of nfp_gap_saved_floats");
+  float* part = saved + (long long)stats_of(g.measure) * g.B * g.P;
+  KP gfold = g;
+  gfold.N = 0;   // (rows of C floats: pool_fold joins the channel sums alone)
+  if (g.ws != nullptr && fast_ok(g, x, x)) {
+    int rc;
+    if (bf) {
+      rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr);
+      if (rc != kNotApplicable) return rc;
+    }
+    int nb = 1;
+    if (bf) rc = nhwc ? launch_fwd_band_t<R, M, true, true, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb)
+                      : launch_fwd_band_t<R, M, true, false, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
+    else rc = nhwc ? launch_fwd_band_t<R, M, false, true, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb)
+                   : launch_fwd_band_t<R, M, false, false, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
+    if (rc == NFP_OK && nb > 1) {
+      t_pool_scratch = (long long)g.B * nb * g.C;
+      strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+      return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
+    }
+    if (rc != kNotApplicable) return rc;
+  }
+  if (!tile_ok(g, x, x)) return kNotApplicable;
+  int nb = 0;
+  if (int rc = tile_forward(g, x, out_map, saved, st, kPoolGap, part, &nb, gap, nullptr); rc != NFP_OK) return rc;
+  t_pool_scratch = (long long)g.B * nb * g.C;
+  strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+  return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
+}
+template <int R, int M>
+int gap_backward_rm(KP g, const void* x, const void* go, const void* out_map, const float* saved, void* gx, hipStream_t st,
+                    const float* ggap) {
+  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  g.pool_gap = ggap != nullptr ? 1 : 0;   // NULL: GAP(x) took no part in the loss — nothing is added, nothing is read
+  if (g.ws != nullptr && fast_ok(g, x, gx)) {
+    int rc;
+    if (bf) {
+      rc = nhwc ? launch_bwd_gemm_t<R, M, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
+                : launch_bwd_gemm_t<R, M, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
+      if (rc != kNotApplicable) return rc;
+      rc = nhwc ? launch_bwd_fast_t<R, M, true, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
+                : launch_bwd_fast_t<R, M, true, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
+    } else {
+      rc = nhwc ? launch_bwd_fast_t<R, M, false, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
+                : launch_bwd_fast_t<R, M, false, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
+    }
+    if (rc != kNotApplicable) return rc;
+  }
+  return tile_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1207,6 +1271,97 @@ int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, c
     rc = g.R == 1 ? pool_backward_rm<1, NFP_NORM>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm)
                   : pool_backward_rm<2, NFP_NORM>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm);
   return finish(rc, "nfp_pool_backward");
+}
+
+// ---- GAP(x) beside the full maps: the first step of an NFP head (nfp_heads.py) -------------------------------------------
+// As pool_plan: both launchers in plan mode, so that a 1 means nfp_gap_forward AND nfp_gap_backward will launch.
+static int gap_plan(const KP& g, bool backward) {
+  const bool was_dry = t_dry;
+  char keep_variant[sizeof(g_variant)], keep_plan[sizeof(t_plan)], keep_err[sizeof(g_err)];
+  memcpy(keep_variant, g_variant, sizeof(keep_variant));
+  memcpy(keep_plan, t_plan, sizeof(keep_plan));
+  memcpy(keep_err, g_err, sizeof(keep_err));
+  t_dry = true;
+  void* fake = (void*)(uintptr_t)0x1000;
+  const float* cf = (const float*)fake;
+  int rc;
+  if (!backward) {
+    if (hot_product(g))
+      rc = g.R == 1 ? gap_forward_rm<1, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
+                    : gap_forward_rm<2, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
+    else
+      rc = g.R == 1 ? gap_forward_rm<1, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
+                    : gap_forward_rm<2, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
+  } else {
+    if (hot_product(g))
+      rc = g.R == 1 ? gap_backward_rm<1, NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf)
+                    : gap_backward_rm<2, NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf);
+    else
+      rc = g.R == 1 ? gap_backward_rm<1, NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf)
+                    : gap_backward_rm<2, NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf);
+  }
+  t_dry = was_dry;
+  memcpy(g_variant, keep_variant, sizeof(keep_variant));
+  memcpy(t_plan, keep_plan, sizeof(keep_plan));
+  memcpy(g_err, keep_err, sizeof(keep_err));
+  return rc;
+}
+
+int nfp_gap_supported(const nfp_desc* d) {
+  KP g;
+  if (make_kp(d, &g)) return 0;
+  if (!pool_measure_ok(g)) return 0;
+  if (g.B == 0) return 1;
+  return gap_plan(g, false) == NFP_OK && gap_plan(g, true) == NFP_OK ? 1 : 0;
+}
+
+int64_t nfp_gap_saved_floats(const nfp_desc* d) {
+  KP g;
+  if (make_kp(d, &g)) return -1;
+  if (!pool_measure_ok(g) || g.B == 0) return 0;
+  if (gap_plan(g, false) != NFP_OK) return 0;
+  return (int64_t)stats_of(g.measure) * g.B * g.P + t_pool_scratch;
+}
+
+int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map, float* saved, int64_t saved_floats,
+                    void* hip_stream) {
+  KP g;
+  if (int rc = make_kp(d, &g)) return rc;
+  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (g.B == 0) return NFP_OK;
+  if (!x || !gap || !out_map) return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = std::max<int64_t>(nfp_gap_saved_floats(d), 1);
+  if (saved == nullptr || saved_floats < need)
+    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_gap_saved_floats is %lld", (long long)(saved ? saved_floats : 0),
+                (long long)need);
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc;
+  if (hot_product(g))
+    rc = g.R == 1 ? gap_forward_rm<1, NFP_COSINE>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, NFP_COSINE>(g, x, out_map, saved, st, gap);
+  else
+    rc = g.R == 1 ? gap_forward_rm<1, NFP_NORM>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, NFP_NORM>(g, x, out_map, saved, st, gap);
+  return finish(rc, "nfp_gap_forward");
+}
+
+int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, const void* grad_out, const void* out_map,
+                     const float* saved, int64_t saved_floats, void* grad_x, void* hip_stream) {
+  KP g;
+  if (int rc = make_kp(d, &g)) return rc;
+  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (g.B == 0) return NFP_OK;
+  if (!x || !grad_out || !out_map || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = (int64_t)stats_of(g.measure) * g.B * g.P;   // (the backward reads the per-pixel state alone)
+  if (need > 0 && (saved == nullptr || saved_floats < need))
+    return fail(NFP_E_INVALID, "saved holds %lld floats, the backward reads %lld", (long long)(saved ? saved_floats : 0), (long long)need);
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc;
+  if (hot_product(g))
+    rc = g.R == 1 ? gap_backward_rm<1, NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
+                  : gap_backward_rm<2, NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
+  else
+    rc = g.R == 1 ? gap_backward_rm<1, NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
+                  : gap_backward_rm<2, NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
+  return finish(rc, "nfp_gap_backward");
 }
 
 // ---- ABI 7: NFPPooling(bias=True) — nfp_bias.hip ---------------------------------------------------------------------

@@ -197,6 +197,7 @@ inline const char* hot_name(const KP& g) {
 inline bool force_generic() { return g_sw.force_generic.load(std::memory_order_relaxed) != 0; }
 inline int round4(int v) { return (v + 3) & ~3; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline const char* pool_tag(int pool) { return pool == nfp::kPoolBoth ? ",pool" : (pool == nfp::kPoolGap ? ",gap" : ""); }
 // fewest groups (<= gmax) that still finish ncq channel quads in ceil(ncq/gmax) rounds
 inline int even_groups(int ncq, int gmax) {
   int rounds = (ncq + gmax - 1) / gmax;
@@ -205,12 +206,13 @@ inline int even_groups(int ncq, int gmax) {
 
 // ---- the row-band kernels of nfp_tile.h (defined in nfp_tile.hip) -------------------------------------------------------
 // Each returns NFP_OK, kNotApplicable (this descriptor is not theirs / does not fit) or an NFP_E_* code; g_variant names
-// the launch.  pool: the fused nfp_pooling tail (part = scratch for the bands' partial sums; *nb = bands per image).
+// the launch.  pool: nfp::kPoolNone / kPoolBoth (the fused nfp_pooling tail) / kPoolGap (GAP(x) beside the maps); part = scratch
+// for the bands' partial sums, rows of C + N floats (kPoolGap: C); *nb = rows per image.
 bool tile_ok(const KP& g, const void* x, const void* gx);
-int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, bool pool, float* part, int* nb,
+int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
                  float* gap, float* nfpm);
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                  bool pool, const float* ggap, const float* gnfpm);
+                  int pool, const float* ggap, const float* gnfpm);
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st);
 
 // ---- NFPPooling(bias=True) (nfp_bias.hip, ABI 7) -------------------------------------------------------------------------

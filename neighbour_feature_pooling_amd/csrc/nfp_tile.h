@@ -352,12 +352,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 // as they lie in memory — in its storage type: bf16 maps keep 8 channels per piece and are summed with v_dot2c_f32_bf16
 // (cosine: one instruction per channel pair and direction), half the LDS bytes of the float4 slab.  With several channel
 // chunks the NEXT chunk's DMA runs under the current chunk's sums (two slabs).  See the block in the kernel.
-template <int R, int M, bool BF, bool NHWC, bool POOL = false, bool GFC = false, bool DMA = false>
+// POOL = kPoolGap (nfp_common.h): the channel sums alone, rows of C floats — no map staging, no map sums.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool DMA = false>
 __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
                                                  void* __restrict__ out, float* __restrict__ saved,
                                                  float* __restrict__ part, float* __restrict__ gap, float* __restrict__ nfpm) {
   constexpr int N = Win<R>::N, NF = Win<R>::NF;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool MAPSUM = POOL == kPoolBoth;   // the N pooled map sums (and their staging)
+  constexpr int NP = MAPSUM ? N : 0;            // map sums behind the channel sums of a scratch row
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   lds_poison(lds4, tg.ldsw);
   int b, band;
@@ -378,7 +381,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
   const int lpc = DMA ? g.Tc : 0, PC = 1 << lpc, npu64 = (npu + 63) & ~63;
   const int nbuf = (DMA && g.C > g.Cc) ? 2 : 1;
   const int slabq = ((dump + 1) * (int)sizeof(QT) + 15) >> 4;   // the slab and its spare slot, in 16-byte units
-  const int tt0 = DMA ? nbuf * npu64 * PC : (POOL ? max(slabq, (N * nbpA + 3) >> 2) : slabq);
+  const int tt0 = DMA ? nbuf * npu64 * PC : (MAPSUM ? max(slabq, (N * nbpA + 3) >> 2) : slabq);
   float* Tt = (float*)(lds4 + tt0);                 // [NF][npu] pair sums per direction, then the per-position factor
   float* Fq = Tt + NF * npu;
   const Rsrc xb = make_rsrc((const char*)x + (long long)b * g.sB * ES, (long long)g.C * P * ES);
@@ -536,7 +539,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
       const int t = ps.gl + G * v, lane = t & 63, wv = t >> 6, nw = (G * npu) >> 6;
       const int nbp = (bd.y1 - bd.y0) * W, seg = (nbp + kPoolSub - 1) / kPoolSub;
       // (scratch rows another workgroup may fold: written through — nfp_common.h::pool_last_band)
-      const Rsrc pb = pool_rsrc(part + ((long long)b * tg.nb + band) * kPoolSub * (g.C + N), (long long)kPoolSub * (g.C + N));
+      const Rsrc pb = pool_rsrc(part + ((long long)b * tg.nb + band) * kPoolSub * (g.C + NP), (long long)kPoolSub * (g.C + NP));
       if (wv < nw) {
         for (int it = wv; it < ncq * kPoolSub; it += nw) {
           const int cq = it / kPoolSub, sub = it - cq * kPoolSub, hi = min(nbp, (sub + 1) * seg);
@@ -553,7 +556,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
           s4.y = wave_sum(s4.y);
           s4.z = wave_sum(s4.z);
           s4.w = wave_sum(s4.w);
-          if (lane == 63) pool_store4(pb, sub * (g.C + N) + c0 + 4 * cq, s4);
+          if (lane == 63) pool_store4(pb, sub * (g.C + NP) + c0 + 4 * cq, s4);
         }
       } else if (nw == 0 && t == 0) {  // (a workgroup below 64 threads: tiny maps, one thread adds them up)
         for (int cq = 0; cq < ncq; ++cq) {
@@ -567,7 +570,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
             s4.w += q.w;
           }
           for (int sub = 0; sub < kPoolSub; ++sub)
-            pool_store4(pb, sub * (g.C + N) + c0 + 4 * cq, sub == 0 ? s4 : make_float4(0.f, 0.f, 0.f, 0.f));
+            pool_store4(pb, sub * (g.C + NP) + c0 + 4 * cq, sub == 0 ? s4 : make_float4(0.f, 0.f, 0.f, 0.f));
         }
       }
     }
@@ -681,7 +684,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
         store_1<BF>(ob, p, n * P, val);
       else
         store_1<BF>(ob, n * P + p, 0, val);
-      if constexpr (POOL) vm[n * nbpA + lpf] = val;
+      if constexpr (MAPSUM) vm[n * nbpA + lpf] = val;
     };
     if (G == 1) {  // (the usual case on large maps: every tap's offsets are compile-time constants)
 #pragma unroll
@@ -692,7 +695,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
     if (M == NFP_COSINE && !g.unit && saved != nullptr && ps.gl == 0)
       saved[(long long)b * P + p] = GFC ? Fp : __builtin_amdgcn_sqrtf(nrm);
   }
-  if constexpr (POOL) {
+  if constexpr (MAPSUM) {
     // this band's share of sum over pixels of out[n]: (map, segment) items over the full wavefronts, a fixed order
     lds_barrier();   // (not __syncthreads(): the map stores just issued drain under the sums — nfp_common.h)
     const int t = ps.gl + G * v, lane = t & 63, wv = t >> 6, nw = (G * npu) >> 6;
@@ -766,13 +769,15 @@ __global__ void __launch_bounds__(256) pool_fold(const float* __restrict__ part,
 // (Cosine: the pair {r, r + d} has ONE similarity s, which reaches the backward twice — out[n][r] and
 // out[opp n][r + d], equal up to the forward's rounding; the pull of both on |x_r| uses r's own copy, so that only the
 // gradients travel through LDS.)
-template <int R, int M, bool BF, bool NHWC, bool POOL = false, bool GFC = false, bool CST = false>
+// POOL = kPoolGap: grad_out IS a map, read as the plain backward reads it; ggap[b,c] / P joins in the same store.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool CST = false>
 __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8) : 4)) bwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
                                                 const void* __restrict__ go, const void* __restrict__ out,
                                                 const float* __restrict__ saved, void* __restrict__ gx,
                                                 const float* __restrict__ ggap, const float* __restrict__ gnfpm) {
   constexpr int N = Win<R>::N, K = Win<R>::K, K2 = Win<R>::K2;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool GO_POOLED = POOL == kPoolBoth, HAS_GAP = POOL != kPoolNone;   // what grad_out is / whether grad(GAP) joins
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   lds_poison(lds4, tg.ldsw);
   int b, item;
@@ -796,7 +801,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
   float* Wr = (float*)(slab + dump + 1) + 2 * K2;           // (2 K2 floats of slack either side: shifted reads)
   const Rsrc xb = make_rsrc((const char*)x + (long long)b * g.sB * ES, (long long)g.C * P * ES);
   const Rsrc gxb = make_rsrc((char*)gx + (long long)b * g.gB * ES, (long long)g.C * P * ES);
-  const Rsrc gob = make_rsrc((const char*)go + (long long)b * N * P * ES, POOL ? 0 : (long long)N * P * ES);
+  const Rsrc gob = make_rsrc((const char*)go + (long long)b * N * P * ES, GO_POOLED ? 0 : (long long)N * P * ES);
   const Rsrc outb = make_rsrc((const char*)out + (long long)b * N * P * ES, (long long)N * P * ES);
   // (DotProduct has no saved norms: an empty resource, every load reads 0)
   const Rsrc svb = make_rsrc((const char*)saved + (long long)b * P * 4, (M == NFP_COSINE && !g.unit) ? (long long)P * 4 : 0);
@@ -833,7 +838,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
         e = (rbad[dy + R] || cbad[dx + R]) ? Oob<BF>::e : e;
       }
       sv[n] = M == kNormP1 ? 0.f : load_1<BF>(outb, e, 0);   // (p = 1: the gradient does not depend on the distance)
-      gov[n] = POOL ? 0.f : load_1<BF>(gob, ep, n * P);
+      gov[n] = GO_POOLED ? 0.f : load_1<BF>(gob, ep, n * P);
     }
     float nrm = 0.f;
     if (M == NFP_COSINE) nrm = load_1<false>(svb, ps.src | ps.zf, 0);
@@ -847,7 +852,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
     for (int n = 0; n < N; ++n) {
       const int j = n < K2 / 2 ? n : n + 1;
       float gc = gov[n];
-      if constexpr (POOL) gc = ps.real ? gnfpm[(long long)b * N + n] * g.invP : 0.f;
+      if constexpr (GO_POOLED) gc = ps.real ? gnfpm[(long long)b * N + n] * g.invP : 0.f;
       if (M == NFP_COSINE) {
         sv[n] = fmaf(sa, sv[n], sb);
         w[j] = sa * gc;
@@ -1000,7 +1005,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
     auto one = [&](int cq) {
       const QT* rc = slab + cq * Ppb + v - R;
       float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (POOL && g.pool_gap) {
+      if (HAS_GAP && g.pool_gap) {
         const float4 gg = *(const float4*)(ggap + (long long)b * g.C + c0 + 4 * cq);
         r4 = make_float4(gg.x * g.invP, gg.y * g.invP, gg.z * g.invP, gg.w * g.invP);
       }

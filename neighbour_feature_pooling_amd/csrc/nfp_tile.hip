@@ -75,10 +75,11 @@ int tile_groups(const KP& g, int nb, int npu, int cap, int cq) {
   return lg;
 }
 
-template <int R, int M, bool BF, bool NHWC, bool POOL = false>
+template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone>
 int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* part = nullptr, int* nb_out = nullptr,
                       float* gap = nullptr, float* nfpm = nullptr) {
   constexpr int NF = Win<R>::NF, N = Win<R>::N;
+  constexpr int NP = POOL == nfp::kPoolBoth ? N : 0;   // map sums behind the channel sums of a scratch row
   const int Wu = g.W + 2 * R;
   for (int attempt = 0; attempt < 2; ++attempt) {
     // first choice: two workgroups of up to 1024 threads per compute unit — half of LDS each, 64 registers.
@@ -93,7 +94,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
       const int lg = tile_groups(g, nb, npu, kCap, g.C / 4), G = 1 << lg;
       const int ppb = nfp::band_row_slots((npu + 3) & ~3, lg);
       const size_t tail = 16 + (size_t)(NF + 1) * npu * 4;                      // spare slot, pair sums, factors
-      const size_t vmb = POOL ? (((size_t)N * nbp + 3) / 4) * 16 : 0;            // pooled: the band's maps, over the slab
+      const size_t vmb = POOL == nfp::kPoolBoth ? (((size_t)N * nbp + 3) / 4) * 16 : 0;            // pooled: the band's maps, over the slab
       constexpr size_t SB = BF ? 8 : 16;   // bytes of a slab slot (four channels of a position in the storage type: nfp_tile.h::Quad)
       if (tail + std::max((size_t)ppb * SB, vmb) > budget) continue;
       int ncq = (int)((budget - tail) / ((size_t)ppb * SB));
@@ -135,7 +136,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
       nfp::TileGeo tg = {nb, rows, Wu, ppb, 1, g.H / nb, g.H % nb, (int)(lds / 4)};
       if (nb_out) *nb_out = POOL ? nb * nfp::kPoolSub : nb;   // (pooled: rows of partial sums per image)
       snprintf(g_variant, sizeof(g_variant), "fwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), BF ? "bf16" : "f32",
-               NHWC ? "nhwc" : "nchw", dma ? ",dma" : "", POOL ? ",pool" : "", nb);
+               NHWC ? "nhwc" : "nchw", dma ? ",dma" : "", pool_tag(POOL), nb);
       const dim3 block(G, Wu, rows);
       // (tile_ids' exact range: batches beyond kTileMaxGrid workgroups go out as several launches, images in order)
       const int es = BF ? 2 : 4, bmax = std::max(8, (tile_max_grid() / nb) & ~7);
@@ -146,7 +147,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
         const void* xs = (const char*)x + (long long)b0 * g.sB * es;
         void* os = (char*)out + (long long)b0 * N * g.P * es;
         float* ss = saved ? saved + (long long)b0 * g.P : nullptr;
-        float* ps = part ? part + (long long)b0 * nb * nfp::kPoolSub * (g.C + N) : nullptr;
+        float* ps = part ? part + (long long)b0 * nb * nfp::kPoolSub * (g.C + NP) : nullptr;
         float* gs_ = gap ? gap + (long long)b0 * g.C : nullptr;
         float* ns_ = nfpm ? nfpm + (long long)b0 * N : nullptr;
         int rc;
@@ -168,7 +169,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   return kNotApplicable;
 }
 
-template <int R, int M, bool BF, bool NHWC, bool POOL = false>
+template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone>
 int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                       const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
@@ -222,7 +223,7 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
 #endif
       const bool cst = NHWC && G == 1 && g.C * (BF ? 2 : 4) >= NFP_TILE_CST_MINB && npu <= 640;
       snprintf(g_variant, sizeof(g_variant), "bwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), BF ? "bf16" : "f32",
-               NHWC ? "nhwc" : "nchw", cst ? ",dense" : "", POOL ? ",pool" : "", nb);
+               NHWC ? "nhwc" : "nchw", cst ? ",dense" : "", pool_tag(POOL), nb);
       const std::true_type T_;
       const std::false_type F_;
       const int es = BF ? 2 : 4, bmax = std::max(8, (tile_max_grid() / (nb * S)) & ~7);
@@ -261,7 +262,7 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
   return kNotApplicable;
 }
 
-template <int R, int M, bool POOL>
+template <int R, int M, int POOL>
 int fwd_rm(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* part, int* nb, float* gap = nullptr,
            float* nfpm = nullptr) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
@@ -270,7 +271,7 @@ int fwd_rm(const KP& g, const void* x, void* out, float* saved, hipStream_t st, 
   return nhwc ? launch_fwd_tile_t<R, M, false, true, POOL>(g, x, out, saved, st, part, nb, gap, nfpm)
               : launch_fwd_tile_t<R, M, false, false, POOL>(g, x, out, saved, st, part, nb, gap, nfpm);
 }
-template <int R, int M, bool POOL>
+template <int R, int M, int POOL>
 int bwd_rm(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
            const float* ggap, const float* gnfpm) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
@@ -282,7 +283,7 @@ int bwd_rm(const KP& g, const void* x, const void* go, const void* out, const fl
 
 }  // namespace
 
-int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, bool pool, float* part, int* nb,
+int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
                  float* gap, float* nfpm) {
   if (!tile_ok(g, x, x)) return kNotApplicable;
   const bool cosv = hot_product(g);
@@ -296,6 +297,12 @@ int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_
     if (pool || g.P < 196) return kNotApplicable;
     return g.R == 1 ? fwd_rm<1, kSymTerm, false>(g, x, out, saved, st, part, nb) : fwd_rm<2, kSymTerm, false>(g, x, out, saved, st, part, nb);
   }
+  if (pool == nfp::kPoolGap) {   // GAP(x) beside the maps: the channel sums alone
+    if (cosv) return g.R == 1 ? fwd_rm<1, NFP_COSINE, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm)
+                              : fwd_rm<2, NFP_COSINE, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm);
+    return g.R == 1 ? fwd_rm<1, NFP_NORM, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm)
+                    : fwd_rm<2, NFP_NORM, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm);
+  }
   if (pool) {
     if (cosv) return g.R == 1 ? fwd_rm<1, NFP_COSINE, true>(g, x, out, saved, st, part, nb, gap, nfpm)
                               : fwd_rm<2, NFP_COSINE, true>(g, x, out, saved, st, part, nb, gap, nfpm);
@@ -307,7 +314,7 @@ int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_
 }
 
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                  bool pool, const float* ggap, const float* gnfpm) {
+                  int pool, const float* ggap, const float* gnfpm) {
   if (!tile_ok(g, x, gx)) return kNotApplicable;
   const bool cosv = hot_product(g);
   if (hot_l1(g)) {
@@ -319,6 +326,12 @@ int tile_backward(const KP& g, const void* x, const void* go, const void* out, c
     if (pool) return kNotApplicable;
     return g.R == 1 ? bwd_rm<1, kSymTerm, false>(g, x, go, out, saved, gx, st, ggap, gnfpm)
                     : bwd_rm<2, kSymTerm, false>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+  }
+  if (pool == nfp::kPoolGap) {   // grad_out is a map; grad(GAP) joins in the store
+    if (cosv) return g.R == 1 ? bwd_rm<1, NFP_COSINE, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm)
+                              : bwd_rm<2, NFP_COSINE, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+    return g.R == 1 ? bwd_rm<1, NFP_NORM, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm)
+                    : bwd_rm<2, NFP_NORM, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm);
   }
   if (pool) {
     if (cosv) return g.R == 1 ? bwd_rm<1, NFP_COSINE, true>(g, x, go, out, saved, gx, st, ggap, gnfpm) : bwd_rm<2, NFP_COSINE, true>(g, x, go, out, saved, gx, st, ggap, gnfpm);

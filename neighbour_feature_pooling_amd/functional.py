@@ -527,6 +527,164 @@ def nfp(x, cfg):
     return nfp_host(x, cfg)
 
 
+# ---- GAP(x) beside the full maps — the first step of an NFP head (include/nfp.h: nfp_gap_*) ------------------------------
+def _gap_saved_floats(x, layout, cfg, d):
+    """nfp_gap_saved_floats of the plan's descriptor (cached with the plans)."""
+    key = ("gap_ns", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
+    ns = _plans_get(key)
+    if ns is None:
+        ns = int(_abi.load().nfp_gap_saved_floats(ctypes.byref(d)))
+        if getattr(d, "cacheable", True):
+            _plans_put(key, ns)
+    return ns
+
+
+def nfp_gap_fused_ok(x, cfg):
+    """True when one pass can yield GAP(x) and the NFP maps of this call: the set `nfp_pool_fused_ok` describes (the
+    library answers with a dry run of both launchers)."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES) or cfg.inner_R or cfg.measure == "scs":
+        return False
+    layout = _inner_layout(x)
+    if layout is None or (x.shape[0] > 1 and x.stride(0) < x.shape[1] * x.shape[2] * x.shape[3]):
+        return False
+    if layout == "nhwc" and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
+        return False          # (the channels-last kernels load 16 bytes per lane)
+    key = ("gap", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
+    ok = _plans_get(key)
+    if ok is None:
+        d = _plan(x, layout, cfg)[0]
+        ok = bool(_abi.load().nfp_gap_supported(ctypes.byref(d)))
+        if getattr(d, "cacheable", True):
+            _plans_put(key, ok)
+    return ok
+
+
+def gap_servable_static(shape, stride, dtype, cfg):
+    """The trace-time form of `nfp_gap_fused_ok` (torch.compile: no data pointer, no workspace yet): nfp_gap_supported on
+    the static shape and strides, with the workspace the descriptor is entitled to stood in for — a host-only dry run."""
+    if dtype not in _DTYPES or len(shape) != 4 or cfg.inner_R or cfg.measure == "scs":
+        return False
+    B, C, H, W = (int(v) for v in shape)
+    st = tuple(int(v) for v in stride)
+    if all(n == 1 or s == c for n, s, c in zip((C, H, W), st[1:], (H * W, W, 1))):
+        inner = (H * W, W, 1)
+    elif all(n == 1 or s == c for n, s, c in zip((C, H, W), st[1:], (1, W * C, C))):
+        inner = (1, W * C, C)
+    else:
+        return False
+    sB = st[0] if B > 1 else C * H * W
+    if sB < C * H * W or (inner[0] == 1 and (sB * (4 if dtype == torch.float32 else 2)) % 16):
+        return False
+    L = _abi.load()
+    d = _abi.NfpDesc()
+    d.B, d.C, d.H, d.W = B, C, H, W
+    d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
+    d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
+    d.measure = _abi.measure_id(cfg.measure)
+    d.similarity, d.diff_weights = int(bool(cfg.similarity)), int(bool(cfg.diff_weights))
+    d.dtype = _DTYPES[dtype]
+    d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
+    d.sxB, (d.sxC, d.sxH, d.sxW) = sB, inner
+    d.sgB = C * H * W
+    if int(L.nfp_workspace_bytes(ctypes.byref(d))) > 0:
+        d.ws = 0x1000       # (never dereferenced: the dry run launches nothing)
+    return bool(L.nfp_gap_supported(ctypes.byref(d)))
+
+
+@torch.compiler.assume_constant_result
+def _gap_servable_traced(shape, stride, dtype, cfg_fields):
+    """`gap_servable_static` as Dynamo sees it: run at trace time on the static shape, its answer a constant of the graph."""
+    from . import _ops
+    return gap_servable_static(shape, stride, dtype, _ops._cfg(*cfg_fields))
+
+
+def gap_forward_call(x, cfg, ns=None):
+    """(gap, maps, saved) from nfp_gap_forward on a call `nfp_gap_fused_ok` accepted; `saved` holds ns floats (at least
+    nfp_gap_saved_floats) and is torch-allocated (graph-capture safe)."""
+    L = _abi.load()
+    xd, layout = _dense(x)
+    d, oshape, _, _ = _plan(xd, layout, cfg)
+    need = max(_gap_saved_floats(xd, layout, cfg, d), 1)
+    ns = need if ns is None else max(int(ns), need)
+    with _on_device(x.device):
+        gap = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+        maps = torch.empty(oshape, dtype=x.dtype, device=x.device)
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_gap_forward(ctypes.byref(d), xd.data_ptr(), gap.data_ptr(), maps.data_ptr(), saved.data_ptr(),
+                                     saved.numel(), _raw_stream(x.device)))
+    return gap, maps, saved
+
+
+def gap_backward_call(x, cfg, maps, saved, grad_gap, grad_out):
+    """grad_x from nfp_gap_backward.  grad_gap None: GAP(x) took no part in the loss (ggap = NULL in the library);
+    grad_out None (only the mean was used): a zero map."""
+    L = _abi.load()
+    xd, layout = _dense(x)
+    d = _plan(xd, layout, cfg)[0]
+    gg = grad_gap.contiguous().float() if grad_gap is not None else None
+    go = torch.zeros_like(maps) if grad_out is None else grad_out.contiguous()
+    if go.dtype != x.dtype:
+        go = go.to(x.dtype)
+    with _on_device(x.device):
+        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
+                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
+        _abi.check(L.nfp_gap_backward(ctypes.byref(d), xd.data_ptr(), gg.data_ptr() if gg is not None else None,
+                                      go.data_ptr(), maps.data_ptr(), saved.data_ptr(), saved.numel(), gx.data_ptr(),
+                                      _raw_stream(x.device)))
+    return gx
+
+
+class _NfpGapHip(torch.autograd.Function):
+    """(gap [B,C] f32, maps [B,N,H,W]) in one pass over x; one backward kernel takes both gradients."""
+
+    @staticmethod
+    def forward(ctx, x, cfg):
+        gap, maps, saved = gap_forward_call(x, cfg)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)    # an unused output arrives as None, not as a zero tensor
+        ctx.save_for_backward(x, maps, saved)
+        return gap, maps
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_gap, g_maps):
+        x, maps, saved = ctx.saved_tensors
+        if g_gap is None and g_maps is None:
+            return None, None
+        return gap_backward_call(x, ctx.cfg, maps, saved, g_gap, g_maps), None
+
+
+def nfp_with_gap(x, cfg):
+    """(GAP(x) [B,C] float32, NFP(x) [B,N,H',W']) — the first step of every NFP head (models/nfp_heads.py: `gap(fmap)` and
+    `nfp(fmap)` of one feature map).  On the GPU one pass over x yields both, and one backward kernel takes the gradients
+    of both (either may be missing); where the fused kernels do not serve the call — CPU tensors, SCS, measures or
+    geometries outside `nfp_pool`'s set — the composition `(x.mean((2, 3)).float(), nfp(x, cfg))`.  The maps come out typed
+    exactly as `nfp(x, cfg)` types them."""
+    if x.dim() != 4:
+        raise RuntimeError(f"NFP expects a 4-D [B,C,H,W] feature map, got {tuple(x.shape)}")
+    xin, cast = _amp_input(x)
+    if xin is not x:
+        with torch.autocast("cuda", enabled=False):
+            gap, maps = nfp_with_gap(xin, cfg)
+        return gap, (maps if cast is None else maps.to(cast))
+    if x.is_cuda and torch.compiler.is_compiling():
+        # under torch.compile: servability is decided NOW, on the static shape (a host-only dry run); a call the fused
+        # kernels refuse is traced as the composition, so nothing can raise inside the compiled graph that eager serves
+        from . import _ops
+        if _gap_servable_traced(tuple(x.shape), tuple(x.stride()), x.dtype, _ops.cfg_args(cfg)):
+            gap, maps, _ = torch.ops.nfp_amd.nfp_gap(x, *_ops.cfg_args(cfg))
+            return gap, maps
+    elif x.is_cuda and nfp_gap_fused_ok(x, cfg):
+        try:
+            if x.requires_grad and torch.is_grad_enabled():
+                return _NfpGapHip.apply(x, cfg)
+            gap, maps, _ = gap_forward_call(x, cfg)
+            return gap, maps
+        except _abi.NfpUnsupported:
+            pass    # (nfp_gap_supported is a dry run of both launchers; should it ever disagree, the composition serves)
+    return x.mean((2, 3)).float(), nfp(x, cfg)
+
+
 # ---- NFPPooling(bias=True) — include/nfp.h, ABI 7 (csrc/nfp_bias.hip) ------------------------------------------------------
 def bias_no_centre(cfg):
     """Norm and RMSE never call center_value (nfp.py:141-148, 172-179): its bias gets no gradient (None, as in the reference)."""

@@ -205,6 +205,38 @@ class NFPNet(nn.Module):
         return self.fc(x.view(x.size(0), -1))
 
 
+class NFPHeadNet(nn.Module):
+    """A backbone under an NFP head of the kind models/nfp_heads.py::NFPHead describes: the head consumes GAP(fmap) AND the
+    full NFP maps of the same feature map — the maps through a trainable 1x1 compress conv, so gradients come back for both.
+    Its first step is NFPWithGap (one pass over fmap on the GPU); then compress (1x1 conv + BN + ReLU) and its mean, a
+    fusion MLP over cat(gap, nfp_vec), and the classifier."""
+
+    def __init__(self, backbone="resnet18", num_classes=10, num_input_channels=3, nfp_layer=None, bottleneck_dim=512, R=1,
+                 measure="cosine", **backbone_kw):
+        super().__init__()
+        from .nfp import EnhancedNFPPooling, NFPWithGap
+        self.backbone = BACKBONES[backbone](in_chans=num_input_channels, **backbone_kw)
+        C = self.backbone.num_features
+        if nfp_layer is None:
+            nfp_layer = EnhancedNFPPooling(in_channels=C, R=R, measure=measure, padding=R)
+        self.gap_nfp = NFPWithGap(nfp_layer)
+        self.compress = nn.Sequential(nn.Conv2d(self.gap_nfp.out_channels, bottleneck_dim, 1, bias=False),
+                                      nn.BatchNorm2d(bottleneck_dim), nn.ReLU(inplace=True))
+        self.fusion_mlp = nn.Sequential(nn.Linear(C + bottleneck_dim, bottleneck_dim), nn.ReLU(inplace=True),
+                                        nn.Linear(bottleneck_dim, bottleneck_dim))
+        self.fc = nn.Linear(bottleneck_dim, num_classes)
+
+    def forward(self, x):
+        feats = self.backbone.forward_features(x)
+        if feats.dim() == 3:  # ViT tokens -> grid, read in place (as NFPNet)
+            tok = feats[:, 1:]
+            H = W = int(math.isqrt(tok.shape[1]))
+            feats = tok.transpose(1, 2).unflatten(2, (H, W))
+        gap, maps = self.gap_nfp(feats)
+        nfp_vec = self.compress(maps.to(feats.dtype)).mean((2, 3))
+        return self.fc(self.fusion_mlp(torch.cat([gap.to(nfp_vec.dtype), nfp_vec], dim=1)))
+
+
 class MultiStageNFPNet(nn.Module):
     """texture_pooling.py::MobileNetV3_MultiStageNFP (211-268) with the local backbone: NFP(cosine, R = 1, padding = 1) on all
     five stage outputs (112x112x16 ... 7x7x960 at 224x224), each averaged to 8 values (249-252), the 40 values projected to

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _abi
-from .functional import NfpConfig, nfp, nfp_biased, nfp_multi_radius
+from .functional import NfpConfig, nfp, nfp_biased, nfp_multi_radius, nfp_with_gap
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -172,3 +172,30 @@ class MultiRadiusNFPPooling(nn.Module):
                                    f"got {x.shape[1]} channels instead")
             return nfp_multi_radius(x, blocks[0].config, blocks[1].config)
         return torch.cat([b(x) for b in blocks], dim=1)
+
+
+class NFPWithGap(nn.Module):
+    """(GAP(x) [B,C] float32, NFP(x) [B,N,H',W']) of one feature map — how every head of models/nfp_heads.py starts
+    (`gap(fmap)` and `nfp(fmap)`, nfp_heads.py:39-42).  Wraps any NFPPooling / EnhancedNFPPooling, which stays reachable
+    (and keeps its state-dict entries) as `.nfp`.  On the GPU both come from one pass over x and one backward kernel
+    takes the gradients of both (functional.nfp_with_gap); a bias=True layer has no fused form: its own forward, then
+    the mean."""
+
+    def __init__(self, nfp_layer):
+        super().__init__()
+        if not isinstance(nfp_layer, NFPPooling):
+            raise TypeError(f"NFPWithGap wraps an NFPPooling / EnhancedNFPPooling layer, got {type(nfp_layer).__name__}")
+        self.nfp = nfp_layer
+
+    @property
+    def out_channels(self):
+        return self.nfp.out_channels
+
+    def forward(self, x):
+        layer = self.nfp
+        if layer.bias:
+            return x.mean((2, 3)).float(), layer(x)
+        if x.dim() == 4 and x.shape[1] != layer.in_channels:
+            raise RuntimeError(f"NFPPooling expected input with {layer.in_channels} channels, "
+                               f"got {x.shape[1]} channels instead")
+        return nfp_with_gap(x, layer.config)
