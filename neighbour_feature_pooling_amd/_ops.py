@@ -17,15 +17,16 @@ import ctypes
 import torch
 
 from . import _abi
+from . import functional as F
 
 _CFG_SCHEMA = ("int R, str measure, float p, int stride, int padding, int dilation, str padding_mode, bool similarity, "
                "float eps, float q_scs, bool diff_weights, int inner_R")
 
 
 def _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
-    from .functional import NfpConfig
-    return NfpConfig(R=R, measure=measure, p=p, stride=stride, padding=padding, dilation=dilation, padding_mode=padding_mode,
-                     similarity=similarity, eps=eps, q_scs=q_scs, diff_weights=diff_weights, inner_R=inner_R)
+    return F.NfpConfig(R=R, measure=measure, p=p, stride=stride, padding=padding, dilation=dilation,
+                       padding_mode=padding_mode, similarity=similarity, eps=eps, q_scs=q_scs, diff_weights=diff_weights,
+                       inner_R=inner_R)
 
 
 def cfg_args(cfg):
@@ -40,22 +41,17 @@ def _out_hw(H, W, cfg):
     return (H + 2 * cfg.padding - span) // cfg.stride + 1, (W + 2 * cfg.padding - span) // cfg.stride + 1
 
 
+def _nchw_desc(shape, dtype, cfg):
+    """The descriptor of a dense NCHW tensor: enough for the library's sizes that follow from the shape and the measure."""
+    return ctypes.byref(F.build_desc(shape, F._canon(shape, "nchw"), dtype, cfg))
+
+
 def _saved_floats(shape, dtype, cfg, need_grad):
     """Floats of forward-to-backward state of nfp_forward for this call — a function of the shape and the measure alone
     (include/nfp.h: nfp_saved_floats), so the fake implementation can state it without a GPU."""
-    if not need_grad and not (cfg.measure == "attention" and dtype != torch.float32):
+    if not F._keeps_state(cfg, dtype, need_grad):
         return 0
-    d = _abi.NfpDesc()
-    d.B, d.C, d.H, d.W = shape
-    d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
-    d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
-    d.measure = _abi.measure_id(cfg.measure)
-    d.similarity, d.diff_weights = int(cfg.similarity), int(cfg.diff_weights)
-    d.dtype = _abi.F32 if dtype == torch.float32 else _abi.BF16
-    d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
-    d.sxB, d.sxC, d.sxH, d.sxW = shape[1] * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1
-    d.inner_R = int(cfg.inner_R)
-    return max(int(_abi.load().nfp_saved_floats(ctypes.byref(d))), 0)
+    return max(int(_abi.load().nfp_saved_floats(_nchw_desc(shape, dtype, cfg))), 0)
 
 
 def _pool_saved_bound(shape, dtype, cfg):
@@ -69,19 +65,7 @@ def _pool_saved_bound(shape, dtype, cfg):
 @torch.library.custom_op("nfp_amd::nfp", mutates_args=(), device_types="cuda", schema=f"(Tensor x, {_CFG_SCHEMA}, bool need_grad) -> (Tensor, Tensor)")
 def nfp_op(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R, need_grad):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
-    L = _abi.load()
-    xd, layout = F._dense(x)
-    d, oshape, _, no_bwd = F._plan(xd, layout, cfg)
-    if need_grad and no_bwd is not None:
-        raise _abi.NfpUnsupported(f"libnfp_hip: the forward of this call is served but its backward is not ({no_bwd})")
-    ns = _saved_floats(tuple(x.shape), x.dtype, cfg, need_grad)
-    with F._on_device(x.device):
-        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
-        saved = torch.empty(max(ns, 0), dtype=torch.float32, device=x.device)
-        _abi.check(L.nfp_forward(ctypes.byref(d), xd.data_ptr(), out.data_ptr(), saved.data_ptr() if ns > 0 else None,
-                                 F._raw_stream(x.device)))
-    return out, saved
+    return F.nfp_forward_call(x, cfg, need_grad, _saved_floats(tuple(x.shape), x.dtype, cfg, need_grad))[:2]
 
 
 @nfp_op.register_fake
@@ -98,19 +82,7 @@ def _(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps
 def nfp_backward_op(x, out, saved, grad_out, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs,
                     diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
-    L = _abi.load()
-    xd, layout = F._dense(x)
-    d = F._plan(xd, layout, cfg)[0]
-    go = grad_out.contiguous()
-    if go.dtype != x.dtype:
-        go = go.to(x.dtype)
-    with F._on_device(x.device):
-        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
-                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
-        _abi.check(L.nfp_backward(ctypes.byref(d), xd.data_ptr(), go.data_ptr(), out.data_ptr(),
-                                  saved.data_ptr() if saved.numel() else None, gx.data_ptr(), F._raw_stream(x.device)))
-    return gx
+    return F.nfp_backward_call(*F._planned(x, cfg), out, saved, grad_out)
 
 
 @nfp_backward_op.register_fake
@@ -139,7 +111,6 @@ nfp_op.register_autograd(_nfp_bwd, setup_context=_nfp_setup)
 def nfp_pool_op(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R,
                 want_gap, need_grad):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     f32 = dict(dtype=torch.float32, device=x.device)
     if not F.nfp_pool_fused_ok(x, cfg):
         # (calls the fused kernels do not serve: the two means of the maps' own op.  The state buffer has the size the fake
@@ -149,20 +120,7 @@ def nfp_pool_op(x, R, measure, p, stride, padding, dilation, padding_mode, simil
         saved[:sv.numel()] = sv
         gap = x.float().mean((2, 3)) if want_gap else torch.empty(0, x.shape[1], **f32)
         return gap, maps.float().mean((2, 3)), maps if need_grad else maps.new_empty(0), saved
-    L = _abi.load()
-    xd, layout = F._dense(x)
-    d, (B, N, Ho, Wo), _, _ = F._plan(xd, layout, cfg)
-    ns = _pool_saved_bound(tuple(x.shape), x.dtype, cfg)
-    assert F._pool_saved_floats(xd, layout, cfg, d) <= ns
-    with F._on_device(x.device):
-        gap = torch.empty(B if want_gap else 0, x.shape[1], **f32)
-        nfpm = torch.empty(B, N, **f32)
-        out_map = torch.empty((B, N, Ho, Wo) if need_grad else (0,), dtype=x.dtype, device=x.device)
-        saved = torch.empty(max(ns, 0), **f32)
-        _abi.check(L.nfp_pool_forward(ctypes.byref(d), xd.data_ptr(), gap.data_ptr() if want_gap else None, nfpm.data_ptr(),
-                                      out_map.data_ptr() if need_grad else None, saved.data_ptr() if ns > 0 else None,
-                                      F._raw_stream(x.device)))
-    return gap, nfpm, out_map, saved
+    return F.pool_forward_call(x, cfg, want_gap, need_grad, _pool_saved_bound(tuple(x.shape), x.dtype, cfg))[:4]
 
 
 @nfp_pool_op.register_fake
@@ -182,7 +140,6 @@ def _(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps
 def nfp_pool_backward_op(x, out_map, saved, grad_gap, grad_nfpm, R, measure, p, stride, padding, dilation, padding_mode,
                          similarity, eps, q_scs, diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     P = out_map.shape[2] * out_map.shape[3]
     if not F.nfp_pool_fused_ok(x, cfg):
         go = (grad_nfpm.to(out_map.dtype) / P)[:, :, None, None].expand_as(out_map).contiguous()
@@ -190,18 +147,7 @@ def nfp_pool_backward_op(x, out_map, saved, grad_gap, grad_nfpm, R, measure, p, 
         if grad_gap is not None:
             gx = gx + (grad_gap.float() / (x.shape[2] * x.shape[3]))[:, :, None, None]
         return gx.to(x.dtype)
-    L = _abi.load()
-    xd, layout = F._dense(x)
-    d = F._plan(xd, layout, cfg)[0]
-    gg = grad_gap.contiguous().float() if grad_gap is not None else None
-    gn = grad_nfpm.contiguous().float()
-    with F._on_device(x.device):
-        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
-                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
-        _abi.check(L.nfp_pool_backward(ctypes.byref(d), xd.data_ptr(), gg.data_ptr() if gg is not None else None, gn.data_ptr(),
-                                       out_map.data_ptr(), saved.data_ptr() if saved.numel() else None, gx.data_ptr(),
-                                       F._raw_stream(x.device)))
-    return gx
+    return F.pool_backward_call(*F._planned(x, cfg), out_map, saved, grad_gap, grad_nfpm)
 
 
 @nfp_pool_backward_op.register_fake
@@ -236,7 +182,6 @@ def _gap_saved_bound(shape, dtype, cfg):
                          schema=f"(Tensor x, {_CFG_SCHEMA}) -> (Tensor, Tensor, Tensor)")
 def nfp_gap_op(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     ns = _gap_saved_bound(tuple(x.shape), x.dtype, cfg)
     if not F.nfp_gap_fused_ok(x, cfg):
         # (functional.nfp_with_gap asked the library at trace time; what only the run shows — a misaligned channels-last
@@ -263,7 +208,6 @@ def _(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps
 def nfp_gap_backward_op(x, maps, saved, grad_gap, grad_maps, R, measure, p, stride, padding, dilation, padding_mode,
                         similarity, eps, q_scs, diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     if not F.nfp_gap_fused_ok(x, cfg):
         go = torch.zeros_like(maps) if grad_maps is None else grad_maps
         ns = _saved_floats(tuple(x.shape), x.dtype, cfg, True)
@@ -299,16 +243,7 @@ nfp_gap_op.register_autograd(_gap_bwd, setup_context=_gap_setup)
 # ---- nfp_biased: (x, centre_bias, neighbour_bias) -> (maps, saved) — NFPPooling(bias=True), include/nfp.h ABI 7 ------------
 def _bias_saved_floats(shape, dtype, cfg):
     """nfp_bias_saved_floats for this call — a function of the shape and the measure alone."""
-    d = _abi.NfpDesc()
-    d.B, d.C, d.H, d.W = shape
-    d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
-    d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
-    d.measure = _abi.measure_id(cfg.measure)
-    d.similarity, d.diff_weights = int(cfg.similarity), int(cfg.diff_weights)
-    d.dtype = _abi.F32 if dtype == torch.float32 else _abi.BF16
-    d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
-    d.sxB, d.sxC, d.sxH, d.sxW = shape[1] * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1
-    return max(int(_abi.load().nfp_bias_saved_floats(ctypes.byref(d))), 0)
+    return max(int(_abi.load().nfp_bias_saved_floats(_nchw_desc(shape, dtype, cfg))), 0)
 
 
 @torch.library.custom_op("nfp_amd::nfp_biased", mutates_args=(), device_types="cuda",
@@ -316,7 +251,6 @@ def _bias_saved_floats(shape, dtype, cfg):
 def nfp_biased_op(x, centre_bias, neighbour_bias, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps,
                   q_scs, diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     return F.bias_forward_call(x, centre_bias, neighbour_bias, cfg)
 
 
@@ -336,7 +270,6 @@ def _(x, centre_bias, neighbour_bias, R, measure, p, stride, padding, dilation, 
 def nfp_biased_backward_op(x, centre_bias, neighbour_bias, out, saved, grad_out, R, measure, p, stride, padding, dilation,
                            padding_mode, similarity, eps, q_scs, diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    from . import functional as F
     gx, gcb, gnb = F.bias_backward_call(x, centre_bias, neighbour_bias, out, saved, grad_out, cfg)
     if gcb is None:     # (Norm / RMSE: no centre-bias gradient; the autograd formula below returns None for it)
         gcb = torch.zeros(centre_bias.shape, dtype=torch.float32, device=x.device)

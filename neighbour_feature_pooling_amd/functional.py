@@ -81,15 +81,13 @@ def _cpp_call(fn, *args):
         raise
 
 
-def _inner_layout(x):
-    """'nchw' / 'nhwc' when every image of x is dense in that order — whatever the batch stride: the kernels take the
-    batch stride from the descriptor, so e.g. ViT patch tokens behind a class token (a [B,1+HW,C] buffer viewed as
-    [B,C,H,W], texture_pooling.py:181-188) are read in place — else None."""
-    _, C, H, W = x.shape
-    st = x.stride()
+def _layout_of(shape, strides):
+    """'nchw' / 'nhwc' when every image of a [B,C,H,W] tensor with these element strides is dense in that order —
+    whatever the batch stride — else None.  (Size-1 dimensions carry arbitrary strides in torch: they match anything.)"""
+    _, C, H, W = shape
 
     def matches(canon):
-        return all(n == 1 or s == c for n, s, c in zip((C, H, W), st[1:], canon))
+        return all(n == 1 or s == c for n, s, c in zip((C, H, W), strides[1:], canon))
 
     if matches((H * W, W, 1)):
         return "nchw"
@@ -98,40 +96,68 @@ def _inner_layout(x):
     return None
 
 
-def _canonical_strides(x, layout):
-    """Element strides handed to the library (size-1 dimensions carry arbitrary strides in torch)."""
-    B, C, H, W = x.shape
-    sB = x.stride(0) if B > 1 else C * H * W
+def _inner_layout(x):
+    """`_layout_of` a tensor: the kernels take the batch stride from the descriptor, so e.g. ViT patch tokens behind a
+    class token (a [B,1+HW,C] buffer viewed as [B,C,H,W], texture_pooling.py:181-188) are read in place."""
+    return _layout_of(x.shape, x.stride())
+
+
+def _in_place_layout(shape, strides, itemsize=0, ptr=0):
+    """The layout in which the kernels read such a tensor where it lies — images dense in NCHW or channels-last order that
+    do not overlap (batch stride >= C*H*W) — else None.  With `itemsize` (and the data pointer) also what the fused
+    channels-last kernels ask: they load 16 bytes per lane, so images start on 16-byte boundaries."""
+    layout = _layout_of(shape, strides)
+    if layout is None or (shape[0] > 1 and strides[0] < shape[1] * shape[2] * shape[3]):
+        return None
+    if layout == "nhwc" and (ptr % 16 or (strides[0] * itemsize) % 16):
+        return None
+    return layout
+
+
+def _canon(shape, layout, sB=None):
+    """Element strides handed to the library for a dense-image layout (batch stride sB; None or B = 1: dense)."""
+    B, C, H, W = shape
+    if sB is None or B == 1:
+        sB = C * H * W
     return (sB, H * W, W, 1) if layout == "nchw" else (sB, 1, W * C, C)
+
+
+def _canonical_strides(x, layout):
+    """`_canon` of a tensor (size-1 dimensions carry arbitrary strides in torch)."""
+    return _canon(x.shape, layout, x.stride(0))
 
 
 def _dense(x):
     """(x, layout): x itself when its images are dense NCHW or channels-last (read in place by strides), otherwise an
     NCHW copy."""
-    layout = _inner_layout(x)
-    if layout is None or (x.shape[0] > 1 and x.stride(0) < x.shape[1] * x.shape[2] * x.shape[3]):
-        return x.contiguous(), "nchw"
-    return x, layout
+    layout = _in_place_layout(x.shape, x.stride())
+    return (x, layout) if layout is not None else (x.contiguous(), "nchw")
 
 
-def make_desc(x, cfg, layout=None):
-    if x.dtype not in _DTYPES:
-        raise _abi.NfpUnsupported(f"NFP HIP kernels take float32 or bfloat16 feature maps, got {x.dtype}")
-    if layout is None:
-        x, layout = _dense(x)
+def build_desc(shape, strides, dtype, cfg):
+    """The NfpDesc of a call from plain values — the one place a descriptor is filled; `ws` is left unset."""
+    if dtype not in _DTYPES:
+        raise _abi.NfpUnsupported(f"NFP HIP kernels take float32 or bfloat16 feature maps, got {dtype}")
     d = _abi.NfpDesc()
-    d.B, d.C, d.H, d.W = x.shape
+    d.B, d.C, d.H, d.W = shape
     d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
     d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
     d.measure = _abi.measure_id(cfg.measure)
     d.similarity = int(bool(cfg.similarity))
     d.diff_weights = int(bool(cfg.diff_weights))
-    d.dtype = _DTYPES[x.dtype]
+    d.dtype = _DTYPES[dtype]
     d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
-    d.sxB, d.sxC, d.sxH, d.sxW = _canonical_strides(x, layout)
+    d.sxB, d.sxC, d.sxH, d.sxW = strides
     d.sgB = d.C * d.H * d.W          # grad_x is always allocated dense, in x's inner layout
     d.inner_R = int(cfg.inner_R)
     return d
+
+
+def make_desc(x, cfg, layout=None):
+    """`build_desc` of a tensor (one that is not dense inside its images: of its NCHW copy)."""
+    if layout is None:
+        x, layout = _dense(x)
+    return build_desc(x.shape, _canonical_strides(x, layout), x.dtype, cfg)
 
 
 def output_shape(d):
@@ -203,8 +229,7 @@ def _workspace(d, device):
     return rec[0].data_ptr()
 
 
-_DESC_TENSORS = {}          # id(descriptor) -> (descriptor, uint8 tensor over its bytes)
-_PLANS = OrderedDict()      # least recently used first
+_PLANS = OrderedDict()      # plan key -> _Plan, least recently used first
 _PLANS_MAX = 256
 
 
@@ -221,12 +246,38 @@ def _plans_put(key, plan):
         _PLANS.popitem(last=False)
 
 
+class _Plan:
+    """What the host side of a call needs, asked of the library once per input signature: the descriptor, a uint8 tensor
+    over the descriptor's own bytes (what the C++ nodes take and save for their backward: the tensor keeps the descriptor
+    alive, in the cache or not), the output shape, the floats of saved state and `no_bwd` — None when nfp_backward serves
+    the descriptor too, else the library's message: forward and backward envelopes differ for a few large maps, and a call
+    that will need a gradient must fail in forward(), not inside loss.backward().  `cacheable` is False for the table-less
+    plan of a geometry first seen under a graph capture: it says nothing about later calls.  Whatever else the library
+    says about the descriptor (`ask`) is kept here too, so that nothing about a plan outlives it."""
+    __slots__ = ("desc", "desc_tensor", "nhwc", "oshape", "saved_floats", "no_bwd", "cacheable", "_asked")
+
+    def __init__(self, desc, layout, cacheable=True):
+        self.desc = desc
+        self.desc_tensor = torch.frombuffer(desc, dtype=torch.uint8)
+        self.nhwc = layout == "nhwc"
+        self.oshape = output_shape(desc)
+        self.saved_floats = 0
+        self.no_bwd = None
+        self.cacheable = cacheable
+        self._asked = {}
+
+    def ask(self, fn):
+        """int(<fn>(descriptor)) of the library's descriptor-only queries (nfp_pool_saved_floats, nfp_gap_saved_floats,
+        nfp_pool_supported, nfp_gap_supported, nfp_bias_saved_floats, nfp_bias_scratch_floats), each asked once."""
+        v = self._asked.get(fn)
+        if v is None:
+            v = self._asked[fn] = int(getattr(_abi.load(), fn)(ctypes.byref(self.desc)))
+        return v
+
+
 def _plan(x, layout, cfg):
-    """(descriptor, output shape, saved floats, why-no-backward) for this input signature — cached (LRU): in eager
-    mode the host side of a call (a few ctypes round trips) otherwise costs more than the two kernels.  The last
-    entry is None when nfp_backward serves the descriptor too, else the library's message: forward and backward
-    envelopes differ for a few large maps, and a call that will need a gradient must fail in forward(), not inside
-    loss.backward()."""
+    """The _Plan of this input signature — cached (LRU): in eager mode the host side of a call (a few ctypes round trips)
+    otherwise costs more than the two kernels."""
     key = (tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
     plan = _plans_get(key)
     if _PENDING_FILLS:
@@ -235,20 +286,20 @@ def _plan(x, layout, cfg):
         L = _abi.load()
         d = make_desc(x, cfg, layout)
         d.ws = _workspace(d, x.device)
-        cacheable = d.ws is not None or not torch.cuda.is_current_stream_capturing()
-        d.cacheable = cacheable     # (a Python attribute of the ctypes object: the pooled-tail caches below ask)
+        plan = _Plan(d, layout, cacheable=d.ws is not None or not torch.cuda.is_current_stream_capturing())
         buf = ctypes.create_string_buffer(1024)
-        rc = L.nfp_plan(ctypes.byref(d), 1, buf, len(buf))
-        no_bwd = None if rc == 0 else L.nfp_last_error().decode()
-        plan = (d, output_shape(d), int(L.nfp_saved_floats(ctypes.byref(d))), no_bwd)
-        if cacheable:
+        if L.nfp_plan(ctypes.byref(d), 1, buf, len(buf)) != 0:
+            plan.no_bwd = L.nfp_last_error().decode()
+        plan.saved_floats = int(L.nfp_saved_floats(ctypes.byref(d)))
+        if plan.cacheable:
             _plans_put(key, plan)
-        _DESC_TENSORS[id(d)] = (d, torch.frombuffer(d, dtype=torch.uint8))   # (same memory; for the C++ nodes)
-        if len(_DESC_TENSORS) > 4 * _PLANS_MAX:
-            live = {id(p[0]) for p in _PLANS.values() if isinstance(p, tuple)}
-            for k in [k for k in _DESC_TENSORS if k not in live]:
-                del _DESC_TENSORS[k]
     return plan
+
+
+def _planned(x, cfg):
+    """(x as the kernels read it, its plan)."""
+    x, layout = _dense(x)
+    return x, _plan(x, layout, cfg)
 
 
 def _raw_stream(dev):
@@ -276,28 +327,67 @@ class _on_device:
             self.ctx.__exit__(*a)
 
 
+def _keeps_state(cfg, dtype, need_grad):
+    """No saved state without a gradient to follow — except bf16 Attention, which keeps its raw dots there regardless."""
+    return need_grad or (cfg.measure == "attention" and dtype != torch.float32)
+
+
+def _saved_len(plan, cfg, dtype, need_grad):
+    """Floats of saved state nfp_forward gets for this call; refuses a call whose gradient could not be served."""
+    if need_grad and plan.no_bwd is not None:
+        raise _abi.NfpUnsupported(f"libnfp_hip: the forward of this call is served but its backward is not "
+                                  f"({plan.no_bwd}); run it under torch.no_grad() or on a detached input")
+    return max(plan.saved_floats, 0) if _keeps_state(cfg, dtype, need_grad) else 0
+
+
+def _scratch_len(need, ns):
+    """The scratch length of a launch: what the library asks for, or the caller's (the compiled graph's shape-only bound)."""
+    if ns is None:
+        return need
+    assert need <= ns, f"the library needs {need} floats of saved state, the caller allots {ns}"
+    return ns
+
+
+def _empty_grad_x(x, nhwc):
+    """grad_x: dense, in x's inner layout (desc.sgB) — a batch-strided view of x does not get a gradient with gaps."""
+    return torch.empty(x.shape, dtype=x.dtype, device=x.device,
+                       memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+
+
+def _grad_out_as(grad_out, dtype):
+    go = grad_out.contiguous()
+    return go if go.dtype == dtype else go.to(dtype)
+
+
+def nfp_forward_call(x, cfg, need_grad, ns=None):
+    """(out, saved, x as launched, plan) from nfp_forward.  need_grad: x.requires_grad and grad mode on, sampled by the
+    caller (grad mode is always off inside an autograd.Function, and ctx.needs_input_grad ignores torch.no_grad())."""
+    L = _abi.load()
+    x, plan = _planned(x, cfg)
+    ns = _scratch_len(_saved_len(plan, cfg, x.dtype, need_grad), ns)
+    with _on_device(x.device):
+        out = torch.empty(plan.oshape, dtype=x.dtype, device=x.device)
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_forward(ctypes.byref(plan.desc), x.data_ptr(), out.data_ptr(),
+                                 saved.data_ptr() if ns > 0 else None, _raw_stream(x.device)))
+    return out, saved, x, plan
+
+
+def nfp_backward_call(x, plan, out, saved, grad_out):
+    """grad_x from nfp_backward; (x, plan) as `_planned` or the forward call gave them."""
+    L = _abi.load()
+    go = _grad_out_as(grad_out, x.dtype)
+    with _on_device(x.device):
+        gx = _empty_grad_x(x, plan.nhwc)
+        _abi.check(L.nfp_backward(ctypes.byref(plan.desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
+                                  saved.data_ptr() if saved.numel() else None, gx.data_ptr(), _raw_stream(x.device)))
+    return gx
+
+
 class _NfpHip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, need_grad):
-        # need_grad: x.requires_grad and grad mode on, sampled by the caller (grad mode is always off in here, and
-        # ctx.needs_input_grad ignores torch.no_grad())
-        L = _abi.load()
-        x, layout = _dense(x)
-        d, oshape, ns, no_bwd = _plan(x, layout, cfg)
-        if need_grad:
-            if no_bwd is not None:
-                raise _abi.NfpUnsupported(f"libnfp_hip: the forward of this call is served but its backward is not "
-                                          f"({no_bwd}); run it under torch.no_grad() or on a detached input")
-        elif not (cfg.measure == "attention" and x.dtype != torch.float32):
-            ns = 0      # (bf16 Attention keeps its raw dots in this scratch even without a backward)
-        with _on_device(x.device):
-            out = torch.empty(oshape, dtype=x.dtype, device=x.device)
-            saved = torch.empty(max(ns, 0), dtype=torch.float32, device=x.device)
-            stream = _raw_stream(x.device)
-            _abi.check(L.nfp_forward(ctypes.byref(d), x.data_ptr(), out.data_ptr(),
-                                     saved.data_ptr() if ns > 0 else None, stream))
-        ctx.desc = d
-        ctx.layout = layout
+        out, saved, x, ctx.plan = nfp_forward_call(x, cfg, need_grad)
         ctx.save_for_backward(x, out, saved)
         return out
 
@@ -305,43 +395,48 @@ class _NfpHip(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, out, saved = ctx.saved_tensors
-        L = _abi.load()
-        d = ctx.desc
-        go = grad_out.contiguous()
-        if go.dtype != x.dtype:
-            go = go.to(x.dtype)
-        with _on_device(x.device):
-            # dense, in x's inner layout (desc.sgB): a batch-strided view of x does not get a gradient with gaps
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device,
-                             memory_format=torch.channels_last if ctx.layout == "nhwc" else torch.contiguous_format)
-            stream = _raw_stream(x.device)
-            _abi.check(L.nfp_backward(ctypes.byref(d), x.data_ptr(), go.data_ptr(), out.data_ptr(),
-                                      saved.data_ptr() if saved.numel() else None, gx.data_ptr(), stream))
-        return gx, None, None
+        return nfp_backward_call(x, ctx.plan, out, saved, grad_out), None, None
+
+
+def pool_forward_call(x, cfg, want_gap, need_grad, ns=None):
+    """(gap [B,C], nfpm [B,N], maps, saved, x as launched, plan) from nfp_pool_forward on a call `nfp_pool_fused_ok`
+    accepted.  want_gap = False: gap comes back empty and its sums are never taken; need_grad = False: the maps themselves
+    are not stored either (include/nfp.h, ABI 6)."""
+    L = _abi.load()
+    x, plan = _planned(x, cfg)
+    B, N, Ho, Wo = plan.oshape
+    ns = _scratch_len(max(plan.ask("nfp_pool_saved_floats"), 0), ns)
+    with _on_device(x.device):
+        gap = torch.empty(B if want_gap else 0, x.shape[1], dtype=torch.float32, device=x.device)
+        nfpm = torch.empty(B, N, dtype=torch.float32, device=x.device)
+        out_map = torch.empty((B, N, Ho, Wo) if need_grad else (0,), dtype=x.dtype, device=x.device)
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_pool_forward(ctypes.byref(plan.desc), x.data_ptr(), gap.data_ptr() if want_gap else None,
+                                      nfpm.data_ptr(), out_map.data_ptr() if need_grad else None,
+                                      saved.data_ptr() if ns > 0 else None, _raw_stream(x.device)))
+    return gap, nfpm, out_map, saved, x, plan
+
+
+def pool_backward_call(x, plan, out_map, saved, grad_gap, grad_nfpm):
+    """grad_x from nfp_pool_backward; grad_gap None: GAP(x) took no part (ggap = NULL in the library)."""
+    L = _abi.load()
+    gg = grad_gap.contiguous().float() if grad_gap is not None else None
+    gn = grad_nfpm.contiguous().float()
+    with _on_device(x.device):
+        gx = _empty_grad_x(x, plan.nhwc)
+        _abi.check(L.nfp_pool_backward(ctypes.byref(plan.desc), x.data_ptr(), gg.data_ptr() if gg is not None else None,
+                                       gn.data_ptr(), out_map.data_ptr(), saved.data_ptr() if saved.numel() else None,
+                                       gx.data_ptr(), _raw_stream(x.device)))
+    return gx
 
 
 class _NfpPoolHip(torch.autograd.Function):
     """(gap [B,C], nfpm [B,N]) = fused tail of models/NFP_Pooling.py:27-31 in one pass over x.  want_gap = False: the
-    pooled NFP maps alone (texture_pooling.py:251-252, 320-321) — gap comes back empty and its sums are never taken;
-    need_grad = False: the maps themselves are not stored either (include/nfp.h, ABI 6)."""
+    pooled NFP maps alone (texture_pooling.py:251-252, 320-321)."""
 
     @staticmethod
     def forward(ctx, x, cfg, want_gap, need_grad):
-        L = _abi.load()
-        x, layout = _dense(x)
-        d, (B, N, Ho, Wo), _, _ = _plan(x, layout, cfg)
-        ns = _pool_saved_floats(x, layout, cfg, d)
-        with _on_device(x.device):
-            gap = torch.empty(B if want_gap else 0, x.shape[1], dtype=torch.float32, device=x.device)
-            nfpm = torch.empty(B, N, dtype=torch.float32, device=x.device)
-            out_map = torch.empty((B, N, Ho, Wo) if need_grad else (0,), dtype=x.dtype, device=x.device)
-            saved = torch.empty(max(ns, 0), dtype=torch.float32, device=x.device)
-            stream = _raw_stream(x.device)
-            _abi.check(L.nfp_pool_forward(ctypes.byref(d), x.data_ptr(), gap.data_ptr() if want_gap else None,
-                                          nfpm.data_ptr(), out_map.data_ptr() if need_grad else None,
-                                          saved.data_ptr() if ns > 0 else None, stream))
-        ctx.desc = d
-        ctx.layout = layout
+        gap, nfpm, out_map, saved, x, ctx.plan = pool_forward_call(x, cfg, want_gap, need_grad)
         ctx.want_gap = want_gap
         ctx.save_for_backward(x, out_map, saved)
         return gap, nfpm
@@ -350,50 +445,23 @@ class _NfpPoolHip(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_gap, g_nfpm):
         x, out_map, saved = ctx.saved_tensors
-        L = _abi.load()
-        g_gap = g_gap.contiguous().float() if ctx.want_gap else None
-        g_nfpm = g_nfpm.contiguous().float()
-        with _on_device(x.device):
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device,
-                             memory_format=torch.channels_last if ctx.layout == "nhwc" else torch.contiguous_format)
-            stream = _raw_stream(x.device)
-            _abi.check(L.nfp_pool_backward(ctypes.byref(ctx.desc), x.data_ptr(),
-                                           g_gap.data_ptr() if g_gap is not None else None, g_nfpm.data_ptr(),
-                                           out_map.data_ptr(), saved.data_ptr() if saved.numel() else None,
-                                           gx.data_ptr(), stream))
-        return gx, None, None, None
+        return pool_backward_call(x, ctx.plan, out_map, saved, g_gap if ctx.want_gap else None, g_nfpm), None, None, None
 
 
-def _pool_saved_floats(x, layout, cfg, d):
-    """nfp_pool_saved_floats of the plan's descriptor (cached with the plans)."""
-    key = ("pool_ns", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
-    ns = _plans_get(key)
-    if ns is None:
-        ns = int(_abi.load().nfp_pool_saved_floats(ctypes.byref(d)))
-        if getattr(d, "cacheable", True):   # (a table-less plan made under a graph capture says nothing about later calls)
-            _plans_put(key, ns)
-    return ns
+def _fused_ok(x, cfg, supported):
+    """True when the library's `supported` predicate (a dry run of both launchers) accepts this call as it lies in memory:
+    float32 or bfloat16, readable in place, channels-last images on 16-byte boundaries."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES):
+        return False
+    layout = _in_place_layout(x.shape, x.stride(), x.element_size(), x.data_ptr())
+    return layout is not None and bool(_plan(x, layout, cfg).ask(supported))
 
 
 def nfp_pool_fused_ok(x, cfg):
     """True when the fused GAP + pooled-NFP kernels can serve this call: "same" maps (stride 1, pad = R; above 512 pixels:
     rows of W <= 254 / 142 pixels for k = 3 / 5, any height), cosine / dot / gfc / L2 / rmse, float32 or bfloat16, images dense in NCHW
-    or channels-last order.  (The library answers: a dry run of both launchers.)"""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES):
-        return False
-    layout = _inner_layout(x)
-    if layout is None or (x.shape[0] > 1 and x.stride(0) < x.shape[1] * x.shape[2] * x.shape[3]):
-        return False
-    if layout == "nhwc" and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
-        return False          # (the channels-last kernels load 16 bytes per lane)
-    key = ("pool", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
-    ok = _plans_get(key)
-    if ok is None:
-        d = _plan(x, layout, cfg)[0]
-        ok = bool(_abi.load().nfp_pool_supported(ctypes.byref(d)))
-        if getattr(d, "cacheable", True):
-            _plans_put(key, ok)
-    return ok
+    or channels-last order."""
+    return _fused_ok(x, cfg, "nfp_pool_supported")
 
 
 _WARNED_F64 = False
@@ -447,11 +515,9 @@ def nfp_pool(x, cfg, want_gap=True):
         try:
             cpp = _cpp_nodes()
             if cpp:
-                xd, layout = _dense(x)
-                d, oshape, _, _ = _plan(xd, layout, cfg)
-                ns = _pool_saved_floats(xd, layout, cfg, d)
-                gap, nfpm = _cpp_call(cpp.nfp_pool_apply, xd, _DESC_TENSORS[id(d)][1], list(oshape), max(ns, 0),
-                                      layout == "nhwc", bool(want_gap), bool(need_grad))
+                xd, plan = _planned(x, cfg)
+                gap, nfpm = _cpp_call(cpp.nfp_pool_apply, xd, plan.desc_tensor, list(plan.oshape),
+                                      max(plan.ask("nfp_pool_saved_floats"), 0), plan.nhwc, bool(want_gap), bool(need_grad))
             else:
                 gap, nfpm = _NfpPoolHip.apply(x, cfg, bool(want_gap), bool(need_grad))
             return (gap if want_gap else None), nfpm
@@ -484,6 +550,12 @@ def nfp_multi_radius(x, cfg1, cfg2):
     return torch.cat([nfp(x, cfg1), nfp(x, cfg2)], dim=1)
 
 
+def _warn_scs():
+    import warnings
+    warnings.warn("NFP measure 'scs' (SharpenedCosine) mixes batch elements in the reference; it runs as "
+                  "PyTorch ops on the GPU, not through the HIP kernels", RuntimeWarning, stacklevel=4)
+
+
 def nfp(x, cfg):
     """[B,C,H,W] -> [B, k*k-1, H', W'] neighbour-similarity maps (NFPPooling.forward, nfp.py:132-134)."""
     if x.dim() != 4:
@@ -503,22 +575,15 @@ def nfp(x, cfg):
         # (B,N,H,W) by (B,1,N,H,W) and so averages over the BATCH (nfp.py:359-374).  Its exact behaviour
         # is reproduced with torch ops on the tensor's own device, and said out loud; every other
         # measure on a CUDA tensor is served by libnfp_hip.so or raises.
-        import warnings
-        warnings.warn("NFP measure 'scs' (SharpenedCosine) mixes batch elements in the reference; it runs as "
-                      "PyTorch ops on the GPU, not through the HIP kernels", RuntimeWarning, stacklevel=3)
+        _warn_scs()
         return nfp_host(x, cfg)
     if x.is_cuda:
         need_grad = x.requires_grad and torch.is_grad_enabled()
         cpp = _cpp_nodes()
         if cpp:
-            xd, layout = _dense(x)
-            d, oshape, ns, no_bwd = _plan(xd, layout, cfg)
-            if need_grad and no_bwd is not None:
-                raise _abi.NfpUnsupported(f"libnfp_hip: the forward of this call is served but its backward is not "
-                                          f"({no_bwd}); run it under torch.no_grad() or on a detached input")
-            if not need_grad and not (cfg.measure == "attention" and x.dtype != torch.float32):
-                ns = 0
-            return _cpp_call(cpp.nfp_apply, xd, _DESC_TENSORS[id(d)][1], list(oshape), max(ns, 0), layout == "nhwc")
+            xd, plan = _planned(x, cfg)
+            return _cpp_call(cpp.nfp_apply, xd, plan.desc_tensor, list(plan.oshape),
+                             _saved_len(plan, cfg, x.dtype, need_grad), plan.nhwc)
         return _NfpHip.apply(x, cfg, need_grad)
     if cfg.inner_R:
         import dataclasses
@@ -528,35 +593,9 @@ def nfp(x, cfg):
 
 
 # ---- GAP(x) beside the full maps — the first step of an NFP head (include/nfp.h: nfp_gap_*) ------------------------------
-def _gap_saved_floats(x, layout, cfg, d):
-    """nfp_gap_saved_floats of the plan's descriptor (cached with the plans)."""
-    key = ("gap_ns", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
-    ns = _plans_get(key)
-    if ns is None:
-        ns = int(_abi.load().nfp_gap_saved_floats(ctypes.byref(d)))
-        if getattr(d, "cacheable", True):
-            _plans_put(key, ns)
-    return ns
-
-
 def nfp_gap_fused_ok(x, cfg):
-    """True when one pass can yield GAP(x) and the NFP maps of this call: the set `nfp_pool_fused_ok` describes (the
-    library answers with a dry run of both launchers)."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES) or cfg.inner_R or cfg.measure == "scs":
-        return False
-    layout = _inner_layout(x)
-    if layout is None or (x.shape[0] > 1 and x.stride(0) < x.shape[1] * x.shape[2] * x.shape[3]):
-        return False
-    if layout == "nhwc" and (x.data_ptr() % 16 or (x.stride(0) * x.element_size()) % 16):
-        return False          # (the channels-last kernels load 16 bytes per lane)
-    key = ("gap", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
-    ok = _plans_get(key)
-    if ok is None:
-        d = _plan(x, layout, cfg)[0]
-        ok = bool(_abi.load().nfp_gap_supported(ctypes.byref(d)))
-        if getattr(d, "cacheable", True):
-            _plans_put(key, ok)
-    return ok
+    """True when one pass can yield GAP(x) and the NFP maps of this call: the set `nfp_pool_fused_ok` describes."""
+    return not (cfg.inner_R or cfg.measure == "scs") and _fused_ok(x, cfg, "nfp_gap_supported")
 
 
 def gap_servable_static(shape, stride, dtype, cfg):
@@ -564,28 +603,15 @@ def gap_servable_static(shape, stride, dtype, cfg):
     the static shape and strides, with the workspace the descriptor is entitled to stood in for — a host-only dry run."""
     if dtype not in _DTYPES or len(shape) != 4 or cfg.inner_R or cfg.measure == "scs":
         return False
-    B, C, H, W = (int(v) for v in shape)
+    shape = tuple(int(v) for v in shape)
     st = tuple(int(v) for v in stride)
-    if all(n == 1 or s == c for n, s, c in zip((C, H, W), st[1:], (H * W, W, 1))):
-        inner = (H * W, W, 1)
-    elif all(n == 1 or s == c for n, s, c in zip((C, H, W), st[1:], (1, W * C, C))):
-        inner = (1, W * C, C)
-    else:
-        return False
-    sB = st[0] if B > 1 else C * H * W
-    if sB < C * H * W or (inner[0] == 1 and (sB * (4 if dtype == torch.float32 else 2)) % 16):
+    if shape[0] == 1:
+        st = (shape[1] * shape[2] * shape[3],) + st[1:]
+    layout = _in_place_layout(shape, st, dtype.itemsize)
+    if layout is None:
         return False
     L = _abi.load()
-    d = _abi.NfpDesc()
-    d.B, d.C, d.H, d.W = B, C, H, W
-    d.R, d.pad, d.stride, d.dilation = cfg.R, cfg.padding, cfg.stride, cfg.dilation
-    d.pad_mode = _abi.PAD_MODES.index(cfg.padding_mode)
-    d.measure = _abi.measure_id(cfg.measure)
-    d.similarity, d.diff_weights = int(bool(cfg.similarity)), int(bool(cfg.diff_weights))
-    d.dtype = _DTYPES[dtype]
-    d.p, d.eps, d.q_scs = float(cfg.p), float(cfg.eps), float(cfg.q_scs)
-    d.sxB, (d.sxC, d.sxH, d.sxW) = sB, inner
-    d.sgB = C * H * W
+    d = build_desc(shape, _canon(shape, layout, st[0]), dtype, cfg)
     if int(L.nfp_workspace_bytes(ctypes.byref(d))) > 0:
         d.ws = 0x1000       # (never dereferenced: the dry run launches nothing)
     return bool(L.nfp_gap_supported(ctypes.byref(d)))
@@ -602,9 +628,9 @@ def gap_forward_call(x, cfg, ns=None):
     """(gap, maps, saved) from nfp_gap_forward on a call `nfp_gap_fused_ok` accepted; `saved` holds ns floats (at least
     nfp_gap_saved_floats) and is torch-allocated (graph-capture safe)."""
     L = _abi.load()
-    xd, layout = _dense(x)
-    d, oshape, _, _ = _plan(xd, layout, cfg)
-    need = max(_gap_saved_floats(xd, layout, cfg, d), 1)
+    xd, plan = _planned(x, cfg)
+    d, oshape = plan.desc, plan.oshape
+    need = max(plan.ask("nfp_gap_saved_floats"), 1)
     ns = need if ns is None else max(int(ns), need)
     with _on_device(x.device):
         gap = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
@@ -619,16 +645,12 @@ def gap_backward_call(x, cfg, maps, saved, grad_gap, grad_out):
     """grad_x from nfp_gap_backward.  grad_gap None: GAP(x) took no part in the loss (ggap = NULL in the library);
     grad_out None (only the mean was used): a zero map."""
     L = _abi.load()
-    xd, layout = _dense(x)
-    d = _plan(xd, layout, cfg)[0]
+    xd, plan = _planned(x, cfg)
     gg = grad_gap.contiguous().float() if grad_gap is not None else None
-    go = torch.zeros_like(maps) if grad_out is None else grad_out.contiguous()
-    if go.dtype != x.dtype:
-        go = go.to(x.dtype)
+    go = torch.zeros_like(maps) if grad_out is None else _grad_out_as(grad_out, x.dtype)
     with _on_device(x.device):
-        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
-                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
-        _abi.check(L.nfp_gap_backward(ctypes.byref(d), xd.data_ptr(), gg.data_ptr() if gg is not None else None,
+        gx = _empty_grad_x(xd, plan.nhwc)
+        _abi.check(L.nfp_gap_backward(ctypes.byref(plan.desc), xd.data_ptr(), gg.data_ptr() if gg is not None else None,
                                       go.data_ptr(), maps.data_ptr(), saved.data_ptr(), saved.numel(), gx.data_ptr(),
                                       _raw_stream(x.device)))
     return gx
@@ -692,15 +714,12 @@ def bias_no_centre(cfg):
 
 
 def _bias_plan(x, layout, cfg):
-    """(descriptor, output shape, saved floats, scratch floats) of a biased call — cached with the plans."""
+    """The _Plan of a biased call — a plan of its own, without a workspace (the biased kernels keep no tables); its sizes
+    are `ask("nfp_bias_saved_floats")` and `ask("nfp_bias_scratch_floats")`."""
     key = ("bias", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
     plan = _plans_get(key)
     if plan is None:
-        L = _abi.load()
-        d = make_desc(x, cfg, layout)
-        d.ws = None     # (the biased kernels keep no tables)
-        plan = (d, output_shape(d), int(L.nfp_bias_saved_floats(ctypes.byref(d))),
-                int(L.nfp_bias_scratch_floats(ctypes.byref(d))))
+        plan = _Plan(make_desc(x, cfg, layout), layout)
         _plans_put(key, plan)
     return plan
 
@@ -713,7 +732,8 @@ def bias_forward_call(x, centre_bias, neighbour_bias, cfg):
     """(out, saved) from nfp_bias_forward; saved is torch-allocated (graph capture safe)."""
     L = _abi.load()
     xd, layout = _dense(x)
-    d, oshape, ns, _ = _bias_plan(xd, layout, cfg)
+    plan = _bias_plan(xd, layout, cfg)
+    d, oshape, ns = plan.desc, plan.oshape, plan.ask("nfp_bias_saved_floats")
     cb, nb = _bias_f32(centre_bias), _bias_f32(neighbour_bias)
     with _on_device(x.device):
         out = torch.empty(oshape, dtype=x.dtype, device=x.device)
@@ -728,14 +748,12 @@ def bias_backward_call(x, centre_bias, neighbour_bias, out, saved, grad_out, cfg
     float32 in the biases' shapes."""
     L = _abi.load()
     xd, layout = _dense(x)
-    d, _, ns, nsc = _bias_plan(xd, layout, cfg)
+    plan = _bias_plan(xd, layout, cfg)
+    d, nsc = plan.desc, plan.ask("nfp_bias_scratch_floats")
     cb, nb = _bias_f32(centre_bias), _bias_f32(neighbour_bias)
-    go = grad_out.contiguous()
-    if go.dtype != x.dtype:
-        go = go.to(x.dtype)
+    go = _grad_out_as(grad_out, x.dtype)
     with _on_device(x.device):
-        gx = torch.empty(xd.shape, dtype=x.dtype, device=x.device,
-                         memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format)
+        gx = _empty_grad_x(xd, plan.nhwc)
         gcb = None if bias_no_centre(cfg) else torch.empty(cb.shape, dtype=torch.float32, device=x.device)
         gnb = torch.empty(nb.shape, dtype=torch.float32, device=x.device)
         scratch = torch.empty(max(nsc, 0), dtype=torch.float32, device=x.device)
@@ -777,9 +795,7 @@ def nfp_biased(x, cfg, centre_bias, neighbour_bias):
             out = nfp_biased(xin, cfg, centre_bias, neighbour_bias)
         return out if cast is None else out.to(cast)
     if x.is_cuda and cfg.measure == "scs":
-        import warnings
-        warnings.warn("NFP measure 'scs' (SharpenedCosine) mixes batch elements in the reference; it runs as "
-                      "PyTorch ops on the GPU, not through the HIP kernels", RuntimeWarning, stacklevel=3)
+        _warn_scs()
         return nfp_host(x, cfg, centre_bias, neighbour_bias)
     if x.is_cuda and torch.compiler.is_compiling():
         from . import _ops

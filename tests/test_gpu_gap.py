@@ -164,7 +164,8 @@ def test_short_saved_is_refused_without_a_launch(dev):
     L = _abi.load()
     cfg = NFPPooling(8, R=1, measure="cosine", padding=1).config
     x = torch.from_numpy(feature_map((2, 8, 24, 24), 41)).to(dev)
-    d, oshape, _, _ = F._plan(x, "nchw", cfg)
+    plan = F._plan(x, "nchw", cfg)
+    d, oshape = plan.desc, plan.oshape
     need = int(L.nfp_gap_saved_floats(ctypes.byref(d)))
     assert need > 2 * 576
     gap = torch.empty(2, 8, device=dev)

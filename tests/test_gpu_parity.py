@@ -910,8 +910,8 @@ def test_forward_and_backward_envelopes_agree(dev):
     x = torch.randn(2, 8, 6, 6, device=dev, requires_grad=True)
     m(x)                                                        # builds the plan
     key = next(k for k in functional._PLANS if k[0] == (2, 8, 6, 6))
-    d_, shape_, ns_, _ = functional._PLANS[key]
-    functional._PLANS[key] = (d_, shape_, ns_, "test: backward unserved")
+    assert functional._PLANS[key].no_bwd is None
+    functional._PLANS[key].no_bwd = "test: backward unserved"
     try:
         n0 = _launches()
         with pytest.raises(_abi.NfpUnsupported, match="backward is not"):
@@ -1145,6 +1145,98 @@ def test_cpp_autograd_nodes_equal_python_nodes(dev):
             assert torch.equal(u, v)
     with pytest.raises(_abi.NfpUnsupported, match="norm order"):
         NFPPooling(8, padding=1, measure="norm", p=float("inf"))(torch.randn(1, 8, 5, 5, device=dev))
+
+
+def test_registered_ops_called_eagerly_equal_the_cpp_nodes(dev):
+    """The third flavour: torch.ops.nfp_amd.nfp / nfp_pool called without a compile and differentiated through their
+    registered autograd.  They share one launch sequence per ABI entry point with the Python nodes (functional.*_call),
+    and give what the C++ nodes give: identical outputs and gradients, same launches — also where the op allocates its
+    shape-only scratch bound and the node the exact size, on a batch-strided view, and on a call that is not fused."""
+    from neighbour_feature_pooling_amd import NFPPooling, _ops, functional
+    from neighbour_feature_pooling_amd.functional import nfp, nfp_pool
+    assert functional._cpp_nodes(), "the C++ autograd nodes (_nfp_torch.so) are not built / do not load"
+    torch.manual_seed(7)
+
+    def feat(shape, dtype=torch.float32, nhwc=False):
+        x = (torch.rand(shape, device=dev) + 0.25).to(dtype)
+        return x.contiguous(memory_format=torch.channels_last) if nhwc else x
+
+    flavours = {"maps": (lambda x, cfg: (nfp(x, cfg),),
+                         lambda x, cfg: torch.ops.nfp_amd.nfp(x, *_ops.cfg_args(cfg), x.requires_grad)[:1]),
+                "pool": (lambda x, cfg: nfp_pool(x, cfg),
+                         lambda x, cfg: torch.ops.nfp_amd.nfp_pool(x, *_ops.cfg_args(cfg), True, x.requires_grad)[:2])}
+
+    def run(fn, x0, cfg, grad):
+        x = x0.detach().requires_grad_(grad)        # (detach keeps the strides of a view)
+        n0 = _launches()
+        with torch.set_grad_enabled(grad):
+            outs = fn(x, cfg)
+        res = [o.detach() for o in outs]
+        if grad:
+            loss = sum((i + 1.0) * (o.float() * 0.5).sum() for i, o in enumerate(outs))
+            res.append(torch.autograd.grad(loss, x)[0])
+        torch.cuda.synchronize()
+        return res, _launches() - n0
+
+    cos = dict(R=1, measure="cosine", padding=1)
+    att = dict(R=1, measure="attention", padding=1)
+    tok = torch.rand(2, 1 + 36, 8, device=dev) + 0.25
+    view = tok[:, 1:].transpose(1, 2).unflatten(2, (6, 6))         # channels-last images, batch stride 37 * 8 != C*H*W
+    assert view.stride() == (296, 1, 48, 8)
+    cases = [(feat((8, 64, 7, 7)), cos, ("maps", "pool"), True),
+             (feat((4, 192, 14, 14), torch.bfloat16, True), dict(R=2, measure="norm", p=2, padding=2), ("maps", "pool"), True),
+             (feat((2, 12, 9, 8)), dict(R=1, measure="canberra", padding=2, stride=2), ("maps", "pool"), True),   # pool: not fused
+             (feat((3, 16, 6, 6), torch.bfloat16), att, ("maps",), True),
+             (feat((2, 16, 24, 24)), cos, ("pool",), True),         # several row bands: the scratch behind the norms is in use
+             (view, cos, ("maps", "pool"), True),
+             (feat((3, 16, 6, 6), torch.bfloat16), att, ("maps",), False)]
+    for x0, ctor, kinds, grad in cases:
+        cfg = NFPPooling(x0.shape[1], **ctor).config
+        for kind in kinds:
+            node, op = flavours[kind]
+            run(node, x0, cfg, grad)                               # (a geometry's first call also fills its tables)
+            (a, na), (b, nb) = run(node, x0, cfg, grad), run(op, x0, cfg, grad)
+            assert na == nb and len(a) == len(b), (ctor, kind, na, nb)
+            for u, v in zip(a, b):
+                assert u.dtype == v.dtype and torch.equal(u, v), (ctor, kind)
+            if x0 is view:
+                assert a[-1].stride() == b[-1].stride() == (288, 1, 48, 8)     # dense channels-last: no gaps for the class token
+    x = feat((2, 16, 24, 24))
+    cfg = NFPPooling(16, **cos).config
+    saved = torch.ops.nfp_amd.nfp_pool(x, *_ops.cfg_args(cfg), True, True)[3]
+    assert saved.numel() == _ops._pool_saved_bound((2, 16, 24, 24), x.dtype, cfg) \
+        > functional._planned(x, cfg)[1].ask("nfp_pool_saved_floats") > 2 * 576
+    x = feat((3, 16, 6, 6), torch.bfloat16)
+    saved = torch.ops.nfp_amd.nfp(x, *_ops.cfg_args(NFPPooling(16, **att).config), False)[1]
+    assert saved.numel() > 0                                       # bf16 Attention keeps its raw dots without a gradient too
+
+
+@pytest.mark.parametrize("nodes", ["cpp", "python"])
+def test_backward_after_the_plan_was_evicted(nodes, dev):
+    """A node's backward needs nothing from the plan cache: the C++ node saved the descriptor's bytes (a tensor that keeps
+    them alive), the Python node holds its forward's plan."""
+    import gc
+    from neighbour_feature_pooling_amd import NFPPooling, functional
+    cpp = functional._cpp_nodes()
+    assert cpp, "the C++ autograd nodes (_nfp_torch.so) are not built / do not load"
+    m = NFPPooling(8, R=1, measure="cosine", padding=1)
+    torch.manual_seed(11)
+    x0, go = torch.randn(2, 8, 6, 6, device=dev), torch.randn(2, 8, 6, 6, device=dev)
+    grads = []
+    functional._CPP = cpp if nodes == "cpp" else False
+    try:
+        for evict in (False, True):
+            x = x0.clone().requires_grad_(True)
+            out = m(x)
+            if evict:
+                functional._PLANS.clear()
+                gc.collect()
+            out.backward(go)
+            torch.cuda.synchronize()
+            grads.append(x.grad)
+    finally:
+        functional._CPP = cpp
+    assert grads[0].abs().max().item() > 0 and torch.equal(grads[0], grads[1])
 
 
 # ---- round 3: parity hardening -------------------------------------------------------------------------------------
