@@ -184,8 +184,14 @@ int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, c
  * loss): nothing is added and nothing is read.  No atomics: several row bands per image write partial channel sums to
  * the scratch in `saved` and a second, tiny launch joins them in band order.
  * Served where nfp_gap_supported(d) != 0 — the set of nfp_pool_supported: cosine / dot / gfc / L2 / rmse on "same" maps,
- * NCHW or channels-last, f32 or bf16, inner_R = 0; the answer is a host-only dry run of both launchers.  Otherwise compose
- * nfp_forward with an ordinary mean.  Additive to ABI 7 (nfp_desc is unchanged); the length convention of the bias calls:
+ * NCHW or channels-last, f32 or bf16; the answer is a host-only dry run of both launchers.  Otherwise compose
+ * nfp_forward with an ordinary mean.
+ * inner_R = 1 (radii 1 and 2 from one pass, MultiRadiusNFPHead: R = 2, pad = 2, stride 1, dilation 1) is served too:
+ * out_map / grad_out are [B, 8 + 24, H, W] in torch.cat order, exactly as nfp_forward writes them for such a descriptor.
+ * Its set is what both parents serve: the measures above, maps of at most 512 pixels with the descriptor's workspace set,
+ * C % 4 == 0, either layout (or a batch-strided view of it), f32 or bf16 — one launch each way on the table kernels, one
+ * band per image, no second launch (Norm p = 1 / EMD, which nfp_forward fuses for two radii, stay composed here;
+ * nfp_pool_supported keeps answering 0 for inner_R = 1).  Additive to ABI 7 (nfp_desc is unchanged); the length convention of the bias calls:
  * `saved` comes with its length in floats, and a buffer shorter than nfp_gap_saved_floats(d) (min 1 float; the backward
  * reads the per-pixel part alone) returns NFP_E_INVALID and launches nothing.
  */

@@ -6,6 +6,7 @@ Drop-in for the reference's NFP hot path:
     MultiRadiusNFPPooling            <- the per-radius layers + concatenation of models/nfp_heads.py::MultiRadiusNFPHead
     nfp_op, nfp_pool, NfpConfig      functional forms (autograd ops over libnfp_hip.so)
     nfp_with_gap, NFPWithGap         <- gap(fmap) and nfp(fmap) of one feature map, the first step of models/nfp_heads.py's heads
+                                        (NFPWithGap over a MultiRadiusNFPPooling: MultiRadiusNFPHead's gap + 32 maps, one pass)
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
 from .functional import NfpConfig, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_with_gap

@@ -1012,6 +1012,9 @@ int pool_backward_rm(const KP& g, const void* x, const void* out_map, const floa
 // partial sums to the scratch behind the norms, joined in band order by pool_fold — never by the arrival counters (no
 // atomics on this path).  Backward: grad_out read as a map, ggap[b,c] / P added in the same store.
 // bf16: fwd_gram (its channel sums are a run-time option) and the matrix-core backwards serve this mode as well.
+// R = 12 (radii 1 and 2 from one pass, MultiRadiusNFPHead): the table kernels alone — the two-radius window has no
+// matrix-core and no row-band form, so bf16 runs on the vector kernels (as nfp_forward's) and maps above 512 pixels are
+// not served; one band per image (no counters on this path), so no pool_fold launch either.
 template <int R, int M>
 int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
@@ -1024,9 +1027,11 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
   gfold.N = 0;   // (rows of C floats: pool_fold joins the channel sums alone)
   if (g.ws != nullptr && fast_ok(g, x, x)) {
     int rc;
-    if (bf) {
-      rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr);
-      if (rc != kNotApplicable) return rc;
+    if constexpr (R != 12) {
+      if (bf) {
+        rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr);
+        if (rc != kNotApplicable) return rc;
+      }
     }
     int nb = 1;
     if (bf) rc = nhwc ? launch_fwd_band_t<R, M, true, true, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb)
@@ -1040,7 +1045,7 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
     }
     if (rc != kNotApplicable) return rc;
   }
-  if (!tile_ok(g, x, x)) return kNotApplicable;
+  if (R == 12 || !tile_ok(g, x, x)) return kNotApplicable;
   int nb = 0;
   if (int rc = tile_forward(g, x, out_map, saved, st, kPoolGap, part, &nb, gap, nullptr); rc != NFP_OK) return rc;
   t_pool_scratch = (long long)g.B * nb * g.C;
@@ -1055,9 +1060,11 @@ int gap_backward_rm(KP g, const void* x, const void* go, const void* out_map, co
   if (g.ws != nullptr && fast_ok(g, x, gx)) {
     int rc;
     if (bf) {
-      rc = nhwc ? launch_bwd_gemm_t<R, M, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
-                : launch_bwd_gemm_t<R, M, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
-      if (rc != kNotApplicable) return rc;
+      if constexpr (R != 12) {
+        rc = nhwc ? launch_bwd_gemm_t<R, M, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
+                  : launch_bwd_gemm_t<R, M, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
+        if (rc != kNotApplicable) return rc;
+      }
       rc = nhwc ? launch_bwd_fast_t<R, M, true, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
                 : launch_bwd_fast_t<R, M, true, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
     } else {
@@ -1066,7 +1073,21 @@ int gap_backward_rm(KP g, const void* x, const void* go, const void* out_map, co
     }
     if (rc != kNotApplicable) return rc;
   }
+  if (R == 12) return kNotApplicable;
   return tile_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr);
+}
+// the radius spec of the descriptor: 1, 2, or 12 (inner_R = 1: both)
+template <int M>
+int gap_forward_m(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
+  if (g.rs == 12) return gap_forward_rm<12, M>(g, x, out_map, saved, st, gap);
+  return g.R == 1 ? gap_forward_rm<1, M>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, M>(g, x, out_map, saved, st, gap);
+}
+template <int M>
+int gap_backward_m(const KP& g, const void* x, const void* go, const void* out_map, const float* saved, void* gx,
+                   hipStream_t st, const float* ggap) {
+  if (g.rs == 12) return gap_backward_rm<12, M>(g, x, go, out_map, saved, gx, st, ggap);
+  return g.R == 1 ? gap_backward_rm<1, M>(g, x, go, out_map, saved, gx, st, ggap)
+                  : gap_backward_rm<2, M>(g, x, go, out_map, saved, gx, st, ggap);
 }
 
 }  // namespace
@@ -1285,21 +1306,12 @@ static int gap_plan(const KP& g, bool backward) {
   void* fake = (void*)(uintptr_t)0x1000;
   const float* cf = (const float*)fake;
   int rc;
-  if (!backward) {
-    if (hot_product(g))
-      rc = g.R == 1 ? gap_forward_rm<1, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
-                    : gap_forward_rm<2, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
-    else
-      rc = g.R == 1 ? gap_forward_rm<1, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
-                    : gap_forward_rm<2, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
-  } else {
-    if (hot_product(g))
-      rc = g.R == 1 ? gap_backward_rm<1, NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf)
-                    : gap_backward_rm<2, NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf);
-    else
-      rc = g.R == 1 ? gap_backward_rm<1, NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf)
-                    : gap_backward_rm<2, NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf);
-  }
+  if (!backward)
+    rc = hot_product(g) ? gap_forward_m<NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
+                        : gap_forward_m<NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
+  else
+    rc = hot_product(g) ? gap_backward_m<NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf)
+                        : gap_backward_m<NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf);
   t_dry = was_dry;
   memcpy(g_variant, keep_variant, sizeof(keep_variant));
   memcpy(t_plan, keep_plan, sizeof(keep_plan));
@@ -1307,10 +1319,13 @@ static int gap_plan(const KP& g, bool backward) {
   return rc;
 }
 
+// The gap calls also take radii (1, 2) together (inner_R = 1: make_kp); Norm p = 1 / EMD are outside hot_measure.
+static bool gap_measure_ok(const KP& g) { return hot_measure(g); }
+
 int nfp_gap_supported(const nfp_desc* d) {
   KP g;
   if (make_kp(d, &g)) return 0;
-  if (!pool_measure_ok(g)) return 0;
+  if (!gap_measure_ok(g)) return 0;
   if (g.B == 0) return 1;
   return gap_plan(g, false) == NFP_OK && gap_plan(g, true) == NFP_OK ? 1 : 0;
 }
@@ -1318,7 +1333,7 @@ int nfp_gap_supported(const nfp_desc* d) {
 int64_t nfp_gap_saved_floats(const nfp_desc* d) {
   KP g;
   if (make_kp(d, &g)) return -1;
-  if (!pool_measure_ok(g) || g.B == 0) return 0;
+  if (!gap_measure_ok(g) || g.B == 0) return 0;
   if (gap_plan(g, false) != NFP_OK) return 0;
   return (int64_t)stats_of(g.measure) * g.B * g.P + t_pool_scratch;
 }
@@ -1327,7 +1342,7 @@ int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map,
                     void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (!gap_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse");
   if (g.B == 0) return NFP_OK;
   if (!x || !gap || !out_map) return fail(NFP_E_INVALID, "null tensor pointer");
   const int64_t need = std::max<int64_t>(nfp_gap_saved_floats(d), 1);
@@ -1336,10 +1351,8 @@ int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map,
                 (long long)need);
   hipStream_t st = (hipStream_t)hip_stream;
   int rc;
-  if (hot_product(g))
-    rc = g.R == 1 ? gap_forward_rm<1, NFP_COSINE>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, NFP_COSINE>(g, x, out_map, saved, st, gap);
-  else
-    rc = g.R == 1 ? gap_forward_rm<1, NFP_NORM>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, NFP_NORM>(g, x, out_map, saved, st, gap);
+  rc = hot_product(g) ? gap_forward_m<NFP_COSINE>(g, x, out_map, saved, st, gap)
+                      : gap_forward_m<NFP_NORM>(g, x, out_map, saved, st, gap);
   return finish(rc, "nfp_gap_forward");
 }
 
@@ -1347,7 +1360,7 @@ int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, co
                      const float* saved, int64_t saved_floats, void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (!gap_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse");
   if (g.B == 0) return NFP_OK;
   if (!x || !grad_out || !out_map || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
   const int64_t need = (int64_t)stats_of(g.measure) * g.B * g.P;   // (the backward reads the per-pixel state alone)
@@ -1355,12 +1368,8 @@ int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, co
     return fail(NFP_E_INVALID, "saved holds %lld floats, the backward reads %lld", (long long)(saved ? saved_floats : 0), (long long)need);
   hipStream_t st = (hipStream_t)hip_stream;
   int rc;
-  if (hot_product(g))
-    rc = g.R == 1 ? gap_backward_rm<1, NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
-                  : gap_backward_rm<2, NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
-  else
-    rc = g.R == 1 ? gap_backward_rm<1, NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
-                  : gap_backward_rm<2, NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
+  rc = hot_product(g) ? gap_backward_m<NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
+                      : gap_backward_m<NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
   return finish(rc, "nfp_gap_backward");
 }
 

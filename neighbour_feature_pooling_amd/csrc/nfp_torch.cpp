@@ -1,9 +1,9 @@
 // nfp_torch.cpp — C++ autograd nodes over the C ABI of libnfp_hip.so (include/nfp.h).
 //
 // The reference's NFP is a chain of ATen ops whose autograd graph PyTorch builds (nfp.py:132-159); here one
-// forward and one backward kernel stand for it, and these two torch::autograd::Function classes are the graph
+// forward and one backward kernel stand for it, and these three torch::autograd::Function classes are the graph
 // nodes.  They do what functional.py's Python autograd.Functions do — allocate out / saved / grad_x, take torch's
-// current stream, call nfp_forward / nfp_backward (nfp_pool_forward / nfp_pool_backward) — without the Python
+// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_*) — without the Python
 // interpreter on the launch path: eager host cost per forward + backward drops from ~75 us to the autograd
 // engine's own (scripts/host_overhead.py).  No device code in this file; plain pointers go across the ABI.
 //
@@ -101,6 +101,40 @@ struct NfpPoolNode : torch::autograd::Function<NfpPoolNode> {
   }
 };
 
+// GAP(x) beside the full maps (nfp_gap_forward / nfp_gap_backward): one radius, or radii (1, 2) together (desc.inner_R).
+// An output that took no part in the loss arrives undefined (set_materialize_grads(false)): gap undefined -> grad_gap =
+// NULL, maps undefined -> a zero map, both undefined -> no launch.
+struct NfpGapNode : torch::autograd::Function<NfpGapNode> {
+  static variable_list forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+    c10::DeviceGuard guard(x.device());
+    const nfp_desc* d = desc_of(desc);
+    const auto f32 = x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous);
+    Tensor gap = torch::empty({x.size(0), x.size(1)}, f32);
+    Tensor maps = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
+    Tensor saved = torch::empty({ns > 0 ? ns : 1}, f32);
+    check(nfp_gap_forward(d, x.data_ptr(), gap.data_ptr<float>(), maps.data_ptr(), saved.data_ptr<float>(), saved.numel(),
+                          stream_of(x)));
+    ctx->set_materialize_grads(false);
+    ctx->save_for_backward({x, maps, saved, desc});
+    ctx->saved_data["nhwc"] = nhwc;
+    return {gap, maps};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    if (!grads[0].defined() && !grads[1].defined()) return {Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    const auto sv = ctx->get_saved_variables();
+    const Tensor &x = sv[0], &maps = sv[1], &saved = sv[2], &desc = sv[3];
+    c10::DeviceGuard guard(x.device());
+    const bool has_gap = grads[0].defined();
+    Tensor ggap = has_gap ? grads[0].contiguous().to(torch::kFloat32) : Tensor();
+    Tensor go = grads[1].defined() ? grads[1].contiguous() : torch::zeros_like(maps);
+    if (go.scalar_type() != x.scalar_type()) go = go.to(x.scalar_type());
+    Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
+    check(nfp_gap_backward(desc_of(desc), x.data_ptr(), has_gap ? ggap.data_ptr<float>() : nullptr, go.data_ptr(),
+                           maps.data_ptr(), saved.data_ptr<float>(), saved.numel(), gx.data_ptr(), stream_of(x)));
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 Tensor nfp_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return NfpNode::apply(x, desc, oshape, ns, nhwc);
 }
@@ -109,10 +143,15 @@ std::vector<Tensor> nfp_pool_apply(Tensor x, Tensor desc, std::vector<int64_t> o
   return NfpPoolNode::apply(x, desc, oshape, ns, nhwc, want_gap, need_grad);
 }
 
+std::vector<Tensor> nfp_gap_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+  return NfpGapNode::apply(x, desc, oshape, ns, nhwc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nfp_apply", &nfp_apply, "NFPPooling.forward as one autograd node (nfp_forward / nfp_backward)");
   m.def("nfp_pool_apply", &nfp_pool_apply, "the fused nfp_pooling tail as one autograd node (nfp_pool_forward / _backward)");
+  m.def("nfp_gap_apply", &nfp_gap_apply, "GAP(x) beside the full maps as one autograd node (nfp_gap_forward / _backward)");
   m.attr("desc_bytes") = (int64_t)sizeof(nfp_desc);
 }

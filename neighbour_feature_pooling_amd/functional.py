@@ -47,7 +47,7 @@ _CPP = None     # the C++ autograd nodes (csrc/nfp_torch.cpp), None until looked
 
 
 def _cpp_nodes():
-    """neighbour_feature_pooling_amd/_nfp_torch.so — the same two autograd nodes as the Python classes below, in C++
+    """neighbour_feature_pooling_amd/_nfp_torch.so — the same autograd nodes as the Python classes below, in C++
     (no interpreter on the launch path).  Optional: NFP_PY_NODES=1 or a missing module selects the Python nodes."""
     global _CPP
     if _CPP is None:
@@ -533,18 +533,26 @@ def nfp_pooled(x, cfg):
     return nfp_pool(x, cfg, want_gap=False)[1]
 
 
+def multi_radius_config(cfg1, cfg2):
+    """The one configuration (R = 2, inner_R = 1) that stands for two which differ only in R / padding (radii 1 and 2,
+    padding = R) and whose measure the two-radius kernels serve — else None."""
+    import dataclasses
+    if (cfg1.R == 1 and cfg2.R == 2 and cfg1.padding == 1 and cfg2.padding == 2
+            and dataclasses.replace(cfg1, R=2, padding=2) == cfg2 and cfg2.inner_R == 0
+            and cfg2.measure in ("cosine", "norm", "dot", "gfc", "rmse", "emd")):   # (norm: p = 1 or 2; else refused by the library)
+        return dataclasses.replace(cfg2, inner_R=1)
+    return None
+
+
 def nfp_multi_radius(x, cfg1, cfg2):
     """torch.cat([NFP_R1(x), NFP_R2(x)], dim=1) for two configurations that differ only in R / padding (radii 1 and 2,
     padding = R): what MultiRadiusNFPHead.forward computes with two layers (models/nfp_heads.py:109-110).  On the GPU
     both radii come from ONE pass over x (and one backward pass) where the hot-path kernels serve the map; otherwise
     the two maps are computed one after the other."""
-    import dataclasses
-    fusable = (x.is_cuda and x.dim() == 4 and cfg1.R == 1 and cfg2.R == 2 and cfg1.padding == 1 and cfg2.padding == 2
-               and dataclasses.replace(cfg1, R=2, padding=2) == cfg2 and cfg2.inner_R == 0
-               and cfg2.measure in ("cosine", "norm", "dot", "gfc", "rmse", "emd"))   # (norm: p = 1 or 2; else refused below)
-    if fusable:
+    cfg = multi_radius_config(cfg1, cfg2) if x.is_cuda and x.dim() == 4 else None
+    if cfg is not None:
         try:
-            return nfp(x, dataclasses.replace(cfg2, inner_R=1))
+            return nfp(x, cfg)
         except _abi.NfpUnsupported:
             pass
     return torch.cat([nfp(x, cfg1), nfp(x, cfg2)], dim=1)
@@ -594,14 +602,15 @@ def nfp(x, cfg):
 
 # ---- GAP(x) beside the full maps — the first step of an NFP head (include/nfp.h: nfp_gap_*) ------------------------------
 def nfp_gap_fused_ok(x, cfg):
-    """True when one pass can yield GAP(x) and the NFP maps of this call: the set `nfp_pool_fused_ok` describes."""
-    return not (cfg.inner_R or cfg.measure == "scs") and _fused_ok(x, cfg, "nfp_gap_supported")
+    """True when one pass can yield GAP(x) and the NFP maps of this call: the set `nfp_pool_fused_ok` describes and, for
+    radii (1, 2) together (cfg.inner_R = 1), its maps of at most 512 pixels with C % 4 == 0 — the library's answer."""
+    return cfg.measure != "scs" and _fused_ok(x, cfg, "nfp_gap_supported")
 
 
 def gap_servable_static(shape, stride, dtype, cfg):
     """The trace-time form of `nfp_gap_fused_ok` (torch.compile: no data pointer, no workspace yet): nfp_gap_supported on
     the static shape and strides, with the workspace the descriptor is entitled to stood in for — a host-only dry run."""
-    if dtype not in _DTYPES or len(shape) != 4 or cfg.inner_R or cfg.measure == "scs":
+    if dtype not in _DTYPES or len(shape) != 4 or cfg.measure == "scs":
         return False
     shape = tuple(int(v) for v in shape)
     st = tuple(int(v) for v in stride)
@@ -622,6 +631,15 @@ def _gap_servable_traced(shape, stride, dtype, cfg_fields):
     """`gap_servable_static` as Dynamo sees it: run at trace time on the static shape, its answer a constant of the graph."""
     from . import _ops
     return gap_servable_static(shape, stride, dtype, _ops._cfg(*cfg_fields))
+
+
+def gap_servable(x, cfg):
+    """Will `nfp_with_gap` run this CUDA call on the fused kernels?  `nfp_gap_fused_ok`, or under torch.compile its trace-time
+    form.  For callers whose composition is not `nfp(x, cfg)` itself (NFPWithGap over two radii: the layer's own forward)."""
+    if torch.compiler.is_compiling():
+        from . import _ops
+        return _gap_servable_traced(tuple(x.shape), tuple(x.stride()), x.dtype, _ops.cfg_args(cfg))
+    return x.dim() == 4 and nfp_gap_fused_ok(x, cfg)
 
 
 def gap_forward_call(x, cfg, ns=None):
@@ -678,7 +696,8 @@ class _NfpGapHip(torch.autograd.Function):
 
 def nfp_with_gap(x, cfg):
     """(GAP(x) [B,C] float32, NFP(x) [B,N,H',W']) — the first step of every NFP head (models/nfp_heads.py: `gap(fmap)` and
-    `nfp(fmap)` of one feature map).  On the GPU one pass over x yields both, and one backward kernel takes the gradients
+    `nfp(fmap)` of one feature map; with cfg.inner_R = 1 the 8 + 24 maps of radii 1 and 2, MultiRadiusNFPHead's
+    concatenation).  On the GPU one pass over x yields both, and one backward kernel takes the gradients
     of both (either may be missing); where the fused kernels do not serve the call — CPU tensors, SCS, measures or
     geometries outside `nfp_pool`'s set — the composition `(x.mean((2, 3)).float(), nfp(x, cfg))`.  The maps come out typed
     exactly as `nfp(x, cfg)` types them."""
@@ -699,6 +718,13 @@ def nfp_with_gap(x, cfg):
     elif x.is_cuda and nfp_gap_fused_ok(x, cfg):
         try:
             if x.requires_grad and torch.is_grad_enabled():
+                # the C++ node where the module has it (an older _nfp_torch.so: the Python node below)
+                apply = getattr(_cpp_nodes() or None, "nfp_gap_apply", None)
+                if apply is not None:
+                    xd, plan = _planned(x, cfg)
+                    gap, maps = _cpp_call(apply, xd, plan.desc_tensor, list(plan.oshape),
+                                          max(plan.ask("nfp_gap_saved_floats"), 1), plan.nhwc)
+                    return gap, maps
                 return _NfpGapHip.apply(x, cfg)
             gap, maps, _ = gap_forward_call(x, cfg)
             return gap, maps

@@ -209,21 +209,38 @@ class NFPHeadNet(nn.Module):
     """A backbone under an NFP head of the kind models/nfp_heads.py::NFPHead describes: the head consumes GAP(fmap) AND the
     full NFP maps of the same feature map — the maps through a trainable 1x1 compress conv, so gradients come back for both.
     Its first step is NFPWithGap (one pass over fmap on the GPU); then compress (1x1 conv + BN + ReLU) and its mean, a
-    fusion MLP over cat(gap, nfp_vec), and the classifier."""
+    fusion MLP over cat(gap, nfp_vec), and the classifier.
+    R_list (a tuple of radii): the maps of MultiRadiusNFPHead (nfp_heads.py:80-118) — one NFP layer per radius on the same
+    feature map, concatenated; radii (1, 2) come from the same single pass.  fusion="gate": that head's SE gate instead of
+    the MLP — fused = gap + alpha * nfp_vec with alpha = sigmoid(MLP(cat(gap, nfp_vec))), one scalar per image
+    (nfp_heads.py:103-117); the sum needs bottleneck_dim == the backbone's channel count."""
 
     def __init__(self, backbone="resnet18", num_classes=10, num_input_channels=3, nfp_layer=None, bottleneck_dim=512, R=1,
-                 measure="cosine", **backbone_kw):
+                 measure="cosine", R_list=None, fusion="mlp", **backbone_kw):
         super().__init__()
-        from .nfp import EnhancedNFPPooling, NFPWithGap
+        from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPWithGap
+        if fusion not in ("mlp", "gate"):
+            raise ValueError(f"fusion must be 'mlp' or 'gate', got {fusion!r}")
         self.backbone = BACKBONES[backbone](in_chans=num_input_channels, **backbone_kw)
         C = self.backbone.num_features
+        if fusion == "gate" and bottleneck_dim != C:
+            raise ValueError(f"fusion='gate' adds the compressed NFP vector to GAP(fmap): bottleneck_dim ({bottleneck_dim}) "
+                             f"must equal the backbone's {C} channels")
         if nfp_layer is None:
-            nfp_layer = EnhancedNFPPooling(in_channels=C, R=R, measure=measure, padding=R)
+            if R_list is not None:
+                nfp_layer = MultiRadiusNFPPooling(C, R_list=tuple(R_list), measure=measure)
+            else:
+                nfp_layer = EnhancedNFPPooling(in_channels=C, R=R, measure=measure, padding=R)
+        self.fusion = fusion
         self.gap_nfp = NFPWithGap(nfp_layer)
         self.compress = nn.Sequential(nn.Conv2d(self.gap_nfp.out_channels, bottleneck_dim, 1, bias=False),
                                       nn.BatchNorm2d(bottleneck_dim), nn.ReLU(inplace=True))
-        self.fusion_mlp = nn.Sequential(nn.Linear(C + bottleneck_dim, bottleneck_dim), nn.ReLU(inplace=True),
-                                        nn.Linear(bottleneck_dim, bottleneck_dim))
+        if fusion == "gate":
+            self.se_gate = nn.Sequential(nn.Linear(C + bottleneck_dim, (C + bottleneck_dim) // 2), nn.ReLU(inplace=True),
+                                         nn.Linear((C + bottleneck_dim) // 2, 1), nn.Sigmoid())
+        else:
+            self.fusion_mlp = nn.Sequential(nn.Linear(C + bottleneck_dim, bottleneck_dim), nn.ReLU(inplace=True),
+                                            nn.Linear(bottleneck_dim, bottleneck_dim))
         self.fc = nn.Linear(bottleneck_dim, num_classes)
 
     def forward(self, x):
@@ -234,7 +251,10 @@ class NFPHeadNet(nn.Module):
             feats = tok.transpose(1, 2).unflatten(2, (H, W))
         gap, maps = self.gap_nfp(feats)
         nfp_vec = self.compress(maps.to(feats.dtype)).mean((2, 3))
-        return self.fc(self.fusion_mlp(torch.cat([gap.to(nfp_vec.dtype), nfp_vec], dim=1)))
+        gap = gap.to(nfp_vec.dtype)
+        if self.fusion == "gate":
+            return self.fc(gap + self.se_gate(torch.cat([gap, nfp_vec], dim=1)) * nfp_vec)
+        return self.fc(self.fusion_mlp(torch.cat([gap, nfp_vec], dim=1)))
 
 
 class MultiStageNFPNet(nn.Module):

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _abi
-from .functional import NfpConfig, nfp, nfp_biased, nfp_multi_radius, nfp_with_gap
+from .functional import NfpConfig, gap_servable, multi_radius_config, nfp, nfp_biased, nfp_multi_radius, nfp_with_gap
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -176,23 +176,42 @@ class MultiRadiusNFPPooling(nn.Module):
 
 class NFPWithGap(nn.Module):
     """(GAP(x) [B,C] float32, NFP(x) [B,N,H',W']) of one feature map — how every head of models/nfp_heads.py starts
-    (`gap(fmap)` and `nfp(fmap)`, nfp_heads.py:39-42).  Wraps any NFPPooling / EnhancedNFPPooling, which stays reachable
-    (and keeps its state-dict entries) as `.nfp`.  On the GPU both come from one pass over x and one backward kernel
-    takes the gradients of both (functional.nfp_with_gap); a bias=True layer has no fused form: its own forward, then
-    the mean."""
+    (`gap(fmap)` and `nfp(fmap)`, nfp_heads.py:39-42).  Wraps any NFPPooling / EnhancedNFPPooling, or a
+    MultiRadiusNFPPooling (MultiRadiusNFPHead, nfp_heads.py:80-118: the 8 + 24 maps of radii 1 and 2), which stays
+    reachable (and keeps its state-dict entries) as `.nfp`.  On the GPU both come from one pass over x and one backward
+    kernel takes the gradients of both (functional.nfp_with_gap); a bias=True layer, and a multi-radius layer other than
+    two unbiased blocks that `nfp_multi_radius` would fuse, has no fused form: its own forward, then the mean."""
 
     def __init__(self, nfp_layer):
         super().__init__()
-        if not isinstance(nfp_layer, NFPPooling):
-            raise TypeError(f"NFPWithGap wraps an NFPPooling / EnhancedNFPPooling layer, got {type(nfp_layer).__name__}")
+        if not isinstance(nfp_layer, (NFPPooling, MultiRadiusNFPPooling)):
+            raise TypeError("NFPWithGap wraps an NFPPooling / EnhancedNFPPooling / MultiRadiusNFPPooling layer, "
+                            f"got {type(nfp_layer).__name__}")
         self.nfp = nfp_layer
 
     @property
     def out_channels(self):
         return self.nfp.out_channels
 
+    def _fused_pair_config(self):
+        """The inner_R = 1 configuration of a MultiRadiusNFPPooling whose two blocks `nfp_multi_radius` would fuse, else None."""
+        blocks = list(self.nfp.nfp_blocks)
+        if len(blocks) != 2 or not all(isinstance(b, NFPPooling) and not b.bias for b in blocks):
+            return None
+        return multi_radius_config(blocks[0].config, blocks[1].config)
+
     def forward(self, x):
         layer = self.nfp
+        if isinstance(layer, MultiRadiusNFPPooling):
+            cfg = self._fused_pair_config()
+            if cfg is not None and x.dim() == 4 and x.shape[1] != layer.in_channels:
+                raise RuntimeError(f"MultiRadiusNFPPooling expected input with {layer.in_channels} channels, "
+                                   f"got {x.shape[1]} channels instead")
+            # (a CUDA call the gap kernels refuse — a map above 512 pixels, Norm p = 1 — is the layer's own forward, which
+            # knows its own fallbacks, not nfp(x, cfg) with both radii in one descriptor)
+            if cfg is not None and (not x.is_cuda or gap_servable(x, cfg)):
+                return nfp_with_gap(x, cfg)
+            return x.mean((2, 3)).float(), layer(x)
         if layer.bias:
             return x.mean((2, 3)).float(), layer(x)
         if x.dim() == 4 and x.shape[1] != layer.in_channels:

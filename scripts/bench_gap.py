@@ -5,9 +5,10 @@ One JSON line per shape, two figures each way (microseconds):
   eager   median of per-step device-event times over --iters steps after --warmup (host launch gaps included)
   graph   the step captured into a CUDA graph, replayed --replays times between two events, per replay (kernels alone)
 
-    python scripts/bench_gap.py [--iters 20 --warmup 5 --replays 50] [--shapes 0,1,2,3]
+    python scripts/bench_gap.py [--iters 20 --warmup 5 --replays 50] [--shapes 0,1,2,3,4,5,6]   (rows 4-6: radii (1, 2) together)
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -21,6 +22,11 @@ SHAPES = [  # (B, C, H, W), NFPPooling kwargs, dtype, channels-last
     ((256, 512, 7, 7), dict(R=1, measure="cosine", padding=1), torch.float32, True),
     ((256, 192, 14, 14), dict(R=2, measure="norm", p=2, padding=2), torch.bfloat16, True),
     ((256, 24, 56, 56), dict(R=1, measure="cosine", padding=1), torch.float32, False),
+    # radii (1, 2) from one pass (MultiRadiusNFPHead; kwargs of the R = 2 layer, run with inner_R = 1): `composed` is
+    # x.mean + the fused two-radius nfp_op — the best there was before, not two separate layers
+    ((64, 512, 7, 7), dict(R=2, measure="cosine", padding=2), torch.float32, False, 1),
+    ((256, 512, 7, 7), dict(R=2, measure="cosine", padding=2), torch.float32, True, 1),
+    ((256, 192, 14, 14), dict(R=2, measure="norm", p=2, padding=2), torch.bfloat16, True, 1),
 ]
 
 
@@ -67,20 +73,21 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--replays", type=int, default=50)
-    ap.add_argument("--shapes", default="0,1,2,3")
+    ap.add_argument("--shapes", default="0,1,2,3,4,5,6")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_gap.py measures on the GPU; there is no CPU timing"
     from neighbour_feature_pooling_amd import NFPPooling, _abi, nfp_op, nfp_with_gap
     dev = torch.device("cuda:0")
     L = _abi.load()
     for i in (int(s) for s in a.shapes.split(",")):
-        shape, kw, dtype, cl = SHAPES[i]
+        shape, kw, dtype, cl = SHAPES[i][:4]
+        inner_R = SHAPES[i][4] if len(SHAPES[i]) > 4 else 0
         torch.manual_seed(0)
         x = torch.randn(shape, device=dev).to(dtype)
         if cl:
             x = x.contiguous(memory_format=torch.channels_last)
         x.requires_grad_(True)
-        cfg = NFPPooling(shape[1], **kw).config
+        cfg = dataclasses.replace(NFPPooling(shape[1], **kw).config, inner_R=inner_R)
         gg = torch.randn(shape[:2], device=dev)
         go = torch.randn(nfp_op(x.detach(), cfg).shape, device=dev).to(dtype)
 
@@ -95,6 +102,8 @@ def main():
             torch.autograd.backward([gap, maps], [gg, go])
 
         row = dict(shape=list(shape), kw=kw, dtype=str(dtype).split(".")[-1], channels_last=cl)
+        if inner_R:
+            row["radii"] = [inner_R, kw["R"]]
         for name, fn in (("fused", fused), ("composed", composed)):
             row[name + "_eager_us"] = round(eager_us(fn, a.iters, a.warmup), 2)
             n0 = L.nfp_launch_count()
