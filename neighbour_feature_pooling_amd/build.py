@@ -14,8 +14,14 @@ SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip"]   # three translation 
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)
+# -amdgpu-kernarg-preload-count=14: the leading pointer / 32-bit arguments of a kernel arrive in SGPRs at wavefront start
+# instead of being fetched from the argument block — fwd_band (9 dwords) and bwd_fast (14, all the user SGPRs there are
+# beside the block's address) take what stands in front of their first memory request that way (csrc/nfp_common.h: the
+# HEAD).  LLVM preloads arguments in order and stops at the first by-value struct: every kernel whose first argument is
+# still `KP` keeps .amdhsa_user_sgpr_kernarg_preload_length 0 and compiles as before (pool_fold and bias_reduce, whose
+# arguments are all pointers and scalars, get theirs preloaded as well).
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize",
-               "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
+               "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 
 def _newest_source_mtime():

@@ -65,34 +65,40 @@ struct FoffQ {
 // instructions of the general form sit on the critical path of a 5 us kernel (4.97 vs 4.87 us at the headline shape).
 // POOL = kPoolGap: the channel sums alone beside the maps — no map staging, no map sums; scratch rows of C floats.
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool VAR = false>
-__global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restrict__ x, void* __restrict__ out,
-                                                 float* __restrict__ saved, const unsigned char* __restrict__ ws,
-                                                 int rb, float* __restrict__ gap, float* __restrict__ nfpm,
-                                                 float* __restrict__ part) {
+__global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, const unsigned char* __restrict__ ws,
+                                                 uint32_t sB_lo, uint32_t sB_hi, int C, uint32_t hchunk, uint32_t hgeom,
+                                                 void* __restrict__ out, float* __restrict__ saved,
+                                                 float* __restrict__ gap, float* __restrict__ nfpm,
+                                                 float* __restrict__ part, const KP g) {
+  NFP_STAMP_ENTRY();
+  // The HEAD (nfp_common.h: band_head_*): nine dwords the hardware hands over in SGPRs at wavefront start.  Everything in
+  // front of the first x request reads the head alone; the fields of `g` are fetched while that request is in flight.
+  const int H = (int)(hgeom & 1023u), W = (int)((hgeom >> 10) & 1023u), rb = (int)(hgeom >> 20);
+  const int Cc = (int)(hchunk & 0xFFFFFu), lg = (int)((hchunk >> 20) & 7u), RR = (int)((hchunk >> 23) & 3u), G = 1 << lg;
+  const int T = (int)(hchunk >> 25) << 6;   // (= blockDim.x, which would be a load from the argument block)
+  const int kmode = g.mode;                 // (asked for here, first used behind the x request)
+  const long long sB = (long long)(((unsigned long long)sB_hi << 32) | sB_lo);
   constexpr int N = Win<R>::N, NF = Win<R>::NF;
   constexpr int ES = BF ? 2 : 4;
   constexpr bool MAPSUM = POOL == kPoolBoth;   // the N pooled map sums (and their staging)
   constexpr int NP = MAPSUM ? N : 0;            // map sums behind the channel sums of a scratch row
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   float4* slab = lds4;
-  const int P = g.P, W = g.W;
-  const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x, T = blockDim.x;
+  const int P = H * W;
+  const int b = blockIdx.x, band = blockIdx.y, t = threadIdx.x;
   // rows: owned [y0, y1), staged [y0, ye); pixels: owned [p0, po), staged [p0, pe)
-  const int y0 = band * rb, y1 = min(g.H, y0 + rb), ye = min(g.H, y1 + g.R);
+  const int y0 = band * rb, y1 = min(H, y0 + rb), ye = min(H, y1 + RR);
   const int p0 = y0 * W, po = y1 * W, pe = ye * W, Ps = pe - p0;
   const int base = p0 & ~7;                          // slot origin of the band's slab rows
-  const int G = g.G, lg = g.Tc;                      // channel groups (power of two), log2
   const int Ppb = band_row_slots(((pe + 3) & ~3) - base, lg);   // slots per slab row (one channel quad)
   const int gl = t & (G - 1), lpc = t >> lg;         // channel-sum map
   const bool active = lpc < Ps;
   const int lp = min(lpc, Ps - 1), p = p0 + lp;
   const int glf = fdivi(t, Ps), lpf = t - glf * Ps, pf = p0 + lpf;   // output map
-  const Rsrc xb = make_rsrc((const char*)x + (long long)b * g.sB * ES, (long long)g.C * P * ES);  // wave-uniform
-  const WsLayout L = ws_layout(P, R, g.mode);
-  float* Tt = (float*)(lds4 + (g.Cc >> 2) * Ppb);    // [NF+1][Ps] behind the slab: pair sums per direction, then |x|^2
+  const Rsrc xb = make_rsrc((const char*)x + (long long)b * sB * ES, (long long)C * P * ES);  // wave-uniform
+  const WsLayout L = ws_layout(P, R, kmode);
+  float* Tt = (float*)(lds4 + (Cc >> 2) * Ppb);    // [NF+1][Ps] behind the slab: pair sums per direction, then |x|^2
 
-  NFP_STAMP_INIT();
-  NFP_STAMP(0);
   // ---- the x chunk FIRST, then the tables (round 4) ------------------------------------------------------------------
   // Rounds 2-3 requested the tables first ("small, L2"): ~170 instructions of index arithmetic and two table requests
   // stood between kernel entry and the first x request (hipcc -S of the headline instantiation), on the critical path of
@@ -131,7 +137,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
 #pragma unroll
       for (int k = 0; k < kBandRN; ++k) {
         const int cq = min(gl + k * G, last);
-        nv[k] = load_px4<BF>(xb, p * g.C + c0 + 4 * cq, 0);
+        nv[k] = load_px4<BF>(xb, p * C + c0 + 4 * cq, 0);
       }
     } else {
       const int nblk = ncq * NQb;
@@ -185,12 +191,13 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
       }
     }
   };
-  issue(0, min(g.Cc, g.C) >> 2);
+  issue(0, min(Cc, C) >> 2);
   __builtin_amdgcn_sched_barrier(0);
   if (!NFP_BAND_TABLES_FIRST) {
     tables();
     __builtin_amdgcn_sched_barrier(0);
   }
+  NFP_STAMP_INIT_ENTRY();   // (the entry clocks, read at the first instruction, are stored here: behind the requests)
   NFP_STAMP(1);
 
   int off[NF];
@@ -205,8 +212,8 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
   float nrm = 0.f;
   const int sp = swz(p) - base;
 
-  for (int c0 = 0; c0 < g.C; c0 += g.Cc) {
-    const int ncq = min(g.Cc, g.C - c0) >> 2;
+  for (int c0 = 0; c0 < C; c0 += Cc) {
+    const int ncq = min(Cc, C - c0) >> 2;
     // Several chunks (batches beyond one workgroup per CU): the NEXT chunk's loads are issued right after this chunk's
     // commit, so that they fly under its sums (round 3 issued them after the sums and left each workgroup with nothing in
     // flight two thirds of the time: SQ_WAIT_ANY 42 % of the wave cycles at [4096,512,7,7], profiles/r03_p_…csv).  The
@@ -217,8 +224,8 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
     }
     commit(ncq);
     __syncthreads();
-    if (g.pf && c0 + g.Cc < g.C) {
-      issue(c0 + g.Cc, min(g.Cc, g.C - c0 - g.Cc) >> 2);
+    if (g.pf && c0 + Cc < C) {
+      issue(c0 + Cc, min(Cc, C - c0 - Cc) >> 2);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (c0 == 0) NFP_STAMP(2);
@@ -227,7 +234,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
       // pixels p0 + part, p0 + part + 4, ...; joined by a fixed xor tree.  One band per image: the mean goes straight to
       // gap[b][c]; several bands: the band's sum goes to its row of the scratch (pool_fold joins the bands in order).
       const int nbands = gridDim.y;
-      float* gdst = nbands == 1 ? gap + (long long)b * g.C : part + ((long long)b * nbands + band) * (g.C + NP);
+      float* gdst = nbands == 1 ? gap + (long long)b * C : part + ((long long)b * nbands + band) * (C + NP);
       const float gscale = nbands == 1 ? g.invP : 1.f;
       for (int i0 = 0; i0 < ncq * 4; i0 += T) {
         const int i = i0 + t, cq = min(i >> 2, ncq - 1), quarter = i & 3;   // (which quarter of the pixels this lane sums)
@@ -248,7 +255,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
           if (nbands == 1)
             *(float4*)(gdst + c0 + 4 * cq) = gv;
           else   // (a scratch row another workgroup may fold: written through — nfp_common.h::pool_last_band)
-            pool_store4(pool_rsrc(gdst, g.C + NP), c0 + 4 * cq, gv);
+            pool_store4(pool_rsrc(gdst, C + NP), c0 + 4 * cq, gv);
         }
       }
     }
@@ -366,15 +373,15 @@ __global__ void __launch_bounds__(1024) fwd_band(const KP g, const void* __restr
         if (nbands == 1)
           nfpm[(long long)b * N + n] = sacc * g.invP;
         else
-          pool_store1(pool_rsrc(part + ((long long)b * nbands + band) * (g.C + N), g.C + N), g.C + n, sacc);
+          pool_store1(pool_rsrc(part + ((long long)b * nbands + band) * (C + N), C + N), C + n, sacc);
       }
     }
     // several bands and a ticket counter: the band that arrives last folds all of them (nfp_common.h::pool_last_band);
     // without counters (no workspace) the caller launches pool_fold
     if (nbands > 1 && g.tickets != nullptr) {
       if (pool_last_band(g.tickets + b, nbands, (int*)lds4, t == 0))
-        pool_fold_image(part + (long long)b * nbands * (g.C + N), nbands, g.C, N, g.invP,
-                        g.pool_gap ? gap + (long long)b * g.C : nullptr, nfpm + (long long)b * N, t, T);
+        pool_fold_image(part + (long long)b * nbands * (C + N), nbands, C, N, g.invP,
+                        g.pool_gap ? gap + (long long)b * C : nullptr, nfpm + (long long)b * N, t, T);
     }
   }
   NFP_STAMP(5);

@@ -62,6 +62,26 @@ struct KP {
 //   kPoolGap   nfp_gap_*: GAP(x) beside the full maps (an NFP head, nfp_heads.py: gap(fmap) and nfp(fmap) of one feature
 //              map) — no pooled map sums; the backward reads grad_out as a map and adds ggap[b,c] / P in the same store
 constexpr int kPoolNone = 0, kPoolBoth = 1, kPoolGap = 2;
+
+// ---- the preloadable HEAD of fwd_band (nfp_band.h) and bwd_fast (nfp_fast.h) ---------------------------------------------
+// A kernel's arguments lie in a block of memory the host (or the graph) wrote, which no earlier launch has read: whatever the
+// code in front of the first memory request needs from it costs a scalar-cache and L2 miss first.  gfx950 can hand the
+// LEADING arguments over in SGPRs at wavefront start instead (build.py: -amdgpu-kernarg-preload-count) — pointers and
+// 32-bit scalars only, up to the first by-value struct, at most 14 dwords beside the block's own address.  So the two
+// kernels take what their entry code needs as individual leading arguments, small fields packed by the helpers below, and
+// `KP` as the LAST argument: its fetch then runs under the first requests' latency.  The workgroup size rides in the head
+// too (in wavefronts: it is a multiple of 64) — blockDim.x is itself a load from the hidden part of the argument block.
+// Ranges: H, W, rb <= 512 (P <= 512), log2 G <= 5, R <= 2, Cc < 2^20 (a chunk fits the LDS), T <= 1024; the backward:
+// P <= 512, mode <= 3, G <= 256.
+__host__ __device__ inline uint32_t band_head_geom(int H, int W, int rb) {
+  return (uint32_t)H | ((uint32_t)W << 10) | ((uint32_t)rb << 20);
+}
+__host__ __device__ inline uint32_t band_head_chunk(int Cc, int lg, int R, int T) {
+  return (uint32_t)Cc | ((uint32_t)lg << 20) | ((uint32_t)R << 23) | ((uint32_t)(T >> 6) << 25);
+}
+__host__ __device__ inline uint32_t bwd_head_geom(int P, int mode, int unit, int G, int T) {
+  return (uint32_t)P | ((uint32_t)mode << 10) | ((uint32_t)(unit != 0) << 12) | ((uint32_t)G << 13) | ((uint32_t)(T >> 6) << 22);
+}
 constexpr int kTicketWords = 4096;              // (batches beyond it: no counters — make_kp)
 constexpr int kTicketBytes = kTicketWords * 4;
 
@@ -211,6 +231,8 @@ __device__ __forceinline__ int nbr_pixel(const KP& g, int o, int n) {
 #include "nfp_diag.h"
 #else
 #define NFP_STAMP_INIT() do { } while (0)
+#define NFP_STAMP_ENTRY() do { } while (0)
+#define NFP_STAMP_INIT_ENTRY() do { } while (0)
 #define NFP_STAMP(id) do { } while (0)
 #endif
 

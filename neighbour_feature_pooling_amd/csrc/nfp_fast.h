@@ -123,9 +123,13 @@ struct Staged<true> {
 __host__ __device__ inline int bwd_row_slots(int P, bool nhwc) {
   return (nhwc && NFP_BWD_NHWC_LANES) ? (((P + 3) & ~3) | 1) : ((P + 3) & ~3);
 }
+// what the staging helpers need of the launch (bwd_fast fills it from its preloaded head, not from KP)
+struct StageGeo {
+  int P, C, G;
+};
 // channels-last: slot (cq, p) is 4 contiguous channels; thread (p, gl) takes cq = gl, gl+G, ...
 template <bool BF>
-__device__ __forceinline__ void stage_load(Staged<true>& s, Rsrc x, const KP& g, int c0, int ncq, int p, int gl,
+__device__ __forceinline__ void stage_load(Staged<true>& s, Rsrc x, const StageGeo& g, int c0, int ncq, int p, int gl,
                                            bool active) {
   const int g0 = active ? gl : 0;
   const int last = g0 < ncq ? g0 + ((ncq - 1 - g0) / g.G) * g.G : 0;
@@ -135,7 +139,7 @@ __device__ __forceinline__ void stage_load(Staged<true>& s, Rsrc x, const KP& g,
     s.v[k] = load_px4<BF>(x, p * g.C + c0 + 4 * cq, 0);
   }
 }
-__device__ __forceinline__ void stage_store(const Staged<true>& s, float4* slab, const KP& g, int ncq, int p, int gl,
+__device__ __forceinline__ void stage_store(const Staged<true>& s, float4* slab, const StageGeo& g, int ncq, int p, int gl,
                                             bool active) {
 #pragma unroll
   for (int k = 0; k < kRN; ++k) {
@@ -151,7 +155,7 @@ struct StagedOvl {
   float4 blk[kRB][4];
 };
 template <bool BF>
-__device__ __forceinline__ void stage_load_ovl(StagedOvl& s, Rsrc x, const KP& g, int c0, int ncq, int t, int T) {
+__device__ __forceinline__ void stage_load_ovl(StagedOvl& s, Rsrc x, const StageGeo& g, int c0, int ncq, int t, int T) {
   const int P = g.P, NQb = (P + 3) >> 2, nblk = ncq * NQb;
 #pragma unroll
   for (int r = 0; r < kRB; ++r) {
@@ -162,7 +166,7 @@ __device__ __forceinline__ void stage_load_ovl(StagedOvl& s, Rsrc x, const KP& g
     for (int j = 0; j < 4; ++j) s.blk[r][j] = load_px4<BF>(x, e, j * P);
   }
 }
-__device__ __forceinline__ void stage_store_ovl(const StagedOvl& s, float4* slab, const KP& g, int ncq, int t, int T) {
+__device__ __forceinline__ void stage_store_ovl(const StagedOvl& s, float4* slab, const StageGeo& g, int ncq, int t, int T) {
   const int P = g.P, NQb = (P + 3) >> 2, nblk = ncq * NQb, Pp = (P + 3) & ~3;
 #pragma unroll
   for (int r = 0; r < kRB; ++r) {
@@ -630,13 +634,25 @@ struct L_BRQ {
 // POOL = kPoolGap (nfp_common.h): the head's pass — grad_out IS a map, read as the plain backward reads it, and every
 // grad_x[b,c,p] also receives ggap[b,c]/P where the pooled mode adds it.
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0>   // GEMM: 0 vector phase B, 1 / 2 matrix cores
-__global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g, const void* __restrict__ x,
+__global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void* __restrict__ x,
                                                         const void* __restrict__ go, const void* __restrict__ out,
-                                                        const float* __restrict__ saved, void* __restrict__ gx,
+                                                        const float* __restrict__ saved,
+                                                        const unsigned char* __restrict__ ws, uint32_t hgeom, int C,
+                                                        int Cwg, int Cc, void* __restrict__ gx,
                                                         const float* __restrict__ ggap,
-                                                        const float* __restrict__ gnfpm,
-                                                        const unsigned char* __restrict__ ws) {
+                                                        const float* __restrict__ gnfpm, const KP g) {
   static_assert(!GEMM || BF, "matrix-core phase B: bf16 storage only");
+  NFP_STAMP_ENTRY();
+  // The HEAD (nfp_common.h: bwd_head_geom): five pointers and four dwords, 14 SGPRs handed over at wavefront start.  The
+  // table rows, the pair values and the norms — the first requests — are addressed from the head alone; what does not fit
+  // (the batch strides, 1 / P of the thread map) comes from `g`, whose fetch runs under those requests.
+  const int P = (int)(hgeom & 1023u), hmode = (int)((hgeom >> 10) & 3u), hG = (int)((hgeom >> 13) & 511u);
+  const bool hunit = ((hgeom >> 12) & 1u) != 0;
+  const int T = (int)(hgeom >> 22) << 6;   // (= blockDim.x, which would be a load from the argument block)
+  const StageGeo sg = {P, C, hG};
+  // asked for here, first used behind the first requests (below)
+  const long long ksB = g.sB, kgB = g.gB;
+  const float kinvP = g.invP;
   constexpr int K2 = Win<R>::K2, N = Win<R>::N;
   constexpr bool GO_POOLED = POOL == kPoolBoth, HAS_GAP = POOL != kPoolNone;   // what grad_out is / whether grad(GAP) joins
   // the diagonal is folded by a phase of its own when the weights are consumed as a table (matrix cores) or the
@@ -644,7 +660,6 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   constexpr bool FOLD_PHASE = GEMM || Win<R>::RAD != 1;  // (R: radius spec of nfp_tables.h::Win)
   constexpr bool G3 = GEMM == 2;  // every row tile's densified weights written by phase A itself: bwd_gemm_phase3
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
-  const int P = g.P;
   // LDS: Wt | Dt | ipn | dfn (live to the end) | pair values | x slab.  The slab lies OVER the pair values (dead
   // once Wt is built) when both do not fit side by side (g.early == 0).
   // Matrix-core variant (round 4): Dt is dead once the diagonal is folded (A3), so it sits BEHIND the tables that live to
@@ -658,7 +673,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   float* dfn = ipn + P;            // [P] -1 / (|x_p| max(|x_p|, eps)), 0 where |x_p| = 0
   float* Wc = dfn + P;             // (GEMM = 2) [P] centre weights before the fold
   const int g3_band = Win<R>::RAD * g.W + Win<R>::RAD, g3_wq = odd_up(2 * gemm_kw(g3_band) + 1);
-  const int g3_fixed4 = (3 * P + (HAS_GAP ? (int)(g.Cwg) : 0) + 3) >> 2;   // float4 slots in front of Wd
+  const int g3_fixed4 = (3 * P + (HAS_GAP ? Cwg : 0) + 3) >> 2;   // float4 slots in front of Wd
   uint4* g3_Wd = (uint4*)(lds4 + g3_fixed4);
   float4* g3_pv4 = (float4*)(g3_Wd + (long long)((P + 31) >> 5) * 64 * g3_wq);
   float4* pv4 = G3 ? g3_pv4 : (GEMM ? lds4 + ((P * K2 + 2 * P + 3) >> 2) + ((P * K2 + 3) >> 2) : lds4 + ((2 * P * K2 + 2 * P + 3) >> 2));
@@ -666,13 +681,11 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
                  : (GEMM ? (float*)(lds4 + ((P * K2 + 2 * P + 3) >> 2)) : Wt + P * K2);   // [P][K2] diagonal terms collected per slot
   float2* AD = (float2*)pv4;       // cosine: [N*P] {sg, sg*s} of pair o = n*P + p
   float* CC = (float*)pv4;         // L2:     [N*P] c = -+g/d
-  float4* slab = g.early ? pv4 + (((M == NFP_COSINE ? 2 : 1) * (N * P + 1) + 3) >> 2) : pv4;  // [Cc/4][P]
-  const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
-  const int cb0 = blockIdx.y * g.Cwg, cb1 = min(g.C, cb0 + g.Cwg);
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int cb0 = blockIdx.y * Cwg, cb1 = min(C, cb0 + Cwg);
   // matrix-core variant: Xt over Dt and the pair values (dead once Wt is built and folded), Wd behind it
   uint4* gemm_Xt = G3 ? (uint4*)g3_pv4 : (uint4*)Dt;
   uint4* gemm_Wd = G3 ? g3_Wd : gemm_Xt + (long long)(cb1 - cb0) * gemm_xq(P);
-  const uint16_t* x16 = (const uint16_t*)x + (long long)b * g.sB;
   // fused pooling tail, matrix-core variant: grad(GAP(x)) / P of this workgroup's channels goes to LDS behind Wd (read
   // from global memory in the tile loop it cost 4 of 22 us at config 5).  Two values per thread are requested here.
   // (The vector kernel keeps its 16-byte global loads in the channel loop: staged the same way it measured 7.3 vs 6.7 us.)
@@ -682,38 +695,17 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
     const int ncw = cb1 - cb0;
     const int band = Win<R>::RAD * g.W + Win<R>::RAD, KW = gemm_kw(band);
     gg_s = G3 ? Wc + P : (float*)(gemm_Wd + (long long)g.Tc * 2 * 32 * odd_up(2 * KW + 1));
-    if (g.pool_gap && t < ncw) ggv0 = ggap[(long long)b * g.C + cb0 + t];
-    if (g.pool_gap && t + T < ncw) ggv1 = ggap[(long long)b * g.C + cb0 + t + T];
-  }
-  // Thread map.  NCHW: t = gl * P + p — lanes along the pixels of a channel row (coalesced 4-byte stores).  Channels-last
-  // (round 4): t = p * G + gl — lanes along the channel groups of a pixel, so that G adjacent lanes read and write 16 G
-  // contiguous bytes; with lanes along the pixels every load / store instruction touched 64 cache lines for 1 KB, and the
-  // eight quads of a 128-byte line were written by eight different wavefronts (the backward ran 20-40 % behind NCHW on the
-  // same bytes: [4096,512,7,7] 231 vs 163 us, profiles/r04_a_…).
-  int gl, p;
-  bool active;
-  if constexpr (NHWC && !GEMM && NFP_BWD_NHWC_LANES) {
-    const int pp = fdivi(t, g.G);
-    gl = t - pp * g.G;
-    active = pp < P;
-    p = min(pp, P - 1);
-  } else {
-    gl = fast_div(t, g.invP);
-    p = t - gl * P;
-    active = gl < g.G;
+    if (g.pool_gap && t < ncw) ggv0 = ggap[(long long)b * C + cb0 + t];
+    if (g.pool_gap && t + T < ncw) ggv1 = ggap[(long long)b * C + cb0 + t + T];
   }
   constexpr int ES = BF ? 2 : 4;
-  const Rsrc xb = make_rsrc((const char*)x + (long long)b * g.sB * ES, (long long)g.C * P * ES);  // wave-uniform
-  const Rsrc gxb = make_rsrc((char*)gx + (long long)b * g.gB * ES, (long long)g.C * P * ES);
   const void* gob = (const char*)go + (long long)b * N * P * ES;
   const void* outb = (const char*)out + (long long)b * N * P * ES;
-  const WsLayout L = ws_layout(P, R, g.mode);
+  const WsLayout L = ws_layout(P, R, hmode);
   const int LQ = L.LW >> 3;  // 16-byte pieces per link row
   const uint4* lnk = (const uint4*)(ws + L.lnk);
   const uint16_t* tqt = (const uint16_t*)(ws + L.tq);
 
-  NFP_STAMP_INIT();
-  NFP_STAMP(0);
   // Phase A, table driven (nfp_tables.h).  Loads are issued in the order their data is needed: the geometry tables
   // and this image's grad_out / out / norms first (small, L2-resident), then the x chunk, so that the pair
   // arithmetic runs while x streams in.  One table entry / pair per thread and round, the next round's loads in
@@ -771,8 +763,31 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   // (DotProduct has no saved norms: the load reads the output map instead — in bounds, unused — rather than sit under a branch)
   // (DotProduct has no saved norms: the load reads the output map instead — in bounds, rather than sit under a branch —
   // and its bits are masked to 0: read as floats, a bf16 map holds NaN / Inf patterns, and NaN * 0 would reach ipn)
-  const float nrm_raw = (M == NFP_COSINE) ? (g.unit ? (const float*)out : saved)[(long long)b * P + min(t, P - 1)] : 0.f;
-  const float nrm = __int_as_float(__float_as_int(nrm_raw) & (g.unit ? 0 : -1));
+  const float nrm_raw = (M == NFP_COSINE) ? (hunit ? (const float*)out : saved)[(long long)b * P + min(t, P - 1)] : 0.f;
+  const float nrm = __int_as_float(__float_as_int(nrm_raw) & (hunit ? 0 : -1));
+  // ---- everything above reads the head alone; from here on the fields of `g` (their fetch was started at entry) ----------
+  __builtin_amdgcn_sched_barrier(0);
+  float4* slab = g.early ? pv4 + (((M == NFP_COSINE ? 2 : 1) * (N * P + 1) + 3) >> 2) : pv4;  // [Cc/4][P]
+  const uint16_t* x16 = (const uint16_t*)x + (long long)b * ksB;
+  // Thread map.  NCHW: t = gl * P + p — lanes along the pixels of a channel row (coalesced 4-byte stores).  Channels-last
+  // (round 4): t = p * G + gl — lanes along the channel groups of a pixel, so that G adjacent lanes read and write 16 G
+  // contiguous bytes; with lanes along the pixels every load / store instruction touched 64 cache lines for 1 KB, and the
+  // eight quads of a 128-byte line were written by eight different wavefronts (the backward ran 20-40 % behind NCHW on the
+  // same bytes: [4096,512,7,7] 231 vs 163 us, profiles/r04_a_…).
+  int gl, p;
+  bool active;
+  if constexpr (NHWC && !GEMM && NFP_BWD_NHWC_LANES) {
+    const int pp = fdivi(t, hG);
+    gl = t - pp * hG;
+    active = pp < P;
+    p = min(pp, P - 1);
+  } else {
+    gl = fast_div(t, kinvP);
+    p = t - gl * P;
+    active = gl < hG;
+  }
+  const Rsrc xb = make_rsrc((const char*)x + (long long)b * ksB * ES, (long long)C * P * ES);  // wave-uniform
+  const Rsrc gxb = make_rsrc((char*)gx + (long long)b * kgB * ES, (long long)C * P * ES);
   uint4 bo[L_BRQ<R>::v];  // this pixel's window offsets (phase B)
   if constexpr (!GEMM) {
     const uint4* bot = (const uint4*)(ws + L.boff) + (long long)p * L_BRQ<R>::v;
@@ -783,15 +798,15 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   typename std::conditional<NHWC, Staged<true>, StagedOvl>::type st;
   auto x_issue = [&](int c0, int ncq) {
     if constexpr (NHWC)
-      stage_load<BF>(st, xb, g, c0, ncq, p, gl, active);
+      stage_load<BF>(st, xb, sg, c0, ncq, p, gl, active);
     else
-      stage_load_ovl<BF>(st, xb, g, c0, ncq, t, T);
+      stage_load_ovl<BF>(st, xb, sg, c0, ncq, t, T);
   };
   auto x_commit = [&](int ncq) {
     if constexpr (NHWC)
-      stage_store(st, slab, g, ncq, p, gl, active);
+      stage_store(st, slab, sg, ncq, p, gl, active);
     else
-      stage_store_ovl(st, slab, g, ncq, t, T);
+      stage_store_ovl(st, slab, sg, ncq, t, T);
   };
   GemmX<NHWC> gxr;
 #ifndef NFP_VEC_X_LATE
@@ -800,10 +815,11 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
                            // measures the same either way and keeps the request at entry), 0 = none, 2 = all do
 #endif
   constexpr bool X_LATE = !GEMM && (NFP_VEC_X_LATE == 2 || (NFP_VEC_X_LATE == 1 && Win<R>::RAD >= 2));
-  if constexpr (!GEMM && !X_LATE) x_issue(cb0, min(g.Cc, cb1 - cb0) >> 2);
+  if constexpr (!GEMM && !X_LATE) x_issue(cb0, min(Cc, cb1 - cb0) >> 2);
   // nothing that consumes a loaded value may be scheduled above this line (hipcc otherwise hoists consumers into
   // the load sequence and stalls the remaining loads behind a vmcnt wait)
   __builtin_amdgcn_sched_barrier(0);
+  NFP_STAMP_INIT_ENTRY();   // (the entry clocks, read at the first instruction, are stored here: behind the requests)
   NFP_STAMP(1);
   if constexpr (G3) {   // Wd: whatever phase A does not write reads as zero; Dt: slots outside the image — under the first loads' latency
     const int nwd = ((P + 31) >> 5) * 64 * g3_wq;
@@ -884,12 +900,12 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
     const int ncw = cb1 - cb0;
     if (t < ncw) gg_s[t] = ggv0 * g.invP;
     if (t + T < ncw) gg_s[t + T] = ggv1 * g.invP;
-    for (int i = t + 2 * T; i < ncw; i += T) gg_s[i] = g.pool_gap ? ggap[(long long)b * g.C + cb0 + i] * g.invP : 0.f;  // (more than 2T channels)
+    for (int i = t + 2 * T; i < ncw; i += T) gg_s[i] = g.pool_gap ? ggap[(long long)b * C + cb0 + i] * g.invP : 0.f;  // (more than 2T channels)
   }
   __syncthreads();
   NFP_STAMP(2);
   if constexpr (X_LATE) {
-    x_issue(cb0, min(g.Cc, cb1 - cb0) >> 2);
+    x_issue(cb0, min(Cc, cb1 - cb0) >> 2);
     __builtin_amdgcn_sched_barrier(0);
   }
 
@@ -1067,7 +1083,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   // (the pair values stay readable until the barrier: with g.early the slab does not overlap them, so the x chunk
   // is committed here, while slower wavefronts still gather)
   if constexpr (!GEMM) {
-    if (g.early) x_commit(min(g.Cc, cb1 - cb0) >> 2);
+    if (g.early) x_commit(min(Cc, cb1 - cb0) >> 2);
   }
   __syncthreads();
   NFP_STAMP(3);
@@ -1110,23 +1126,23 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
   // 16-byte store for channels-last (store policy: NFP_BWD_STORE_AUX above; an LDS-transposed 16-byte NCHW epilogue
   // was 1.6 us slower).
   const int Pp = bwd_row_slots(P, NHWC), sp = swz(p);
-  for (int c0 = cb0; c0 < cb1; c0 += g.Cc) {
-    const int ncq = min(g.Cc, cb1 - c0) >> 2;
+  for (int c0 = cb0; c0 < cb1; c0 += Cc) {
+    const int ncq = min(Cc, cb1 - c0) >> 2;
     if (c0 > cb0) __syncthreads();  // previous chunk fully consumed
     if (c0 > cb0 || !g.early) {
       x_commit(ncq);
       __syncthreads();
     }
     // the next chunk's loads fly while this one is processed (the staging registers are free once committed)
-    if (c0 + g.Cc < cb1) x_issue(c0 + g.Cc, min(g.Cc, cb1 - c0 - g.Cc) >> 2);
+    if (c0 + Cc < cb1) x_issue(c0 + Cc, min(Cc, cb1 - c0 - Cc) >> 2);
     NFP_STAMP(5);
     if (active) {
 #pragma unroll NFP_UNROLL_B
-      for (int cq = gl; cq < ncq; cq += g.G) {
+      for (int cq = gl; cq < ncq; cq += hG) {
         const float4* row = slab + cq * Pp + sp;
         float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (HAS_GAP && g.pool_gap) {
-          const float4 gg = *(const float4*)(ggap + (long long)b * g.C + c0 + 4 * cq);
+          const float4 gg = *(const float4*)(ggap + (long long)b * C + c0 + 4 * cq);
           r4 = make_float4(gg.x * g.invP, gg.y * g.invP, gg.z * g.invP, gg.w * g.invP);
         }
         if constexpr (M == kSymTerm) {
@@ -1173,7 +1189,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const KP g
           }
         }
         if constexpr (NHWC) {
-          store_px4<BF>(gxb, p * g.C + c0 + 4 * cq, 0, r4);
+          store_px4<BF>(gxb, p * C + c0 + 4 * cq, 0, r4);
         } else {
           const int e = (c0 + 4 * cq) * P + p;  // one address VGPR, channel rows through the SGPR offset
           store_1<BF>(gxb, e, 0, r4.x);

@@ -449,13 +449,16 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   snprintf(g_variant, sizeof(g_variant), "fwd_band<R%s,%s,%s,%s%s>x%d", R == 12 ? "1+2" : (R == 1 ? "1" : "2"), hot_name(g),
            BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
   if (nb_out) *nb_out = nb;
+  // the kernel's preloadable head (nfp_common.h): what stands in front of its first x request
+  const uint32_t sB_lo = (uint32_t)((unsigned long long)g.sB & 0xFFFFFFFFull), sB_hi = (uint32_t)((unsigned long long)g.sB >> 32);
+  const uint32_t hchunk = nfp::band_head_chunk(g.Cc, lg, g.R, T), hgeom = nfp::band_head_geom(g.H, g.W, rb);
   // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — pool_forward_rm)
   if constexpr (M != kSymTerm)
   if (g.unit || g.gfc || g.d2s != 1.f)   // DotProduct / GFC / RMSE: the finalize with the run-time constants
-    return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, true>, dim3(g.B, nb), dim3(T), lds, st, g, x, out, saved, g.ws,
-                  rb, gap, nfpm, part);
-  return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, false>, dim3(g.B, nb), dim3(T), lds, st, g, x, out, saved, g.ws,
-                rb, gap, nfpm, part);
+    return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, true>, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi,
+                  g.C, hchunk, hgeom, out, saved, gap, nfpm, part, g);
+  return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, false>, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi,
+                g.C, hchunk, hgeom, out, saved, gap, nfpm, part, g);
 }
 
 template <int R, int M>
@@ -525,8 +528,8 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
   if (lds > (size_t)kLdsMax) return kNotApplicable;  // tables + slab do not fit: the generic kernels serve it
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%s,%s,%s,%s%s>", R == 12 ? "1+2" : (R == 1 ? "1" : "2"),
            hot_name(g), BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL));
-  return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, g, x, go, out, saved, gx,
-                ggap, gnfpm, g.ws);
+  return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws,
+                nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
 }
 
 // Matrix-core forward (nfp_mfma.h): bf16, dense channels-last, C a multiple of 16.
@@ -650,8 +653,8 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
       g.early = 0;
       snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma2%s>", R, hot_name(g), NHWC ? "nhwc" : "nchw",
                pool_tag(POOL));
-      return launch("bwd_fast_mfma2", bwd_fast<R, M, true, NHWC, POOL, 2>, dim3(g.B, S), dim3(T), lds3, st, g, x, go, out, saved,
-                    gx, ggap, gnfpm, g.ws);
+      return launch("bwd_fast_mfma2", bwd_fast<R, M, true, NHWC, POOL, 2>, dim3(g.B, S), dim3(T), lds3, st, x, go, out, saved,
+                    g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
     }
   }
   if (rt >= 2 && rt < nt) rt = (nt + ((nt + rt - 1) / rt) - 1) / ((nt + rt - 1) / rt);  // even rounds
@@ -663,8 +666,8 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   if (lds > (size_t)kLdsMax) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma%s>", R, hot_name(g),
            NHWC ? "nhwc" : "nchw", pool_tag(POOL));
-  return launch("bwd_fast_mfma", bwd_fast<R, M, true, NHWC, POOL, 1>, dim3(g.B, S), dim3(T), lds, st, g, x, go, out,
-                saved, gx, ggap, gnfpm, g.ws);
+  return launch("bwd_fast_mfma", bwd_fast<R, M, true, NHWC, POOL, 1>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
+                g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
 }
 
 // the vector (VALU) backward, for any radius spec
