@@ -42,6 +42,7 @@ namespace nfp {
 #endif
 constexpr int kRB = NFP_RB;  // NCHW staging: 4x4 blocks per thread per chunk
 constexpr int kRN = 4;    // channels-last staging: slots per thread per chunk
+constexpr int kRS = 6;    // NCHW staging by pixel rows (StagedRows): slots per thread per chunk
 constexpr int kBwdThreads = NFP_BWD_THREADS;  // backward keeps (2R+1)^2 weights + offsets + staged x in registers
 
 // exact i / d for 0 <= i, quotient < 2048 (d >= 1): float multiply instead of the ~20-instruction
@@ -180,6 +181,41 @@ __device__ __forceinline__ void stage_store_ovl(const StagedOvl& s, float4* slab
       d[swz(ps + 2)] = make_float4(s.blk[r][0].z, s.blk[r][1].z, s.blk[r][2].z, s.blk[r][3].z);
       d[swz(ps + 3)] = make_float4(s.blk[r][0].w, s.blk[r][1].w, s.blk[r][2].w, s.blk[r][3].w);
     }
+  }
+}
+
+// NCHW staging by pixel rows (round 5): the backward's compute thread map is already t = gl * P + p — lanes along the
+// pixels of a channel row — so thread (gl, p) loads the slots it will itself read first, (cq = gl, gl + G, ...; p): four
+// coalesced 4-byte loads each, the channel row in the scalar offset, and holds the slot's float4 with no transposition.
+// Every thread of the workgroup stages (the block form has ceil(P / 4) * ncq blocks for P * G threads: at the headline
+// shape half of them stage and half wait).  Slots past the chunk's last quad — and the lanes beyond the last channel
+// group — load the last quad's row instead and commit nothing.
+// The rule above `Staged` stands: no load sits under a per-lane condition (a select or an exec-mask branch around a load
+// makes hipcc wait for the earlier loads first).  The `break` below is not one: G and ncq are the same in every lane of
+// the launch, so it is a scalar branch over a whole round that NO thread needs, taken the same way by every wavefront —
+// the form fwd_band's block staging uses to skip its unused rounds (NFP_BAND_SKIP_ROUNDS); the loads of the rounds that
+// run are issued back to back with no wait between them (hipcc -S of the headline instantiation).
+struct StagedRows {
+  float v[kRS][4];
+};
+template <bool BF>
+__device__ __forceinline__ void stage_load_rows(StagedRows& s, Rsrc x, const StageGeo& g, int c0, int ncq, int p, int gl) {
+#pragma unroll
+  for (int k = 0; k < kRS; ++k) {
+    if (k > 0 && k * g.G >= ncq) break;   // (a round no thread needs: wave-uniform)
+    const int e = (c0 + 4 * min(gl + k * g.G, ncq - 1)) * g.P + p;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s.v[k][j] = load_1<BF>(x, e, j * g.P);
+  }
+}
+__device__ __forceinline__ void stage_store_rows(const StagedRows& s, float4* slab, const StageGeo& g, int ncq, int p, int gl,
+                                                 bool active) {
+  const int Pp = (g.P + 3) & ~3, sp = swz(p);
+#pragma unroll
+  for (int k = 0; k < kRS; ++k) {
+    if (k > 0 && k * g.G >= ncq) break;
+    const int cq = gl + k * g.G;
+    if (active && cq < ncq) slab[cq * Pp + sp] = make_float4(s.v[k][0], s.v[k][1], s.v[k][2], s.v[k][3]);
   }
 }
 
@@ -633,7 +669,9 @@ struct L_BRQ {
 // for every p, and every grad_x[b,c,p] also receives ggap[b,c]/P (adjoint of the two means).
 // POOL = kPoolGap (nfp_common.h): the head's pass — grad_out IS a map, read as the plain backward reads it, and every
 // grad_x[b,c,p] also receives ggap[b,c]/P where the pooled mode adds it.
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0>   // GEMM: 0 vector phase B, 1 / 2 matrix cores
+// ROWS: the x chunk staged by pixel rows (StagedRows above) instead of 4 x 4 blocks; the launcher's choice (nfp_hip.hip).
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0,   // GEMM: 0 vector phase B, 1 / 2 matrix cores
+          bool ROWS = false>
 __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void* __restrict__ x,
                                                         const void* __restrict__ go, const void* __restrict__ out,
                                                         const float* __restrict__ saved,
@@ -642,6 +680,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void
                                                         const float* __restrict__ ggap,
                                                         const float* __restrict__ gnfpm, const KP g) {
   static_assert(!GEMM || BF, "matrix-core phase B: bf16 storage only");
+  static_assert(!ROWS || (!NHWC && !GEMM), "pixel-row staging: NCHW, vector phase B");
   NFP_STAMP_ENTRY();
   // The HEAD (nfp_common.h: bwd_head_geom): five pointers and four dwords, 14 SGPRs handed over at wavefront start.  The
   // table rows, the pair values and the norms — the first requests — are addressed from the head alone; what does not fit
@@ -795,16 +834,20 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void
     for (int u = 0; u < L_BRQ<R>::v; ++u) bo[u] = bot[u];
   }
   __builtin_amdgcn_sched_barrier(0);  // keep these (small, needed first) loads ahead of the x chunk
-  typename std::conditional<NHWC, Staged<true>, StagedOvl>::type st;
+  typename std::conditional<NHWC, Staged<true>, typename std::conditional<ROWS, StagedRows, StagedOvl>::type>::type st;
   auto x_issue = [&](int c0, int ncq) {
     if constexpr (NHWC)
       stage_load<BF>(st, xb, sg, c0, ncq, p, gl, active);
+    else if constexpr (ROWS)
+      stage_load_rows<BF>(st, xb, sg, c0, ncq, p, gl);
     else
       stage_load_ovl<BF>(st, xb, sg, c0, ncq, t, T);
   };
   auto x_commit = [&](int ncq) {
     if constexpr (NHWC)
       stage_store(st, slab, sg, ncq, p, gl, active);
+    else if constexpr (ROWS)
+      stage_store_rows(st, slab, sg, ncq, p, gl, active);
     else
       stage_store_ovl(st, slab, sg, ncq, t, T);
   };

@@ -452,13 +452,21 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   // the kernel's preloadable head (nfp_common.h): what stands in front of its first x request
   const uint32_t sB_lo = (uint32_t)((unsigned long long)g.sB & 0xFFFFFFFFull), sB_hi = (uint32_t)((unsigned long long)g.sB >> 32);
   const uint32_t hchunk = nfp::band_head_chunk(g.Cc, lg, g.R, T), hgeom = nfp::band_head_geom(g.H, g.W, rb);
+  // (NCHW staging: always the 4 x 4 blocks here.  The pixel-row form bwd_fast takes — launch_bwd_fast_t — was built for this
+  // kernel too and measured no faster at the headline shape, 4.80 -> 4.86 us: profiles/r05_b_nchw_row_staging_ab.txt)
+  auto go = [&](auto kernel) {
+    if constexpr (NHWC)
+      return launch("fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk, hgeom, out, saved,
+                    gap, nfpm, part, g);
+    else
+      return launch_staged(false, "fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk,
+                           hgeom, out, saved, gap, nfpm, part, g);
+  };
   // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — pool_forward_rm)
   if constexpr (M != kSymTerm)
   if (g.unit || g.gfc || g.d2s != 1.f)   // DotProduct / GFC / RMSE: the finalize with the run-time constants
-    return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, true>, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi,
-                  g.C, hchunk, hgeom, out, saved, gap, nfpm, part, g);
-  return launch("fwd_band", fwd_band<R, M, BF, NHWC, POOL, false>, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi,
-                g.C, hchunk, hgeom, out, saved, gap, nfpm, part, g);
+    return go(fwd_band<R, M, BF, NHWC, POOL, true>);
+  return go(fwd_band<R, M, BF, NHWC, POOL, false>);
 }
 
 template <int R, int M>
@@ -528,8 +536,25 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
   if (lds > (size_t)kLdsMax) return kNotApplicable;  // tables + slab do not fit: the generic kernels serve it
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%s,%s,%s,%s%s>", R == 12 ? "1+2" : (R == 1 ? "1" : "2"),
            hot_name(g), BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL));
-  return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws,
-                nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+  // NCHW staging form (nfp_fast.h: StagedRows).  By pixel rows for ONE class: float32, k = 3, plain maps, the cosine and L2
+  // instantiations (with their dot / gfc / rmse riders; Norm p = 1 and the symmetric-term measures keep the blocks: an
+  // instantiation more each for measures no in-tree model uses), a single chunk (Cc covers the workgroup's channels), at
+  // most one workgroup per CU (beyond that latency no longer counts) and at most kRS slots per thread.  Everything else:
+  // 4 x 4 blocks, as before.  NFP_STAGE_BLOCKS=1 forces the blocks; the two forms agree bitwise.
+  // (the slot bound is this change's own, a register budget: kRS slots are 24 staging registers against the blocks' 48;
+  // a single-chunk launch beyond it — [128,512,7,7]: 64 quads on 10 groups, 7 slots — keeps the blocks)
+  const uint32_t hgeom = nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T);
+  if constexpr (R == 1 && !BF && !NHWC && POOL == kPoolNone && (M == NFP_COSINE || M == NFP_NORM)) {
+    if (!satb && g.Cc >= g.Cwg && ceil_div(g.Cwg / 4, g.G) <= nfp::kRS && !g_sw.stage_blocks.load(std::memory_order_relaxed))
+      return launch_staged(true, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, true>, dim3(g.B, S), dim3(T), lds, st, x, go, out,
+                           saved, g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+  }
+  if constexpr (!NHWC)
+    return launch_staged(false, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
+                         g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+  else
+    return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws, hgeom,
+                  g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
 }
 
 // Matrix-core forward (nfp_mfma.h): bf16, dense channels-last, C a multiple of 16.

@@ -54,6 +54,8 @@ struct Switches {
                                      // more per pixel (8 pieces per position: [256,128,28,28] 23.9 -> 18.8 us, [256,64,56,56] 44.2 ->
                                      // 42.2) — 0 = never, 1 = wherever it applies (float32 loses: 72 -> 121 us at
                                      // [256,16,112,112]; profiles/r04_h_…)
+  std::atomic<int> stage_blocks{0};  // A/B, tests: NCHW maps staged in 4 x 4 blocks also where bwd_fast's launcher would stage
+                                     // them by pixel rows (nfp_fast.h: StagedRows) — the two forms agree bitwise
 };
 inline Switches g_sw;
 #ifndef NFP_MFMA_DEFAULT
@@ -81,6 +83,7 @@ inline void read_env() {
     const char* e = getenv("NFP_TILE_DMA");
     g_sw.tile_dma = e ? (e[0] == '1' ? 1 : 0) : -1;
   }
+  g_sw.stage_blocks = flag("NFP_STAGE_BLOCKS", 0);
   g_sw.tile_first = flag("NFP_TILE_FIRST", 0);   // A/B: the row-band kernels of nfp_tile.h also for maps the table kernels serve
   auto num = [](const char* name) {
     const char* e = getenv(name);
@@ -143,6 +146,10 @@ int set_lds(K kernel, size_t bytes) {
 // GPU: the launch is only described, so the dispatcher's decisions are testable without a device.
 inline thread_local bool t_dry = false;
 inline thread_local char t_plan[512] = "";
+// How the launch being made stages an NCHW map (" stage=rows" / " stage=blocks"; "" for every other launch): appended to
+// its record in plan mode, behind lds=, so that the form shows without a change to variant strings.  Set and put back by
+// launch_staged() alone, around its one call of launch().
+inline thread_local const char* t_stage = "";
 
 template <typename K, typename... A>
 int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
@@ -153,8 +160,8 @@ int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds, hipStr
                 grid.x, grid.y, grid.z, threads, lds);
   if (t_dry) {
     const size_t n = strlen(t_plan);
-    snprintf(t_plan + n, sizeof(t_plan) - n, "%s%s grid=(%u,%u,%u) block=%u lds=%zu", n ? "; " : "", name, grid.x, grid.y,
-             grid.z, threads, lds);
+    snprintf(t_plan + n, sizeof(t_plan) - n, "%s%s grid=(%u,%u,%u) block=%u lds=%zu%s", n ? "; " : "", name, grid.x, grid.y,
+             grid.z, threads, lds, t_stage);
     return NFP_OK;
   }
   if (int rc = set_lds(kernel, lds)) return rc;
@@ -169,6 +176,15 @@ int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds, hipStr
   }
   if (name[0] != '#') g_launches++;  // ('#': one-time setup kernels, not part of a forward / backward)
   return hip_ok(hipGetLastError(), name);
+}
+
+// launch() of fwd_band / bwd_fast on a dense NCHW map: the record names the staging form
+template <typename K, typename... A>
+int launch_staged(bool rows, const char* name, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  t_stage = rows ? " stage=rows" : " stage=blocks";
+  const int rc = launch(name, kernel, grid, block, lds, st, args...);
+  t_stage = "";
+  return rc;
 }
 
 // The hot-path kernels (nfp_band.h / nfp_fast.h / nfp_mfma.h / nfp_tile.h) are instantiated for the product form (Cosine) and
