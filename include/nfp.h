@@ -98,7 +98,16 @@ typedef struct nfp_desc {
                                 out / grad_out are then [B, 8 + 24, H, W], the 8 maps of radius 1
                                 first (torch.cat order).  Hot-path descriptors only (cosine / L2,
                                 stride 1, padding = R, workspace set)                      */
-  int32_t reserved_;         /* 0                                                           */
+  int32_t map_f32;           /* 0, or 1 with dtype = NFP_BF16: x / grad_x are bf16, out / grad_out (and the out
+                                the backward reads) are FLOAT32 [B,N,Ho,Wo] — the call torch.autocast makes: its
+                                float32 list holds cosine_similarity and linalg.norm, so a bf16 feature map yields
+                                float32 maps and takes a bf16 gradient.  `saved` as before.  NFP_E_INVALID with
+                                dtype = NFP_F32 or any other value; NFP_E_UNSUPPORTED (keep a float32 copy of x
+                                instead) with inner_R = 1, Attention, SCS and from the nfp_bias_* calls;
+                                nfp_pool_supported / nfp_gap_supported answer 0.  Additive to ABI 7: the field was
+                                reserved_ (0) and no earlier library reads it.  Cosine / dot / gfc / L2 / rmse on
+                                "same" maps run on the hot-path vector kernels (variant tag `mix`; not the
+                                matrix-core or LDS-DMA ones), everything else on the any-geometry kernels     */
 } nfp_desc;
 
 int nfp_abi_version(void);
@@ -135,13 +144,13 @@ int64_t nfp_saved_floats(const nfp_desc* d);
 
 /* NFPPooling.forward (nfp.py:132-134) for the measure in d.
  *   x      [B,C,H,W] by strides, dtype d->dtype
- *   out    [B,N,Ho,Wo] contiguous, dtype d->dtype
+ *   out    [B,N,Ho,Wo] contiguous, dtype d->dtype (float32 when d->map_f32)
  *   saved  float[nfp_saved_floats(d)] or NULL when no backward will follow
  *          (Attention on bf16 maps always needs it: the raw dots live there) */
 int nfp_forward(const nfp_desc* d, const void* x, void* out, float* saved, void* hip_stream);
 
 /* The autograd backward of the same call: grad_x = d(sum(out*grad_out))/dx.
- *   grad_out [B,N,Ho,Wo] contiguous;  out / saved as written by nfp_forward
+ *   grad_out [B,N,Ho,Wo] contiguous, the dtype of out;  out / saved as written by nfp_forward
  *   grad_x   [B,C,H,W] with the strides of x; fully overwritten */
 int nfp_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out,
                  const float* saved, void* grad_x, void* hip_stream);

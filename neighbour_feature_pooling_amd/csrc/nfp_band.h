@@ -64,7 +64,8 @@ struct FoffQ {
 // nfp_common.h).  Cosine and L2 themselves keep the finalize of round 2, constants folded: the three extra transcendental
 // instructions of the general form sit on the critical path of a 5 us kernel (4.97 vs 4.87 us at the headline shape).
 // POOL = kPoolGap: the channel sums alone beside the maps — no map staging, no map sums; scratch rows of C floats.
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool VAR = false>
+// MF: float32 maps beside bf16 storage of x (nfp_desc.map_f32: the torch.autocast call) — `out` is stored as float32.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool VAR = false, bool MF = false>
 __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, const unsigned char* __restrict__ ws,
                                                  uint32_t sB_lo, uint32_t sB_hi, int C, uint32_t hchunk, uint32_t hgeom,
                                                  void* __restrict__ out, float* __restrict__ saved,
@@ -80,6 +81,9 @@ __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, con
   const long long sB = (long long)(((unsigned long long)sB_hi << 32) | sB_lo);
   constexpr int N = Win<R>::N, NF = Win<R>::NF;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool OBF = BF && !MF;              // the maps' storage type
+  constexpr int OES = OBF ? 2 : 4;
+  static_assert(!MF || (BF && POOL == kPoolNone), "float32 maps beside bf16 x: plain maps only");
   constexpr bool MAPSUM = POOL == kPoolBoth;   // the N pooled map sums (and their staging)
   constexpr int NP = MAPSUM ? N : 0;            // map sums behind the channel sums of a scratch row
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -311,7 +315,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, con
   const float* n2 = Tt + NF * Ps;
   const int Gn = fdivi(T, Ps);
   if (glf < Gn) {
-    void* ob = (char*)out + (long long)b * N * P * ES;
+    void* ob = (char*)out + (long long)b * N * P * OES;
     const float n2p = n2[lpf];
     const float ip = VAR ? unit_or(g, inv_norm(n2p, g.inv_eps)) : inv_norm(n2p, g.inv_eps);
     int it = 0;
@@ -351,7 +355,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, con
             v = g.similarity ? -dd : dd;
           }
         }
-        if (!POOL || g.pool_map) stx(ob, n * P + pf, v, BF ? NFP_BF16 : NFP_F32);
+        if (!POOL || g.pool_map) stx(ob, n * P + pf, v, OBF ? NFP_BF16 : NFP_F32);
         if constexpr (MAPSUM) Tt[NV + n * Ps + lpf] = v;  // vm[n][p], behind the half-stencil table
       } else if constexpr (MAPSUM) {
         Tt[NV + n * Ps + lpf] = 0.f;                    // (an output another band writes: not part of this band's sum)

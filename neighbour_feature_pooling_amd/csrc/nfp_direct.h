@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256) bwd_direct(const KP g, const void* __rest
         for (int n = 0; n < g.N; ++n) {
           const int q = nbr_pixel(g, o, n);
           const long long oi = (b * g.N + n) * g.O + o;
-          const Coef cf = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.dtype), sp0, sp1, st0(q), st1(q), g);
+          const Coef cf = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, st0(q), st1(q), g);
 #pragma unroll
           for (int u = 0; u < CB; ++u) {
             const float bv = (q >= 0 && c0 + u < g.C) ? at(q, c0 + u) : 0.f;
@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(256) bwd_direct(const KP g, const void* __rest
         const int n = tap < (g.k * g.k) / 2 ? tap : tap - 1;
         const int pc = tap_pixel(g, o, g.R, g.R);
         const long long oi = (b * g.N + n) * g.O + o;
-        const Coef cf = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.dtype), st0(pc), st1(pc), st0((int)r),
+        const Coef cf = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), st0(pc), st1(pc), st0((int)r),
                                       st1((int)r), g);
 #pragma unroll
         for (int u = 0; u < CB; ++u) {

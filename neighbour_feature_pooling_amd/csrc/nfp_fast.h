@@ -670,8 +670,9 @@ struct L_BRQ {
 // POOL = kPoolGap (nfp_common.h): the head's pass — grad_out IS a map, read as the plain backward reads it, and every
 // grad_x[b,c,p] also receives ggap[b,c]/P where the pooled mode adds it.
 // ROWS: the x chunk staged by pixel rows (StagedRows above) instead of 4 x 4 blocks; the launcher's choice (nfp_hip.hip).
+// MF: float32 grad_out / out beside bf16 x / grad_x (nfp_desc.map_f32: the torch.autocast call); vector phase B only.
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0,   // GEMM: 0 vector phase B, 1 / 2 matrix cores
-          bool ROWS = false>
+          bool ROWS = false, bool MF = false>
 __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void* __restrict__ x,
                                                         const void* __restrict__ go, const void* __restrict__ out,
                                                         const float* __restrict__ saved,
@@ -681,6 +682,7 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void
                                                         const float* __restrict__ gnfpm, const KP g) {
   static_assert(!GEMM || BF, "matrix-core phase B: bf16 storage only");
   static_assert(!ROWS || (!NHWC && !GEMM), "pixel-row staging: NCHW, vector phase B");
+  static_assert(!MF || (BF && !GEMM && POOL == kPoolNone), "float32 maps beside bf16 x: plain maps, vector phase B");
   NFP_STAMP_ENTRY();
   // The HEAD (nfp_common.h: bwd_head_geom): five pointers and four dwords, 14 SGPRs handed over at wavefront start.  The
   // table rows, the pair values and the norms — the first requests — are addressed from the head alone; what does not fit
@@ -738,8 +740,10 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void
     if (g.pool_gap && t + T < ncw) ggv1 = ggap[(long long)b * C + cb0 + t + T];
   }
   constexpr int ES = BF ? 2 : 4;
-  const void* gob = (const char*)go + (long long)b * N * P * ES;
-  const void* outb = (const char*)out + (long long)b * N * P * ES;
+  constexpr bool OBF = BF && !MF;   // the maps' storage type
+  constexpr int OES = OBF ? 2 : 4;
+  const void* gob = (const char*)go + (long long)b * N * P * OES;
+  const void* outb = (const char*)out + (long long)b * N * P * OES;
   const WsLayout L = ws_layout(P, R, hmode);
   const int LQ = L.LW >> 3;  // 16-byte pieces per link row
   const uint4* lnk = (const uint4*)(ws + L.lnk);
@@ -775,17 +779,17 @@ __global__ void __launch_bounds__(GEMM ? 1024 : kBwdThreads) bwd_fast(const void
   auto rows_load = [&](int e) { rows_load_to(rw0, rw1, tqv, e); };
   // grad_out / out of this image, 16 bytes per thread and round: VP consecutive pairs (N is a multiple of 8, so
   // N*P values are whole 16-byte pieces and every image's maps start on one)
-  constexpr int VP = BF ? 8 : 4;
+  constexpr int VP = OBF ? 8 : 4;
   uint4 gq, oq, gq0, oq0;  // (the first round's piece in registers of its own: a copy made before the x block is
                            // requested would wait for the data there)
   auto pair_load_to = [&](uint4& gd, uint4& od, int o) {  // o: first pair of the piece
-    if constexpr (!GO_POOLED) gd = *(const uint4*)((const char*)gob + (long long)o * ES);
-    od = *(const uint4*)((const char*)outb + (long long)o * ES);
+    if constexpr (!GO_POOLED) gd = *(const uint4*)((const char*)gob + (long long)o * OES);
+    od = *(const uint4*)((const char*)outb + (long long)o * OES);
   };
   auto pair_load = [&](int o) { pair_load_to(gq, oq, o); };
   auto pair_value = [&](const uint4& q, int k) {  // element k of a 16-byte piece
-    const uint32_t wd = ((const uint32_t*)&q)[BF ? k >> 1 : k];
-    return BF ? __uint_as_float(k & 1 ? wd & 0xFFFF0000u : wd << 16) : __uint_as_float(wd);
+    const uint32_t wd = ((const uint32_t*)&q)[OBF ? k >> 1 : k];
+    return OBF ? __uint_as_float(k & 1 ? wd & 0xFFFF0000u : wd << 16) : __uint_as_float(wd);
   };
   // The matrix-core variant asks for its x block at entry and loads retire in order: every table row of the first
   // PRE gather rounds is requested before it (PRE rounds cover config 5's 2548 entries on 1024 threads; the launcher

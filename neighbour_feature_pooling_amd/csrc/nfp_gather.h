@@ -344,7 +344,7 @@ __global__ void __launch_bounds__(NFP_GATHER_T) bwd_gather(const KP g, const Gat
       const float sp1 = (Meas<M>::NSTAT > 1 && pc >= 0) ? sv[g.P + pc] : 0.f;
       const float sq0 = (Meas<M>::NSTAT > 0 && q >= 0) ? sv[q] : 0.f;
       const float sq1 = (Meas<M>::NSTAT > 1 && q >= 0) ? sv[g.P + q] : 0.f;
-      const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.dtype), sp0, sp1, sq0, sq1, g);
+      const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, sq0, sq1, g);
       cf[j] = c.k0;
       if (NC > 1) cf[ON + j] = c.k1;
       if (NC > 2) cf[2 * ON + j] = c.k2;
@@ -576,7 +576,7 @@ __global__ void __launch_bounds__(512) bwd_gather_banded(const KP g, const BandL
     const float sp1 = (Meas<M>::NSTAT > 1 && pc >= 0) ? sv[g.P + pc] : 0.f;
     const float sq0 = (Meas<M>::NSTAT > 0 && q >= 0) ? sv[q] : 0.f;
     const float sq1 = (Meas<M>::NSTAT > 1 && q >= 0) ? sv[g.P + q] : 0.f;
-    const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.dtype), sp0, sp1, sq0, sq1, g);
+    const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, sq0, sq1, g);
     cf[j] = c.k0;
     if (NC > 1) cf[ON + j] = c.k1;
     if (NC > 2) cf[2 * ON + j] = c.k2;

@@ -31,6 +31,9 @@ int make_kp(const nfp_desc* d, KP* g) {
   if (d->pad_mode < 0 || d->pad_mode > 3) return fail(NFP_E_INVALID, "bad pad_mode %d", d->pad_mode);
   if (d->measure < 0 || d->measure >= NFP_MEASURE_COUNT) return fail(NFP_E_INVALID, "bad measure %d", d->measure);
   if (d->dtype != NFP_F32 && d->dtype != NFP_BF16) return fail(NFP_E_INVALID, "bad dtype %d", d->dtype);
+  if (d->map_f32 != 0 && d->map_f32 != 1) return fail(NFP_E_INVALID, "bad map_f32 %d (0 or 1)", d->map_f32);
+  if (d->map_f32 == 1 && d->dtype != NFP_BF16)
+    return fail(NFP_E_INVALID, "map_f32 = 1 goes with dtype = NFP_BF16 (float32 storage already has float32 maps)");
   const int k = 2 * d->R + 1;
   const int span = d->dilation * (k - 1) + 1;
   if (d->H + 2 * d->pad < span || d->W + 2 * d->pad < span)
@@ -63,8 +66,9 @@ int make_kp(const nfp_desc* d, KP* g) {
   // measure itself — value and autograd gradient (abs: sign, 0 at 0) are those of Norm p = 1 on the difference weights
   // (nfp.py:141-148: LA.norm(ord=1) = sum |.|, backward sgn), so every kernel serves it as that
   if (d->measure == NFP_EMD) { g->measure = NFP_NORM; g->diff = 1; }
-  g->godtype = d->dtype;
-  g->odtype = d->dtype;
+  // map_f32 (the torch.autocast call): out / grad_out in float32 beside bf16 x / grad_x — nfp_launch.h::mixed_maps
+  g->godtype = d->map_f32 ? NFP_F32 : d->dtype;
+  g->odtype = d->map_f32 ? NFP_F32 : d->dtype;
   g->p = d->measure == NFP_EMD ? 1.f : d->p; g->eps = d->eps; g->q_scs = d->q_scs;
   g->sB = d->sxB; g->sC = d->sxC; g->sH = d->sxH; g->sW = d->sxW;
   g->gB = d->sgB != 0 ? d->sgB : d->sxB;
@@ -386,7 +390,7 @@ int chunk_channels(const KP& g, int total, int T, int G, bool nhwc, int budget) 
 #ifndef NFP_BAND_WGS
 #define NFP_BAND_WGS 256
 #endif
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone>
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
 int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
                       float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
   constexpr int NF = Win<R>::NF;
@@ -447,7 +451,7 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   const size_t lds = slab + tail;
   if (lds > (size_t)kLdsMax) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "fwd_band<R%s,%s,%s,%s%s>x%d", R == 12 ? "1+2" : (R == 1 ? "1" : "2"), hot_name(g),
-           BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
+           MF ? "mix" : (BF ? "bf16" : "f32"), NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
   if (nb_out) *nb_out = nb;
   // the kernel's preloadable head (nfp_common.h): what stands in front of its first x request
   const uint32_t sB_lo = (uint32_t)((unsigned long long)g.sB & 0xFFFFFFFFull), sB_hi = (uint32_t)((unsigned long long)g.sB >> 32);
@@ -465,14 +469,21 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — pool_forward_rm)
   if constexpr (M != kSymTerm)
   if (g.unit || g.gfc || g.d2s != 1.f)   // DotProduct / GFC / RMSE: the finalize with the run-time constants
-    return go(fwd_band<R, M, BF, NHWC, POOL, true>);
-  return go(fwd_band<R, M, BF, NHWC, POOL, false>);
+    return go(fwd_band<R, M, BF, NHWC, POOL, true, MF>);
+  return go(fwd_band<R, M, BF, NHWC, POOL, false, MF>);
 }
 
 template <int R, int M>
 int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
   if (g.ws == nullptr) return kNotApplicable;
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  if (mixed_maps(g)) {   // float32 maps beside bf16 x: the cosine and L2 instantiations (with their dot / gfc / rmse riders)
+    if constexpr (R != 12 && (M == NFP_COSINE || M == NFP_NORM))
+      return nhwc ? launch_fwd_band_t<R, M, true, true, kPoolNone, true>(g, x, out, saved, st)
+                  : launch_fwd_band_t<R, M, true, false, kPoolNone, true>(g, x, out, saved, st);
+    else
+      return kNotApplicable;   // (Norm p = 1 and the symmetric-term measures: the any-geometry kernels)
+  }
   if (bf) return nhwc ? launch_fwd_band_t<R, M, true, true>(g, x, out, saved, st)
                       : launch_fwd_band_t<R, M, true, false>(g, x, out, saved, st);
   return nhwc ? launch_fwd_band_t<R, M, false, true>(g, x, out, saved, st)
@@ -487,7 +498,7 @@ size_t bwd_pair_bytes(const KP& g, int M, int N) {
 }
 constexpr size_t kEarlyBudget = 96 * 1024;  // slab beside the pair values (committed during phase A) up to this much LDS
 
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone>
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
 int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                       hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
@@ -535,7 +546,7 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
   const size_t lds = g.early ? fixed + pairs + slab : fixed + std::max(pairs, slab);
   if (lds > (size_t)kLdsMax) return kNotApplicable;  // tables + slab do not fit: the generic kernels serve it
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%s,%s,%s,%s%s>", R == 12 ? "1+2" : (R == 1 ? "1" : "2"),
-           hot_name(g), BF ? "bf16" : "f32", NHWC ? "nhwc" : "nchw", pool_tag(POOL));
+           hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"), NHWC ? "nhwc" : "nchw", pool_tag(POOL));
   // NCHW staging form (nfp_fast.h: StagedRows).  By pixel rows for ONE class: float32, k = 3, plain maps, the cosine and L2
   // instantiations (with their dot / gfc / rmse riders; Norm p = 1 and the symmetric-term measures keep the blocks: an
   // instantiation more each for measures no in-tree model uses), a single chunk (Cc covers the workgroup's channels), at
@@ -550,10 +561,10 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
                            saved, g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
   }
   if constexpr (!NHWC)
-    return launch_staged(false, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
+    return launch_staged(false, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
                          g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
   else
-    return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws, hgeom,
+    return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws, hgeom,
                   g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
 }
 
@@ -564,6 +575,7 @@ template <int R, int M>
 int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
                     float* nfpm = nullptr) {
   if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 15) || g.P > 512) return kNotApplicable;
+  if (mixed_maps(g)) return kNotApplicable;   // (the Gram-form L2 loses digits a float32 map would show: DESIGN §4)
   if (g.unit || g.gfc || g.d2s != 1.f) return kNotApplicable;   // (DotProduct / GFC / RMSE: the vector kernels' run-time constants)
   if (!g.contig && (((uintptr_t)x & 15) || ((g.sB * 2) & 15))) return kNotApplicable;  // 16-byte fragment loads
   const int nt = (g.P + 31) / 32, D = std::min(nt - 1, (g.R * g.W + g.R + 31) / 32);
@@ -593,7 +605,7 @@ template <int R, int M, bool NHWC, int POOL = kPoolNone>
 int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                       hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
-  if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 31)) return kNotApplicable;
+  if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 31) || mixed_maps(g)) return kNotApplicable;
   if (NHWC && (((uintptr_t)x & 15) || ((g.sB * 2) & 15) || ((uintptr_t)gx & 15) || ((g.gB * 2) & 15)))
     return kNotApplicable;  // 16-byte staging loads and grad_x stores
   int S = (NFP_BWD_WGS + g.B - 1) / g.B;  // channel blocks per image, whole 32-channel tiles each
@@ -700,6 +712,13 @@ template <int R, int M>
 int launch_bwd_vec(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                    hipStream_t st) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  if (mixed_maps(g)) {   // (as launch_fwd_band)
+    if constexpr (R != 12 && (M == NFP_COSINE || M == NFP_NORM))
+      return nhwc ? launch_bwd_fast_t<R, M, true, true, kPoolNone, true>(g, x, go, out, saved, gx, st)
+                  : launch_bwd_fast_t<R, M, true, false, kPoolNone, true>(g, x, go, out, saved, gx, st);
+    else
+      return kNotApplicable;
+  }
   if (bf) return nhwc ? launch_bwd_fast_t<R, M, true, true>(g, x, go, out, saved, gx, st)
                       : launch_bwd_fast_t<R, M, true, false>(g, x, go, out, saved, gx, st);
   return nhwc ? launch_bwd_fast_t<R, M, false, true>(g, x, go, out, saved, gx, st)
@@ -710,7 +729,9 @@ template <int R, int M>
 int launch_bwd_fast(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                     hipStream_t st) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (bf) {
+  // (float32 maps beside bf16 x: the vector form — the matrix-core backward stages grad_out / out under an LDS budget sized
+  // for 2-byte values)
+  if (bf && !mixed_maps(g)) {
     const int rc = nhwc ? launch_bwd_gemm_t<R, M, true>(g, x, go, out, saved, gx, st)
                         : launch_bwd_gemm_t<R, M, false>(g, x, go, out, saved, gx, st);
     if (rc != kNotApplicable) return rc;
@@ -823,10 +844,19 @@ KP as_dot(const KP& g) {
   return d;
 }
 
+// map_f32 descriptors nfp_forward / nfp_backward do not serve (include/nfp.h): the caller keeps its float32 copy of x
+int mixed_refused(const nfp_desc* d) {
+  if (!d->map_f32) return NFP_OK;
+  if (d->inner_R != 0 || d->measure == NFP_ATTENTION || d->measure == NFP_SCS)
+    return fail(NFP_E_UNSUPPORTED, "map_f32: one radius, every measure but Attention / SharpenedCosine");
+  return NFP_OK;
+}
+
 int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
   if (!x || !out) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (int rc = mixed_refused(d)) return rc;
   if (g.B == 0) return NFP_OK;
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.rs == 12) {
@@ -922,6 +952,7 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
   if (int rc = make_kp(d, &g)) return rc;
   if (!x || !grad_out || !out || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
   if ((stats_of(g.measure) > 0 || g.measure == NFP_ATTENTION) && !saved) return fail(NFP_E_INVALID, "measure %d needs the saved state of nfp_forward", g.measure);
+  if (int rc = mixed_refused(d)) return rc;
   if (g.B == 0) return NFP_OK;
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.rs == 12) {
@@ -1260,7 +1291,7 @@ static int pool_plan(const KP& g, bool backward) {
 }
 
 static bool pool_measure_ok(const KP& g) {
-  return g.rs != 12 && hot_measure(g);
+  return g.rs != 12 && hot_measure(g) && !mixed_maps(g);   // (map_f32: nfp_forward / nfp_backward only)
 }
 
 int nfp_pool_supported(const nfp_desc* d) {
@@ -1348,7 +1379,7 @@ static int gap_plan(const KP& g, bool backward) {
 }
 
 // The gap calls also take radii (1, 2) together (inner_R = 1: make_kp); Norm p = 1 / EMD are outside hot_measure.
-static bool gap_measure_ok(const KP& g) { return hot_measure(g); }
+static bool gap_measure_ok(const KP& g) { return hot_measure(g) && !mixed_maps(g); }   // (map_f32: nfp_forward / nfp_backward only)
 
 int nfp_gap_supported(const nfp_desc* d) {
   KP g;
@@ -1408,6 +1439,7 @@ int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, co
 static int bias_kp(const nfp_desc* d, KP* g, int* dw) {
   if (int rc = make_kp(d, g)) return rc;
   if (d->inner_R != 0) return fail(NFP_E_UNSUPPORTED, "biased NFP: one radius per call (inner_R = 0)");
+  if (d->map_f32 != 0) return fail(NFP_E_UNSUPPORTED, "biased NFP: maps in the storage type (map_f32 = 0)");
   if (d->measure == NFP_SCS)
     return fail(NFP_E_UNSUPPORTED, "biased NFP: measure %d (SharpenedCosine mixes batch elements) has no HIP kernel", d->measure);
   g->measure = d->measure;

@@ -210,6 +210,10 @@ inline const char* hot_name(const KP& g) {
     return g.measure == NFP_GEMAN ? "geman" : (g.measure == NFP_CANBERRA ? "canberra" : (g.measure == NFP_SQUAREDCHORD ? "sqchord" : (g.measure == NFP_HELLINGER ? "hellinger" : (g.measure == NFP_JEFFREY ? "jeffrey" : "chisq1"))));
   return g.measure == NFP_COSINE ? "cos" : (g.measure == NFP_DOT ? "dot" : (g.measure == NFP_GFC ? "gfc" : (g.measure == NFP_RMSE ? "rmse" : "l2")));
 }
+// nfp_desc.map_f32 (the torch.autocast call): bf16 x / grad_x with float32 out / grad_out.  make_kp writes it as the pair
+// (dtype, odtype) — the only descriptors whose maps' type differs from the storage type on the way into the hot-path
+// launchers (Attention's float32 dots never reach them with bf16 storage).
+inline bool mixed_maps(const KP& g) { return g.dtype == NFP_BF16 && g.odtype == NFP_F32; }
 inline bool force_generic() { return g_sw.force_generic.load(std::memory_order_relaxed) != 0; }
 inline int round4(int v) { return (v + 3) & ~3; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

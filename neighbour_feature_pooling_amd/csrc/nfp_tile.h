@@ -353,12 +353,16 @@ __device__ __forceinline__ float wave_sum(float v) {
 // (cosine: one instruction per channel pair and direction), half the LDS bytes of the float4 slab.  With several channel
 // chunks the NEXT chunk's DMA runs under the current chunk's sums (two slabs).  See the block in the kernel.
 // POOL = kPoolGap (nfp_common.h): the channel sums alone, rows of C floats — no map staging, no map sums.
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool DMA = false>
+// MF: float32 maps beside bf16 storage of x (nfp_desc.map_f32: the torch.autocast call) — `out` is stored as float32.
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool DMA = false, bool MF = false>
 __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
                                                  void* __restrict__ out, float* __restrict__ saved,
                                                  float* __restrict__ part, float* __restrict__ gap, float* __restrict__ nfpm) {
   constexpr int N = Win<R>::N, NF = Win<R>::NF;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool OBF = BF && !MF;   // the maps' storage type
+  constexpr int OES = OBF ? 2 : 4;
+  static_assert(!MF || (BF && POOL == kPoolNone && !DMA), "float32 maps beside bf16 x: plain maps, register staging");
   constexpr bool MAPSUM = POOL == kPoolBoth;   // the N pooled map sums (and their staging)
   constexpr int NP = MAPSUM ? N : 0;            // map sums behind the channel sums of a scratch row
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -654,7 +658,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
     const int p = ps.y * W + ps.x;
     // (buffer stores: one offset register for all N maps of the pixel, the map through the scalar offset)
     // (POOL without a backward to follow: nobody reads the maps — an empty resource drops the stores in the memory pipeline)
-    const Rsrc ob = make_rsrc((char*)out + (long long)b * N * P * ES, (!POOL || g.pool_map) ? (long long)N * P * ES : 0);
+    const Rsrc ob = make_rsrc((char*)out + (long long)b * N * P * OES, (!POOL || g.pool_map) ? (long long)N * P * OES : 0);
     auto one = [&](int n, auto statc) {
       constexpr bool stat = decltype(statc)::value;
       int dy, dx;
@@ -681,9 +685,9 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? 8 : 4)) fwd_t
         val = fin_dist(g, g.diff ? pairv : fq);  // 'Norm' quirk (nfp.py:74 vs 85): |neighbour|
       }
       if constexpr (stat)
-        store_1<BF>(ob, p, n * P, val);
+        store_1<OBF>(ob, p, n * P, val);
       else
-        store_1<BF>(ob, n * P + p, 0, val);
+        store_1<OBF>(ob, n * P + p, 0, val);
       if constexpr (MAPSUM) vm[n * nbpA + lpf] = val;
     };
     if (G == 1) {  // (the usual case on large maps: every tap's offsets are compile-time constants)
@@ -770,13 +774,17 @@ __global__ void __launch_bounds__(256) pool_fold(const float* __restrict__ part,
 // out[opp n][r + d], equal up to the forward's rounding; the pull of both on |x_r| uses r's own copy, so that only the
 // gradients travel through LDS.)
 // POOL = kPoolGap: grad_out IS a map, read as the plain backward reads it; ggap[b,c] / P joins in the same store.
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool CST = false>
+// MF: float32 grad_out / out beside bf16 x / grad_x (nfp_desc.map_f32).
+template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool CST = false, bool MF = false>
 __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8) : 4)) bwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
                                                 const void* __restrict__ go, const void* __restrict__ out,
                                                 const float* __restrict__ saved, void* __restrict__ gx,
                                                 const float* __restrict__ ggap, const float* __restrict__ gnfpm) {
   constexpr int N = Win<R>::N, K = Win<R>::K, K2 = Win<R>::K2;
   constexpr int ES = BF ? 2 : 4;
+  constexpr bool OBF = BF && !MF;   // the maps' storage type
+  constexpr int OES = OBF ? 2 : 4;
+  static_assert(!MF || (BF && POOL == kPoolNone), "float32 maps beside bf16 x: plain maps only");
   constexpr bool GO_POOLED = POOL == kPoolBoth, HAS_GAP = POOL != kPoolNone;   // what grad_out is / whether grad(GAP) joins
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   lds_poison(lds4, tg.ldsw);
@@ -801,8 +809,8 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
   float* Wr = (float*)(slab + dump + 1) + 2 * K2;           // (2 K2 floats of slack either side: shifted reads)
   const Rsrc xb = make_rsrc((const char*)x + (long long)b * g.sB * ES, (long long)g.C * P * ES);
   const Rsrc gxb = make_rsrc((char*)gx + (long long)b * g.gB * ES, (long long)g.C * P * ES);
-  const Rsrc gob = make_rsrc((const char*)go + (long long)b * N * P * ES, GO_POOLED ? 0 : (long long)N * P * ES);
-  const Rsrc outb = make_rsrc((const char*)out + (long long)b * N * P * ES, (long long)N * P * ES);
+  const Rsrc gob = make_rsrc((const char*)go + (long long)b * N * P * OES, GO_POOLED ? 0 : (long long)N * P * OES);
+  const Rsrc outb = make_rsrc((const char*)out + (long long)b * N * P * OES, (long long)N * P * OES);
   // (DotProduct has no saved norms: an empty resource, every load reads 0)
   const Rsrc svb = make_rsrc((const char*)saved + (long long)b * P * 4, (M == NFP_COSINE && !g.unit) ? (long long)P * 4 : 0);
   NFP_STAMP_INIT();
@@ -814,7 +822,7 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
   float w[K2], sv[N];
   float dfn = 0.f, ipr = 1.f;
   {
-    const int ep = ps.real ? ps.y * W + ps.x : Oob<BF>::e;
+    const int ep = ps.real ? ps.y * W + ps.x : Oob<OBF>::e;
     float gov[N];
     // Cosine: a RING position needs the similarity of every pair that ends on it — the output of its real neighbour's
     // opposite tap (plane N-1-n at pixel u + d_n).  Same load instruction as everybody's own outputs: the plane
@@ -835,10 +843,10 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
       int e = ep + n * P;
       if (M == NFP_COSINE) {
         e = ea + n * P + (((N - 1 - 2 * n) * P + dy * W + dx) & rm);
-        e = (rbad[dy + R] || cbad[dx + R]) ? Oob<BF>::e : e;
+        e = (rbad[dy + R] || cbad[dx + R]) ? Oob<OBF>::e : e;
       }
-      sv[n] = M == kNormP1 ? 0.f : load_1<BF>(outb, e, 0);   // (p = 1: the gradient does not depend on the distance)
-      gov[n] = GO_POOLED ? 0.f : load_1<BF>(gob, ep, n * P);
+      sv[n] = M == kNormP1 ? 0.f : load_1<OBF>(outb, e, 0);   // (p = 1: the gradient does not depend on the distance)
+      gov[n] = GO_POOLED ? 0.f : load_1<OBF>(gob, ep, n * P);
     }
     float nrm = 0.f;
     if (M == NFP_COSINE) nrm = load_1<false>(svb, ps.src | ps.zf, 0);

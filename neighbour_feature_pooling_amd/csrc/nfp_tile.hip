@@ -41,6 +41,7 @@ bool tile_ok(const KP& g, const void* x, const void* gx) {
   const int es = g.dtype == NFP_F32 ? 4 : 2;
   // 32-bit buffer offsets inside an image, and room for the "reads zero" offset (nfp_tile.h::Oob)
   if ((long long)std::max(g.C, g.N) * g.P * es >= 0x7ffffff0LL) return false;
+  if (mixed_maps(g) && (long long)g.N * g.P * 4 >= 0x7ffffff0LL) return false;   // (float32 maps beside bf16 x)
   if (!g.contig) {
     const uintptr_t m = g.dtype == NFP_F32 ? 15 : 7;
     if (((uintptr_t)x & m) || ((uintptr_t)gx & m) || ((g.sB * es) & m) || ((g.gB * es) & m)) return false;
@@ -75,7 +76,8 @@ int tile_groups(const KP& g, int nb, int npu, int cap, int cq) {
   return lg;
 }
 
-template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone>
+// MF: float32 maps beside bf16 x (mixed_maps, nfp_launch.h) — the register-staged kernel, not the LDS-DMA one
+template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone, bool MF = false>
 int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* part = nullptr, int* nb_out = nullptr,
                       float* gap = nullptr, float* nfpm = nullptr) {
   constexpr int NF = Win<R>::NF, N = Win<R>::N;
@@ -117,7 +119,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
       bool dma = false;
       const int dma_sw = g_sw.tile_dma.load(std::memory_order_relaxed);
       const bool dma_auto = BF && (g.C * 2) % 128 == 0;   // (8 pieces per position and chunk: where it measured faster)
-      if ((dma_sw == 1 || (dma_sw < 0 && dma_auto)) && M != nfp::kSymTerm && NHWC && !POOL && G == 1 && !g.gfc && (g.C * (BF ? 2 : 4)) % 16 == 0 &&
+      if (!MF && (dma_sw == 1 || (dma_sw < 0 && dma_auto)) && M != nfp::kSymTerm && NHWC && !POOL && G == 1 && !g.gfc && (g.C * (BF ? 2 : 4)) % 16 == 0 &&
           !(((uintptr_t)x) & 15) && !((g.sB * (BF ? 2 : 4)) & 15)) {
         const int tp = g.C * (BF ? 2 : 4) / 16, npu64 = (npu + 63) & ~63;
         for (int lpc = 3; lpc >= 0; --lpc) {
@@ -135,31 +137,31 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
       }
       nfp::TileGeo tg = {nb, rows, Wu, ppb, 1, g.H / nb, g.H % nb, (int)(lds / 4)};
       if (nb_out) *nb_out = POOL ? nb * nfp::kPoolSub : nb;   // (pooled: rows of partial sums per image)
-      snprintf(g_variant, sizeof(g_variant), "fwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), BF ? "bf16" : "f32",
+      snprintf(g_variant, sizeof(g_variant), "fwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"),
                NHWC ? "nhwc" : "nchw", dma ? ",dma" : "", pool_tag(POOL), nb);
       const dim3 block(G, Wu, rows);
       // (tile_ids' exact range: batches beyond kTileMaxGrid workgroups go out as several launches, images in order)
-      const int es = BF ? 2 : 4, bmax = std::max(8, (tile_max_grid() / nb) & ~7);
+      const int es = BF ? 2 : 4, oes = MF ? 4 : es, bmax = std::max(8, (tile_max_grid() / nb) & ~7);
       for (int b0 = 0; b0 < g.B; b0 += bmax) {
         KP gs = g;
         gs.B = std::min(bmax, g.B - b0);
         const dim3 grid((unsigned)(gs.B * nb));
         const void* xs = (const char*)x + (long long)b0 * g.sB * es;
-        void* os = (char*)out + (long long)b0 * N * g.P * es;
+        void* os = (char*)out + (long long)b0 * N * g.P * oes;
         float* ss = saved ? saved + (long long)b0 * g.P : nullptr;
         float* ps = part ? part + (long long)b0 * nb * nfp::kPoolSub * (g.C + NP) : nullptr;
         float* gs_ = gap ? gap + (long long)b0 * g.C : nullptr;
         float* ns_ = nfpm ? nfpm + (long long)b0 * N : nullptr;
         int rc;
         if (M == NFP_COSINE && g.gfc) {
-          rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, M == NFP_COSINE>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
+          rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, M == NFP_COSINE, false, MF>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
         } else if (dma) {
-          if constexpr (NHWC && !POOL)
+          if constexpr (NHWC && !POOL && !MF)
             rc = launch("fwd_tile_dma", fwd_tile<R, M, BF, true, false, false, true>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
           else
             rc = kNotApplicable;
         } else {
-          rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, false>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
+          rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, false, false, MF>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
         }
         if (rc != NFP_OK) return rc;
       }
@@ -169,7 +171,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   return kNotApplicable;
 }
 
-template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone>
+template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone, bool MF = false>
 int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                       const float* ggap = nullptr, const float* gnfpm = nullptr) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
@@ -222,24 +224,24 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
 #define NFP_TILE_CST_MINB (BF ? 80 : 256)
 #endif
       const bool cst = NHWC && G == 1 && g.C * (BF ? 2 : 4) >= NFP_TILE_CST_MINB && npu <= 640;
-      snprintf(g_variant, sizeof(g_variant), "bwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), BF ? "bf16" : "f32",
+      snprintf(g_variant, sizeof(g_variant), "bwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"),
                NHWC ? "nhwc" : "nchw", cst ? ",dense" : "", pool_tag(POOL), nb);
       const std::true_type T_;
       const std::false_type F_;
-      const int es = BF ? 2 : 4, bmax = std::max(8, (tile_max_grid() / (nb * S)) & ~7);
+      const int es = BF ? 2 : 4, oes = MF ? 4 : es, bmax = std::max(8, (tile_max_grid() / (nb * S)) & ~7);
       for (int b0 = 0; b0 < g.B; b0 += bmax) {   // (tile_ids' exact range: see launch_fwd_tile_t)
         KP gs = g;
         gs.B = std::min(bmax, g.B - b0);
         const dim3 grid((unsigned)(gs.B * nb * S));
         const void* xs = (const char*)x + (long long)b0 * g.sB * es;
-        const void* gos = go ? (const char*)go + (long long)b0 * N * g.P * es : nullptr;
-        const void* os = (const char*)out + (long long)b0 * N * g.P * es;
+        const void* gos = go ? (const char*)go + (long long)b0 * N * g.P * oes : nullptr;
+        const void* os = (const char*)out + (long long)b0 * N * g.P * oes;
         const float* ss = saved ? saved + (long long)b0 * g.P : nullptr;
         void* gxs = (char*)gx + (long long)b0 * g.gB * es;
         const float* ggs = ggap ? ggap + (long long)b0 * g.C : nullptr;
         const float* gns = gnfpm ? gnfpm + (long long)b0 * N : nullptr;
         auto go_ = [&](auto gfc, auto cstv) {
-          return launch("bwd_tile", bwd_tile<R, M, BF, NHWC, POOL, decltype(gfc)::value, decltype(cstv)::value>, grid, block, lds, st,
+          return launch("bwd_tile", bwd_tile<R, M, BF, NHWC, POOL, decltype(gfc)::value, decltype(cstv)::value, MF>, grid, block, lds, st,
                         gs, tg, xs, gos, os, ss, gxs, ggs, gns);
         };
         int rc;
@@ -266,6 +268,13 @@ template <int R, int M, int POOL>
 int fwd_rm(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* part, int* nb, float* gap = nullptr,
            float* nfpm = nullptr) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  if (mixed_maps(g)) {   // float32 maps beside bf16 x: plain cosine / L2 maps (with their riders); the rest is the any-geometry kernels'
+    if constexpr (POOL == nfp::kPoolNone && (M == NFP_COSINE || M == NFP_NORM))
+      return nhwc ? launch_fwd_tile_t<R, M, true, true, POOL, true>(g, x, out, saved, st, part, nb, gap, nfpm)
+                  : launch_fwd_tile_t<R, M, true, false, POOL, true>(g, x, out, saved, st, part, nb, gap, nfpm);
+    else
+      return kNotApplicable;
+  }
   if (bf) return nhwc ? launch_fwd_tile_t<R, M, true, true, POOL>(g, x, out, saved, st, part, nb, gap, nfpm)
                       : launch_fwd_tile_t<R, M, true, false, POOL>(g, x, out, saved, st, part, nb, gap, nfpm);
   return nhwc ? launch_fwd_tile_t<R, M, false, true, POOL>(g, x, out, saved, st, part, nb, gap, nfpm)
@@ -275,6 +284,13 @@ template <int R, int M, int POOL>
 int bwd_rm(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
            const float* ggap, const float* gnfpm) {
   const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
+  if (mixed_maps(g)) {   // (as fwd_rm)
+    if constexpr (POOL == nfp::kPoolNone && (M == NFP_COSINE || M == NFP_NORM))
+      return nhwc ? launch_bwd_tile_t<R, M, true, true, POOL, true>(g, x, go, out, saved, gx, st, ggap, gnfpm)
+                  : launch_bwd_tile_t<R, M, true, false, POOL, true>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+    else
+      return kNotApplicable;
+  }
   if (bf) return nhwc ? launch_bwd_tile_t<R, M, true, true, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm)
                       : launch_bwd_tile_t<R, M, true, false, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm);
   return nhwc ? launch_bwd_tile_t<R, M, false, true, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm)

@@ -44,7 +44,8 @@ struct NfpNode : torch::autograd::Function<NfpNode> {
   static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
     c10::DeviceGuard guard(x.device());
     const nfp_desc* d = desc_of(desc);
-    Tensor out = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
+    // (d->map_f32: bf16 x with float32 maps — the torch.autocast call, include/nfp.h)
+    Tensor out = torch::empty(oshape, (d->map_f32 ? x.options().dtype(torch::kFloat32) : x.options()).memory_format(at::MemoryFormat::Contiguous));
     Tensor saved = torch::empty({ns}, x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous));
     check(nfp_forward(d, x.data_ptr(), out.data_ptr(), ns > 0 ? saved.data_ptr<float>() : nullptr, stream_of(x)));
     ctx->save_for_backward({x, out, saved, desc});
@@ -56,7 +57,7 @@ struct NfpNode : torch::autograd::Function<NfpNode> {
     const Tensor &x = sv[0], &out = sv[1], &saved = sv[2], &desc = sv[3];
     c10::DeviceGuard guard(x.device());
     Tensor go = grads[0].contiguous();
-    if (go.scalar_type() != x.scalar_type()) go = go.to(x.scalar_type());
+    if (go.scalar_type() != out.scalar_type()) go = go.to(out.scalar_type());   // (grad_out in the maps' type: x's, or float32)
     Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
     check(nfp_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
                        saved.numel() ? saved.data_ptr<float>() : nullptr, gx.data_ptr(), stream_of(x)));

@@ -6,6 +6,8 @@ pixel.  Nothing else can serve a CUDA tensor: if the library is missing or refus
 the configuration the call raises.  CPU tensors use `_host.nfp_host` (see there).
 """
 import ctypes
+import dataclasses
+import os
 from collections import OrderedDict
 from dataclasses import dataclass
 
@@ -31,6 +33,8 @@ class NfpConfig:
     diff_weights: bool = True      # raw measure string in ['norm','rmse','mahalanobis'] (nfp.py:74)
     inner_R: int = 0               # 1 with R = 2: also the maps of radius 1 (padding 1), first in the channel axis —
                                    # the concatenation models/nfp_heads.py:80-118 builds from two layers
+    map_f32: int = 0               # 1 with a bf16 x: float32 maps, a bf16 gradient (nfp_desc.map_f32) — set by `nfp` itself
+                                   # for a bf16 map under torch.autocast, never by a module's constructor
 
     @property
     def kernel_size(self):
@@ -150,6 +154,7 @@ def build_desc(shape, strides, dtype, cfg):
     d.sxB, d.sxC, d.sxH, d.sxW = strides
     d.sgB = d.C * d.H * d.W          # grad_x is always allocated dense, in x's inner layout
     d.inner_R = int(cfg.inner_R)
+    d.map_f32 = int(cfg.map_f32)
     return d
 
 
@@ -251,10 +256,11 @@ class _Plan:
     over the descriptor's own bytes (what the C++ nodes take and save for their backward: the tensor keeps the descriptor
     alive, in the cache or not), the output shape, the floats of saved state and `no_bwd` — None when nfp_backward serves
     the descriptor too, else the library's message: forward and backward envelopes differ for a few large maps, and a call
-    that will need a gradient must fail in forward(), not inside loss.backward().  `cacheable` is False for the table-less
+    that will need a gradient must fail in forward(), not inside loss.backward(); `no_fwd` likewise for nfp_forward (asked
+    of map_f32 plans alone: the native autocast call needs both directions).  `cacheable` is False for the table-less
     plan of a geometry first seen under a graph capture: it says nothing about later calls.  Whatever else the library
     says about the descriptor (`ask`) is kept here too, so that nothing about a plan outlives it."""
-    __slots__ = ("desc", "desc_tensor", "nhwc", "oshape", "saved_floats", "no_bwd", "cacheable", "_asked")
+    __slots__ = ("desc", "desc_tensor", "nhwc", "oshape", "saved_floats", "no_bwd", "no_fwd", "cacheable", "_asked")
 
     def __init__(self, desc, layout, cacheable=True):
         self.desc = desc
@@ -263,6 +269,7 @@ class _Plan:
         self.oshape = output_shape(desc)
         self.saved_floats = 0
         self.no_bwd = None
+        self.no_fwd = None
         self.cacheable = cacheable
         self._asked = {}
 
@@ -290,6 +297,8 @@ def _plan(x, layout, cfg):
         buf = ctypes.create_string_buffer(1024)
         if L.nfp_plan(ctypes.byref(d), 1, buf, len(buf)) != 0:
             plan.no_bwd = L.nfp_last_error().decode()
+        if d.map_f32 and L.nfp_plan(ctypes.byref(d), 0, buf, len(buf)) != 0:
+            plan.no_fwd = L.nfp_last_error().decode()
         plan.saved_floats = int(L.nfp_saved_floats(ctypes.byref(d)))
         if plan.cacheable:
             _plans_put(key, plan)
@@ -366,7 +375,7 @@ def nfp_forward_call(x, cfg, need_grad, ns=None):
     x, plan = _planned(x, cfg)
     ns = _scratch_len(_saved_len(plan, cfg, x.dtype, need_grad), ns)
     with _on_device(x.device):
-        out = torch.empty(plan.oshape, dtype=x.dtype, device=x.device)
+        out = torch.empty(plan.oshape, dtype=torch.float32 if plan.desc.map_f32 else x.dtype, device=x.device)
         saved = torch.empty(ns, dtype=torch.float32, device=x.device)
         _abi.check(L.nfp_forward(ctypes.byref(plan.desc), x.data_ptr(), out.data_ptr(),
                                  saved.data_ptr() if ns > 0 else None, _raw_stream(x.device)))
@@ -376,7 +385,7 @@ def nfp_forward_call(x, cfg, need_grad, ns=None):
 def nfp_backward_call(x, plan, out, saved, grad_out):
     """grad_x from nfp_backward; (x, plan) as `_planned` or the forward call gave them."""
     L = _abi.load()
-    go = _grad_out_as(grad_out, x.dtype)
+    go = _grad_out_as(grad_out, out.dtype)      # (the maps' type: x's, or float32 for a map_f32 plan)
     with _on_device(x.device):
         gx = _empty_grad_x(x, plan.nhwc)
         _abi.check(L.nfp_backward(ctypes.byref(plan.desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
@@ -495,6 +504,32 @@ def _amp_input(x):
     return x, None
 
 
+_MIXED_CFGS = {}      # cfg -> the same with map_f32 = 1
+
+
+def _autocast_native(x, cfg):
+    """(x as launched, plan, the map_f32 configuration) of the native torch.autocast call — bf16 x in, float32 maps out, a bf16 grad_x back
+    (nfp_desc.map_f32): no float32 copy of x, no cast of the gradient — or None where `_amp_input`'s upcast serves:
+    anything but a bf16 CUDA map under autocast, torch.compile, SharpenedCosine / Attention, two radii at once, a
+    descriptor the library does not plan in both directions, or NFP_AMP_UPCAST=1 (read at call time: a safety valve).
+    OPT-IN: taken only with NFP_AMP_NATIVE=1 in the environment (read at call time).  The timing that was to decide, per
+    shape class, whether this call replaces the upcast has not been made; until it is, the upcast stays the
+    default for every class."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and torch.is_autocast_enabled("cuda")):
+        return None
+    if (torch.compiler.is_compiling() or cfg.measure in ("scs", "attention") or cfg.inner_R
+            or os.environ.get("NFP_AMP_NATIVE") != "1" or os.environ.get("NFP_AMP_UPCAST") == "1"):
+        return None
+    mcfg = _MIXED_CFGS.get(cfg)
+    if mcfg is None:
+        mcfg = _MIXED_CFGS[cfg] = dataclasses.replace(cfg, map_f32=1)
+    try:
+        xd, plan = _planned(x, mcfg)
+    except _abi.NfpError:
+        return None
+    return (xd, plan, mcfg) if plan.no_fwd is None and plan.no_bwd is None else None
+
+
 def nfp_pool(x, cfg, want_gap=True):
     """(GAP(x) [B,C], GAP(NFP(x)) [B,N]) — NFP_Pooling.py:27-31.  Fused on the GPU where supported,
     otherwise the same two reductions composed from `nfp` and torch ops.  want_gap = False: (None, GAP(NFP(x))) — the
@@ -549,6 +584,11 @@ def nfp_multi_radius(x, cfg1, cfg2):
     padding = R): what MultiRadiusNFPHead.forward computes with two layers (models/nfp_heads.py:109-110).  On the GPU
     both radii come from ONE pass over x (and one backward pass) where the hot-path kernels serve the map; otherwise
     the two maps are computed one after the other."""
+    xin, cast = _amp_input(x)       # (autocast / float16: the float32 upcast, also where the two layers run one by one)
+    if xin is not x:
+        with torch.autocast("cuda", enabled=False):
+            out = nfp_multi_radius(xin, cfg1, cfg2)
+        return out if cast is None else out.to(cast)
     cfg = multi_radius_config(cfg1, cfg2) if x.is_cuda and x.dim() == 4 else None
     if cfg is not None:
         try:
@@ -568,6 +608,16 @@ def nfp(x, cfg):
     """[B,C,H,W] -> [B, k*k-1, H', W'] neighbour-similarity maps (NFPPooling.forward, nfp.py:132-134)."""
     if x.dim() != 4:
         raise RuntimeError(f"NFP expects a 4-D [B,C,H,W] feature map, got {tuple(x.shape)}")
+    native = _autocast_native(x, cfg)
+    if native is not None:
+        xd, plan, mcfg = native
+        need_grad = x.requires_grad and torch.is_grad_enabled()
+        with torch.autocast("cuda", enabled=False):
+            cpp = _cpp_nodes()
+            if cpp:
+                return _cpp_call(cpp.nfp_apply, xd, plan.desc_tensor, list(plan.oshape),
+                                 _saved_len(plan, mcfg, x.dtype, need_grad), plan.nhwc)
+            return _NfpHip.apply(xd, mcfg, need_grad)     # (xd is dense: the node's own `_dense` copies nothing)
     xin, cast = _amp_input(x)
     if xin is not x:
         with torch.autocast("cuda", enabled=False):
