@@ -155,3 +155,23 @@ def test_map_f32_zero_plans_what_it_did(lib, kw, fwd, bwd):
     for back, general in ((False, "fwd_pairs |"), (True, "bwd_gather |")):
         rc, text = plan(lib, f, back)
         assert rc == 0 and "mix" not in text and (",f32," in text or text.startswith(general)), text
+
+
+@pytest.mark.parametrize("family,seed", [("table", 5151), ("band", 5152), ("general", 5153)])
+def test_the_stress_seeds_plan_onto_their_family(lib, family, seed):
+    """tests/test_gpu_mixed.py runs 24 draws of scripts/stress_mixed.py per family and fails a case the intended kernels do
+    not serve: the descriptors of those seeds, planned here without a GPU."""
+    import random
+    from test_gpu_parity import _load_script
+    sm = _load_script("stress_mixed")
+    rnd = random.Random(seed)
+    plans = []
+    for _ in range(24):
+        case = sm.draw(rnd, family)
+        fwd, bwd = sm.planned(case)
+        assert sm.in_family(family, fwd, bwd), (sm.describe(case), fwd, bwd)
+        plans.append((fwd, bwd))
+    if family == "band":
+        assert any(",dense>" in bwd for _, bwd in plans)
+    if family == "general":
+        assert ("fwd_pairs", "bwd_gather") in plans
