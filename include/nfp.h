@@ -236,6 +236,31 @@ int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias
                       float* grad_centre_bias, float* grad_neighbour_bias, float* scratch, int64_t scratch_floats,
                       void* hip_stream);
 
+/*
+ * The tail of models/nfp_heads.py::SimilarityAwarePooling.forward (nfp_heads.py:224-232) on the maps an NFP layer has
+ * produced: att_proj (a trainable 1x1 conv N -> 1: w [N], b [1]), a softmax over the P = Ho*Wo pixels and the
+ * attention-weighted sum — six ATen launches in the reference, one kernel each way here (csrc/nfp_attpool.hip):
+ *   l_p = b + sum_n w_n m_np      att = softmax_p(l)      pooled_n = sum_p att_p m_np
+ *   maps    [B,N,P] dense (the layer's [B,N,Ho,Wo] output), dtype = enum nfp_dtype; w, b, pooled [B,N], att [B,P] and
+ *           every gradient but grad_maps are float32 DEVICE pointers; all arithmetic is float32
+ *   att     written for the backward; NULL when none will follow
+ * nfp_attpool_backward, given grad_pooled [B,N] and the att the forward wrote: grad_maps [B,N,P] in the maps' dtype (one
+ * rounding), grad_w [N] and grad_b [1] — sums over the batch in image order through per-image partials in `scratch`
+ * (nfp_attpool_scratch_floats(B, N) = B*(N+1) floats, min 1; needed only with grad_w or grad_b).  Each of the three may be
+ * NULL: it is then neither computed nor written.  No atomics: two runs agree bitwise, and image b's pooled / grad_maps do
+ * not depend on B.  The launch counter moves by 1 (forward), by 1 or — with grad_w or grad_b — 2 (backward);
+ * nfp_last_variant names attpool_fwd<f32|bf16> / attpool_bwd<f32|bf16>.
+ * NFP_E_INVALID, launching nothing (checked before any HIP call): a NULL required pointer, B < 0, N < 1, P < 1, an unknown
+ * dtype, a scratch shorter than nfp_attpool_scratch_floats.  NFP_E_UNSUPPORTED: N*P >= 2^31, N > 1024.  B = 0 returns
+ * NFP_OK without a launch (and writes nothing).  Additive to ABI 7: no descriptor, no workspace.
+ */
+int64_t nfp_attpool_scratch_floats(int32_t B, int32_t N);
+int nfp_attpool_forward(int32_t B, int32_t N, int64_t P, int32_t dtype, const void* maps, const float* w, const float* b,
+                        float* pooled, float* att, void* hip_stream);
+int nfp_attpool_backward(int32_t B, int32_t N, int64_t P, int32_t dtype, const void* maps, const float* w, const float* att,
+                         const float* grad_pooled, void* grad_maps, float* grad_w, float* grad_b, float* scratch,
+                         int64_t scratch_floats, void* hip_stream);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

@@ -7,14 +7,16 @@ Drop-in for the reference's NFP hot path:
     nfp_op, nfp_pool, NfpConfig      functional forms (autograd ops over libnfp_hip.so)
     nfp_with_gap, NFPWithGap         <- gap(fmap) and nfp(fmap) of one feature map, the first step of models/nfp_heads.py's heads
                                         (NFPWithGap over a MultiRadiusNFPPooling: MultiRadiusNFPHead's gap + 32 maps, one pass)
+    SimilarityAwarePooling           <- models/nfp_heads.py::SimilarityAwarePooling (attention-weighted sum of unpadded NFP maps)
+    nfp_attention_pool               its tail (1x1 conv, softmax over the pixels, weighted sum) as one op
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
-from .functional import NfpConfig, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_with_gap
+from .functional import NfpConfig, nfp_attention_pool, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_with_gap
 from .functional import nfp as nfp_op  # (`nfp` itself is the submodule holding NFPPooling)
-from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPPooling, NFPWithGap
+from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPPooling, NFPWithGap, SimilarityAwarePooling
 from .pooling import nfp_pooling
 from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
 
 __all__ = ["NFPPooling", "EnhancedNFPPooling", "MultiRadiusNFPPooling", "nfp_pooling", "nfp_op", "nfp_pool", "nfp_pooled",
-           "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap"]
+           "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool"]
 __version__ = "0.4.0"

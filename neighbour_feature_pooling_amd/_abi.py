@@ -22,7 +22,8 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_backward", "nfp_pool_supported", "nfp_pool_saved_floats", "nfp_pool_forward", "nfp_pool_backward", "nfp_launch_count",
            "nfp_last_variant", "nfp_plan", "nfp_reload_env", "nfp_workspace_bytes", "nfp_workspace_init", "nfp_time_next_launch",
            "nfp_bias_saved_floats", "nfp_bias_scratch_floats", "nfp_bias_forward", "nfp_bias_backward",
-           "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward"]
+           "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward",
+           "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward"]
 
 
 class NfpDesc(ctypes.Structure):
@@ -93,6 +94,12 @@ def load():
         L.nfp_gap_saved_floats.restype = i64
         L.nfp_gap_forward.argtypes = [dp, vp, vp, vp, vp, i64, vp]
         L.nfp_gap_backward.argtypes = [dp, vp, vp, vp, vp, vp, i64, vp, vp]
+    if hasattr(L, "nfp_attpool_forward"):       # (absent only from an older library loaded for an A/B run)
+        i32 = ctypes.c_int32
+        L.nfp_attpool_scratch_floats.argtypes = [i32, i32]
+        L.nfp_attpool_scratch_floats.restype = i64
+        L.nfp_attpool_forward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp]
+        L.nfp_attpool_backward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

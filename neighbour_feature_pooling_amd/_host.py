@@ -106,3 +106,14 @@ def nfp_host(x, cfg, centre_bias=None, neighbour_bias=None):
             r = 1 - r
         return r.mean(dim=1)
     raise RuntimeError(f"Similarity measure {m} not implemented")
+
+
+def attention_pool_host(maps, w, b):
+    """The tail of SimilarityAwarePooling.forward (models/nfp_heads.py:224-232) in plain torch ops, any dtype and device:
+    maps [B,N,...] -> [B,N], att = softmax over the pixels of the 1x1 conv (w [N] or [1,N,1,1], b [1]) of the maps, the
+    maps summed under it.  Autograd differentiates."""
+    B, N = maps.shape[:2]
+    m = maps.reshape(B, N, -1)
+    logits = (m * w.reshape(1, N, 1).to(m.dtype)).sum(1) + b.reshape(1, 1).to(m.dtype)
+    att = torch.softmax(logits, dim=-1)
+    return (m * att.unsqueeze(1)).sum(-1)

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libnfp_hip.so")
-SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip"]   # three translation units, compiled in parallel
+SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip"]   # four translation units, compiled in parallel
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)

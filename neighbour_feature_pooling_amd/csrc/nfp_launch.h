@@ -1,5 +1,6 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI,
-// table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True)).  Separate
+// table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
+// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 #pragma once
 #include <hip/hip_runtime.h>

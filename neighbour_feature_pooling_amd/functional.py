@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _abi
-from ._host import nfp_host
+from ._host import attention_pool_host, nfp_host
 
 
 @dataclass(frozen=True)
@@ -879,3 +879,88 @@ def nfp_biased(x, cfg, centre_bias, neighbour_bias):
     if x.is_cuda:
         return _NfpBiasHip.apply(x, centre_bias, neighbour_bias, cfg)
     return nfp_host(x, cfg, centre_bias, neighbour_bias)
+
+
+# ---- the softmax-pool tail of SimilarityAwarePooling — include/nfp.h: nfp_attpool_* (csrc/nfp_attpool.hip) ----------------
+def attpool_forward_call(maps, w, b, need_grad):
+    """(pooled [B,N] float32, att [B,P] float32 or None) from nfp_attpool_forward on dense CUDA maps [B,N,...] and float32
+    w [N], b [1].  need_grad = False: att is not written (NULL in the library)."""
+    L = _abi.load()
+    B, N = maps.shape[:2]
+    P = maps.numel() // (B * N)
+    with _on_device(maps.device):
+        pooled = torch.empty(B, N, dtype=torch.float32, device=maps.device)
+        att = torch.empty(B, P, dtype=torch.float32, device=maps.device) if need_grad else None
+        _abi.check(L.nfp_attpool_forward(B, N, P, _DTYPES[maps.dtype], maps.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                         pooled.data_ptr(), att.data_ptr() if need_grad else None, _raw_stream(maps.device)))
+    return pooled, att
+
+
+def attpool_backward_call(maps, w, att, grad_pooled, want_maps, want_w, want_b):
+    """(grad_maps in the maps' dtype, grad_w [N], grad_b [1]) from nfp_attpool_backward — None for each gradient nobody
+    wants (a NULL pointer in the library: neither computed nor written)."""
+    L = _abi.load()
+    B, N = maps.shape[:2]
+    P = maps.numel() // (B * N)
+    gp = grad_pooled.contiguous().float()
+    with _on_device(maps.device):
+        gm = torch.empty_like(maps) if want_maps else None
+        gw = torch.empty(N, dtype=torch.float32, device=maps.device) if want_w else None
+        gb = torch.empty(1, dtype=torch.float32, device=maps.device) if want_b else None
+        ns = int(L.nfp_attpool_scratch_floats(B, N)) if (want_w or want_b) else 0
+        scratch = torch.empty(ns, dtype=torch.float32, device=maps.device) if ns else None
+        _abi.check(L.nfp_attpool_backward(B, N, P, _DTYPES[maps.dtype], maps.data_ptr(), w.data_ptr(), att.data_ptr(),
+                                          gp.data_ptr(), gm.data_ptr() if want_maps else None,
+                                          gw.data_ptr() if want_w else None, gb.data_ptr() if want_b else None,
+                                          scratch.data_ptr() if ns else None, ns, _raw_stream(maps.device)))
+    return gm, gw, gb
+
+
+class _AttPoolHip(torch.autograd.Function):
+    """pooled [B,N] float32 of dense CUDA maps and float32 (w [N], b [1]); one kernel each way plus the batch reduce of the
+    parameters' gradients.  need_grad: some input requires a gradient and grad mode is on, sampled by the caller."""
+
+    @staticmethod
+    def forward(ctx, maps, w, b, need_grad):
+        pooled, att = attpool_forward_call(maps, w, b, need_grad)
+        if need_grad:
+            ctx.save_for_backward(maps, w, att)
+        return pooled
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_pooled):
+        maps, w, att = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        gm, gw, gb = attpool_backward_call(maps, w, att, grad_pooled, want[0], want[1], want[2])
+        return gm, gw, gb, None
+
+
+def _attpool_hip_serves(maps):
+    """The HIP tail serves dense CUDA float32 / bfloat16 maps of a non-empty batch, outside torch.compile (where the tail is
+    traced as ATen ops), unless NFP_SAP_TORCH=1 (read at call time) asks for the torch formulation."""
+    return (not torch.compiler.is_compiling() and maps.is_cuda and maps.dtype in _DTYPES and maps.is_contiguous()
+            and maps.shape[0] > 0 and os.environ.get("NFP_SAP_TORCH") != "1")
+
+
+def nfp_attention_pool(maps, weight, bias):
+    """SimilarityAwarePooling's tail (models/nfp_heads.py:224-232): maps [B,N,H',W'] (or [B,N,P]) -> [B,N], the maps summed
+    under softmax_over_pixels(att_proj(maps)), att_proj a 1x1 conv N -> 1 given by weight ([1,N,1,1] or [N]) and bias [1].
+    Dense CUDA float32 / bfloat16 maps run one HIP kernel each way (include/nfp.h: nfp_attpool_*; float32 arithmetic, the
+    result cast once to the maps' dtype; gradients for the maps, the weight and the bias, each only where wanted);
+    everything else — CPU, float16, float64, strided maps, torch.compile, NFP_SAP_TORCH=1 — the torch formulation
+    `_host.attention_pool_host`.  Under torch.autocast the inputs are taken as float32 and the result is float32, the
+    reference's output type there (its softmax is on autocast's float32 list)."""
+    if maps.dim() < 3:
+        raise RuntimeError(f"nfp_attention_pool expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
+    if weight.numel() != maps.shape[1] or bias.numel() != 1:
+        raise RuntimeError(f"nfp_attention_pool: {maps.shape[1]} maps need a weight of {maps.shape[1]} elements and a bias "
+                           f"of 1, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    if maps.is_cuda and torch.is_autocast_enabled("cuda"):
+        with torch.autocast("cuda", enabled=False):
+            return nfp_attention_pool(maps.float(), weight.float(), bias.float())
+    if not _attpool_hip_serves(maps):
+        return attention_pool_host(maps, weight, bias)
+    need_grad = torch.is_grad_enabled() and (maps.requires_grad or weight.requires_grad or bias.requires_grad)
+    pooled = _AttPoolHip.apply(maps, weight.reshape(-1).float().contiguous(), bias.reshape(-1).float(), need_grad)
+    return pooled if pooled.dtype == maps.dtype else pooled.to(maps.dtype)

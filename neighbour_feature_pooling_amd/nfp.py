@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from . import _abi
-from .functional import NfpConfig, gap_servable, multi_radius_config, nfp, nfp_biased, nfp_multi_radius, nfp_with_gap
+from .functional import (NfpConfig, gap_servable, multi_radius_config, nfp, nfp_attention_pool, nfp_biased, nfp_multi_radius,
+                         nfp_with_gap)
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -218,3 +219,33 @@ class NFPWithGap(nn.Module):
             raise RuntimeError(f"NFPPooling expected input with {layer.in_channels} channels, "
                                f"got {x.shape[1]} channels instead")
         return nfp_with_gap(x, layer.config)
+
+
+class SimilarityAwarePooling(nn.Module):
+    """Drop-in for models/nfp_heads.py::SimilarityAwarePooling (nfp_heads.py:204-232): the NFP maps of an unpadded layer,
+    a trainable 1x1 conv `att_proj` over them, a softmax over the pixels, and the maps summed under that attention —
+    [B,C,H,W] -> [B,N].  Same constructor, attributes and state-dict keys (nfp.comp_neighbors.weight,
+    nfp.center_value.weight, att_proj.weight, att_proj.bias, the nfp.* biases with bias=True); the 7x7 CPU probe is drawn
+    before att_proj is built, as in the reference, so the same seed gives bit-identical att_proj parameters.  On the GPU
+    the tail behind the layer is one HIP kernel each way (functional.nfp_attention_pool)."""
+
+    def __init__(self, in_channels=512, R=1, measure='cosine', **kwargs):
+        super().__init__()
+        # (`padding` in kwargs: TypeError, a keyword given twice — as in the reference, nfp_heads.py:208-214)
+        self.nfp = EnhancedNFPPooling(in_channels=in_channels, R=R, measure=measure, padding=0, **kwargs)
+        if not self.nfp.bias:
+            # The reference's layer draws the weights of its two depthwise convs before it overwrites them (nfp.py:42-59);
+            # NFPPooling(bias=False) here draws nothing, so the same draws are made — and dropped — at this point: the probe
+            # and att_proj then see the RNG where the reference's do.  (bias=True: the layer has built both convs itself.)
+            C, k = int(in_channels), self.nfp.kernel_size
+            nn.Conv2d(C, self.nfp.out_channels * C, k, groups=C, bias=False)
+            nn.Conv2d(C, C, k, groups=C, bias=False)
+        with torch.no_grad():                                   # nfp_heads.py:216-219
+            nfp_out = self.nfp(torch.randn(1, in_channels, 7, 7))
+        nfp_channels = nfp_out.shape[1]
+        self.att_proj = nn.Conv2d(nfp_channels, 1, kernel_size=1)
+        self.softmax = nn.Softmax(dim=-1)
+        self.nfp_channels = nfp_channels
+
+    def forward(self, x):
+        return nfp_attention_pool(self.nfp(x), self.att_proj.weight, self.att_proj.bias)
