@@ -261,6 +261,28 @@ int nfp_attpool_backward(int32_t B, int32_t N, int64_t P, int32_t dtype, const v
                          const float* grad_pooled, void* grad_maps, float* grad_w, float* grad_b, float* scratch,
                          int64_t scratch_floats, void* hip_stream);
 
+/*
+ * NFP on VALID maps — stride 1, dilation 1, pad = 0, R = 1 or 2: the layer inside every block of
+ * models/nfp_heads.py::NFPBottleneck (nfp_heads.py:234-278) and in front of SimilarityAwarePooling's softmax.  Kernels of
+ * their own (csrc/nfp_valid.hip: fwd_valid / bwd_valid), one launch each way, no workspace, no atomics: two runs agree
+ * bitwise and image b's results do not depend on B.  out / grad_out are [B, N, H-2R, W-2R] contiguous in d->dtype, exactly
+ * what nfp_forward writes for the descriptor; grad_x is fully overwritten, border pixels included.
+ *   nfp_valid_supported(d)     1: both calls below will launch (a host-only dry run; 4 KiB-aligned buffers assumed)
+ *   nfp_valid_saved_floats(d)  floats of `saved` (|x| per input pixel for cosine / gfc, else 0); -1 for a malformed d
+ * Served: cosine / dot / gfc / Norm p = 2 / rmse (the distances on the difference weights), either `similarity`,
+ * float32 / bf16, rows of W <= 128 pixels, any height and batch the descriptor allows; images dense in NCHW order (any
+ * C) or in channels-last order (C % 4 == 0 for float32, C % 8 == 0 for bf16, images on 16-byte boundaries), any batch
+ * stride.  NFP_E_UNSUPPORTED, launching nothing: everything else — pad != 0, map_f32 = 1, inner_R != 0, other measures,
+ * wider rows.  The length convention of the bias / gap calls: a `saved` shorter than nfp_valid_saved_floats(d) returns
+ * NFP_E_INVALID and launches nothing (forward: `saved` may be NULL when no backward follows).  B = 0 returns NFP_OK
+ * without a launch.  nfp_last_variant names fwd_valid<R,prod|dist,f32|bf16,nchw|nhwc> / bwd_valid<...>.  Additive to ABI 7.
+ */
+int nfp_valid_supported(const nfp_desc* d);
+int64_t nfp_valid_saved_floats(const nfp_desc* d);
+int nfp_valid_forward(const nfp_desc* d, const void* x, void* out, float* saved, int64_t saved_floats, void* hip_stream);
+int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out, const float* saved,
+                       int64_t saved_floats, void* grad_x, void* hip_stream);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

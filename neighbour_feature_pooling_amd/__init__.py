@@ -9,14 +9,17 @@ Drop-in for the reference's NFP hot path:
                                         (NFPWithGap over a MultiRadiusNFPPooling: MultiRadiusNFPHead's gap + 32 maps, one pass)
     SimilarityAwarePooling           <- models/nfp_heads.py::SimilarityAwarePooling (attention-weighted sum of unpadded NFP maps)
     nfp_attention_pool               its tail (1x1 conv, softmax over the pixels, weighted sum) as one op
+    NFPBottleneck                    <- models/nfp_heads.py::NFPBottleneck (a residual block around an unpadded cosine NFP layer)
+    nfp_valid                        `nfp_op` for padding = 0 on the valid-map kernels (one launch each way)
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
-from .functional import NfpConfig, nfp_attention_pool, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_with_gap
+from .functional import NfpConfig, nfp_attention_pool, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_valid, nfp_with_gap
 from .functional import nfp as nfp_op  # (`nfp` itself is the submodule holding NFPPooling)
-from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPPooling, NFPWithGap, SimilarityAwarePooling
+from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPBottleneck, NFPPooling, NFPWithGap, SimilarityAwarePooling
 from .pooling import nfp_pooling
 from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
 
 __all__ = ["NFPPooling", "EnhancedNFPPooling", "MultiRadiusNFPPooling", "nfp_pooling", "nfp_op", "nfp_pool", "nfp_pooled",
-           "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool"]
+           "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool",
+           "NFPBottleneck", "nfp_valid"]
 __version__ = "0.4.0"

@@ -23,7 +23,8 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_last_variant", "nfp_plan", "nfp_reload_env", "nfp_workspace_bytes", "nfp_workspace_init", "nfp_time_next_launch",
            "nfp_bias_saved_floats", "nfp_bias_scratch_floats", "nfp_bias_forward", "nfp_bias_backward",
            "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward",
-           "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward"]
+           "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
+           "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward"]
 
 
 class NfpDesc(ctypes.Structure):
@@ -100,6 +101,12 @@ def load():
         L.nfp_attpool_scratch_floats.restype = i64
         L.nfp_attpool_forward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp]
         L.nfp_attpool_backward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    if hasattr(L, "nfp_valid_forward"):         # (absent only from an older library loaded for an A/B run)
+        L.nfp_valid_supported.argtypes = [dp]
+        L.nfp_valid_saved_floats.argtypes = [dp]
+        L.nfp_valid_saved_floats.restype = i64
+        L.nfp_valid_forward.argtypes = [dp, vp, vp, vp, i64, vp]
+        L.nfp_valid_backward.argtypes = [dp, vp, vp, vp, vp, i64, vp, vp]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

@@ -11,6 +11,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libnfp_hip.so")
 SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip"]   # four translation units, compiled in parallel
+# ... and the fifth, the valid-map kernels (padding 0).  A list of its own: tests/test_sap_host.py pins SOURCES at the four
+# units above, so the library's units are ALL_SOURCES.
+VALID_SOURCES = ["nfp_valid.hip"]
+ALL_SOURCES = SOURCES + VALID_SOURCES
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)
@@ -36,7 +40,7 @@ def hipcc_path():
 
 
 def compile_hip(out_lib, extra_flags=(), verbose=False):
-    """hipcc: every source of SOURCES to an object (in parallel), then one shared library."""
+    """hipcc: every source of ALL_SOURCES to an object (in parallel), then one shared library."""
     import concurrent.futures as cf
     import tempfile
     with tempfile.TemporaryDirectory(prefix="nfp_build_") as tmp:
@@ -47,8 +51,8 @@ def compile_hip(out_lib, extra_flags=(), verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             return obj
-        with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-            objs = list(ex.map(one, SOURCES))
+        with cf.ThreadPoolExecutor(max_workers=len(ALL_SOURCES)) as ex:
+            objs = list(ex.map(one, ALL_SOURCES))
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc", "-o", out_lib] + objs
         if verbose:
             print(" ".join(cmd))

@@ -1432,6 +1432,73 @@ int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, co
   return finish(rc, "nfp_gap_backward");
 }
 
+// ---- valid maps (padding 0): nfp_valid.hip ---------------------------------------------------------------------------------
+// Both launchers in plan mode, so that a 1 means nfp_valid_forward AND nfp_valid_backward will launch (4 KiB-aligned
+// buffers assumed, as nfp_plan does); nothing of the calling thread's variant / plan / error strings changes.
+static int valid_plan(const KP& g, bool backward) {
+  const bool was_dry = t_dry;
+  char keep_variant[sizeof(g_variant)], keep_plan[sizeof(t_plan)], keep_err[sizeof(g_err)];
+  memcpy(keep_variant, g_variant, sizeof(keep_variant));
+  memcpy(keep_plan, t_plan, sizeof(keep_plan));
+  memcpy(keep_err, g_err, sizeof(keep_err));
+  t_dry = true;
+  void* fake = (void*)(uintptr_t)0x1000;
+  const int rc = backward ? valid_backward(g, fake, fake, fake, (const float*)fake, fake, nullptr)
+                          : valid_forward(g, fake, fake, (float*)fake, nullptr);
+  t_dry = was_dry;
+  memcpy(g_variant, keep_variant, sizeof(keep_variant));
+  memcpy(t_plan, keep_plan, sizeof(keep_plan));
+  memcpy(g_err, keep_err, sizeof(keep_err));
+  return rc;
+}
+
+int nfp_valid_supported(const nfp_desc* d) {
+  KP g;
+  char keep_err[sizeof(g_err)];
+  memcpy(keep_err, g_err, sizeof(keep_err));
+  const bool ok = make_kp(d, &g) == NFP_OK && valid_refusal(g) == nullptr &&
+                  (g.B == 0 || (valid_plan(g, false) == NFP_OK && valid_plan(g, true) == NFP_OK));
+  memcpy(g_err, keep_err, sizeof(keep_err));
+  return ok ? 1 : 0;
+}
+
+int64_t nfp_valid_saved_floats(const nfp_desc* d) {
+  KP g;
+  if (make_kp(d, &g)) return -1;
+  if (valid_refusal(g) != nullptr) return 0;
+  return (int64_t)stats_of(g.measure) * g.B * g.P;   // |x| per input pixel (cosine / gfc)
+}
+
+static int valid_kp(const nfp_desc* d, KP* g) {
+  if (int rc = make_kp(d, g)) return rc;
+  if (const char* why = valid_refusal(*g)) return fail(NFP_E_UNSUPPORTED, "valid maps: %s", why);
+  return NFP_OK;
+}
+
+int nfp_valid_forward(const nfp_desc* d, const void* x, void* out, float* saved, int64_t saved_floats, void* hip_stream) {
+  KP g;
+  if (int rc = valid_kp(d, &g)) return rc;
+  if (g.B > 0 && (!x || !out)) return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = nfp_valid_saved_floats(d);
+  if (saved != nullptr && saved_floats < need)
+    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_valid_saved_floats is %lld", (long long)saved_floats, (long long)need);
+  if (g.B == 0) return NFP_OK;
+  return finish(valid_forward(g, x, out, saved, (hipStream_t)hip_stream), "nfp_valid_forward");
+}
+
+int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out, const float* saved,
+                       int64_t saved_floats, void* grad_x, void* hip_stream) {
+  KP g;
+  if (int rc = valid_kp(d, &g)) return rc;
+  if (g.B > 0 && (!x || !grad_out || !out || !grad_x)) return fail(NFP_E_INVALID, "null tensor pointer");
+  const int64_t need = nfp_valid_saved_floats(d);
+  if (need > 0 && (saved == nullptr || saved_floats < need))
+    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_valid_saved_floats is %lld", (long long)(saved ? saved_floats : 0),
+                (long long)need);
+  if (g.B == 0) return NFP_OK;
+  return finish(valid_backward(g, x, grad_out, out, saved, grad_x, (hipStream_t)hip_stream), "nfp_valid_backward");
+}
+
 // ---- ABI 7: NFPPooling(bias=True) — nfp_bias.hip ---------------------------------------------------------------------
 // The descriptor's own measure: make_kp serves EMD as Norm p = 1 on the difference weights, which a bias on the
 // neighbour side breaks (|(a + bc) - (x_n + beta)| is not |(a - x_n) + beta|).  The difference weights are applied by the

@@ -1,6 +1,6 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI,
 // table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
-// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail).  Separate
+// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -245,5 +245,13 @@ int bias_forward(const KP& g, int dw, const void* x, const float* bc, const floa
                  float* dots, hipStream_t st);
 int bias_backward(const KP& g, int dw, const void* x, const float* bc, const float* beta, const void* go, const void* out,
                   const float* saved, void* gx, float* gbc, float* gbeta, float* scratch, hipStream_t st);
+
+// ---- valid maps: stride 1, dilation 1, padding 0 (nfp_valid.hip; include/nfp.h: nfp_valid_*) --------------------------------
+// valid_refusal: why the descriptor lies outside the kernels' set (measure, geometry, layout), or null.  The two launchers
+// return NFP_OK or an NFP_E_* code (NFP_E_UNSUPPORTED also for channels-last images off 16-byte boundaries); g_variant
+// names the launch.
+const char* valid_refusal(const KP& g);
+int valid_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st);
+int valid_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st);
 
 }  // namespace nfp_host

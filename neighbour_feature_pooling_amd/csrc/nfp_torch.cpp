@@ -1,9 +1,9 @@
 // nfp_torch.cpp — C++ autograd nodes over the C ABI of libnfp_hip.so (include/nfp.h).
 //
 // The reference's NFP is a chain of ATen ops whose autograd graph PyTorch builds (nfp.py:132-159); here one
-// forward and one backward kernel stand for it, and these three torch::autograd::Function classes are the graph
+// forward and one backward kernel stand for it, and these torch::autograd::Function classes are the graph
 // nodes.  They do what functional.py's Python autograd.Functions do — allocate out / saved / grad_x, take torch's
-// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_*) — without the Python
+// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_* / nfp_valid_*) — without the Python
 // interpreter on the launch path: eager host cost per forward + backward drops from ~75 us to the autograd
 // engine's own (scripts/host_overhead.py).  No device code in this file; plain pointers go across the ABI.
 //
@@ -136,8 +136,37 @@ struct NfpGapNode : torch::autograd::Function<NfpGapNode> {
   }
 };
 
+// The maps of an unpadded layer on the valid-map kernels (nfp_valid_forward / nfp_valid_backward): NfpNode with the length
+// convention of those calls.  ns = 0: no backward will follow (nothing is saved, `saved` goes over as NULL).
+struct NfpValidNode : torch::autograd::Function<NfpValidNode> {
+  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+    c10::DeviceGuard guard(x.device());
+    Tensor out = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
+    Tensor saved = torch::empty({ns}, x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous));
+    check(nfp_valid_forward(desc_of(desc), x.data_ptr(), out.data_ptr(), ns > 0 ? saved.data_ptr<float>() : nullptr, ns,
+                            stream_of(x)));
+    ctx->save_for_backward({x, out, saved, desc});
+    ctx->saved_data["nhwc"] = nhwc;
+    return out;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto sv = ctx->get_saved_variables();
+    const Tensor &x = sv[0], &out = sv[1], &saved = sv[2], &desc = sv[3];
+    c10::DeviceGuard guard(x.device());
+    Tensor go = grads[0].contiguous();
+    if (go.scalar_type() != out.scalar_type()) go = go.to(out.scalar_type());
+    Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
+    check(nfp_valid_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
+                             saved.numel() ? saved.data_ptr<float>() : nullptr, saved.numel(), gx.data_ptr(), stream_of(x)));
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 Tensor nfp_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return NfpNode::apply(x, desc, oshape, ns, nhwc);
+}
+Tensor nfp_valid_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+  return NfpValidNode::apply(x, desc, oshape, ns, nhwc);
 }
 std::vector<Tensor> nfp_pool_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc, bool want_gap,
                                    bool need_grad) {
@@ -154,5 +183,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nfp_apply", &nfp_apply, "NFPPooling.forward as one autograd node (nfp_forward / nfp_backward)");
   m.def("nfp_pool_apply", &nfp_pool_apply, "the fused nfp_pooling tail as one autograd node (nfp_pool_forward / _backward)");
   m.def("nfp_gap_apply", &nfp_gap_apply, "GAP(x) beside the full maps as one autograd node (nfp_gap_forward / _backward)");
+  m.def("nfp_valid_apply", &nfp_valid_apply, "an unpadded layer's maps as one autograd node (nfp_valid_forward / _backward)");
   m.attr("desc_bytes") = (int64_t)sizeof(nfp_desc);
 }

@@ -964,3 +964,103 @@ def nfp_attention_pool(maps, weight, bias):
     need_grad = torch.is_grad_enabled() and (maps.requires_grad or weight.requires_grad or bias.requires_grad)
     pooled = _AttPoolHip.apply(maps, weight.reshape(-1).float().contiguous(), bias.reshape(-1).float(), need_grad)
     return pooled if pooled.dtype == maps.dtype else pooled.to(maps.dtype)
+
+
+# ---- valid maps: stride 1, dilation 1, padding 0 — include/nfp.h: nfp_valid_* (csrc/nfp_valid.hip) -------------------------
+def _valid_plan(x, layout, cfg):
+    """The _Plan of a valid-map call — a plan of its own, without a workspace (the kernels keep no tables); what the library
+    says about it is `ask("nfp_valid_supported")` and `ask("nfp_valid_saved_floats")`."""
+    key = ("valid", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
+    plan = _plans_get(key)
+    if plan is None:
+        plan = _Plan(make_desc(x, cfg, layout), layout)
+        _plans_put(key, plan)
+    return plan
+
+
+def _valid_layout(x, cfg):
+    """The layout in which fwd_valid / bwd_valid read this call in place, or None where `nfp` serves it: NFP_VALID_OFF=1
+    (read at call time), torch.compile, a CPU tensor, another dtype, images that are not dense, or a descriptor
+    nfp_valid_supported refuses (another measure, rows above 128 pixels, channels-last maps off the alignment rule)."""
+    if (torch.compiler.is_compiling() or not (x.is_cuda and x.dtype in _DTYPES) or cfg.inner_R or cfg.map_f32
+            or os.environ.get("NFP_VALID_OFF") == "1"):
+        return None
+    if not hasattr(_abi.load(), "nfp_valid_forward"):      # (an older library loaded for an A/B run)
+        return None
+    layout = _in_place_layout(x.shape, x.stride(), x.element_size(), x.data_ptr())
+    if layout is None or not _valid_plan(x, layout, cfg).ask("nfp_valid_supported"):
+        return None
+    return layout
+
+
+def valid_forward_call(x, layout, cfg, need_grad):
+    """(out, saved, plan) from nfp_valid_forward on a call `_valid_layout` accepted; `saved` (|x| per pixel for cosine / gfc)
+    is kept only with a backward to follow."""
+    L = _abi.load()
+    plan = _valid_plan(x, layout, cfg)
+    ns = max(plan.ask("nfp_valid_saved_floats"), 0) if need_grad else 0
+    with _on_device(x.device):
+        out = torch.empty(plan.oshape, dtype=x.dtype, device=x.device)
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_valid_forward(ctypes.byref(plan.desc), x.data_ptr(), out.data_ptr(),
+                                       saved.data_ptr() if ns > 0 else None, ns, _raw_stream(x.device)))
+    return out, saved, plan
+
+
+def valid_backward_call(x, plan, out, saved, grad_out):
+    """grad_x from nfp_valid_backward: dense, in x's inner layout."""
+    L = _abi.load()
+    go = _grad_out_as(grad_out, out.dtype)
+    with _on_device(x.device):
+        gx = _empty_grad_x(x, plan.nhwc)
+        _abi.check(L.nfp_valid_backward(ctypes.byref(plan.desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
+                                        saved.data_ptr() if saved.numel() else None, saved.numel(), gx.data_ptr(),
+                                        _raw_stream(x.device)))
+    return gx
+
+
+class _NfpValidHip(torch.autograd.Function):
+    """The maps of an unpadded layer: one fwd_valid launch, one bwd_valid launch."""
+
+    @staticmethod
+    def forward(ctx, x, layout, cfg, need_grad):
+        out, saved, ctx.plan = valid_forward_call(x, layout, cfg, need_grad)
+        if need_grad:
+            ctx.save_for_backward(x, out, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, saved = ctx.saved_tensors
+        return valid_backward_call(x, ctx.plan, out, saved, grad_out), None, None, None
+
+
+def nfp_valid(x, cfg):
+    """`nfp(x, cfg)` for an unpadded layer — cfg.padding == 0, stride 1, dilation 1 (ValueError otherwise): [B,C,H,W] ->
+    [B, k*k-1, H-2R, W-2R], as models/nfp_heads.py::NFPBottleneck runs it inside every block.  A CUDA call that
+    nfp_valid_supported accepts (cosine / dot / gfc / Norm p=2 / rmse, float32 or bfloat16, rows of at most 128 pixels,
+    NCHW or aligned channels-last images) runs the valid-map kernels, one launch each way; everything else — CPU tensors,
+    other measures, refused shapes, torch.compile, NFP_VALID_OFF=1 in the environment (read at call time) — is `nfp(x, cfg)`
+    unchanged.  Under torch.autocast, and for float16 / float64, the float32 upcast of `_amp_input`, as the fused callers."""
+    if cfg.padding != 0 or cfg.stride != 1 or cfg.dilation != 1:
+        raise ValueError(f"nfp_valid: padding 0, stride 1, dilation 1 only (got padding={cfg.padding}, "
+                         f"stride={cfg.stride}, dilation={cfg.dilation}); use nfp")
+    if x.dim() != 4:
+        raise RuntimeError(f"NFP expects a 4-D [B,C,H,W] feature map, got {tuple(x.shape)}")
+    xin, cast = _amp_input(x)
+    if xin is not x:
+        with torch.autocast("cuda", enabled=False):
+            out = nfp_valid(xin, cfg)
+        return out if cast is None else out.to(cast)
+    layout = _valid_layout(x, cfg)
+    if layout is None:
+        return nfp(x, cfg)
+    need_grad = bool(x.requires_grad and torch.is_grad_enabled())
+    # the C++ node where the module has it (an older _nfp_torch.so, or NFP_PY_NODES=1: the Python node)
+    apply = getattr(_cpp_nodes() or None, "nfp_valid_apply", None)
+    if apply is not None and x.shape[0] > 0:
+        plan = _valid_plan(x, layout, cfg)
+        ns = max(plan.ask("nfp_valid_saved_floats"), 0) if need_grad else 0
+        return _cpp_call(apply, x, plan.desc_tensor, list(plan.oshape), ns, plan.nhwc)
+    return _NfpValidHip.apply(x, layout, cfg, need_grad)

@@ -10,10 +10,11 @@ under the reference's names, comp_neighbors.bias [C*N] and center_value.bias [C]
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _abi
 from .functional import (NfpConfig, gap_servable, multi_radius_config, nfp, nfp_attention_pool, nfp_biased, nfp_multi_radius,
-                         nfp_with_gap)
+                         nfp_valid, nfp_with_gap)
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -249,3 +250,52 @@ class SimilarityAwarePooling(nn.Module):
 
     def forward(self, x):
         return nfp_attention_pool(self.nfp(x), self.att_proj.weight, self.att_proj.bias)
+
+
+class NFPBottleneck(nn.Module):
+    """Drop-in for models/nfp_heads.py::NFPBottleneck (nfp_heads.py:234-278, the second definition — the one Python keeps):
+    a residual block with an unpadded cosine NFP layer between two 1x1 convs,
+        relu(bn1(conv1(x))) -> NFP(R=1, cosine, padding=0) -> bn2(conv2(.)) + downsample(_match(x)) -> relu
+    [B, in, H, W] -> [B, out, H'-2, W'-2] (H' = H behind conv1's stride).  Same constructor, attributes and state-dict keys
+    (conv1 / bn1 / nfp.* / conv2 / bn2 / downsample.*); the RNG is consumed in the reference's order — conv1, bn1, the
+    layer's two depthwise conv weights (drawn and dropped: NFPPooling(bias=False) holds no conv), the 5x5 probe, conv2,
+    bn2, downsample — so the same seed gives bit-identical parameters.  On the GPU the layer runs the valid-map kernels
+    (functional.nfp_valid), forward and backward one launch each."""
+    expansion = 1
+
+    def __init__(self, in_channels: int, out_channels: int, stride=1):
+        super().__init__()
+        mid = out_channels // 4
+        self.conv1 = nn.Conv2d(in_channels, mid, 1, bias=False, stride=stride)
+        self.bn1 = nn.BatchNorm2d(mid)
+        self.nfp = EnhancedNFPPooling(mid, R=1, measure="cosine", padding=0)
+        # (the draws of the reference layer's two depthwise convs, nfp.py:42-59 — as SimilarityAwarePooling.__init__)
+        nn.Conv2d(mid, self.nfp.out_channels * mid, self.nfp.kernel_size, groups=mid, bias=False)
+        nn.Conv2d(mid, mid, self.nfp.kernel_size, groups=mid, bias=False)
+        with torch.no_grad():                                   # nfp_heads.py:245-246
+            mid2 = self.nfp(torch.randn(1, mid, 5, 5)).shape[1]
+        self.conv2 = nn.Conv2d(mid2, out_channels, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=True)
+        if in_channels != out_channels:
+            self.downsample = nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, bias=False),
+                                            nn.BatchNorm2d(out_channels))
+        else:
+            self.downsample = nn.Identity()
+
+    def _match(self, ident, target_hw):
+        # sized from the LAST dimension alone (nfp_heads.py:261-265): a non-square map behind stride 2 fails here as there
+        if ident.shape[-1] == target_hw:
+            return ident
+        k = ident.shape[-1] - target_hw + 1
+        return F.avg_pool2d(ident, kernel_size=k, stride=1, padding=0)
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = nfp_valid(out, self.nfp.config)
+        out = self.bn2(self.conv2(out))
+        identity = self._match(identity, out.shape[-1])
+        identity = self.downsample(identity)
+        out += identity
+        return self.relu(out)
