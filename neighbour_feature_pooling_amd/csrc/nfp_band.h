@@ -25,6 +25,9 @@ namespace nfp {
 constexpr int kBandT = NFP_BAND_T;  // most threads per workgroup: pixels of the band x channel groups (a power of two <= 32)
 constexpr int kBandRB = 3;   // NCHW staging: 4-pixel x 4-channel blocks per thread per chunk
 constexpr int kBandRN = 6;   // channels-last staging: slots per thread per chunk
+#ifndef NFP_BAND_WAVE_ROUNDS
+#define NFP_BAND_WAVE_ROUNDS 1   // (0 builds the per-workgroup round test of rounds 4-5: A/B — profiles/r06_b_…)
+#endif
 #ifndef NFP_BAND_SKIP_ROUNDS
 #define NFP_BAND_SKIP_ROUNDS 1   // ([256,512,7,7] forward 6.64 -> 6.48 us, [256,192,14,14] 10.56 -> 10.10; headline unchanged: profiles/r04_i_…)
 #endif
@@ -133,6 +136,7 @@ __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, con
   // NCHW blocks of the band: 4-pixel blocks q0 .. q1-1 of every channel; the last block of an image whose pixel
   // count is not a multiple of 4 starts at P - 4 instead (it overlaps its predecessor: same values, written twice)
   const int q0 = p0 >> 2, q1 = (pe + 3) >> 2, NQb = q1 - q0;
+  [[maybe_unused]] const int wave0 = __builtin_amdgcn_readfirstlane(t) & ~63;   // the wavefront's first thread, in an SGPR
   float4 blk[kBandRB][4];
   float4 nv[kBandRN];
   auto issue = [&](int c0, int ncq) {
@@ -148,9 +152,12 @@ __global__ void __launch_bounds__(1024) fwd_band(const void* __restrict__ x, con
 #pragma unroll
       for (int r = 0; r < kBandRB; ++r) {
 #if NFP_BAND_SKIP_ROUNDS
-        // (a round no thread of the workgroup needs — the headline shape: 768 blocks on 704 threads, two rounds of three —
-        // is skipped as a whole: a wave-uniform branch around four requests, not a select around a load)
-        if (r > 0 && r * T >= nblk) break;
+        // (a round no thread of the WAVEFRONT needs is skipped as a whole: a scalar branch around four requests, not a select
+        // around a load.  The headline shape has 768 blocks on 704 threads: in its second round wavefront 0 loads 64 blocks
+        // and the other ten, whose threads would each have issued four clamped 16-byte loads, issue none — 48 wavefront
+        // loads of 1 KB instead of 88: forward 4.67 -> 4.46 us, bf16 NCHW 5.00 -> 4.58 us (profiles/r06_b_…).  Until round 6
+        // the test was per workgroup, r * T >= nblk.)
+        if (r > 0 && (NFP_BAND_WAVE_ROUNDS ? wave0 : 0) + r * T >= nblk) break;
 #endif
         const int i = min(t + r * T, nblk - 1);
         const int cq = fdivi(i, NQb), pq = q0 + i - cq * NQb;
