@@ -283,6 +283,45 @@ int nfp_valid_forward(const nfp_desc* d, const void* x, void* out, float* saved,
 int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out, const float* saved,
                        int64_t saved_floats, void* grad_x, void* hip_stream);
 
+/*
+ * The tail the three trained heads of models/nfp_heads.py share behind their NFP maps (NFPHead nfp_heads.py:28-32,42-43,
+ * MultiRadiusNFPHead 98-102,114-115, AdaptiveFusionNFP 301-305,323-324):
+ *   compress = Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU        out [B,D] = GAP(compress(maps))
+ * without the [B,D,P] activation (csrc/nfp_cpool.hip): train-mode BatchNorm statistics of a 1x1 conv's output follow from
+ * the mean mu [N] and the biased covariance Sigma [N,N] of its input over the M = B*P pixels of the batch, the pre-activation
+ * is formed from the image's maps in LDS and averaged at once, and the backward recomputes it.
+ *   maps    [B,N,P] dense, dtype = enum nfp_dtype; w [D,N], gamma [D], beta [D], the running statistics [D], out [B,D] and
+ *           every gradient but grad_maps (the maps' dtype, one rounding) are float32 DEVICE pointers
+ *   training != 0   batch statistics (second moments taken centred, joined in float64); running_mean / running_var, given
+ *                   together or both NULL, are updated in the same call: rm <- (1 - momentum) rm + momentum mean,
+ *                   rv <- (1 - momentum) rv + momentum var M / (M - 1).  `saved` (nfp_cpool_saved_floats(N, D) = 2N + N*N + D
+ *                   floats: mu as two floats, Sigma, 1/sqrt(var + eps)) is written for the backward and required;
+ *                   `scratch` holds nfp_cpool_scratch_floats(B, N, P, D, 0) floats
+ *   training == 0   the running statistics stand for mean and var (both required; read again by the backward); saved and
+ *                   scratch are not touched and may be NULL
+ * nfp_cpool_backward, given grad_out [B,D]: grad_maps [B,N,P], grad_w [D,N], grad_gamma [D], grad_beta [D] — each may be
+ * NULL and is then neither computed nor written; scratch of nfp_cpool_scratch_floats(B, N, P, D, 1) floats (not needed for
+ * an eval-mode grad_maps alone).  Launches: forward 3 in training (moments, finish, main) and 1 in eval; backward at most 3
+ * (per-slice partial sums, the batch reduce with the parameter gradients, grad_maps), the last skipped without grad_maps,
+ * the first two for an eval-mode grad_maps alone.  No atomics: two runs agree bitwise, and in eval image b's row of out /
+ * grad_maps does not depend on the batch around it.  nfp_last_variant names cpool_fwd<f32|bf16,train|eval> / cpool_bwd<...>.
+ * Every caller buffer that has a length query comes with its length: a short (or missing) one returns NFP_E_INVALID and
+ * launches nothing, as do a NULL required pointer, B < 0, N < 1, P < 1, D < 1, an unknown dtype, a negative eps — all checked
+ * before any HIP call.  NFP_E_UNSUPPORTED: N > 32, N*P >= 2^31, D > 2^22, B*P < 2 in training.  B = 0 returns NFP_OK
+ * without a launch.  Additive to ABI 7: no descriptor, no workspace.
+ */
+int64_t nfp_cpool_saved_floats(int32_t N, int32_t D);
+int64_t nfp_cpool_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward);
+int nfp_cpool_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                      const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                      double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
+                      int64_t scratch_floats, void* hip_stream);
+int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                       const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const float* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

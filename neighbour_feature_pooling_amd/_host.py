@@ -117,3 +117,15 @@ def attention_pool_host(maps, w, b):
     logits = (m * w.reshape(1, N, 1).to(m.dtype)).sum(1) + b.reshape(1, 1).to(m.dtype)
     att = torch.softmax(logits, dim=-1)
     return (m * att.unsqueeze(1)).sum(-1)
+
+
+def compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps):
+    """The tail the heads of models/nfp_heads.py share (NFPHead nfp_heads.py:28-32,42-43): GAP(relu(batch_norm(conv1x1(maps))))
+    as the four ATen ops — conv2d, batch_norm, relu, mean — any dtype and device, under torch.compile and torch.autocast:
+    maps [B,N,H,W] (or [B,N,P]) -> [B,D].  weight [D,N,1,1] or [D,N]; gamma / beta may be None (affine=False); the running
+    statistics, where given, are updated in place by batch_norm when use_batch_stats (momentum: its exponential factor).
+    Autograd differentiates."""
+    B, N = maps.shape[:2]
+    y = F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
+    y = F.batch_norm(y, running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
+    return F.relu(y).mean((2, 3))

@@ -15,6 +15,10 @@ SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip"]   #
 # units above, so the library's units are ALL_SOURCES.
 VALID_SOURCES = ["nfp_valid.hip"]
 ALL_SOURCES = SOURCES + VALID_SOURCES
+# ... and the sixth, the heads' compress-BN-ReLU-GAP tail.  Again a list of its own: tests/test_bottleneck_host.py pins
+# ALL_SOURCES at the five units above, so what the library is compiled from is LIB_SOURCES.
+CPOOL_SOURCES = ["nfp_cpool.hip"]
+LIB_SOURCES = ALL_SOURCES + CPOOL_SOURCES
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)
@@ -40,7 +44,7 @@ def hipcc_path():
 
 
 def compile_hip(out_lib, extra_flags=(), verbose=False):
-    """hipcc: every source of ALL_SOURCES to an object (in parallel), then one shared library."""
+    """hipcc: every source of LIB_SOURCES to an object (in parallel), then one shared library."""
     import concurrent.futures as cf
     import tempfile
     with tempfile.TemporaryDirectory(prefix="nfp_build_") as tmp:
@@ -51,8 +55,8 @@ def compile_hip(out_lib, extra_flags=(), verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             return obj
-        with cf.ThreadPoolExecutor(max_workers=len(ALL_SOURCES)) as ex:
-            objs = list(ex.map(one, ALL_SOURCES))
+        with cf.ThreadPoolExecutor(max_workers=len(LIB_SOURCES)) as ex:
+            objs = list(ex.map(one, LIB_SOURCES))
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc", "-o", out_lib] + objs
         if verbose:
             print(" ".join(cmd))

@@ -1,0 +1,797 @@
+// nfp_cpool.hip — the tail every head of models/nfp_heads.py shares behind its NFP maps (NFPHead nfp_heads.py:28-32,42-43,
+// MultiRadiusNFPHead 98-102,114-115, AdaptiveFusionNFP 301-305,323-324):
+//   compress = Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU        nfp_vec = GAP(compress(maps))    [B,N,P] -> [B,D]
+// which the reference runs as four ATen ops over a [B,D,P] activation (and twice that backward).  Here [B,D,P] never
+// exists.  Train-mode BatchNorm statistics of a 1x1 conv's output follow from the moments of its N-channel input,
+//   mean_d = w_d . mu        var_d = w_d^T Sigma w_d        (mu [N], Sigma [N,N]: mean and biased covariance over M = B*P)
+// so with c = m - mu, inv_d = 1/sqrt(var_d + eps), s_d = gamma_d inv_d:
+//   a_bdp = s_d (w_d . c_bp) + beta_d          out_bd = (1/P) sum_p relu(a_bdp)
+// (eval: mu = 0, inv_d from the running variance, the shift beta_d - s_d running_mean_d).  Backward, the pre-activation
+// recomputed, ga_bdp = (G_bd / P) [a_bdp > 0]:
+//   T_dn = sum_bp ga c_n      grad_beta_d = sum_bp ga      grad_gamma_d = inv_d sum_n w_dn T_dn   (eval: - inv_d rm_d grad_beta_d)
+//   grad_w_dn = s_d (T_dn - grad_gamma_d inv_d (Sigma w_d)_n)                                     (eval: s_d T_dn)
+//   k_n = sum_d w_dn s_d grad_beta_d / M      Q = sum_d s_d (grad_gamma_d inv_d / M) w_d w_d^T    (eval: both 0)
+//   grad_m_bnp = sum_d w_dn s_d ga_bdp - k_n - (Q c_bp)_n
+//
+// Kernels (no atomics; every sum in a fixed order: two runs agree bitwise, and in eval image b's row does not depend on B):
+//   cpool_moments   one workgroup per chunk of an image's pixels: the chunk's maps in LDS, its mean as a float32 anchor a_n
+//                   plus the mean r_n of what is left after subtracting it, and the Gram of the maps about the anchor
+//   cpool_finish    float64: mu = sum_k n_k (a_k + r_k) / M, Sigma = sum_k [Gram_k + n_k (r d' + d r' + d d')] / M with
+//                   d = a_k - mu (the scatter about mu from the scatter about each anchor — within plus between, exact),
+//                   slices of consecutive chunks joined in order; then w^T Sigma w, inv_d and the running statistics.  mu is
+//                   kept as two floats
+//   cpool_fwd       one workgroup per (image, 128 channels of D): lanes along d, two channels per lane with their scaled
+//                   weight rows in registers; the image's centred maps in LDS, walked in chunks, read as broadcast
+//                   ds_read_b128 along p (four pixels of one map per read, eight FMAs); the eight wavefronts split the pixels
+//   cpool_bwd_part  the same walk over a slice of the batch: T and grad_beta of the slice for the workgroup's channels
+//   cpool_bwd_reduce  one workgroup per 32 channels: the slices in order, the parameter gradients, this tile's share of k, Q
+//   cpool_bwd_maps  lanes along 64 pixels (their c_n in registers); D in blocks of 128 channels whose scaled rows are staged in
+//                   LDS and dealt to the wavefronts, joined in wave order through LDS; then - k - Q c
+#include "nfp_launch.h"
+
+#include <cmath>
+
+namespace nfp {
+namespace {
+
+constexpr int kCpT = 512;         // threads of cpool_fwd / cpool_bwd_part / cpool_bwd_maps: 8 wavefronts
+constexpr int kCpW = kCpT / 64;
+constexpr int kCpDT = 128;        // channels of D per workgroup: 64 lanes x 2
+constexpr int kCpBudget = 8192;   // floats of maps per chunk (32 KiB): with the join buffers a workgroup stays near 50 KiB
+constexpr int kCpMaxN = 32;
+constexpr int kCpRT = 32;         // channels of D per workgroup of cpool_bwd_reduce
+constexpr int kCpMT = 256;        // threads of cpool_moments / cpool_bwd_reduce
+constexpr int kCpFT = 1024;       // threads of cpool_finish
+constexpr int kCpMB = 128;        // channels of D per LDS block of cpool_bwd_maps
+
+struct CpK {
+  int B, N, P, CH, CHs, D, bf16, eval, S, ipw, nc, ntr;
+  float eps;
+  double eps64, mom, M;
+  const void* maps;
+  const float *w, *gamma, *beta, *rm, *rv, *stats, *go, *part, *kq;
+  float *out, *stats_w, *part_w, *kq_w, *rm_w, *rv_w, *gw, *gg, *gb;
+  void* gm;
+};
+// stats (the forward's saved state, training): mu_hi [N], mu_lo [N], Sigma [N*N], inv [D]
+__device__ __forceinline__ const float* cp_inv(const CpK& k) { return k.stats + 2 * k.N + k.N * k.N; }
+
+__device__ __forceinline__ float cp_wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// s_d = gamma_d inv_d and the shift of channel d (file comment)
+__device__ __forceinline__ void cp_coef(const CpK& k, int d, float& scale, float& shift) {
+  const float inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
+  scale = k.gamma[d] * inv;
+  shift = k.eval ? k.beta[d] - scale * k.rm[d] : k.beta[d];
+}
+
+// The chunk [p0, p0 + ch) of image b into sm[NP][CHs] as centred float32; rows n >= N and pixels >= ch are zero.
+__device__ __forceinline__ void cp_stage(const CpK& k, int NP, float* sm, int b, int p0, int ch, bool centre) {
+  const long long base = (long long)b * k.N * k.P + p0;
+  const int total = NP * k.CHs;
+  for (int i = threadIdx.x; i < total; i += blockDim.x) {
+    const int n = i / k.CHs, pl = i - n * k.CHs;
+    float v = 0.f;
+    if (n < k.N && pl < ch) {
+      const long long j = base + (long long)n * k.P + pl;
+      v = k.bf16 ? bf16_to_f32(((const uint16_t*)k.maps)[j]) : ((const float*)k.maps)[j];
+      if (centre) v = (v - k.stats[n]) - k.stats[k.N + n];
+    }
+    sm[i] = v;
+  }
+}
+
+// ---- moments ---------------------------------------------------------------------------------------------------------------
+// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP], red[max(NP * NP, 256)].
+// part_w: per chunk [a (N), r (N), Gram (N * N)].
+__global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* anchor = sm + NP * k.CHs;
+  float* red = anchor + NP;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kCpMT >> 6;
+  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
+  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
+  const int N = k.N, NN = NP * NP;
+  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
+  cp_stage(k, NP, sm, b, p0, ch, false);
+  __syncthreads();
+  for (int n = wv; n < NP; n += nw) {
+    float s = 0.f;
+    for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
+    s = cp_wave_sum(s);
+    if (lane == 0) anchor[n] = s / (float)ch;
+  }
+  __syncthreads();
+  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
+    const float an = anchor[n];
+    float s = 0.f;
+    for (int pl = lane; pl < ch; pl += 64) {
+      const float c = sm[n * k.CHs + pl] - an;
+      sm[n * k.CHs + pl] = c;
+      s += c;
+    }
+    s = cp_wave_sum(s);
+    if (lane == 0) {
+      outp[n] = an;
+      outp[N + n] = s / (float)ch;
+    }
+  }
+  __syncthreads();
+  // Gram about the anchor: pair (n, n2) per thread, the pixels in quads; with fewer pairs than threads the quads are dealt
+  // to T / NN slices and joined in slice order
+  const int nq = (ch + 3) >> 2;
+  const int nsl = NN >= kCpMT ? 1 : kCpMT / NN;
+  for (int pr0 = 0; pr0 < NN; pr0 += kCpMT) {
+    const int pr = nsl > 1 ? tid % NN : pr0 + tid;
+    const int sl = nsl > 1 ? tid / NN : 0;
+    if (pr < NN && sl < nsl) {
+      const int n = pr / NP, n2 = pr - n * NP;
+      const float4* ra = (const float4*)(sm + n * k.CHs);
+      const float4* rb = (const float4*)(sm + n2 * k.CHs);
+      float g = 0.f;
+      for (int q = sl; q < nq; q += nsl) {
+        const float4 x = ra[q], y = rb[q];
+        g = fmaf(x.x, y.x, g);
+        g = fmaf(x.y, y.y, g);
+        g = fmaf(x.z, y.z, g);
+        g = fmaf(x.w, y.w, g);
+      }
+      if (nsl > 1) {
+        red[sl * NN + pr] = g;
+      } else if (n < N && n2 < N) {
+        outp[2 * N + n * N + n2] = g;
+      }
+    }
+  }
+  if (nsl > 1) {
+    __syncthreads();
+    if (tid < NN) {
+      const int n = tid / NP, n2 = tid - n * NP;
+      float g = red[tid];
+      for (int s = 1; s < nsl; ++s) g += red[s * NN + tid];
+      if (n < N && n2 < N) outp[2 * N + n * N + n2] = g;
+    }
+  }
+}
+
+// grid = ceil(D / 1024), block = 1024; every workgroup joins the chunks itself (the same sums in the same order).  The chunks
+// are dealt to slices of consecutive chunks — 32 slices for mu, 1024 / N^2 for Sigma — whose sums are joined in slice order:
+// one thread walking all B * nc chunks is a chain of dependent global loads (measured: 100 us at 64 chunks).
+__global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
+  __shared__ double mu[kCpMaxN];
+  __shared__ double sig[kCpMaxN * kCpMaxN];   // [32][32], zero beyond N
+  __shared__ double red[kCpFT];
+  const int tid = threadIdx.x, N = k.N, NN = N * N, K = k.B * k.nc, rec = 2 * N + NN;
+  const int last = k.P - (k.nc - 1) * k.CH;   // pixels of an image's last chunk
+  {
+    const int n = tid & 31, sl = tid >> 5, Kc = (K + 31) / 32;
+    const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
+    double s = 0.0;
+    if (n < N) {
+      int j = c0 % k.nc;
+#pragma unroll 4
+      for (int c = c0; c < c1; ++c) {
+        const float* r = k.part + (long long)c * rec;
+        const double cnt = j == k.nc - 1 ? last : k.CH;
+        s += cnt * ((double)r[n] + (double)r[N + n]);
+        if (++j == k.nc) j = 0;
+      }
+    }
+    red[tid] = s;
+    sig[tid] = 0.0;
+    __syncthreads();
+    if (tid < N) {
+      double t = red[tid];
+      for (int i = 1; i < 32; ++i) t += red[i * 32 + tid];
+      mu[tid] = t / k.M;
+    }
+    __syncthreads();
+  }
+  {
+    const int nsl = kCpFT / NN, pr = tid % NN, sl = tid / NN, Kc = (K + nsl - 1) / nsl;
+    const int n = pr / N, n2 = pr - n * N;
+    if (sl < nsl) {
+      const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
+      const double m1 = mu[n], m2 = mu[n2];
+      double s = 0.0;
+      int j = c0 % k.nc;
+#pragma unroll 4
+      for (int c = c0; c < c1; ++c) {
+        const float* r = k.part + (long long)c * rec;
+        const double cnt = j == k.nc - 1 ? last : k.CH;
+        const double d1 = (double)r[n] - m1, d2 = (double)r[n2] - m2, r1 = r[N + n], r2 = r[N + n2];
+        s += (double)r[2 * N + pr] + cnt * (r1 * d2 + d1 * r2 + d1 * d2);
+        if (++j == k.nc) j = 0;
+      }
+      red[sl * NN + pr] = s;
+    }
+    __syncthreads();
+    if (tid < NN) {
+      double t = red[tid];
+      for (int i = 1; i < nsl; ++i) t += red[i * NN + tid];
+      sig[n * kCpMaxN + n2] = t / k.M;
+    }
+    __syncthreads();
+  }
+  if (blockIdx.x == 0) {
+    if (tid < N) {
+      const float hi = (float)mu[tid];
+      k.stats_w[tid] = hi;
+      k.stats_w[N + tid] = (float)(mu[tid] - (double)hi);
+    }
+    if (tid < NN) k.stats_w[2 * N + tid] = (float)sig[(tid / N) * kCpMaxN + tid % N];
+  }
+  const int d = blockIdx.x * kCpFT + tid;
+  if (d >= k.D) return;
+  const float* wd = k.w + (long long)d * N;
+  double wr[kCpMaxN];   // (every index a constant below: registers)
+#pragma unroll
+  for (int n = 0; n < kCpMaxN; ++n) wr[n] = n < N ? (double)wd[n] : 0.0;
+  double var = 0.0, mean = 0.0;
+#pragma unroll
+  for (int n = 0; n < kCpMaxN; ++n) {
+    if (n < N) {   // (the same in every thread)
+      double v = 0.0;
+#pragma unroll
+      for (int n2 = 0; n2 < kCpMaxN; ++n2) v += sig[n * kCpMaxN + n2] * wr[n2];
+      var += wr[n] * v;
+      mean += wr[n] * mu[n];
+    }
+  }
+  var = var > 0.0 ? var : 0.0;
+  k.stats_w[2 * N + NN + d] = (float)(1.0 / sqrt(var + k.eps64));
+  if (k.rm_w != nullptr) {
+    k.rm_w[d] = (float)((1.0 - k.mom) * (double)k.rm_w[d] + k.mom * mean);
+    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (k.M / (k.M - 1.0)));
+  }
+}
+
+// ---- lanes along d -----------------------------------------------------------------------------------------------------------
+// The two channels of a lane: d0 = tile * 128 + lane and d0 + 64.  ws = s_d w_d (zero beyond D and N), sh the shift.
+template <int NP>
+__device__ __forceinline__ void cp_rows(const CpK& k, int tile, int lane, float (&ws)[2][NP], float (&sh)[2]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int d = tile * kCpDT + lane + 64 * j;
+    float scale = 0.f;
+    sh[j] = 0.f;
+    if (d < k.D) cp_coef(k, d, scale, sh[j]);
+#pragma unroll
+    for (int n = 0; n < NP; ++n) ws[j][n] = (d < k.D && n < k.N) ? k.w[(long long)d * k.N + n] * scale : 0.f;
+  }
+}
+// a of the lane's two channels at the four pixels of quad q: the shift first, then the maps in order (cpool_bwd_maps forms
+// the same chain: the same bits, the same mask)
+template <int NP>
+__device__ __forceinline__ void cp_preact(const float* sm, int CHs, int q, const float (&ws)[2][NP], const float (&sh)[2],
+                                          float (&a)[2][4]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[j][i] = sh[j];
+#pragma unroll
+  for (int n = 0; n < NP; ++n) {
+    const float4 c = ((const float4*)(sm + n * CHs))[q];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      a[j][0] = fmaf(ws[j][n], c.x, a[j][0]);
+      a[j][1] = fmaf(ws[j][n], c.y, a[j][1]);
+      a[j][2] = fmaf(ws[j][n], c.z, a[j][2]);
+      a[j][3] = fmaf(ws[j][n], c.w, a[j][3]);
+    }
+  }
+}
+
+// grid = (B, ceil(D / 128)), block = 512.  LDS: sm[NP * CHs], red[8 * 128].
+template <int NP>
+__global__ void __launch_bounds__(kCpT) cpool_fwd(CpK k) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* red = sm + NP * k.CHs;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = blockIdx.x, tile = blockIdx.y;
+  float ws[2][NP], sh[2], s[2] = {0.f, 0.f};
+  cp_rows<NP>(k, tile, lane, ws, sh);
+  for (int p0 = 0; p0 < k.P; p0 += k.CH) {
+    const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
+    if (p0 > 0) __syncthreads();   // (the previous chunk has been read)
+    cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+    __syncthreads();
+    for (int q = wv; q < nq; q += kCpW) {
+      float a[2][4];
+      cp_preact<NP>(sm, k.CHs, q, ws, sh, a);
+      const int nv = min(4, ch - 4 * q);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < nv) {
+          s[0] += fmaxf(a[0][i], 0.f);
+          s[1] += fmaxf(a[1][i], 0.f);
+        }
+    }
+  }
+  red[wv * kCpDT + lane] = s[0];
+  red[wv * kCpDT + lane + 64] = s[1];
+  __syncthreads();
+  const int d = tile * kCpDT + tid;
+  if (tid < kCpDT && d < k.D) {
+    float t = red[tid];
+#pragma unroll
+    for (int w = 1; w < kCpW; ++w) t += red[w * kCpDT + tid];
+    k.out[(long long)b * k.D + d] = t / (float)k.P;
+  }
+}
+
+// grid = (S, ceil(D / 128)), block = cp_part_threads: images [s * ipw, (s + 1) * ipw) of the batch.  LDS: sm[NP * CHs],
+// red[128 * (NP + 1)].  part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
+// A lane keeps 2 * NP scaled weights and 2 * NP sums: above 24 maps that passes the 256 registers two wavefronts per SIMD
+// leave each (92 spilled at 512 threads), so those run four wavefronts, one per SIMD, with the whole file.
+template <int NP>
+constexpr int cp_part_threads() { return NP > 24 ? 256 : kCpT; }
+template <int NP>
+__global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
+  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* red = sm + NP * k.CHs;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sl = blockIdx.x, tile = blockIdx.y;
+  float ws[2][NP], sh[2], T[2][NP], gbs[2] = {0.f, 0.f};
+  cp_rows<NP>(k, tile, lane, ws, sh);
+#pragma unroll
+  for (int n = 0; n < NP; ++n) T[0][n] = T[1][n] = 0.f;
+  const int b1 = min(k.B, (sl + 1) * k.ipw);
+  bool first = true;
+  for (int b = sl * k.ipw; b < b1; ++b) {
+    float gs[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int d = tile * kCpDT + lane + 64 * j;
+      gs[j] = d < k.D ? k.go[(long long)b * k.D + d] / (float)k.P : 0.f;
+    }
+    for (int p0 = 0; p0 < k.P; p0 += k.CH) {
+      const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
+      if (!first) __syncthreads();
+      first = false;
+      cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+      __syncthreads();
+      for (int q = wv; q < nq; q += kW) {
+        float a[2][4];
+        cp_preact<NP>(sm, k.CHs, q, ws, sh, a);
+        const int nv = min(4, ch - 4 * q);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            a[j][i] = (i < nv && a[j][i] > 0.f) ? gs[j] : 0.f;   // ga
+            gbs[j] += a[j][i];
+          }
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+          const float4 c = ((const float4*)(sm + n * k.CHs))[q];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            float t = T[j][n];
+            t = fmaf(a[j][0], c.x, t);
+            t = fmaf(a[j][1], c.y, t);
+            t = fmaf(a[j][2], c.z, t);
+            t = fmaf(a[j][3], c.w, t);
+            T[j][n] = t;
+          }
+        }
+      }
+    }
+  }
+  // the eight wavefronts in order into red[dl][NP + 1] (every lane its own words)
+  for (int w = 0; w < kW; ++w) {
+    if (wv == w) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float* r = red + (lane + 64 * j) * (NP + 1);
+#pragma unroll
+        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
+        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
+      }
+    }
+    __syncthreads();
+  }
+  const int N1 = k.N + 1;
+  for (int i = tid; i < kCpDT * N1; i += kT) {
+    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
+    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
+  }
+}
+
+// grid = ceil(D / 32), block = 256.  kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
+__global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
+  __shared__ float Tl[kCpRT * (kCpMaxN + 1)];
+  __shared__ float wl[kCpRT * kCpMaxN];
+  __shared__ float sg[kCpMaxN * kCpMaxN];
+  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
+  const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
+  {
+    // a thread's elements (at most 5 of the 32 * (N + 1)) side by side, the slices in order: their loads are independent, so
+    // several are in flight — one element after the other is a chain of S dependent loads
+    constexpr int kE = (kCpRT * (kCpMaxN + 1) + kCpMT - 1) / kCpMT;
+    float acc[kE];
+    long long off[kE];
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+      const int i = tid + e * kCpMT, dl = i / N1, j = i - dl * N1, d = d0 + dl;
+      acc[e] = 0.f;
+      off[e] = (i < kCpRT * N1 && d < k.D) ? (long long)d * N1 + j : -1;
+    }
+    const long long stride = (long long)k.D * N1;
+    for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
+      float v[kE][8];
+#pragma unroll
+      for (int e = 0; e < kE; ++e)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[e][u] = k.part[min(sl0 + u, k.S - 1) * stride + max(off[e], 0LL)];
+#pragma unroll
+      for (int e = 0; e < kE; ++e)
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
+    }
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+      const int i = tid + e * kCpMT, dl = i / N1, j = i - dl * N1;
+      if (i < kCpRT * N1) Tl[dl * (kCpMaxN + 1) + (j < N ? j : kCpMaxN)] = acc[e];
+    }
+  }
+  for (int i = tid; i < kCpRT * N; i += kCpMT) {
+    const int dl = i / N, n = i - dl * N, d = d0 + dl;
+    wl[dl * kCpMaxN + n] = d < k.D ? k.w[(long long)d * N + n] : 0.f;
+  }
+  if (!k.eval)
+    for (int i = tid; i < NN; i += kCpMT) sg[i] = k.stats[2 * N + i];
+  __syncthreads();
+  if (tid < kCpRT) {
+    const int d = d0 + tid;
+    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
+    if (d < k.D) {
+      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
+      c1 = k.gamma[d] * inv;
+      const float gb = Tl[tid * (kCpMaxN + 1) + kCpMaxN];
+      float dot = 0.f;
+      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * kCpMaxN + n], Tl[tid * (kCpMaxN + 1) + n], dot);
+      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
+      if (!k.eval) {
+        e = c1 * (gb / (float)k.M);
+        f = c1 * (gg * inv / (float)k.M);
+      }
+      if (k.gg != nullptr) k.gg[d] = gg;
+      if (k.gb != nullptr) k.gb[d] = gb;
+    }
+    el[tid] = e;
+    fl[tid] = f;
+    ggl[tid] = gg;
+    c1l[tid] = c1;
+    invl[tid] = inv;
+  }
+  __syncthreads();
+  if (k.gw != nullptr)
+    for (int i = tid; i < kCpRT * N; i += kCpMT) {
+      const int dl = i / N, n = i - dl * N, d = d0 + dl;
+      if (d >= k.D) continue;
+      float t = Tl[dl * (kCpMaxN + 1) + n];
+      if (!k.eval) {
+        float sw = 0.f;
+        for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * kCpMaxN + n2], sw);
+        t -= ggl[dl] * invl[dl] * sw;
+      }
+      k.gw[(long long)d * N + n] = c1l[dl] * t;
+    }
+  if (k.eval || k.kq_w == nullptr) return;
+  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
+  for (int i = tid; i < N + NN; i += kCpMT) {
+    float s = 0.f;
+    if (i < N) {
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * kCpMaxN + i], el[dl], s);
+    } else {
+      const int n = (i - N) / N, n2 = (i - N) - n * N;
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * kCpMaxN + n], wl[dl * kCpMaxN + n2], s);
+    }
+    kq[i] = s;
+  }
+}
+
+// ---- lanes along p -----------------------------------------------------------------------------------------------------------
+// grid = B * ceil(P / 64), block = 512: the 64 pixels from pt * 64 of image b.  LDS: red[NP * 64], kql[N + N * N], the table
+// of a block of channels tb[128][NP + 4].
+template <int NP>
+__global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
+  constexpr int kTS = NP + 4;   // floats per channel of the block's table: the row, the shift, G_bd / P (16-byte rows)
+  __shared__ float red[NP * 64];
+  __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
+  __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
+  __shared__ float cf[kCpMB * 4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
+  const bool live = p < k.P;
+  if (!k.eval)
+    for (int i = tid; i < N + NN; i += kCpT) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
+      kql[i] = s;
+    }
+  float c[NP], g[NP];
+  const long long base = (long long)b * N * k.P + p;
+#pragma unroll
+  for (int n = 0; n < NP; ++n) {
+    float v = 0.f;
+    if (n < N && live) {
+      const long long j = base + (long long)n * k.P;
+      v = k.bf16 ? bf16_to_f32(((const uint16_t*)k.maps)[j]) : ((const float*)k.maps)[j];
+      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
+    }
+    c[n] = v;
+    g[n] = 0.f;
+  }
+  // D in blocks of 128 channels: the block's rows s_d w_d, shifts and G_bd / P go to LDS with coalesced, independent loads
+  // first (fetched per channel inside the loop they were a chain of dependent global loads: 0.6 us per channel, measured),
+  // then every wavefront walks its channels of the block reading them as broadcasts
+  for (int dB = 0; dB < k.D; dB += kCpMB) {
+    const int nd = min(kCpMB, k.D - dB);
+    if (dB > 0) __syncthreads();   // (the previous block has been read)
+    if (tid < nd) {
+      float scale, shift;
+      cp_coef(k, dB + tid, scale, shift);
+      cf[tid * 4] = scale;
+      tb[tid * kTS + NP] = shift;
+      tb[tid * kTS + NP + 1] = k.go[(long long)b * k.D + dB + tid] / (float)k.P;
+    }
+    __syncthreads();
+    for (int i = tid; i < nd * NP; i += kCpT) {
+      const int dl = i / NP, n = i - dl * NP;
+      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl * 4] : 0.f;
+    }
+    __syncthreads();
+    for (int dl = wv; dl < nd; dl += kCpW) {
+      const float* row = tb + dl * kTS;
+      float wsn[NP];
+      float a = row[NP];
+#pragma unroll
+      for (int n = 0; n < NP; ++n) {
+        wsn[n] = row[n];
+        a = fmaf(wsn[n], c[n], a);
+      }
+      const float t = a > 0.f ? row[NP + 1] : 0.f;
+#pragma unroll
+      for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], t, g[n]);
+    }
+  }
+  for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
+    if (wv == w) {
+#pragma unroll
+      for (int n = 0; n < NP; ++n) red[n * 64 + lane] = w == 0 ? g[n] : red[n * 64 + lane] + g[n];
+    }
+    __syncthreads();
+  }
+  if (!live) return;
+  for (int n = wv; n < N; n += kCpW) {
+    float v = red[n * 64 + lane];
+    if (!k.eval) {
+      float qc = kql[n];
+#pragma unroll
+      for (int n2 = 0; n2 < NP; ++n2)
+        if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
+      v -= qc;
+    }
+    const long long j = base + (long long)n * k.P;
+    if (k.bf16)
+      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
+    else
+      ((float*)k.gm)[j] = v;
+  }
+}
+
+}  // namespace
+}  // namespace nfp
+
+namespace nfp_host {
+namespace {
+
+int cpool_np(int N) { return (N + 7) & ~7; }
+// pixels per chunk: the whole image where it fits the budget, else a multiple of 64
+int cpool_chunk(int NP, long long P) {
+  long long ch = std::min<long long>(P, nfp::kCpBudget / NP);
+  if (ch < P) ch &= ~63LL;
+  return (int)ch;
+}
+// floats between two rows of the chunk in LDS: a multiple of 4 (16-byte reads) and an odd number of 16-byte slots, so
+// that sixteen rows at one quad (cpool_moments' Gram) fall on sixteen different slots
+int cpool_stride(int ch) {
+  int s = (ch + 3) & ~3;
+  if (((s >> 2) & 1) == 0) s += 4;
+  return s;
+}
+int cpool_tiles(int D) { return (D + nfp::kCpDT - 1) / nfp::kCpDT; }
+int cpool_rtiles(int D) { return (D + nfp::kCpRT - 1) / nfp::kCpRT; }
+// images per workgroup of cpool_bwd_part: about 512 workgroups, at most one per image
+int cpool_ipw(int B, int D) {
+  const int want = std::min(B, std::max(1, 512 / cpool_tiles(D)));
+  return (B + want - 1) / want;
+}
+int cpool_slices(int B, int D) {
+  const int ipw = cpool_ipw(B, D);
+  return (B + ipw - 1) / ipw;
+}
+
+int cpool_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
+  if (B < 0 || N < 1 || P < 1 || D < 1)
+    return fail(NFP_E_INVALID, "%s: B = %d, N = %d, P = %lld, D = %d", what, B, N, (long long)P, D);
+  if (dtype != NFP_F32 && dtype != NFP_BF16) return fail(NFP_E_INVALID, "%s: unknown dtype %d", what, dtype);
+  if (N > nfp::kCpMaxN) return fail(NFP_E_UNSUPPORTED, "%s: N = %d maps (more than %d) has no kernel", what, N, nfp::kCpMaxN);
+  if ((long long)N * P >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: an image of N * P = %lld map elements (2^31 and more) has no kernel", what,
+                (long long)N * P);
+  if (D > (1 << 22)) return fail(NFP_E_UNSUPPORTED, "%s: D = %d (more than 2^22) has no kernel", what, D);
+  const long long nc = (P + cpool_chunk(cpool_np(N), P) - 1) / cpool_chunk(cpool_np(N), P);
+  if ((long long)B * std::max<long long>(nc, (P + 63) / 64) >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: B = %d images of P = %lld pixels make 2^31 workgroups and more", what, B, (long long)P);
+  if (training && B > 0 && (long long)B * P < 2)
+    return fail(NFP_E_UNSUPPORTED, "%s: train-mode statistics need B * P >= 2 values per channel", what);
+  return NFP_OK;
+}
+
+nfp::CpK cpool_k(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
+  nfp::CpK k;
+  memset(&k, 0, sizeof(k));
+  const int NP = cpool_np(N);
+  k.B = B, k.N = N, k.P = (int)P, k.D = D;
+  k.CH = cpool_chunk(NP, P), k.CHs = cpool_stride(k.CH);
+  k.nc = (int)((P + k.CH - 1) / k.CH);
+  k.bf16 = dtype == NFP_BF16, k.eval = !training;
+  k.ipw = cpool_ipw(std::max(B, 1), D), k.S = cpool_slices(std::max(B, 1), D), k.ntr = cpool_rtiles(D);
+  k.M = (double)B * (double)P;
+  return k;
+}
+
+template <template <int> class F, typename... A>
+int cpool_by_np(int NP, A... a) {
+  switch (NP) {
+    case 8: return F<8>::go(a...);
+    case 16: return F<16>::go(a...);
+    case 24: return F<24>::go(a...);
+    default: return F<32>::go(a...);
+  }
+}
+template <int NP>
+struct LFwd {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const size_t lds = ((size_t)NP * k.CHs + nfp::kCpW * nfp::kCpDT) * sizeof(float);
+    return launch("cpool_fwd", nfp::cpool_fwd<NP>, dim3((unsigned)k.B, (unsigned)cpool_tiles(k.D)), dim3(nfp::kCpT), lds, st, k);
+  }
+};
+template <int NP>
+struct LPart {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCpDT * (NP + 1)) * sizeof(float);
+    return launch("cpool_bwd_part", nfp::cpool_bwd_part<NP>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
+                  dim3(nfp::cp_part_threads<NP>()), lds, st, k);
+  }
+};
+template <int NP>
+struct LMaps {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const int npt = (k.P + 63) / 64;
+    return launch("cpool_bwd_maps", nfp::cpool_bwd_maps<NP>, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st, k,
+                  npt);
+  }
+};
+
+int64_t cpool_fwd_scratch(int32_t B, int32_t N, int64_t P) {
+  const int ch = cpool_chunk(cpool_np(N), P);
+  return (int64_t)B * ((P + ch - 1) / ch) * (2 * N + N * N);
+}
+int64_t cpool_bwd_scratch(int32_t B, int32_t N, int32_t D) {
+  return (int64_t)cpool_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
+}
+
+}  // namespace
+}  // namespace nfp_host
+
+using namespace nfp_host;
+
+extern "C" {
+
+int64_t nfp_cpool_saved_floats(int32_t N, int32_t D) {
+  if (N < 1 || D < 1) return 1;
+  return 2 * (int64_t)N + (int64_t)N * N + D;
+}
+
+int64_t nfp_cpool_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
+  if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
+  return std::max<int64_t>(1, backward ? cpool_bwd_scratch(B, N, D) : cpool_fwd_scratch(B, N, P));
+}
+
+int nfp_cpool_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                      const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                      double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
+                      int64_t scratch_floats, void* hip_stream) {
+  const char* what = "nfp_cpool_forward";
+  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
+  if (!w || !gamma || !beta || (B > 0 && (!maps || !out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
+  if ((running_mean == nullptr) != (running_var == nullptr) || (!training && running_mean == nullptr))
+    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", what);
+  if (!(eps >= 0.0) || !(momentum == momentum)) return fail(NFP_E_INVALID, "%s: eps = %g, momentum = %g", what, eps, momentum);
+  if (training) {
+    if (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D))
+      return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
+                  (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
+    if (B > 0 && (scratch == nullptr || scratch_floats < nfp_cpool_scratch_floats(B, N, P, D, 0)))
+      return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cpool_scratch_floats is %lld", what,
+                  (long long)(scratch ? scratch_floats : 0), (long long)nfp_cpool_scratch_floats(B, N, P, D, 0));
+  }
+  if (B == 0) return NFP_OK;
+  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
+  const int NP = cpool_np(N);
+  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.out = out;
+  k.eps = (float)eps, k.eps64 = eps, k.mom = momentum;
+  hipStream_t st = (hipStream_t)hip_stream;
+  snprintf(g_variant, sizeof(g_variant), "cpool_fwd<%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval");
+  int rc = NFP_OK;
+  if (training) {
+    k.part_w = scratch, k.part = scratch, k.stats_w = saved, k.stats = saved, k.rm_w = running_mean, k.rv_w = running_var;
+    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
+    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
+    if (rc == NFP_OK)
+      rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k);
+  } else {
+    k.rm = running_mean, k.rv = running_var;
+  }
+  if (rc == NFP_OK) rc = cpool_by_np<LFwd>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                       const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const float* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream) {
+  const char* what = "nfp_cpool_backward";
+  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
+  if (!w || !gamma || !beta || (B > 0 && (!maps || !grad_out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
+  if (!training && (running_mean == nullptr || running_var == nullptr))
+    return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", what);
+  if (!(eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", what, eps);
+  if (training && (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D)))
+    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
+                (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
+  const bool params = grad_w != nullptr || grad_gamma != nullptr || grad_beta != nullptr;
+  if (!params && grad_maps == nullptr) return NFP_OK;
+  const bool sums = params || training;   // (train-mode grad_maps needs k and Q: the batch sums)
+  if (sums && B > 0 && (scratch == nullptr || scratch_floats < nfp_cpool_scratch_floats(B, N, P, D, 1)))
+    return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cpool_scratch_floats is %lld", what,
+                (long long)(scratch ? scratch_floats : 0), (long long)nfp_cpool_scratch_floats(B, N, P, D, 1));
+  if (B == 0) return NFP_OK;
+  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
+  const int NP = cpool_np(N);
+  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.go = grad_out, k.stats = saved;
+  k.eps = (float)eps, k.eps64 = eps;
+  if (!training) k.rm = running_mean, k.rv = running_var;
+  k.gm = grad_maps, k.gw = grad_w, k.gg = grad_gamma, k.gb = grad_beta;
+  hipStream_t st = (hipStream_t)hip_stream;
+  snprintf(g_variant, sizeof(g_variant), "cpool_bwd<%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval");
+  int rc = NFP_OK;
+  if (sums) {
+    k.part_w = scratch, k.part = scratch;
+    k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
+    rc = cpool_by_np<LPart>(NP, k, st);
+    if (rc == NFP_OK)
+      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
+  }
+  if (rc == NFP_OK && grad_maps != nullptr) rc = cpool_by_np<LMaps>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI,
 // table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
-// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps).  Separate
+// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_cpool.hip: the heads'
+// compress-BN-ReLU-GAP tail).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _abi
-from ._host import attention_pool_host, nfp_host
+from ._host import attention_pool_host, compress_pool_host, nfp_host
 
 
 @dataclass(frozen=True)
@@ -1064,3 +1064,147 @@ def nfp_valid(x, cfg):
         ns = max(plan.ask("nfp_valid_saved_floats"), 0) if need_grad else 0
         return _cpp_call(apply, x, plan.desc_tensor, list(plan.oshape), ns, plan.nhwc)
     return _NfpValidHip.apply(x, layout, cfg, need_grad)
+
+
+# ---- the heads' compress-BN-ReLU-GAP tail — include/nfp.h: nfp_cpool_* (csrc/nfp_cpool.hip) --------------------------------
+CPOOL_MAX_MAPS = 32     # csrc/nfp_cpool.hip: kCpMaxN (a lane keeps two weight rows in registers)
+CPOOL_ROUTED_MAPS = 8   # what cpool_hip_serves takes by default: the maps counts that measured faster than the composition
+
+
+def _cpool_sizes(maps, w):
+    B, N = maps.shape[:2]
+    return B, N, maps.numel() // max(B * N, 1), w.shape[0]
+
+
+def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps):
+    """(out [B,D] float32, saved) from nfp_cpool_forward on dense CUDA maps [B,N,...] and float32 w [D,N], gamma, beta [D].
+    use_batch_stats: train-mode statistics, the running ones (float32 [D], or both None) updated by the same call; `saved`
+    is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics)."""
+    L = _abi.load()
+    B, N, P, D = _cpool_sizes(maps, w)
+    dev = maps.device
+    with _on_device(dev):
+        out = torch.empty(B, D, dtype=torch.float32, device=dev)
+        ns = int(L.nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
+        nscr = int(L.nfp_cpool_scratch_floats(B, N, P, D, 0)) if use_batch_stats else 0
+        saved = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
+        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
+        _abi.check(L.nfp_cpool_forward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), maps.data_ptr(),
+                                       w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                       rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
+                                       float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
+                                       scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev)))
+    return out, saved
+
+
+def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want):
+    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cpool_backward — None for each
+    gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
+    L = _abi.load()
+    B, N, P, D = _cpool_sizes(maps, w)
+    dev = maps.device
+    go = grad_out.contiguous().float()
+    with _on_device(dev):
+        gm = torch.empty_like(maps) if want[0] else None
+        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
+        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
+        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None
+        sums = use_batch_stats or want[1] or want[2] or want[3]
+        nscr = int(L.nfp_cpool_scratch_floats(B, N, P, D, 1)) if sums else 0
+        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        _abi.check(L.nfp_cpool_backward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), maps.data_ptr(),
+                                        w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                        None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv), float(eps),
+                                        ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(), ptr(gm), ptr(gw),
+                                        ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev)))
+    return gm, gw, gg, gb
+
+
+class _CPoolHip(torch.autograd.Function):
+    """out [B,D] float32 of dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the backward: the maps,
+    the three parameters and the O(N*N + D) statistics — nothing of the size of the [B,D,P] activation.  `stats` = (rm, rv),
+    the running statistics or (None, None): buffers the forward kernel updates in place, handed over outside autograd's
+    view.  need_grad: some input requires a gradient and grad mode is on, sampled by the caller."""
+
+    @staticmethod
+    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, need_grad):
+        out, saved = cpool_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps)
+        if need_grad:
+            ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
+            ctx.stats, ctx.use_batch_stats, ctx.eps = stats, use_batch_stats, eps
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        maps, w, gamma, beta = ctx.saved_tensors[:4]
+        saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        gm, gw, gg, gb = cpool_backward_call(maps, w, gamma, beta, ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats,
+                                             ctx.eps, grad_out, ctx.needs_input_grad[:4])
+        return gm, gw, gg, gb, None, None, None, None, None
+
+
+def cpool_hip_serves(maps, gamma, beta, momentum):
+    """The HIP tail can serve dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] under an affine BatchNorm with a float
+    momentum, outside torch.compile and torch.autocast.  Of those it takes, by default, the ones with at most 8 maps: with 32
+    maps it measured slower than the torch composition ([256,32,7,7] -> 512: 327 against 185 us graph-timed), and
+    16 and 24 maps run the same register-heavy forms and were not measured.  NFP_CPOOL_TORCH (read at call time) is the A/B
+    switch: "1" the torch composition everywhere, "0" the HIP tail wherever it can serve."""
+    env = os.environ.get("NFP_CPOOL_TORCH")
+    if env == "1":
+        return False
+    can = (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
+           and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
+           and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
+    return can and (env == "0" or maps.shape[1] <= CPOOL_ROUTED_MAPS)
+
+
+def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5):
+    """`nfp_compress_pool` on loose tensors: maps [B,N,H,W] (or [B,N,P]) -> [B,D] = GAP(relu(batch_norm(conv1x1(maps)))), the
+    1x1 conv given by weight ([D,N,1,1] or [D,N]), the BatchNorm by gamma / beta [D] (None: affine=False), its running
+    statistics (updated in place when use_batch_stats; both None: not tracked) and `momentum` — the exponential factor
+    F.batch_norm takes; None, a cumulative average, is the caller's to resolve.  use_batch_stats=False reads the running
+    statistics instead (eval).  Where `cpool_hip_serves`, three HIP launches forward and at most three backward that never form
+    the [B,D,H,W] activation (include/nfp.h: nfp_cpool_*; float32 arithmetic, the result cast once to the maps' dtype);
+    everything else — by default also more than 8 maps, see cpool_hip_serves — is `_host.compress_pool_host`."""
+    if maps.dim() < 3:
+        raise RuntimeError(f"nfp_compress_pool expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
+    if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
+        raise RuntimeError(f"nfp_compress_pool: {maps.shape[1]} maps need a 1x1 conv weight [D,{maps.shape[1]},1,1], got "
+                           f"{tuple(weight.shape)}")
+    if not use_batch_stats and (running_mean is None or running_var is None):
+        raise RuntimeError("nfp_compress_pool: without batch statistics the running mean and variance are required")
+    if not cpool_hip_serves(maps, gamma, beta, momentum):
+        return compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps)
+    B, N = maps.shape[:2]
+    D = weight.shape[0]
+    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
+    f32 = lambda t: t if t is None or t.dtype == torch.float32 else t.float()     # noqa: E731
+    rm, rv = running_mean, running_var
+    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+        return compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps)
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (maps, weight, gamma, beta))
+    out = _CPoolHip.apply(maps, f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous(),
+                          (rm, rv), bool(use_batch_stats), float(momentum), float(eps), need_grad)
+    return out if out.dtype == maps.dtype else out.to(maps.dtype)
+
+
+def nfp_compress_pool(maps, weight, bn, training=None):
+    """The tail the trained heads of models/nfp_heads.py share behind their NFP maps (NFPHead nfp_heads.py:28-32,42-43;
+    MultiRadiusNFPHead 98-102,114-115; AdaptiveFusionNFP 301-305,323-324): maps [B,N,H,W] -> [B,D] =
+    GAP(relu(bn(conv1x1(maps)))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its nn.BatchNorm2d — whose mode
+    (`training`: None = bn.training), running statistics and num_batches_tracked are used and updated exactly as
+    bn.forward does.  See nfp_compress_pool_tensors."""
+    training = bn.training if training is None else bool(training)
+    factor = 0.0 if bn.momentum is None else bn.momentum
+    if training and bn.track_running_stats and bn.num_batches_tracked is not None:      # nn.modules.batchnorm._BatchNorm.forward
+        bn.num_batches_tracked.add_(1)
+        factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+    use_batch_stats = training or (bn.running_mean is None and bn.running_var is None)
+    track = not training or bn.track_running_stats
+    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
+    if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
+        return compress_pool_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps)
+    return nfp_compress_pool_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps)

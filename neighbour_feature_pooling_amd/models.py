@@ -213,10 +213,12 @@ class NFPHeadNet(nn.Module):
     R_list (a tuple of radii): the maps of MultiRadiusNFPHead (nfp_heads.py:80-118) — one NFP layer per radius on the same
     feature map, concatenated; radii (1, 2) come from the same single pass.  fusion="gate": that head's SE gate instead of
     the MLP — fused = gap + alpha * nfp_vec with alpha = sigmoid(MLP(cat(gap, nfp_vec))), one scalar per image
-    (nfp_heads.py:103-117); the sum needs bottleneck_dim == the backbone's channel count."""
+    (nfp_heads.py:103-117); the sum needs bottleneck_dim == the backbone's channel count.
+    fused_compress=True: compress and its mean as one call (functional.nfp_compress_pool: on the GPU the [B,D,H,W]
+    activation is never formed); the default keeps the four ATen ops."""
 
     def __init__(self, backbone="resnet18", num_classes=10, num_input_channels=3, nfp_layer=None, bottleneck_dim=512, R=1,
-                 measure="cosine", R_list=None, fusion="mlp", **backbone_kw):
+                 measure="cosine", R_list=None, fusion="mlp", fused_compress=False, **backbone_kw):
         super().__init__()
         from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPWithGap
         if fusion not in ("mlp", "gate"):
@@ -232,6 +234,7 @@ class NFPHeadNet(nn.Module):
             else:
                 nfp_layer = EnhancedNFPPooling(in_channels=C, R=R, measure=measure, padding=R)
         self.fusion = fusion
+        self.fused_compress = bool(fused_compress)
         self.gap_nfp = NFPWithGap(nfp_layer)
         self.compress = nn.Sequential(nn.Conv2d(self.gap_nfp.out_channels, bottleneck_dim, 1, bias=False),
                                       nn.BatchNorm2d(bottleneck_dim), nn.ReLU(inplace=True))
@@ -250,7 +253,11 @@ class NFPHeadNet(nn.Module):
             H = W = int(math.isqrt(tok.shape[1]))
             feats = tok.transpose(1, 2).unflatten(2, (H, W))
         gap, maps = self.gap_nfp(feats)
-        nfp_vec = self.compress(maps.to(feats.dtype)).mean((2, 3))
+        if self.fused_compress:
+            from .functional import nfp_compress_pool
+            nfp_vec = nfp_compress_pool(maps.to(feats.dtype), self.compress[0].weight, self.compress[1])
+        else:
+            nfp_vec = self.compress(maps.to(feats.dtype)).mean((2, 3))
         gap = gap.to(nfp_vec.dtype)
         if self.fusion == "gate":
             return self.fc(gap + self.se_gate(torch.cat([gap, nfp_vec], dim=1)) * nfp_vec)
