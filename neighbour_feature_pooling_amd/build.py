@@ -10,15 +10,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libnfp_hip.so")
-SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip"]   # four translation units, compiled in parallel
-# ... and the fifth, the valid-map kernels (padding 0).  A list of its own: tests/test_sap_host.py pins SOURCES at the four
-# units above, so the library's units are ALL_SOURCES.
-VALID_SOURCES = ["nfp_valid.hip"]
-ALL_SOURCES = SOURCES + VALID_SOURCES
-# ... and the sixth, the heads' compress-BN-ReLU-GAP tail.  Again a list of its own: tests/test_bottleneck_host.py pins
-# ALL_SOURCES at the five units above, so what the library is compiled from is LIB_SOURCES.
-CPOOL_SOURCES = ["nfp_cpool.hip"]
-LIB_SOURCES = ALL_SOURCES + CPOOL_SOURCES
+# the library's translation units, compiled in parallel: every csrc/*.hip (tests/test_sap_host.py holds the list to that)
+SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip", "nfp_valid.hip", "nfp_cpool.hip"]
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)
@@ -44,7 +37,7 @@ def hipcc_path():
 
 
 def compile_hip(out_lib, extra_flags=(), verbose=False):
-    """hipcc: every source of LIB_SOURCES to an object (in parallel), then one shared library."""
+    """hipcc: every source of SOURCES to an object (in parallel), then one shared library."""
     import concurrent.futures as cf
     import tempfile
     with tempfile.TemporaryDirectory(prefix="nfp_build_") as tmp:
@@ -55,8 +48,8 @@ def compile_hip(out_lib, extra_flags=(), verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             return obj
-        with cf.ThreadPoolExecutor(max_workers=len(LIB_SOURCES)) as ex:
-            objs = list(ex.map(one, LIB_SOURCES))
+        with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+            objs = list(ex.map(one, SOURCES))
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc", "-o", out_lib] + objs
         if verbose:
             print(" ".join(cmd))

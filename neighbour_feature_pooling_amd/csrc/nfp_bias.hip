@@ -324,27 +324,8 @@ namespace {
 // the Meas<> of a bias-path descriptor (g.measure is the descriptor's own: EMD stays EMD, Attention is DotProduct here)
 template <typename F>
 int bias_switch(const KP& g, F&& f) {
-  switch (g.measure) {
-    case NFP_NORM:
-      if (g.p == 1.f) return f(std::integral_constant<int, kNormP1>{});
-      if (g.p == 2.f) return f(std::integral_constant<int, kNormP2>{});
-      return f(std::integral_constant<int, NFP_NORM>{});
-    case NFP_COSINE: return f(std::integral_constant<int, NFP_COSINE>{});
-    case NFP_DOT: return f(std::integral_constant<int, NFP_DOT>{});
-    case NFP_RMSE: return f(std::integral_constant<int, NFP_RMSE>{});
-    case NFP_GEMAN: return f(std::integral_constant<int, NFP_GEMAN>{});
-    case NFP_EMD: return f(std::integral_constant<int, NFP_EMD>{});
-    case NFP_CANBERRA: return f(std::integral_constant<int, NFP_CANBERRA>{});
-    case NFP_HELLINGER: return f(std::integral_constant<int, NFP_HELLINGER>{});
-    case NFP_CHISQUARED1: return f(std::integral_constant<int, NFP_CHISQUARED1>{});
-    case NFP_CHISQUARED2: return f(std::integral_constant<int, NFP_CHISQUARED2>{});
-    case NFP_GFC: return f(std::integral_constant<int, NFP_GFC>{});
-    case NFP_PEARSON: return f(std::integral_constant<int, NFP_PEARSON>{});
-    case NFP_JEFFREY: return f(std::integral_constant<int, NFP_JEFFREY>{});
-    case NFP_SQUAREDCHORD: return f(std::integral_constant<int, NFP_SQUAREDCHORD>{});
-    case NFP_SMITH: return f(std::integral_constant<int, NFP_SMITH>{});
-    default: return fail(NFP_E_UNSUPPORTED, "measure %d has no biased HIP kernel", g.measure);
-  }
+  const int rc = with_measure(g, f);
+  return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "measure %d has no biased HIP kernel", g.measure) : rc;
 }
 
 unsigned flat_blocks(long long n) { return (unsigned)std::min<long long>((n + kBiasT - 1) / kBiasT, 1LL << 20); }

@@ -9,9 +9,6 @@
 #include "nfp_gather.h"
 #include "nfp_mfma.h"
 #include "nfp_direct.h"
-#ifdef NFP_GEMM2_ARM   // (A/B arm, not part of the product build: the matrix-core backward with bwd_tile's table-free phase A —
-#include "nfp_gemm2.h" //  measured SLOWER at config 5, 25.5 vs 17.2 us: profiles/r04_g_…; scripts/ab_flags.py --build "-DNFP_GEMM2_ARM")
-#endif
 
 using namespace nfp;
 using namespace nfp_host;
@@ -473,21 +470,13 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   return go(fwd_band<R, M, BF, NHWC, POOL, false, MF>);
 }
 
-template <int R, int M>
-int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
+template <int R, int M, int POOL = kPoolNone>
+int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
+                    float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
   if (g.ws == nullptr) return kNotApplicable;
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (mixed_maps(g)) {   // float32 maps beside bf16 x: the cosine and L2 instantiations (with their dot / gfc / rmse riders)
-    if constexpr (R != 12 && (M == NFP_COSINE || M == NFP_NORM))
-      return nhwc ? launch_fwd_band_t<R, M, true, true, kPoolNone, true>(g, x, out, saved, st)
-                  : launch_fwd_band_t<R, M, true, false, kPoolNone, true>(g, x, out, saved, st);
-    else
-      return kNotApplicable;   // (Norm p = 1 and the symmetric-term measures: the any-geometry kernels)
-  }
-  if (bf) return nhwc ? launch_fwd_band_t<R, M, true, true>(g, x, out, saved, st)
-                      : launch_fwd_band_t<R, M, true, false>(g, x, out, saved, st);
-  return nhwc ? launch_fwd_band_t<R, M, false, true>(g, x, out, saved, st)
-              : launch_fwd_band_t<R, M, false, false>(g, x, out, saved, st);
+  return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
+    return launch_fwd_band_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, gap, nfpm, part, nb_out);
+  });
 }
 
 // LDS of bwd_fast's phase A: tables that live to the end of the kernel (Wt, Dt, two norm factors per pixel), and
@@ -613,41 +602,6 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   if (S < 1) S = 1;
   g.Cwg = ((g.C / 32 + S - 1) / S) * 32;
   S = (g.C + g.Cwg - 1) / g.Cwg;
-  // Round 4 experiment (-DNFP_GEMM2_ARM builds it; NFP_GEMM2=0 switches it off at run time): phase A without tables, one
-  // thread per padded position (nfp_gemm2.h) — while every position has a thread and its planes fit beside the window
-  // table.  At config 5 a third of the workgroup's threads hold a position and walk ~500 instructions each: 13.8 us of
-  // phase A against 6.0 us for the table-driven one spread over all 1024 threads (in-kernel stamps, profiles/r04_g_…).
-#ifdef NFP_GEMM2_ARM
-  if constexpr (R != 12 && POOL != kPoolGap) {
-    const int npu2 = (g.H + 2 * R) * (g.W + 2 * R);
-    if (g_sw.gemm2.load(std::memory_order_relaxed) && !g.gfc && npu2 <= 1024 && !(!NHWC && (g.P & 3) && S < 2)) {
-      KP h = g;
-      h.Cc = h.Cwg;
-      const int band2 = R * g.W + R, KW2 = nfp::gemm_kw(band2);
-      const size_t xq2 = (size_t)((((g.P + 15) >> 4 << 1) + 1) | 1), wq2 = (size_t)((2 * KW2 + 1) | 1);
-      const int nt2 = (g.P + 31) / 32;
-      const size_t wtb = (((size_t)g.P * K2 + 3) & ~(size_t)3) * 4, planes = (size_t)nfp::gemm2_plane_floats<R>(g.H, g.W) * 4;
-      const size_t xt2 = (size_t)h.Cwg * xq2 * 16, wd2 = (size_t)2 * 32 * wq2 * 16, ggb2 = POOL ? (size_t)h.Cwg * 4 : 0;
-      int rt2 = wtb + xt2 + ggb2 < (size_t)kLdsMax ? (int)(((size_t)kLdsMax - wtb - xt2 - ggb2) / wd2) : 0;
-      rt2 = std::min(rt2, nt2);
-      if (rt2 >= 2 && rt2 < nt2) rt2 = (nt2 + ((nt2 + rt2 - 1) / rt2) - 1) / ((nt2 + rt2 - 1) / rt2);
-      // (the block's grad(GAP) values are written during phase A: they must lie beyond its planes)
-      const bool gg_clear = !POOL || xt2 + (size_t)rt2 * wd2 >= planes;
-      if (rt2 >= std::min(2, nt2) && gg_clear) {
-        h.Tc = rt2;
-        h.early = 0;
-        const size_t lds2 = wtb + std::max(planes, xt2 + (size_t)rt2 * wd2 + ggb2);
-        h.Ow = (int)(lds2 / 4);
-        if (lds2 <= (size_t)kLdsMax) {
-          snprintf(g_variant, sizeof(g_variant), "bwd_gemm2<R%d,%s,bf16,%s,mfma%s>", R, hot_name(g), NHWC ? "nhwc" : "nchw",
-                   POOL ? ",pool" : "");
-          return launch("bwd_gemm2", bwd_gemm2<R, M, NHWC, POOL>, dim3(g.B, S), dim3(1024), lds2, st, h, x, go, out, saved, gx,
-                        ggap, gnfpm);
-        }
-      }
-    }
-  }
-#endif
   // NCHW rows that are not 8-byte aligned (H*W % 4 != 0) are staged and stored 2 bytes at a time: that only pays
   // while the batch is small enough for the channel split (measured: 7.2 vs 8.4 us at B = 64, 16.1 vs 14.0 at 256)
   if (!NHWC && (g.P & 3) && S < 2) return kNotApplicable;
@@ -707,36 +661,18 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
                 g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
 }
 
-// the vector (VALU) backward, for any radius spec
-template <int R, int M>
-int launch_bwd_vec(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                   hipStream_t st) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (mixed_maps(g)) {   // (as launch_fwd_band)
-    if constexpr (R != 12 && (M == NFP_COSINE || M == NFP_NORM))
-      return nhwc ? launch_bwd_fast_t<R, M, true, true, kPoolNone, true>(g, x, go, out, saved, gx, st)
-                  : launch_bwd_fast_t<R, M, true, false, kPoolNone, true>(g, x, go, out, saved, gx, st);
-    else
-      return kNotApplicable;
-  }
-  if (bf) return nhwc ? launch_bwd_fast_t<R, M, true, true>(g, x, go, out, saved, gx, st)
-                      : launch_bwd_fast_t<R, M, true, false>(g, x, go, out, saved, gx, st);
-  return nhwc ? launch_bwd_fast_t<R, M, false, true>(g, x, go, out, saved, gx, st)
-              : launch_bwd_fast_t<R, M, false, false>(g, x, go, out, saved, gx, st);
-}
-
-template <int R, int M>
+// The table backward: phase B on the matrix cores where that form exists (bf16 maps, one radius, cosine / L2) and applies,
+// else the vector (VALU) form, which serves every radius spec.  (float32 maps beside bf16 x: the vector form — the
+// matrix-core backward stages grad_out / out under an LDS budget sized for 2-byte values.)
+template <int R, int M, int POOL = kPoolNone>
 int launch_bwd_fast(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                    hipStream_t st) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  // (float32 maps beside bf16 x: the vector form — the matrix-core backward stages grad_out / out under an LDS budget sized
-  // for 2-byte values)
-  if (bf && !mixed_maps(g)) {
-    const int rc = nhwc ? launch_bwd_gemm_t<R, M, true>(g, x, go, out, saved, gx, st)
-                        : launch_bwd_gemm_t<R, M, false>(g, x, go, out, saved, gx, st);
-    if (rc != kNotApplicable) return rc;
-  }
-  return launch_bwd_vec<R, M>(g, x, go, out, saved, gx, st);
+                    hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
+  return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
+    if constexpr (bf() && !mf() && R != 12 && (M == NFP_COSINE || M == NFP_NORM))
+      if (int rc = launch_bwd_gemm_t<R, M, nhwc(), POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm); rc != kNotApplicable)
+        return rc;
+    return launch_bwd_fast_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+  });
 }
 
 }  // namespace
@@ -802,27 +738,16 @@ int finish(int rc, const char* what) {
 int hot_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
   if (g_sw.tile_first.load(std::memory_order_relaxed))
     if (int rc = tile_forward(g, x, out, saved, st, false, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
-  if (fast_ok(g, x, x) && hot_l1(g)) {
-    const int rc = g.R == 1 ? launch_fwd_band<1, kNormP1>(g, x, out, saved, st) : launch_fwd_band<2, kNormP1>(g, x, out, saved, st);
-    if (rc != kNotApplicable) return rc;
-  } else if (hot_sym(g) && fast_ok(g, x, x, true)) {   // Geman / Canberra / Hellinger / squared chord / chi-squared 1: one instantiation
-    const int rc = g.R == 1 ? launch_fwd_band<1, kSymTerm>(g, x, out, saved, st) : launch_fwd_band<2, kSymTerm>(g, x, out, saved, st);
-    if (rc != kNotApplicable) return rc;
-  } else if (fast_ok(g, x, x)) {
-    int rc;
-    if (hot_product(g))
-      rc = g.R == 1 ? launch_fwd_gram<1, NFP_COSINE>(g, x, out, saved, st)
-                    : launch_fwd_gram<2, NFP_COSINE>(g, x, out, saved, st);
-    else
-      rc = g.R == 1 ? launch_fwd_gram<1, NFP_NORM>(g, x, out, saved, st)
-                    : launch_fwd_gram<2, NFP_NORM>(g, x, out, saved, st);
-    if (rc != kNotApplicable) return rc;
-    if (hot_product(g))
-      rc = g.R == 1 ? launch_fwd_band<1, NFP_COSINE>(g, x, out, saved, st)
-                    : launch_fwd_band<2, NFP_COSINE>(g, x, out, saved, st);
-    else
-      rc = g.R == 1 ? launch_fwd_band<1, NFP_NORM>(g, x, out, saved, st)
-                    : launch_fwd_band<2, NFP_NORM>(g, x, out, saved, st);
+  // (Geman / Canberra / Hellinger / Jeffrey / squared chord / chi-squared 1 share the kSymTerm instantiation)
+  if (fast_ok(g, x, x, true)) {
+    const int rc = with_radius(g, [&](auto r) {
+      return with_hot<true>(g, [&](auto m) {
+        constexpr int R = decltype(r)::value, M = decltype(m)::value;
+        if constexpr (M == NFP_COSINE || M == NFP_NORM)   // the matrix-core forward has these two forms alone
+          if (int rc = launch_fwd_gram<R, M>(g, x, out, saved, st); rc != kNotApplicable) return rc;
+        return launch_fwd_band<R, M>(g, x, out, saved, st);
+      });
+    });
     if (rc != kNotApplicable) return rc;
   }
   // maps above the table kernels' 512 pixels, or a descriptor without its tables: the row-band kernels (nfp_tile.hip)
@@ -863,51 +788,34 @@ int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void
     if (g.ws == nullptr || !fast_ok(g, x, x))
       return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
                   "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = hot_l1(g) ? launch_fwd_band<12, kNormP1>(g, x, out, saved, st)
-                   : hot_product(g) ? launch_fwd_band<12, NFP_COSINE>(g, x, out, saved, st)
-                                    : launch_fwd_band<12, NFP_NORM>(g, x, out, saved, st);
+    const int rc = with_hot<true>(g, [&](auto m) {
+      if constexpr (m() == kSymTerm) return kNotApplicable;   // (fast_ok above has refused these)
+      else return launch_fwd_band<12, m()>(g, x, out, saved, st);
+    });
     return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path forward") : rc;
   }
   if (int rc = hot_forward(g, x, out, saved, st); rc != kNotApplicable) return rc;
-  switch (g.measure) {
-    case NFP_COSINE: return launch_fwd_generic<NFP_COSINE>(g, x, out, saved, st);
-    case NFP_NORM:
-      if (g.p == 1.f) return launch_fwd_generic<kNormP1>(g, x, out, saved, st);
-      if (g.p == 2.f) return launch_fwd_generic<kNormP2>(g, x, out, saved, st);
-      return launch_fwd_generic<NFP_NORM>(g, x, out, saved, st);
-    case NFP_DOT: return launch_fwd_generic<NFP_DOT>(g, x, out, saved, st);
-    case NFP_RMSE: return launch_fwd_generic<NFP_RMSE>(g, x, out, saved, st);
-    case NFP_GEMAN: return launch_fwd_generic<NFP_GEMAN>(g, x, out, saved, st);
-    case NFP_EMD: return launch_fwd_generic<NFP_EMD>(g, x, out, saved, st);
-    case NFP_CANBERRA: return launch_fwd_generic<NFP_CANBERRA>(g, x, out, saved, st);
-    case NFP_HELLINGER: return launch_fwd_generic<NFP_HELLINGER>(g, x, out, saved, st);
-    case NFP_CHISQUARED1: return launch_fwd_generic<NFP_CHISQUARED1>(g, x, out, saved, st);
-    case NFP_CHISQUARED2: return launch_fwd_generic<NFP_CHISQUARED2>(g, x, out, saved, st);
-    case NFP_GFC: return launch_fwd_generic<NFP_GFC>(g, x, out, saved, st);
-    case NFP_PEARSON: return launch_fwd_generic<NFP_PEARSON>(g, x, out, saved, st);
-    case NFP_JEFFREY: return launch_fwd_generic<NFP_JEFFREY>(g, x, out, saved, st);
-    case NFP_SQUAREDCHORD: return launch_fwd_generic<NFP_SQUAREDCHORD>(g, x, out, saved, st);
-    case NFP_SMITH: return launch_fwd_generic<NFP_SMITH>(g, x, out, saved, st);
-    case NFP_ATTENTION: {
-      // raw dots in f32: in `out` itself for float32 maps, in the caller's scratch (nfp_saved_floats) for bf16
-      if (g.dtype != NFP_F32 && !saved)
-        return fail(NFP_E_INVALID, "attention on bf16 maps needs the scratch of nfp_saved_floats (also without a backward)");
-      float* dots = g.dtype == NFP_F32 ? (float*)out : saved;
-      const KP gd = as_dot(g);
-      // float32 maps: DotProduct's hot-path kernels write the raw dots (round 4; bf16 maps keep float32 dots in the scratch, which
-      // only the any-geometry kernels write)
-      int rc = g.dtype == NFP_F32 ? hot_forward(gd, x, dots, nullptr, st) : kNotApplicable;
-      if (rc == kNotApplicable) rc = launch_fwd_generic<NFP_DOT>(gd, x, dots, nullptr, st);
-      if (rc) return rc;
-      const long long n = (long long)g.B * g.O;
-      strncat(g_variant, "+attn_softmax", sizeof(g_variant) - strlen(g_variant) - 1);
-      return launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                    (const float*)dots, out);
-    }
-    default:
-      return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine mixes batch elements in the reference, "
-                  "nfp.py:359-374) has no HIP kernel", g.measure);
+  if (g.measure == NFP_ATTENTION) {
+    // raw dots in f32: in `out` itself for float32 maps, in the caller's scratch (nfp_saved_floats) for bf16
+    if (g.dtype != NFP_F32 && !saved)
+      return fail(NFP_E_INVALID, "attention on bf16 maps needs the scratch of nfp_saved_floats (also without a backward)");
+    float* dots = g.dtype == NFP_F32 ? (float*)out : saved;
+    const KP gd = as_dot(g);
+    // float32 maps: DotProduct's hot-path kernels write the raw dots (round 4; bf16 maps keep float32 dots in the scratch, which
+    // only the any-geometry kernels write)
+    int rc = g.dtype == NFP_F32 ? hot_forward(gd, x, dots, nullptr, st) : kNotApplicable;
+    if (rc == kNotApplicable) rc = launch_fwd_generic<NFP_DOT>(gd, x, dots, nullptr, st);
+    if (rc) return rc;
+    const long long n = (long long)g.B * g.O;
+    variant_suffix("+attn_softmax");
+    return launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
+                  (const float*)dots, out);
   }
+  const int rc = with_measure(g, [&](auto m) { return launch_fwd_generic<m()>(g, x, out, saved, st); });
+  if (rc == kNotApplicable)
+    return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine mixes batch elements in the reference, "
+                "nfp.py:359-374) has no HIP kernel", g.measure);
+  return rc;
 }
 
 // The hot-path backward of a plain single-radius map, or kNotApplicable (as hot_forward).
@@ -921,25 +829,13 @@ int hot_backward(const KP& g, const void* x, const void* grad_out, const void* o
   // state (the map and |x| per pixel), so the two mix.
   if (g.R == 2 && g.rs != 12 && g.dtype == NFP_F32 && g.contig && g.P >= 196 && hot_measure(g))
     if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
-  if (g.ws != nullptr && fast_ok(g, x, grad_x) && hot_l1(g)) {
-    const int rc = g.R == 1 ? launch_bwd_vec<1, kNormP1>(g, x, grad_out, out, saved, grad_x, st)
-                            : launch_bwd_vec<2, kNormP1>(g, x, grad_out, out, saved, grad_x, st);
-    if (rc != kNotApplicable) return rc;
-  } else if (g.ws != nullptr && hot_sym(g) && fast_ok(g, x, grad_x, true) && NFP_SYM_TABLE_BWD && g.P < 196) {
-    // (from 14 x 14 up the row-band backward is ahead: [256,192,14,14] k = 5 97.5 vs 101.9 us, [256,64,20,20] 37.5 vs 41.4;
-    // at 7 x 7 the table kernel: [64,512,7,7] 10.1-12.3 vs 18.2-22.5 us — profiles/r04_zd_…; the forward stays on the tables
-    // up to 512 pixels: 52.7 vs 66.8 us at [256,192,14,14])
-    const int rc = g.R == 1 ? launch_bwd_vec<1, kSymTerm>(g, x, grad_out, out, saved, grad_x, st)
-                            : launch_bwd_vec<2, kSymTerm>(g, x, grad_out, out, saved, grad_x, st);
-    if (rc != kNotApplicable) return rc;
-  } else if (g.ws != nullptr && fast_ok(g, x, grad_x)) {
-    int rc;
-    if (hot_product(g))
-      rc = g.R == 1 ? launch_bwd_fast<1, NFP_COSINE>(g, x, grad_out, out, saved, grad_x, st)
-                    : launch_bwd_fast<2, NFP_COSINE>(g, x, grad_out, out, saved, grad_x, st);
-    else
-      rc = g.R == 1 ? launch_bwd_fast<1, NFP_NORM>(g, x, grad_out, out, saved, grad_x, st)
-                    : launch_bwd_fast<2, NFP_NORM>(g, x, grad_out, out, saved, grad_x, st);
+  // The table kernels.  The kSymTerm measures only below 14 x 14: from there up the row-band backward is ahead ([256,192,14,14]
+  // k = 5 97.5 vs 101.9 us, [256,64,20,20] 37.5 vs 41.4; at 7 x 7 the table kernel: [64,512,7,7] 10.1-12.3 vs 18.2-22.5 us —
+  // profiles/r04_zd_…; the forward stays on the tables up to 512 pixels: 52.7 vs 66.8 us at [256,192,14,14])
+  if (g.ws != nullptr && fast_ok(g, x, grad_x, true) && !(hot_sym(g) && !(NFP_SYM_TABLE_BWD && g.P < 196))) {
+    const int rc = with_radius(g, [&](auto r) {
+      return with_hot<true>(g, [&](auto m) { return launch_bwd_fast<decltype(r)::value, m()>(g, x, grad_out, out, saved, grad_x, st); });
+    });
     if (rc != kNotApplicable) return rc;
   }
   if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
@@ -959,50 +855,32 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
     if (g.ws == nullptr || !fast_ok(g, x, grad_x))
       return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
                   "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = hot_l1(g) ? launch_bwd_vec<12, kNormP1>(g, x, grad_out, out, saved, grad_x, st)
-                   : hot_product(g) ? launch_bwd_vec<12, NFP_COSINE>(g, x, grad_out, out, saved, grad_x, st)
-                                    : launch_bwd_vec<12, NFP_NORM>(g, x, grad_out, out, saved, grad_x, st);
+    const int rc = with_hot<true>(g, [&](auto m) {
+      if constexpr (m() == kSymTerm) return kNotApplicable;   // (fast_ok above has refused these)
+      else return launch_bwd_fast<12, m()>(g, x, grad_out, out, saved, grad_x, st);
+    });
     return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path backward") : rc;
   }
   if (int rc = hot_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
-  switch (g.measure) {
-    case NFP_COSINE: return launch_bwd_generic<NFP_COSINE>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_NORM:
-      if (g.p == 1.f) return launch_bwd_generic<kNormP1>(g, x, grad_out, out, saved, grad_x, st);
-      if (g.p == 2.f) return launch_bwd_generic<kNormP2>(g, x, grad_out, out, saved, grad_x, st);
-      return launch_bwd_generic<NFP_NORM>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_DOT: return launch_bwd_generic<NFP_DOT>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_RMSE: return launch_bwd_generic<NFP_RMSE>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_GEMAN: return launch_bwd_generic<NFP_GEMAN>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_EMD: return launch_bwd_generic<NFP_EMD>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_CANBERRA: return launch_bwd_generic<NFP_CANBERRA>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_HELLINGER: return launch_bwd_generic<NFP_HELLINGER>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_CHISQUARED1: return launch_bwd_generic<NFP_CHISQUARED1>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_CHISQUARED2: return launch_bwd_generic<NFP_CHISQUARED2>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_GFC: return launch_bwd_generic<NFP_GFC>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_PEARSON: return launch_bwd_generic<NFP_PEARSON>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_JEFFREY: return launch_bwd_generic<NFP_JEFFREY>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_SQUAREDCHORD: return launch_bwd_generic<NFP_SQUAREDCHORD>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_SMITH: return launch_bwd_generic<NFP_SMITH>(g, x, grad_out, out, saved, grad_x, st);
-    case NFP_ATTENTION: {
-      float* gd = const_cast<float*>(saved);  // scratch handed over by nfp_forward's caller (nfp_saved_floats)
-      const long long n = (long long)g.B * g.O;
-      if (int rc = launch("attn_softmax_bwd", attn_softmax_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                          grad_out, out, gd))
-        return rc;
-      KP gdot = as_dot(g);
-      gdot.odtype = g.odtype;
-      gdot.godtype = NFP_F32;
-      // float32 maps: DotProduct's hot-path backward on the gradient with respect to the dots (it keeps no saved state: `out` is
-      // only read in bounds)
-      if (g.dtype == NFP_F32) {
-        if (int rc = hot_backward(gdot, x, gd, out, nullptr, grad_x, st); rc != kNotApplicable) return rc;
-      }
-      return launch_bwd_generic<NFP_DOT>(gdot, x, gd, out, nullptr, grad_x, st);
+  if (g.measure == NFP_ATTENTION) {
+    float* gd = const_cast<float*>(saved);  // scratch handed over by nfp_forward's caller (nfp_saved_floats)
+    const long long n = (long long)g.B * g.O;
+    if (int rc = launch("attn_softmax_bwd", attn_softmax_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
+                        grad_out, out, gd))
+      return rc;
+    KP gdot = as_dot(g);
+    gdot.odtype = g.odtype;
+    gdot.godtype = NFP_F32;
+    // float32 maps: DotProduct's hot-path backward on the gradient with respect to the dots (it keeps no saved state: `out` is
+    // only read in bounds)
+    if (g.dtype == NFP_F32) {
+      if (int rc = hot_backward(gdot, x, gd, out, nullptr, grad_x, st); rc != kNotApplicable) return rc;
     }
-    default:
-      return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine) has no HIP kernel", g.measure);
+    return launch_bwd_generic<NFP_DOT>(gdot, x, gd, out, nullptr, grad_x, st);
   }
+  const int rc = with_measure(g, [&](auto m) { return launch_bwd_generic<m()>(g, x, grad_out, out, saved, grad_x, st); });
+  if (rc == kNotApplicable) return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine) has no HIP kernel", g.measure);
+  return rc;
 }
 
 // Floats of scratch behind the per-pixel state in `saved` that the row-band pooled forward needs: every band's share of
@@ -1011,25 +889,18 @@ thread_local long long t_pool_scratch = 0;
 
 template <int R, int M>
 int pool_forward_rm(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
   t_pool_scratch = 0;
   if (g.ws != nullptr && fast_ok(g, x, x)) {
-    int rc;
-    if (bf) {  // the matrix-core forward where it applies, as in nfp_forward
-      rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nfpm);
-      if (rc != kNotApplicable) return rc;
-    }
+    // the matrix-core forward where it applies, as in nfp_forward (it declines float32 storage itself)
+    if (int rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nfpm); rc != kNotApplicable) return rc;
     // row bands at small batches: each band's share of the pooled sums goes to the scratch behind the norms
     float* part = saved != nullptr ? saved + (long long)stats_of(g.measure) * g.B * g.P : nullptr;
     int nb = 1;
-    if (bf) rc = nhwc ? launch_fwd_band_t<R, M, true, true, true>(g, x, out_map, saved, st, gap, nfpm, part, &nb)
-                      : launch_fwd_band_t<R, M, true, false, true>(g, x, out_map, saved, st, gap, nfpm, part, &nb);
-    else rc = nhwc ? launch_fwd_band_t<R, M, false, true, true>(g, x, out_map, saved, st, gap, nfpm, part, &nb)
-                   : launch_fwd_band_t<R, M, false, false, true>(g, x, out_map, saved, st, gap, nfpm, part, &nb);
+    const int rc = launch_fwd_band<R, M, kPoolBoth>(g, x, out_map, saved, st, gap, nfpm, part, &nb);
     if (rc == NFP_OK && nb > 1) {
       t_pool_scratch = (long long)g.B * nb * (g.C + g.N);
       if (g.tickets != nullptr) return rc;   // (the last band to arrive folded them inside the launch)
-      strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+      variant_suffix("+pool_fold");
       return tile_pool_fold(g, part, gap, nfpm, nb, st);
     }
     if (rc != kNotApplicable) return rc;
@@ -1039,31 +910,18 @@ int pool_forward_rm(const KP& g, const void* x, void* out_map, float* saved, hip
   if (saved == nullptr) return fail(NFP_E_INVALID, "fused pooling tail on this map needs the scratch of nfp_pool_saved_floats");
   float* part = saved + (long long)stats_of(g.measure) * g.B * g.P;
   int nb = 0;
-  if (int rc = tile_forward(g, x, out_map, saved, st, true, part, &nb, gap, nfpm); rc != NFP_OK) return rc;
+  if (int rc = tile_forward(g, x, out_map, saved, st, kPoolBoth, part, &nb, gap, nfpm); rc != NFP_OK) return rc;
   t_pool_scratch = (long long)g.B * nb * (g.C + g.N);
   if (g.tickets != nullptr) return NFP_OK;   // (single launch: the last band to arrive folds, nfp_common.h::pool_last_band)
-  strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+  variant_suffix("+pool_fold");
   return tile_pool_fold(g, part, gap, nfpm, nb, st);
 }
 template <int R, int M>
 int pool_backward_rm(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
                      const float* ggap, const float* gnfpm) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (g.ws != nullptr && fast_ok(g, x, gx)) {
-    int rc;
-    if (bf) {  // phase B on the matrix cores where it applies, as in nfp_backward
-      rc = nhwc ? launch_bwd_gemm_t<R, M, true, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm)
-                : launch_bwd_gemm_t<R, M, false, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm);
-      if (rc != kNotApplicable) return rc;
-      rc = nhwc ? launch_bwd_fast_t<R, M, true, true, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm)
-                : launch_bwd_fast_t<R, M, true, false, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm);
-    } else {
-      rc = nhwc ? launch_bwd_fast_t<R, M, false, true, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm)
-                : launch_bwd_fast_t<R, M, false, false, true>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm);
-    }
-    if (rc != kNotApplicable) return rc;
-  }
-  return tile_backward(g, x, nullptr, out_map, saved, gx, st, true, ggap, gnfpm);
+  if (g.ws != nullptr && fast_ok(g, x, gx))
+    if (int rc = launch_bwd_fast<R, M, kPoolBoth>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm); rc != kNotApplicable) return rc;
+  return tile_backward(g, x, nullptr, out_map, saved, gx, st, kPoolBoth, ggap, gnfpm);
 }
 
 // ---- GAP(x) beside the maps (nfp_gap_*): the pass of an NFP head (nfp_heads.py: gap(fmap) and nfp(fmap) of one feature map) ----
@@ -1076,7 +934,6 @@ int pool_backward_rm(const KP& g, const void* x, const void* out_map, const floa
 // not served; one band per image (no counters on this path), so no pool_fold launch either.
 template <int R, int M>
 int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
   t_pool_scratch = 0;
   g.tickets = nullptr;
   g.pool_gap = g.pool_map = 1;
@@ -1085,21 +942,13 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
   KP gfold = g;
   gfold.N = 0;   // (rows of C floats: pool_fold joins the channel sums alone)
   if (g.ws != nullptr && fast_ok(g, x, x)) {
-    int rc;
-    if constexpr (R != 12) {
-      if (bf) {
-        rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr);
-        if (rc != kNotApplicable) return rc;
-      }
-    }
+    if constexpr (R != 12)
+      if (int rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr); rc != kNotApplicable) return rc;
     int nb = 1;
-    if (bf) rc = nhwc ? launch_fwd_band_t<R, M, true, true, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb)
-                      : launch_fwd_band_t<R, M, true, false, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
-    else rc = nhwc ? launch_fwd_band_t<R, M, false, true, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb)
-                   : launch_fwd_band_t<R, M, false, false, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
+    const int rc = launch_fwd_band<R, M, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
     if (rc == NFP_OK && nb > 1) {
       t_pool_scratch = (long long)g.B * nb * g.C;
-      strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+      variant_suffix("+pool_fold");
       return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
     }
     if (rc != kNotApplicable) return rc;
@@ -1108,45 +957,41 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
   int nb = 0;
   if (int rc = tile_forward(g, x, out_map, saved, st, kPoolGap, part, &nb, gap, nullptr); rc != NFP_OK) return rc;
   t_pool_scratch = (long long)g.B * nb * g.C;
-  strncat(g_variant, "+pool_fold", sizeof(g_variant) - strlen(g_variant) - 1);
+  variant_suffix("+pool_fold");
   return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
 }
 template <int R, int M>
 int gap_backward_rm(KP g, const void* x, const void* go, const void* out_map, const float* saved, void* gx, hipStream_t st,
                     const float* ggap) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
   g.pool_gap = ggap != nullptr ? 1 : 0;   // NULL: GAP(x) took no part in the loss — nothing is added, nothing is read
-  if (g.ws != nullptr && fast_ok(g, x, gx)) {
-    int rc;
-    if (bf) {
-      if constexpr (R != 12) {
-        rc = nhwc ? launch_bwd_gemm_t<R, M, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
-                  : launch_bwd_gemm_t<R, M, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
-        if (rc != kNotApplicable) return rc;
-      }
-      rc = nhwc ? launch_bwd_fast_t<R, M, true, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
-                : launch_bwd_fast_t<R, M, true, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
-    } else {
-      rc = nhwc ? launch_bwd_fast_t<R, M, false, true, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr)
-                : launch_bwd_fast_t<R, M, false, false, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr);
-    }
-    if (rc != kNotApplicable) return rc;
-  }
+  if (g.ws != nullptr && fast_ok(g, x, gx))
+    if (int rc = launch_bwd_fast<R, M, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr); rc != kNotApplicable) return rc;
   if (R == 12) return kNotApplicable;
   return tile_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr);
 }
-// the radius spec of the descriptor: 1, 2, or 12 (inner_R = 1: both)
-template <int M>
-int gap_forward_m(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
-  if (g.rs == 12) return gap_forward_rm<12, M>(g, x, out_map, saved, st, gap);
-  return g.R == 1 ? gap_forward_rm<1, M>(g, x, out_map, saved, st, gap) : gap_forward_rm<2, M>(g, x, out_map, saved, st, gap);
+
+// the four of them by the descriptor's radius and family; the gap calls also take radii (1, 2) together (inner_R = 1)
+int pool_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
+  return with_radius(g, [&](auto r) {
+    return with_hot(g, [&](auto m) { return pool_forward_rm<decltype(r)::value, m()>(g, x, out_map, saved, st, gap, nfpm); });
+  });
 }
-template <int M>
-int gap_backward_m(const KP& g, const void* x, const void* go, const void* out_map, const float* saved, void* gx,
-                   hipStream_t st, const float* ggap) {
-  if (g.rs == 12) return gap_backward_rm<12, M>(g, x, go, out_map, saved, gx, st, ggap);
-  return g.R == 1 ? gap_backward_rm<1, M>(g, x, go, out_map, saved, gx, st, ggap)
-                  : gap_backward_rm<2, M>(g, x, go, out_map, saved, gx, st, ggap);
+int pool_backward(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
+                  const float* ggap, const float* gnfpm) {
+  return with_radius(g, [&](auto r) {
+    return with_hot(g, [&](auto m) { return pool_backward_rm<decltype(r)::value, m()>(g, x, out_map, saved, gx, st, ggap, gnfpm); });
+  });
+}
+int gap_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
+  return with_radius<true>(g, [&](auto r) {
+    return with_hot(g, [&](auto m) { return gap_forward_rm<decltype(r)::value, m()>(g, x, out_map, saved, st, gap); });
+  });
+}
+int gap_backward(const KP& g, const void* x, const void* go, const void* out_map, const float* saved, void* gx,
+                 hipStream_t st, const float* ggap) {
+  return with_radius<true>(g, [&](auto r) {
+    return with_hot(g, [&](auto m) { return gap_backward_rm<decltype(r)::value, m()>(g, x, go, out_map, saved, gx, st, ggap); });
+  });
 }
 
 }  // namespace
@@ -1220,9 +1065,9 @@ int nfp_workspace_init(const nfp_desc* d, void* ws, void* hip_stream) {
   if (!fast_geometry(g)) return NFP_OK;   // (no tables for this geometry)
   unsigned char* tables = (unsigned char*)ws + kTicketBytes;
   const int items = g.P * g.k * g.k, blocks = std::min(64, (items + 255) / 256);
-  if (g.rs == 12) return launch("#fill_workspace", fill_workspace<12>, dim3(blocks), dim3(256), 0, st, g, tables);
-  return g.R == 1 ? launch("#fill_workspace", fill_workspace<1>, dim3(blocks), dim3(256), 0, st, g, tables)
-                  : launch("#fill_workspace", fill_workspace<2>, dim3(blocks), dim3(256), 0, st, g, tables);
+  return with_radius<true>(g, [&](auto r) {
+    return launch("#fill_workspace", fill_workspace<r()>, dim3(blocks), dim3(256), 0, st, g, tables);
+  });
 }
 
 int nfp_forward(const nfp_desc* d, const void* x, void* out, float* saved, void* hip_stream) {
@@ -1240,16 +1085,15 @@ int nfp_backward(const nfp_desc* d, const void* x, const void* grad_out, const v
 int nfp_plan(const nfp_desc* d, int32_t backward, char* buf, int32_t buflen) {
   if (!buf || buflen < 1) return fail(NFP_E_INVALID, "null plan buffer");
   buf[0] = 0;
-  t_dry = true;  // (thread-local, like the variant and plan buffers: concurrent calls do not see each other)
+  const DryFlag dry;  // (thread-local, like the variant and plan buffers: concurrent calls do not see each other)
   t_plan[0] = 0;
-  void* fake = (void*)(uintptr_t)0x1000;
+  void* const fake = kStandIn;
   nfp_desc dd = *d;  // as the caller would run it: with the workspace the descriptor is entitled to
   if (dd.ws == nullptr && nfp_workspace_bytes(&dd) > 0) dd.ws = fake;
   d = &dd;
   const int rc = finish(backward ? backward_impl(d, fake, fake, fake, (const float*)fake, fake, nullptr)
                                  : forward_impl(d, fake, fake, (float*)fake, nullptr),
                         "nfp_plan");
-  t_dry = false;
   if (rc == NFP_OK) snprintf(buf, (size_t)buflen, "%s | %s", g_variant, t_plan);
   return rc;
 }
@@ -1260,34 +1104,11 @@ int nfp_plan(const nfp_desc* d, int32_t backward, char* buf, int32_t buflen) {
 // the backward's table size here and forgot the forward's slab: 576 descriptors with R = 2 and P >= 256 were promised
 // and then refused — ADVICE round 2.)
 static int pool_plan(const KP& g, bool backward) {
-  const bool was_dry = t_dry;
-  char keep_variant[sizeof(g_variant)], keep_plan[sizeof(t_plan)], keep_err[sizeof(g_err)];
-  memcpy(keep_variant, g_variant, sizeof(keep_variant));
-  memcpy(keep_plan, t_plan, sizeof(keep_plan));
-  memcpy(keep_err, g_err, sizeof(keep_err));
-  t_dry = true;
-  void* fake = (void*)(uintptr_t)0x1000;
-  int rc;
-  if (!backward) {
-    if (hot_product(g))
-      rc = g.R == 1 ? pool_forward_rm<1, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake)
-                    : pool_forward_rm<2, NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake);
-    else
-      rc = g.R == 1 ? pool_forward_rm<1, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake)
-                    : pool_forward_rm<2, NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake);
-  } else {
-    if (hot_product(g))
-      rc = g.R == 1 ? pool_backward_rm<1, NFP_COSINE>(g, fake, fake, (const float*)fake, fake, nullptr, (const float*)fake, (const float*)fake)
-                    : pool_backward_rm<2, NFP_COSINE>(g, fake, fake, (const float*)fake, fake, nullptr, (const float*)fake, (const float*)fake);
-    else
-      rc = g.R == 1 ? pool_backward_rm<1, NFP_NORM>(g, fake, fake, (const float*)fake, fake, nullptr, (const float*)fake, (const float*)fake)
-                    : pool_backward_rm<2, NFP_NORM>(g, fake, fake, (const float*)fake, fake, nullptr, (const float*)fake, (const float*)fake);
-  }
-  t_dry = was_dry;
-  memcpy(g_variant, keep_variant, sizeof(keep_variant));
-  memcpy(t_plan, keep_plan, sizeof(keep_plan));
-  memcpy(g_err, keep_err, sizeof(keep_err));
-  return rc;
+  const DryRun dry;
+  void* const fake = kStandIn;
+  const float* cf = (const float*)fake;
+  return backward ? pool_backward(g, fake, fake, cf, fake, nullptr, cf, cf)
+                  : pool_forward(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake);
 }
 
 static bool pool_measure_ok(const KP& g) {
@@ -1323,14 +1144,7 @@ int nfp_pool_forward(const nfp_desc* d, const void* x, float* gap, float* nfpm, 
   g.pool_gap = gap != nullptr ? 1 : 0;       // NULL: GAP(x) is not wanted (texture_pooling.py:251-252)
   g.pool_map = out_map != nullptr ? 1 : 0;   // NULL: no backward will follow, nobody reads the maps
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc;
-  if (hot_product(g))
-    rc = g.R == 1 ? pool_forward_rm<1, NFP_COSINE>(g, x, out_map, saved, st, gap, nfpm)
-                  : pool_forward_rm<2, NFP_COSINE>(g, x, out_map, saved, st, gap, nfpm);
-  else
-    rc = g.R == 1 ? pool_forward_rm<1, NFP_NORM>(g, x, out_map, saved, st, gap, nfpm)
-                  : pool_forward_rm<2, NFP_NORM>(g, x, out_map, saved, st, gap, nfpm);
-  return finish(rc, "nfp_pool_forward");
+  return finish(pool_forward(g, x, out_map, saved, st, gap, nfpm), "nfp_pool_forward");
 }
 
 int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, const float* grad_nfpm,
@@ -1343,39 +1157,17 @@ int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, c
   if (g.B == 0) return NFP_OK;
   g.pool_gap = grad_gap != nullptr ? 1 : 0;  // NULL: GAP(x) took no part in the loss (or was never produced)
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc;
-  if (hot_product(g))
-    rc = g.R == 1 ? pool_backward_rm<1, NFP_COSINE>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm)
-                  : pool_backward_rm<2, NFP_COSINE>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm);
-  else
-    rc = g.R == 1 ? pool_backward_rm<1, NFP_NORM>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm)
-                  : pool_backward_rm<2, NFP_NORM>(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm);
-  return finish(rc, "nfp_pool_backward");
+  return finish(pool_backward(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm), "nfp_pool_backward");
 }
 
 // ---- GAP(x) beside the full maps: the first step of an NFP head (nfp_heads.py) -------------------------------------------
 // As pool_plan: both launchers in plan mode, so that a 1 means nfp_gap_forward AND nfp_gap_backward will launch.
 static int gap_plan(const KP& g, bool backward) {
-  const bool was_dry = t_dry;
-  char keep_variant[sizeof(g_variant)], keep_plan[sizeof(t_plan)], keep_err[sizeof(g_err)];
-  memcpy(keep_variant, g_variant, sizeof(keep_variant));
-  memcpy(keep_plan, t_plan, sizeof(keep_plan));
-  memcpy(keep_err, g_err, sizeof(keep_err));
-  t_dry = true;
-  void* fake = (void*)(uintptr_t)0x1000;
+  const DryRun dry;
+  void* const fake = kStandIn;
   const float* cf = (const float*)fake;
-  int rc;
-  if (!backward)
-    rc = hot_product(g) ? gap_forward_m<NFP_COSINE>(g, fake, fake, (float*)fake, nullptr, (float*)fake)
-                        : gap_forward_m<NFP_NORM>(g, fake, fake, (float*)fake, nullptr, (float*)fake);
-  else
-    rc = hot_product(g) ? gap_backward_m<NFP_COSINE>(g, fake, fake, fake, cf, fake, nullptr, cf)
-                        : gap_backward_m<NFP_NORM>(g, fake, fake, fake, cf, fake, nullptr, cf);
-  t_dry = was_dry;
-  memcpy(g_variant, keep_variant, sizeof(keep_variant));
-  memcpy(t_plan, keep_plan, sizeof(keep_plan));
-  memcpy(g_err, keep_err, sizeof(keep_err));
-  return rc;
+  return backward ? gap_backward(g, fake, fake, fake, cf, fake, nullptr, cf)
+                  : gap_forward(g, fake, fake, (float*)fake, nullptr, (float*)fake);
 }
 
 // The gap calls also take radii (1, 2) together (inner_R = 1: make_kp); Norm p = 1 / EMD are outside hot_measure.
@@ -1409,10 +1201,7 @@ int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map,
     return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_gap_saved_floats is %lld", (long long)(saved ? saved_floats : 0),
                 (long long)need);
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc;
-  rc = hot_product(g) ? gap_forward_m<NFP_COSINE>(g, x, out_map, saved, st, gap)
-                      : gap_forward_m<NFP_NORM>(g, x, out_map, saved, st, gap);
-  return finish(rc, "nfp_gap_forward");
+  return finish(gap_forward(g, x, out_map, saved, st, gap), "nfp_gap_forward");
 }
 
 int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, const void* grad_out, const void* out_map,
@@ -1426,40 +1215,25 @@ int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, co
   if (need > 0 && (saved == nullptr || saved_floats < need))
     return fail(NFP_E_INVALID, "saved holds %lld floats, the backward reads %lld", (long long)(saved ? saved_floats : 0), (long long)need);
   hipStream_t st = (hipStream_t)hip_stream;
-  int rc;
-  rc = hot_product(g) ? gap_backward_m<NFP_COSINE>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap)
-                      : gap_backward_m<NFP_NORM>(g, x, grad_out, out_map, saved, grad_x, st, grad_gap);
-  return finish(rc, "nfp_gap_backward");
+  return finish(gap_backward(g, x, grad_out, out_map, saved, grad_x, st, grad_gap), "nfp_gap_backward");
 }
 
 // ---- valid maps (padding 0): nfp_valid.hip ---------------------------------------------------------------------------------
 // Both launchers in plan mode, so that a 1 means nfp_valid_forward AND nfp_valid_backward will launch (4 KiB-aligned
 // buffers assumed, as nfp_plan does); nothing of the calling thread's variant / plan / error strings changes.
 static int valid_plan(const KP& g, bool backward) {
-  const bool was_dry = t_dry;
-  char keep_variant[sizeof(g_variant)], keep_plan[sizeof(t_plan)], keep_err[sizeof(g_err)];
-  memcpy(keep_variant, g_variant, sizeof(keep_variant));
-  memcpy(keep_plan, t_plan, sizeof(keep_plan));
-  memcpy(keep_err, g_err, sizeof(keep_err));
-  t_dry = true;
-  void* fake = (void*)(uintptr_t)0x1000;
-  const int rc = backward ? valid_backward(g, fake, fake, fake, (const float*)fake, fake, nullptr)
-                          : valid_forward(g, fake, fake, (float*)fake, nullptr);
-  t_dry = was_dry;
-  memcpy(g_variant, keep_variant, sizeof(keep_variant));
-  memcpy(t_plan, keep_plan, sizeof(keep_plan));
-  memcpy(g_err, keep_err, sizeof(keep_err));
-  return rc;
+  const DryRun dry;
+  void* const fake = kStandIn;
+  return backward ? valid_backward(g, fake, fake, fake, (const float*)fake, fake, nullptr)
+                  : valid_forward(g, fake, fake, (float*)fake, nullptr);
 }
 
 int nfp_valid_supported(const nfp_desc* d) {
   KP g;
-  char keep_err[sizeof(g_err)];
-  memcpy(keep_err, g_err, sizeof(keep_err));
-  const bool ok = make_kp(d, &g) == NFP_OK && valid_refusal(g) == nullptr &&
-                  (g.B == 0 || (valid_plan(g, false) == NFP_OK && valid_plan(g, true) == NFP_OK));
-  memcpy(g_err, keep_err, sizeof(keep_err));
-  return ok ? 1 : 0;
+  const DryRun dry;   // (make_kp and valid_refusal's callers write the error string too)
+  return make_kp(d, &g) == NFP_OK && valid_refusal(g) == nullptr &&
+                 (g.B == 0 || (valid_plan(g, false) == NFP_OK && valid_plan(g, true) == NFP_OK))
+             ? 1 : 0;
 }
 
 int64_t nfp_valid_saved_floats(const nfp_desc* d) {
@@ -1551,7 +1325,7 @@ int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias,
   if (g.measure == NFP_ATTENTION) {
     if (int rc = bias_forward(as_dot(g), dw, x, centre_bias, neighbour_bias, nullptr, nullptr, saved, st)) return rc;
     const long long n = (long long)g.B * g.O;
-    strncat(g_variant, "+attn_softmax", sizeof(g_variant) - strlen(g_variant) - 1);
+    variant_suffix("+attn_softmax");
     return finish(launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
                          (const float*)saved, out), "nfp_bias_forward");
   }
@@ -1588,7 +1362,7 @@ int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias
         return rc;
     const int rc = bias_backward(gdot, dw, x, centre_bias, neighbour_bias, gd, saved, nullptr, grad_x, grad_centre_bias,
                                  grad_neighbour_bias, scratch, st);
-    if (rc == NFP_OK) strncat(g_variant, "+attn_softmax", sizeof(g_variant) - strlen(g_variant) - 1);
+    if (rc == NFP_OK) variant_suffix("+attn_softmax");
     return finish(rc, "nfp_bias_backward");
   }
   return finish(bias_backward(g, dw, x, centre_bias, neighbour_bias, grad_out, out, saved, grad_x, nc ? nullptr : grad_centre_bias,

@@ -3,6 +3,10 @@
 // nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_cpool.hip: the heads'
 // compress-BN-ReLU-GAP tail).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
+//
+// Also the one home of "descriptor field -> kernel template argument": with_radius, with_hot, with_measure, with_storage and
+// with_storage_mixed (below, with the list of combinations that have no kernel), and of the dry run: DryFlag / DryRun next
+// to launch(), kStandIn for its pointers, variant_suffix for a second launch's name.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -14,10 +18,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "nfp_common.h"
+#include "nfp_measures.h"   // (the dispatch ids kNormP1 / kNormP2 / kSymTerm; templates only, no code of its own)
 
 namespace nfp_host {
 using namespace nfp;
@@ -50,7 +56,6 @@ struct Switches {
                                      // [256,16,112,112]): off by default
   std::atomic<int> gemm3{1};         // the matrix-core backward's second form (nfp_fast.h::bwd_gemm_phase3: every row tile's densified
                                      // weights written by phase A, x in double-buffered chunks) where its LDS fits; 0 = round 3's form
-  std::atomic<int> gemm2{1};         // A/B: the matrix-core backward with the table-free phase A (nfp_gemm2.h; -DNFP_GEMM2_ARM builds only)
   std::atomic<int> tile_dma{-1};     // the channels-last row-band forward staged by LDS-DMA into a position-major slab
                                      // (nfp_tile.h::fwd_tile, DMA): -1 = where it measured faster — bf16 maps of 64 channels and
                                      // more per pixel (8 pieces per position: [256,128,28,28] 23.9 -> 18.8 us, [256,64,56,56] 44.2 ->
@@ -76,7 +81,6 @@ inline void read_env() {
   g_sw.force_generic = flag("NFP_FORCE_GENERIC", 0);
   g_sw.mfma = flag("NFP_MFMA", NFP_MFMA_DEFAULT);
   g_sw.pool_ticket = flag("NFP_POOL_TICKET", 0);
-  g_sw.gemm2 = flag("NFP_GEMM2", 1);
   {
     const char* e = getenv("NFP_GEMM3");   // 0 = never, 1 = where the first form needs several rounds, 2 = wherever it fits (tests)
     g_sw.gemm3 = e ? (e[0] == '2' ? 2 : (e[0] == '1' ? 1 : 0)) : NFP_GEMM3_DEFAULT;
@@ -152,6 +156,33 @@ inline thread_local char t_plan[512] = "";
 // its record in plan mode, behind lds=, so that the form shows without a change to variant strings.  Set and put back by
 // launch_staged() alone, around its one call of launch().
 inline thread_local const char* t_stage = "";
+// The pointer a dry run hands the launchers for every buffer: 4 KiB-aligned, so every alignment rule passes
+inline void* const kStandIn = (void*)(uintptr_t)0x1000;
+
+// Plan mode for the guard's lifetime.  nfp_plan uses this part alone: it publishes t_plan and leaves g_variant / g_err as the
+// dispatcher wrote them.
+struct DryFlag {
+  const bool was_dry = t_dry;
+  DryFlag() { t_dry = true; }
+  ~DryFlag() { t_dry = was_dry; }
+};
+// ... and the calling thread's variant, plan and error strings put back: a question about a descriptor ("would both
+// launchers launch?" — nfp_pool_supported, nfp_gap_supported, nfp_valid_supported and their saved_floats) leaves no trace
+struct DryRun : DryFlag {
+  char variant[sizeof(g_variant)], plan[sizeof(t_plan)], err[sizeof(g_err)];
+  DryRun() {
+    memcpy(variant, g_variant, sizeof(variant));
+    memcpy(plan, t_plan, sizeof(plan));
+    memcpy(err, g_err, sizeof(err));
+  }
+  ~DryRun() {
+    memcpy(g_variant, variant, sizeof(variant));
+    memcpy(t_plan, plan, sizeof(plan));
+    memcpy(g_err, err, sizeof(err));
+  }
+};
+// "+pool_fold" / "+attn_softmax": a second launch behind the one g_variant names
+inline void variant_suffix(const char* s) { strncat(g_variant, s, sizeof(g_variant) - strlen(g_variant) - 1); }
 
 template <typename K, typename... A>
 int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
@@ -224,6 +255,86 @@ inline const char* pool_tag(int pool) { return pool == nfp::kPoolBoth ? ",pool" 
 inline int even_groups(int ncq, int gmax) {
   int rounds = (ncq + gmax - 1) / gmax;
   return (ncq + rounds - 1) / rounds;
+}
+
+// ---- descriptor fields -> kernel template arguments -------------------------------------------------------------------------
+// Each helper calls a generic callable with the field as a std::integral_constant / std::bool_constant, so a launcher
+// template is named once per call site: with_radius(g, [&](auto r) { return f<decltype(r)::value>(...); }).  A helper
+// enumerates only its own field; which COMBINATIONS have a kernel is the caller's `if constexpr`, returning kNotApplicable:
+//   - kNormP1 / kSymTerm: plain maps only (no pooling tail), and kSymTerm not with radius 12;
+//   - radius 12: the table kernels fwd_band / bwd_fast alone (no fwd_gram, no bwd_gemm, no row-band kernel);
+//   - MF (float32 maps beside bf16 x): kHasMixed below.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// the radius: 1 or 2; R12 (the caller serves both radii from one pass): 12 when g.rs == 12
+template <bool R12 = false, typename F>
+int with_radius(const KP& g, F&& f) {
+  if constexpr (R12)
+    if (g.rs == 12) return f(Int<12>{});
+  return g.R == 1 ? f(Int<1>{}) : f(Int<2>{});
+}
+
+// the hot-path family: the product form or the squared-difference form (hot_measure); ALL: also the instantiations of
+// Norm p = 1 and of the symmetric-term measures
+template <bool ALL = false, typename F>
+int with_hot(const KP& g, F&& f) {
+  if constexpr (ALL) {
+    if (hot_l1(g)) return f(Int<kNormP1>{});
+    if (hot_sym(g)) return f(Int<kSymTerm>{});
+  }
+  return hot_product(g) ? f(Int<NFP_COSINE>{}) : f(Int<NFP_NORM>{});
+}
+
+// every measure with a Meas<> of its own, Norm by its order; Attention and SharpenedCosine (the caller's): kNotApplicable.
+// EMD is a case here for the bias path, whose g.measure is the descriptor's own (nfp_hip.hip::bias_kp); make_kp has
+// turned it into Norm p = 1 on the difference weights for nfp_forward / nfp_backward, which never arrive with it.
+template <typename F>
+int with_measure(const KP& g, F&& f) {
+  switch (g.measure) {
+    case NFP_NORM:
+      if (g.p == 1.f) return f(Int<kNormP1>{});
+      if (g.p == 2.f) return f(Int<kNormP2>{});
+      return f(Int<NFP_NORM>{});
+    case NFP_COSINE: return f(Int<NFP_COSINE>{});
+    case NFP_DOT: return f(Int<NFP_DOT>{});
+    case NFP_RMSE: return f(Int<NFP_RMSE>{});
+    case NFP_GEMAN: return f(Int<NFP_GEMAN>{});
+    case NFP_EMD: return f(Int<NFP_EMD>{});
+    case NFP_CANBERRA: return f(Int<NFP_CANBERRA>{});
+    case NFP_HELLINGER: return f(Int<NFP_HELLINGER>{});
+    case NFP_CHISQUARED1: return f(Int<NFP_CHISQUARED1>{});
+    case NFP_CHISQUARED2: return f(Int<NFP_CHISQUARED2>{});
+    case NFP_GFC: return f(Int<NFP_GFC>{});
+    case NFP_PEARSON: return f(Int<NFP_PEARSON>{});
+    case NFP_JEFFREY: return f(Int<NFP_JEFFREY>{});
+    case NFP_SQUAREDCHORD: return f(Int<NFP_SQUAREDCHORD>{});
+    case NFP_SMITH: return f(Int<NFP_SMITH>{});
+    default: return kNotApplicable;
+  }
+}
+
+// storage: f(BF, NHWC) from g.dtype and the layout (dense NCHW, or channels-last: the launchers' callers have checked)
+template <typename F>
+int with_storage(const KP& g, F&& f) {
+  constexpr std::true_type yes;
+  constexpr std::false_type no;
+  if (g.dtype == NFP_BF16) return g.contig ? f(yes, no) : f(yes, yes);
+  return g.contig ? f(no, no) : f(no, yes);
+}
+// MF kernels exist only for plain maps (no pooling), one radius and the COSINE / NORM instantiations (with their dot / gfc /
+// rmse riders); Norm p = 1 and the symmetric-term measures with float32 maps are the any-geometry kernels'
+template <int R, int M, int POOL>
+constexpr bool kHasMixed = POOL == nfp::kPoolNone && R != 12 && (M == NFP_COSINE || M == NFP_NORM);
+// ... and the launchers that serve mixed_maps descriptors: f(BF, NHWC, MF)
+template <int R, int M, int POOL, typename F>
+int with_storage_mixed(const KP& g, F&& f) {
+  if (!mixed_maps(g)) return with_storage(g, [&](auto bf, auto nhwc) { return f(bf, nhwc, std::false_type{}); });
+  constexpr std::true_type yes;
+  if constexpr (kHasMixed<R, M, POOL>)
+    return g.contig ? f(yes, std::false_type{}, yes) : f(yes, yes, yes);
+  else
+    return kNotApplicable;
 }
 
 // ---- the row-band kernels of nfp_tile.h (defined in nfp_tile.hip) -------------------------------------------------------

@@ -264,97 +264,47 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
   return kNotApplicable;
 }
 
-template <int R, int M, int POOL>
-int fwd_rm(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* part, int* nb, float* gap = nullptr,
-           float* nfpm = nullptr) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (mixed_maps(g)) {   // float32 maps beside bf16 x: plain cosine / L2 maps (with their riders); the rest is the any-geometry kernels'
-    if constexpr (POOL == nfp::kPoolNone && (M == NFP_COSINE || M == NFP_NORM))
-      return nhwc ? launch_fwd_tile_t<R, M, true, true, POOL, true>(g, x, out, saved, st, part, nb, gap, nfpm)
-                  : launch_fwd_tile_t<R, M, true, false, POOL, true>(g, x, out, saved, st, part, nb, gap, nfpm);
-    else
-      return kNotApplicable;
-  }
-  if (bf) return nhwc ? launch_fwd_tile_t<R, M, true, true, POOL>(g, x, out, saved, st, part, nb, gap, nfpm)
-                      : launch_fwd_tile_t<R, M, true, false, POOL>(g, x, out, saved, st, part, nb, gap, nfpm);
-  return nhwc ? launch_fwd_tile_t<R, M, false, true, POOL>(g, x, out, saved, st, part, nb, gap, nfpm)
-              : launch_fwd_tile_t<R, M, false, false, POOL>(g, x, out, saved, st, part, nb, gap, nfpm);
+// the fused tail of the launch: none, nfp_pool_* (both pooled sums) or nfp_gap_* (GAP(x) beside the maps)
+template <typename F>
+int with_pool(int pool, F&& f) {
+  if (pool == nfp::kPoolGap) return f(Int<nfp::kPoolGap>{});
+  return pool ? f(Int<nfp::kPoolBoth>{}) : f(Int<nfp::kPoolNone>{});
 }
-template <int R, int M, int POOL>
-int bwd_rm(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-           const float* ggap, const float* gnfpm) {
-  const bool bf = g.dtype == NFP_BF16, nhwc = !g.contig;
-  if (mixed_maps(g)) {   // (as fwd_rm)
-    if constexpr (POOL == nfp::kPoolNone && (M == NFP_COSINE || M == NFP_NORM))
-      return nhwc ? launch_bwd_tile_t<R, M, true, true, POOL, true>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                  : launch_bwd_tile_t<R, M, true, false, POOL, true>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-    else
-      return kNotApplicable;
-  }
-  if (bf) return nhwc ? launch_bwd_tile_t<R, M, true, true, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                      : launch_bwd_tile_t<R, M, true, false, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  return nhwc ? launch_bwd_tile_t<R, M, false, true, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-              : launch_bwd_tile_t<R, M, false, false, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-}
+// Norm p = 1 (the class default, nfp.py:16; and EMD: make_kp) and the symmetric-term measures: plain maps only
+template <int M, int POOL>
+constexpr bool kHasTile = POOL == nfp::kPoolNone || M == NFP_COSINE || M == NFP_NORM;
 
 }  // namespace
 
 int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
                  float* gap, float* nfpm) {
   if (!tile_ok(g, x, x)) return kNotApplicable;
-  const bool cosv = hot_product(g);
-  if (hot_l1(g)) {   // Norm p = 1 (the class default, nfp.py:16) and EMD (make_kp): plain maps
-    if (pool) return kNotApplicable;
-    return g.R == 1 ? fwd_rm<1, kNormP1, false>(g, x, out, saved, st, part, nb) : fwd_rm<2, kNormP1, false>(g, x, out, saved, st, part, nb);
-  }
-  if (hot_sym(g)) {   // one instantiation for the four of them (nfp_measures.h::kSymTerm)
-    // (below 14 x 14 the any-geometry forward spreads the same arithmetic over more threads: [64,512,7,7] 9 vs 14 us; the
-    // backward wins at every size: 17.6-22.9 vs 20.9-28.6 us there — profiles/r04_zd_…)
-    if (pool || g.P < 196) return kNotApplicable;
-    return g.R == 1 ? fwd_rm<1, kSymTerm, false>(g, x, out, saved, st, part, nb) : fwd_rm<2, kSymTerm, false>(g, x, out, saved, st, part, nb);
-  }
-  if (pool == nfp::kPoolGap) {   // GAP(x) beside the maps: the channel sums alone
-    if (cosv) return g.R == 1 ? fwd_rm<1, NFP_COSINE, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm)
-                              : fwd_rm<2, NFP_COSINE, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm);
-    return g.R == 1 ? fwd_rm<1, NFP_NORM, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm)
-                    : fwd_rm<2, NFP_NORM, nfp::kPoolGap>(g, x, out, saved, st, part, nb, gap, nfpm);
-  }
-  if (pool) {
-    if (cosv) return g.R == 1 ? fwd_rm<1, NFP_COSINE, true>(g, x, out, saved, st, part, nb, gap, nfpm)
-                              : fwd_rm<2, NFP_COSINE, true>(g, x, out, saved, st, part, nb, gap, nfpm);
-    return g.R == 1 ? fwd_rm<1, NFP_NORM, true>(g, x, out, saved, st, part, nb, gap, nfpm)
-                    : fwd_rm<2, NFP_NORM, true>(g, x, out, saved, st, part, nb, gap, nfpm);
-  }
-  if (cosv) return g.R == 1 ? fwd_rm<1, NFP_COSINE, false>(g, x, out, saved, st, part, nb) : fwd_rm<2, NFP_COSINE, false>(g, x, out, saved, st, part, nb);
-  return g.R == 1 ? fwd_rm<1, NFP_NORM, false>(g, x, out, saved, st, part, nb) : fwd_rm<2, NFP_NORM, false>(g, x, out, saved, st, part, nb);
+  // (the symmetric-term measures below 14 x 14: the any-geometry forward spreads the same arithmetic over more threads:
+  // [64,512,7,7] 9 vs 14 us; the backward wins at every size: 17.6-22.9 vs 20.9-28.6 us there — profiles/r04_zd_…)
+  if (hot_sym(g) && g.P < 196) return kNotApplicable;
+  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+    constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
+    if constexpr (kHasTile<M, POOL>)
+      return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
+        return launch_fwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, part, nb, gap, nfpm);
+      });
+    else
+      return kNotApplicable;
+  }); }); });
 }
 
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                   int pool, const float* ggap, const float* gnfpm) {
   if (!tile_ok(g, x, gx)) return kNotApplicable;
-  const bool cosv = hot_product(g);
-  if (hot_l1(g)) {
-    if (pool) return kNotApplicable;
-    return g.R == 1 ? bwd_rm<1, kNormP1, false>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                    : bwd_rm<2, kNormP1, false>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  }
-  if (hot_sym(g)) {
-    if (pool) return kNotApplicable;
-    return g.R == 1 ? bwd_rm<1, kSymTerm, false>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                    : bwd_rm<2, kSymTerm, false>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  }
-  if (pool == nfp::kPoolGap) {   // grad_out is a map; grad(GAP) joins in the store
-    if (cosv) return g.R == 1 ? bwd_rm<1, NFP_COSINE, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                              : bwd_rm<2, NFP_COSINE, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-    return g.R == 1 ? bwd_rm<1, NFP_NORM, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm)
-                    : bwd_rm<2, NFP_NORM, nfp::kPoolGap>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  }
-  if (pool) {
-    if (cosv) return g.R == 1 ? bwd_rm<1, NFP_COSINE, true>(g, x, go, out, saved, gx, st, ggap, gnfpm) : bwd_rm<2, NFP_COSINE, true>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-    return g.R == 1 ? bwd_rm<1, NFP_NORM, true>(g, x, go, out, saved, gx, st, ggap, gnfpm) : bwd_rm<2, NFP_NORM, true>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  }
-  if (cosv) return g.R == 1 ? bwd_rm<1, NFP_COSINE, false>(g, x, go, out, saved, gx, st, ggap, gnfpm) : bwd_rm<2, NFP_COSINE, false>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  return g.R == 1 ? bwd_rm<1, NFP_NORM, false>(g, x, go, out, saved, gx, st, ggap, gnfpm) : bwd_rm<2, NFP_NORM, false>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+    constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
+    if constexpr (kHasTile<M, POOL>)   // (grad_out of kPoolGap is a map; grad(GAP) joins in the store)
+      return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
+        return launch_bwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+      });
+    else
+      return kNotApplicable;
+  }); }); });
 }
 
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st) {

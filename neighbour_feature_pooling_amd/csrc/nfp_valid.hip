@@ -476,9 +476,9 @@ static int valid_forward_rp(const KP& g, const void* x, void* out, float* saved,
   snprintf(g_variant, sizeof(g_variant), "fwd_valid<%d,%s,%s,%s>", R, PROD ? "prod" : "dist", bf ? "bf16" : "f32",
            nhwc ? "nhwc" : "nchw");
   const dim3 grid((unsigned)bands, (unsigned)g.B), block(T);
-#define NFP_VALID_FWD(BF, NH_) launch("fwd_valid", nfp::fwd_valid<R, PROD, BF, NH_>, grid, block, lds, st, g, v, x, out, saved)
-  return bf ? (nhwc ? NFP_VALID_FWD(1, 1) : NFP_VALID_FWD(1, 0)) : (nhwc ? NFP_VALID_FWD(0, 1) : NFP_VALID_FWD(0, 0));
-#undef NFP_VALID_FWD
+  return with_storage(g, [&](auto bf_, auto nhwc_) {   // (valid_nchw is g.contig: make_kp)
+    return launch("fwd_valid", nfp::fwd_valid<R, PROD, bf_(), nhwc_()>, grid, block, lds, st, g, v, x, out, saved);
+  });
 }
 
 template <int R, int FAM>
@@ -511,24 +511,32 @@ static int valid_backward_rp(const KP& g, const void* x, const void* go, const v
   snprintf(g_variant, sizeof(g_variant), "bwd_valid<%d,%s,%s,%s>", R, PROD ? "prod" : "dist", bf ? "bf16" : "f32",
            nhwc ? "nhwc" : "nchw");
   const dim3 grid((unsigned)bands, (unsigned)g.B, (unsigned)nz), block(T);
-#define NFP_VALID_BWD(BF, NH_) launch("bwd_valid", nfp::bwd_valid<R, FAM, BF, NH_>, grid, block, lds, st, g, v, x, go, out, saved, gx)
-  return bf ? (nhwc ? NFP_VALID_BWD(1, 1) : NFP_VALID_BWD(1, 0)) : (nhwc ? NFP_VALID_BWD(0, 1) : NFP_VALID_BWD(0, 0));
-#undef NFP_VALID_BWD
+  return with_storage(g, [&](auto bf_, auto nhwc_) {
+    return launch("bwd_valid", nfp::bwd_valid<R, FAM, bf_(), nhwc_()>, grid, block, lds, st, g, v, x, go, out, saved, gx);
+  });
 }
 
 int valid_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
   if (const char* why = valid_refusal(g)) return fail(NFP_E_UNSUPPORTED, "valid maps: %s", why);
-  if (hot_product(g)) return g.R == 1 ? valid_forward_rp<1, 1>(g, x, out, saved, st) : valid_forward_rp<2, 1>(g, x, out, saved, st);
-  return g.R == 1 ? valid_forward_rp<1, 0>(g, x, out, saved, st) : valid_forward_rp<2, 0>(g, x, out, saved, st);
+  return with_radius(g, [&](auto r) {
+    return with_hot(g, [&](auto m) {   // PROD: the product form
+      return valid_forward_rp<decltype(r)::value, m() == NFP_COSINE ? 1 : 0>(g, x, out, saved, st);
+    });
+  });
 }
 
 int valid_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st) {
   if (const char* why = valid_refusal(g)) return fail(NFP_E_UNSUPPORTED, "valid maps: %s", why);
-  if (g.measure == NFP_COSINE)
-    return g.R == 1 ? valid_backward_rp<1, 2>(g, x, go, out, saved, gx, st) : valid_backward_rp<2, 2>(g, x, go, out, saved, gx, st);
-  if (hot_product(g))
-    return g.R == 1 ? valid_backward_rp<1, 1>(g, x, go, out, saved, gx, st) : valid_backward_rp<2, 1>(g, x, go, out, saved, gx, st);
-  return g.R == 1 ? valid_backward_rp<1, 0>(g, x, go, out, saved, gx, st) : valid_backward_rp<2, 0>(g, x, go, out, saved, gx, st);
+  return with_radius(g, [&](auto r) {
+    return with_hot(g, [&](auto m) {   // FAM: 0 the distances, 1 dot / gfc, 2 cosine (the pairs' cosines are kept too)
+      constexpr int R = decltype(r)::value;
+      if constexpr (m() == NFP_COSINE)
+        return g.measure == NFP_COSINE ? valid_backward_rp<R, 2>(g, x, go, out, saved, gx, st)
+                                       : valid_backward_rp<R, 1>(g, x, go, out, saved, gx, st);
+      else
+        return valid_backward_rp<R, 0>(g, x, go, out, saved, gx, st);
+    });
+  });
 }
 
 }  // namespace nfp_host

@@ -236,8 +236,7 @@ def test_new_exports_are_declared_and_loadable():
     assert NEW_EXPORTS <= declared and NEW_EXPORTS <= set(_abi.EXPORTS)
     assert int(re.search(r"#define NFP_ABI_VERSION (\d+)", src).group(1)) == _abi.ABI_VERSION == 7
     from neighbour_feature_pooling_amd import build
-    assert build.CPOOL_SOURCES == ["nfp_cpool.hip"] and build.LIB_SOURCES == build.ALL_SOURCES + build.CPOOL_SOURCES
-    assert len(build.LIB_SOURCES) == 6
+    assert "nfp_cpool.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "nfp_cpool.hip"))
     build.build_hip()
     L = _abi.load()
     for n in NEW_EXPORTS:
