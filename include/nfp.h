@@ -322,6 +322,36 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream);
 
+/*
+ * The same projection with the map kept (csrc/nfp_cpool.hip, the cproj kernels) — NFPInsert's nfp_proj
+ * (models/mobilenetv3.py:346-350: Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU) and NFPBottleneck's bn2(conv2(.))
+ * (models/nfp_heads.py:270-272, relu = 0):
+ *   out [B,D,P] = [relu](batch_norm(conv1x1(maps)))
+ * stored once, dense, in the maps' dtype (float32 arithmetic, one rounding).  Arguments, statistics, `saved`
+ * (nfp_cpool_saved_floats(N, D) floats) and every convention are those of nfp_cpool_* above, with three differences:
+ *   relu      != 0: the ReLU behind the BatchNorm; 0: none (the pre-activation is the output)
+ *   out       [B,D,P] and grad_out [B,D,P] are DEVICE pointers of the maps' dtype
+ *   scratch   holds nfp_cproj_scratch_floats(B, N, P, D, backward) floats
+ * The backward reads the maps, the parameters, `saved` and grad_out — never `out`, which the caller may have modified in
+ * place — and recomputes the pre-activation for the ReLU's mask.  Launches: forward 3 in training (moments, finish,
+ * cproj_fwd) and 1 in eval; backward at most 3 (cproj_bwd_part, the batch reduce, cproj_bwd_maps), skipped as in
+ * nfp_cpool_backward for the gradients passed as NULL.  No atomics: two runs agree bitwise, and in eval image b's rows of
+ * out / grad_maps do not depend on the batch around it.  nfp_last_variant names cproj_fwd<f32|bf16,train|eval,relu|lin> /
+ * cproj_bwd<...>.  NFP_E_INVALID, launching nothing: a short or missing buffer, a NULL required pointer, B < 0, N < 1, P < 1,
+ * D < 1, an unknown dtype, a negative eps.  NFP_E_UNSUPPORTED: N > 32, N*P >= 2^31, D*P >= 2^31, D > 2^22, B*P < 2 in
+ * training.  B = 0 returns NFP_OK without a launch.  Additive to ABI 7.
+ */
+int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward);
+int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                      float* scratch, int64_t scratch_floats, void* hip_stream);
+int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

@@ -14,12 +14,16 @@ Drop-in for the reference's NFP hot path:
     NFPHead, MultiRadiusNFPHead,     <- models/nfp_heads.py: the three heads the reference trains (GAP + compressed NFP maps,
     AdaptiveFusionNFP                   fused by an MLP or a gate)
     nfp_compress_pool                their shared tail GAP(relu(bn(conv1x1(maps)))) as one op, without the [B,D,H,W] activation
+    NFPInsert                        <- the nfp + nfp_proj block of models/mobilenetv3.py::MOBILENETV3_NFP_INSERT (345-353)
+    nfp_compress_map                 its projection [relu](bn(conv1x1(maps))) as one op that keeps the map (models.NFPInsertNet:
+                                        the whole net; NFPBottleneck(fused_project=True): the same op without the ReLU)
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
-from .functional import (NfpConfig, nfp_attention_pool, nfp_compress_pool, nfp_compress_pool_tensors, nfp_multi_radius,
-                         nfp_pool, nfp_pooled, nfp_valid, nfp_with_gap)
+from .functional import (NfpConfig, nfp_attention_pool, nfp_compress_map, nfp_compress_map_tensors, nfp_compress_pool,
+                         nfp_compress_pool_tensors, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_valid, nfp_with_gap)
 from .functional import nfp as nfp_op  # (`nfp` itself is the submodule holding NFPPooling)
-from .nfp import EnhancedNFPPooling, MultiRadiusNFPPooling, NFPBottleneck, NFPPooling, NFPWithGap, SimilarityAwarePooling
+from .nfp import (EnhancedNFPPooling, MultiRadiusNFPPooling, NFPBottleneck, NFPInsert, NFPPooling, NFPWithGap,
+                  SimilarityAwarePooling)
 from .pooling import nfp_pooling
 from .heads import AdaptiveFusionNFP, MultiRadiusNFPHead, NFPHead
 from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
@@ -27,5 +31,5 @@ from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
 __all__ = ["NFPPooling", "EnhancedNFPPooling", "MultiRadiusNFPPooling", "nfp_pooling", "nfp_op", "nfp_pool", "nfp_pooled",
            "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool",
            "NFPBottleneck", "nfp_valid", "NFPHead", "MultiRadiusNFPHead", "AdaptiveFusionNFP", "nfp_compress_pool",
-           "nfp_compress_pool_tensors"]
+           "nfp_compress_pool_tensors", "NFPInsert", "nfp_compress_map", "nfp_compress_map_tensors"]
 __version__ = "0.4.0"

@@ -25,7 +25,8 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward",
            "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
-           "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward"]
+           "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
+           "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward"]
 
 
 class NfpDesc(ctypes.Structure):
@@ -116,6 +117,13 @@ def load():
         L.nfp_cpool_scratch_floats.restype = i64
         L.nfp_cpool_forward.argtypes = [i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, i64, vp, i64, vp]
         L.nfp_cpool_backward.argtypes = [i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp, vp, vp,
+                                         vp, vp, i64, vp]
+    if hasattr(L, "nfp_cproj_forward"):         # (absent only from an older library loaded for an A/B run)
+        L.nfp_cproj_scratch_floats.argtypes = [i32, i32, i64, i32, i32]
+        L.nfp_cproj_scratch_floats.restype = i64
+        L.nfp_cproj_forward.argtypes = [i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, i64, vp, i64,
+                                        vp]
+        L.nfp_cproj_backward.argtypes = [i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp, vp, vp,
                                          vp, vp, i64, vp]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")

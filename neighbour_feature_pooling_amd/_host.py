@@ -129,3 +129,16 @@ def compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use
     y = F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
     y = F.batch_norm(y, running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
     return F.relu(y).mean((2, 3))
+
+
+def compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps, relu=True):
+    """The projection of NFP maps that keeps the map — NFPInsert's nfp_proj (models/mobilenetv3.py:346-350) and, with
+    relu=False, NFPBottleneck's bn2(conv2(.)) (models/nfp_heads.py:270-272): [relu](batch_norm(conv1x1(maps))) as the ATen
+    ops, any dtype and device, under torch.compile and torch.autocast: maps [B,N,H,W] (or [B,N,P]) -> [B,D,H,W] ([B,D,P]).
+    weight [D,N,1,1] or [D,N]; gamma / beta may be None (affine=False); the running statistics, where given, are updated in
+    place by batch_norm when use_batch_stats (momentum: its exponential factor).  Autograd differentiates."""
+    B, N = maps.shape[:2]
+    y = F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
+    y = F.batch_norm(y, running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
+    y = F.relu(y) if relu else y
+    return y if maps.dim() == 4 else y.reshape(B, weight.shape[0], *maps.shape[2:])

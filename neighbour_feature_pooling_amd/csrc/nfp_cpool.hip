@@ -27,6 +27,19 @@
 //   cpool_bwd_reduce  one workgroup per 32 channels: the slices in order, the parameter gradients, this tile's share of k, Q
 //   cpool_bwd_maps  lanes along 64 pixels (their c_n in registers); D in blocks of 128 channels whose scaled rows are staged in
 //                   LDS and dealt to the wavefronts, joined in wave order through LDS; then - k - Q c
+//
+// The same projection with the map kept — nfp_cproj_* (NFPInsert's nfp_proj, models/mobilenetv3.py:346-350; NFPBottleneck's
+// bn2(conv2(.)), nfp_heads.py:270-272): out_bdp = [relu](a_bdp) stored as [B,D,P] in the maps' dtype, and a backward given
+// grad_out [B,D,P], so ga_bdp = grad_out_bdp [a_bdp > 0] (without the ReLU: grad_out_bdp); every other formula above holds.
+// cpool_moments / cpool_finish / cpool_bwd_reduce serve both; the backward reads grad_out twice, the maps and nothing else
+// of that size — never the forward's output.
+//   cproj_fwd       one workgroup per (chunk of an image's pixels, 64 channels of D): the chunk's centred maps and the
+//                   channels' scaled rows in LDS; lanes along the flattened (d, p) range of the chunk, so adjacent lanes
+//                   store adjacent pixels of a channel (or run on into the next channel where the chunk is the whole image)
+//   cproj_bwd_part  cpool_bwd_part's lanes along d, over a slice of the batch's 64-pixel passes: the pass's maps and the
+//                   [128 channels][64 pixels] tile of grad_out go to LDS with lanes along p (whole lines), and are read back
+//                   as a float4 per channel
+//   cproj_bwd_maps  cpool_bwd_maps with grad_out read per (channel, pixel), lanes along p, four channels' loads in flight
 #include "nfp_launch.h"
 
 #include <cmath>
@@ -52,6 +65,8 @@ struct CpK {
   const float *w, *gamma, *beta, *rm, *rv, *stats, *go, *part, *kq;
   float *out, *stats_w, *part_w, *kq_w, *rm_w, *rv_w, *gw, *gg, *gb;
   void* gm;
+  const void* gov;   // cproj: grad_out [B,D,P] and out [B,D,P] in the maps' dtype
+  void* outv;
 };
 // stats (the forward's saved state, training): mu_hi [N], mu_lo [N], Sigma [N*N], inv [D]
 __device__ __forceinline__ const float* cp_inv(const CpK& k) { return k.stats + 2 * k.N + k.N * k.N; }
@@ -407,6 +422,9 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
 }
 
 // grid = ceil(D / 32), block = 256.  kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
+// LIVE (the cproj backward, whose S reaches 512): loads are issued only from the element rounds and lanes that hold an
+// element; the sums and their order are the same in both forms.
+template <bool LIVE>
 __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
   __shared__ float Tl[kCpRT * (kCpMaxN + 1)];
   __shared__ float wl[kCpRT * kCpMaxN];
@@ -426,17 +444,40 @@ __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
       off[e] = (i < kCpRT * N1 && d < k.D) ? (long long)d * N1 + j : -1;
     }
     const long long stride = (long long)k.D * N1;
-    for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
-      float v[kE][8];
+    if (!LIVE) {
+      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
+        float v[kE][8];
 #pragma unroll
-      for (int e = 0; e < kE; ++e)
+        for (int e = 0; e < kE; ++e)
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[e][u] = k.part[min(sl0 + u, k.S - 1) * stride + max(off[e], 0LL)];
+          for (int u = 0; u < 8; ++u) v[e][u] = k.part[min(sl0 + u, k.S - 1) * stride + max(off[e], 0LL)];
 #pragma unroll
-      for (int e = 0; e < kE; ++e)
+        for (int e = 0; e < kE; ++e)
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
+          for (int u = 0; u < 8; ++u)
+            if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
+      }
+    } else {
+      // the same, but only the ne element rounds that hold an element at all (2 of the 5 at N = 8) and only the lanes that
+      // hold one issue loads: with hundreds of slices the walk is bound by the loads one CU can issue (measured: 90 us over
+      // the 704 slices of cproj_bwd_part at [64,8,26,26] -> 40 with every lane of every round loading)
+      const int ne = (kCpRT * N1 + kCpMT - 1) / kCpMT;
+      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {
+        float v[kE][8];
+#pragma unroll
+        for (int e = 0; e < kE; ++e)
+          if (e < ne) {   // (the same in every thread)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[e][u] = off[e] >= 0 ? k.part[min(sl0 + u, k.S - 1) * stride + off[e]] : 0.f;
+          }
+#pragma unroll
+        for (int e = 0; e < kE; ++e)
+          if (e < ne) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+              if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
+          }
+      }
     }
 #pragma unroll
     for (int e = 0; e < kE; ++e) {
@@ -592,6 +633,239 @@ __global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
   }
 }
 
+// ---- cproj: the projection with the map kept ------------------------------------------------------------------------------
+constexpr int kCjT = 256;    // threads of cproj_fwd
+constexpr int kCjDT = 64;    // channels of D per workgroup of cproj_fwd
+constexpr int kCjSP = 64;    // pixels per pass of cproj_bwd_part
+constexpr int kCjSS = 68;    // floats between two rows of a pass in LDS: 16-byte rows, an odd number of 16-byte slots
+
+__device__ __forceinline__ float cj_load(const CpK& k, const void* p, long long j) {
+  return k.bf16 ? bf16_to_f32(((const uint16_t*)p)[j]) : ((const float*)p)[j];
+}
+
+// grid = B * nc * tiles (the tile fastest), block = 256; k.CH / k.CHs / k.nc are this kernel's own chunks (cproj_fwd_chunk).
+// LDS: sm[NP * CHs], tb[64][NP + 1] — the scaled row of a channel, then its shift.
+template <int NP, bool RELU>
+__global__ void __launch_bounds__(kCjT) cproj_fwd(CpK k, int tiles) {
+  constexpr int kTS = NP + 1;
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* tb = sm + NP * k.CHs;
+  const int tid = threadIdx.x;
+  const int bj = blockIdx.x / tiles, tile = blockIdx.x - bj * tiles;
+  const int b = bj / k.nc, j = bj - b * k.nc;
+  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
+  const int d0 = tile * kCjDT, nd = min(kCjDT, k.D - d0);
+  cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+  for (int i = tid; i < nd * kTS; i += kCjT) {
+    const int dl = i / kTS, n = i - dl * kTS;
+    float scale, shift;
+    cp_coef(k, d0 + dl, scale, shift);
+    tb[i] = n == NP ? shift : (n < k.N ? k.w[(long long)(d0 + dl) * k.N + n] * scale : 0.f);
+  }
+  __syncthreads();
+  // element e = dl * ch + pl of the chunk's [nd][ch] range; a thread's next one is 256 further on
+  const int total = nd * ch, qT = kCjT / ch, rT = kCjT - qT * ch;
+  int dl = tid / ch, pl = tid - dl * ch;
+  const long long obase = ((long long)b * k.D + d0) * k.P + p0;
+  for (int e = tid; e < total; e += kCjT) {
+    const float* row = tb + dl * kTS;
+    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
+#pragma unroll
+    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * k.CHs + pl], a);
+    if (RELU) a = a < 0.f ? 0.f : a;
+    const long long o = obase + (long long)dl * k.P + pl;
+    if (k.bf16)
+      ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
+    else
+      ((float*)k.outv)[o] = a;
+    pl += rT, dl += qT;
+    if (pl >= ch) pl -= ch, ++dl;
+  }
+}
+
+// grid = (S, ceil(D / 128)), block = cp_part_threads: passes [s * upw, (s + 1) * upw) of the batch's B * nsub passes of 64
+// pixels.  LDS: sm[NP * 68], gl[128 * 68] (grad_out of the pass; at the end the join buffer red[128 * (NP + 1)]).
+// part_w: [S][D][N + 1], as cpool_bwd_part.
+template <int NP, bool RELU>
+__global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, int nsub, int upw) {
+  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* gl = sm + NP * kCjSS;
+  float* red = gl;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sl = blockIdx.x, tile = blockIdx.y;
+  float ws[2][NP], sh[2], T[2][NP], gbs[2] = {0.f, 0.f};
+  if (RELU) cp_rows<NP>(k, tile, lane, ws, sh);
+#pragma unroll
+  for (int n = 0; n < NP; ++n) T[0][n] = T[1][n] = 0.f;
+  const int units = k.B * nsub, u0 = sl * upw, u1 = min(units, u0 + upw);
+  for (int u = u0; u < u1; ++u) {
+    const int b = u / nsub, ps = (u - b * nsub) * kCjSP, npx = min(kCjSP, k.P - ps);
+    if (u > u0) __syncthreads();   // (the previous pass has been read)
+    cp_stage(k, NP, sm, b, ps, npx, !k.eval);
+    for (int i = tid; i < kCpDT * kCjSP; i += kT) {
+      const int dl = i >> 6, pl = i & 63, d = tile * kCpDT + dl;
+      float v = 0.f;
+      if (d < k.D && pl < npx) v = cj_load(k, k.gov, ((long long)b * k.D + d) * k.P + ps + pl);
+      gl[dl * kCjSS + pl] = v;
+    }
+    __syncthreads();
+    const int nq = (npx + 3) >> 2;
+    for (int q = wv; q < nq; q += kW) {
+      float ga[2][4];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float4 g4 = ((const float4*)(gl + (lane + 64 * j) * kCjSS))[q];   // (zero beyond npx and D)
+        ga[j][0] = g4.x, ga[j][1] = g4.y, ga[j][2] = g4.z, ga[j][3] = g4.w;
+      }
+      if (RELU) {
+        float a[2][4];
+        cp_preact<NP>(sm, kCjSS, q, ws, sh, a);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ga[j][i] = a[j][i] > 0.f ? ga[j][i] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) gbs[j] += ga[j][i];
+#pragma unroll
+      for (int n = 0; n < NP; ++n) {
+        const float4 c = ((const float4*)(sm + n * kCjSS))[q];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          float t = T[j][n];
+          t = fmaf(ga[j][0], c.x, t);
+          t = fmaf(ga[j][1], c.y, t);
+          t = fmaf(ga[j][2], c.z, t);
+          t = fmaf(ga[j][3], c.w, t);
+          T[j][n] = t;
+        }
+      }
+    }
+  }
+  __syncthreads();   // (gl has been read: red takes its place)
+  for (int w = 0; w < kW; ++w) {   // the wavefronts in order into red[dl][NP + 1] (every lane its own words)
+    if (wv == w) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float* r = red + (lane + 64 * j) * (NP + 1);
+#pragma unroll
+        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
+        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
+      }
+    }
+    __syncthreads();
+  }
+  const int N1 = k.N + 1;
+  for (int i = tid; i < kCpDT * N1; i += kT) {
+    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
+    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
+  }
+}
+
+// grid = B * ceil(P / 64), block = 512: cpool_bwd_maps with grad_out read per (channel, pixel).  LDS: red[NP * 64],
+// kql[N + N * N], tb[128][NP + 4] — a channel's scaled row, then its shift.
+template <int NP, bool RELU>
+__global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
+  constexpr int kTS = NP + 4;
+  __shared__ float red[NP * 64];
+  __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
+  __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
+  __shared__ float cf[kCpMB];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
+  const bool live = p < k.P;
+  if (!k.eval)
+    for (int i = tid; i < N + NN; i += kCpT) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
+      kql[i] = s;
+    }
+  float c[NP], g[NP];
+  const long long base = (long long)b * N * k.P + p;
+#pragma unroll
+  for (int n = 0; n < NP; ++n) {
+    float v = 0.f;
+    if (n < N && live) {
+      v = cj_load(k, k.maps, base + (long long)n * k.P);
+      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
+    }
+    c[n] = v;
+    g[n] = 0.f;
+  }
+  const long long gbase = (long long)b * k.D * k.P + p;
+  for (int dB = 0; dB < k.D; dB += kCpMB) {
+    const int nd = min(kCpMB, k.D - dB);
+    if (dB > 0) __syncthreads();   // (the previous block has been read)
+    if (tid < nd) {
+      float scale, shift;
+      cp_coef(k, dB + tid, scale, shift);
+      cf[tid] = scale;
+      tb[tid * kTS + NP] = shift;
+    }
+    __syncthreads();
+    for (int i = tid; i < nd * NP; i += kCpT) {
+      const int dl = i / NP, n = i - dl * NP;
+      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl] : 0.f;
+    }
+    __syncthreads();
+    for (int dl0 = wv; dl0 < nd; dl0 += 4 * kCpW) {   // four channels' grad_out loads together, used in channel order
+      float t[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int dl = dl0 + u * kCpW;
+        t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int dl = dl0 + u * kCpW;
+        if (dl >= nd) break;   // (the same in every lane)
+        const float* row = tb + dl * kTS;
+        float wsn[NP];
+#pragma unroll
+        for (int n = 0; n < NP; ++n) wsn[n] = row[n];
+        float tu = t[u];
+        if (RELU) {
+          float a = row[NP];
+#pragma unroll
+          for (int n = 0; n < NP; ++n) a = fmaf(wsn[n], c[n], a);
+          tu = a > 0.f ? tu : 0.f;
+        }
+#pragma unroll
+        for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], tu, g[n]);
+      }
+    }
+  }
+  for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
+    if (wv == w) {
+#pragma unroll
+      for (int n = 0; n < NP; ++n) red[n * 64 + lane] = w == 0 ? g[n] : red[n * 64 + lane] + g[n];
+    }
+    __syncthreads();
+  }
+  if (!live) return;
+  for (int n = wv; n < N; n += kCpW) {
+    float v = red[n * 64 + lane];
+    if (!k.eval) {
+      float qc = kql[n];
+#pragma unroll
+      for (int n2 = 0; n2 < NP; ++n2)
+        if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
+      v -= qc;
+    }
+    const long long j = base + (long long)n * k.P;
+    if (k.bf16)
+      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
+    else
+      ((float*)k.gm)[j] = v;
+  }
+}
+
 }  // namespace
 }  // namespace nfp
 
@@ -695,6 +969,74 @@ int64_t cpool_bwd_scratch(int32_t B, int32_t N, int32_t D) {
   return (int64_t)cpool_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
 }
 
+// ---- cproj ----
+// pixels per workgroup of cproj_fwd: cpool_chunk, halved (down to 256) while the grid has fewer than 1024 workgroups
+int cproj_fwd_chunk(int NP, long long B, long long P, int D) {
+  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT;
+  long long ch = cpool_chunk(NP, P);
+  while (ch > 256 && B * ((P + ch - 1) / ch) * tiles < 1024) ch = std::max<long long>(256, (ch / 2) & ~63LL);
+  return (int)ch;
+}
+// passes of 64 pixels per workgroup of cproj_bwd_part: about 512 workgroups (every slice is read again by the few
+// workgroups of cpool_bwd_reduce), at most one per pass
+int cproj_upw(long long B, long long P, int D) {
+  const long long units = B * ((P + nfp::kCjSP - 1) / nfp::kCjSP);
+  const long long want = std::min<long long>(units, std::max(1, 512 / cpool_tiles(D)));
+  return (int)((units + want - 1) / want);
+}
+int cproj_slices(long long B, long long P, int D) {
+  const long long units = B * ((P + nfp::kCjSP - 1) / nfp::kCjSP), upw = cproj_upw(B, P, D);
+  return (int)((units + upw - 1) / upw);
+}
+int64_t cproj_bwd_scratch(int32_t B, int32_t N, int64_t P, int32_t D) {
+  return (int64_t)cproj_slices(std::max(B, 1), P, D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
+}
+int cproj_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
+  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
+  if ((long long)D * P >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: an image of D * P = %lld output elements (2^31 and more) has no kernel", what,
+                (long long)D * P);
+  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT, ch = cproj_fwd_chunk(cpool_np(N), std::max(B, 1), P, D);
+  if ((long long)B * ((P + ch - 1) / ch) * tiles >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: B = %d, P = %lld, D = %d make 2^31 workgroups and more", what, B, (long long)P, D);
+  return NFP_OK;
+}
+
+template <template <int, bool> class F, typename... A>
+int cproj_by_np(int NP, bool relu, A... a) {
+  switch (NP) {
+    case 8: return relu ? F<8, true>::go(a...) : F<8, false>::go(a...);
+    case 16: return relu ? F<16, true>::go(a...) : F<16, false>::go(a...);
+    case 24: return relu ? F<24, true>::go(a...) : F<24, false>::go(a...);
+    default: return relu ? F<32, true>::go(a...) : F<32, false>::go(a...);
+  }
+}
+template <int NP, bool RELU>
+struct JFwd {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
+    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
+    return launch("cproj_fwd", nfp::cproj_fwd<NP, RELU>, dim3((unsigned)((long long)k.B * k.nc * tiles)), dim3(nfp::kCjT), lds, st,
+                  k, tiles);
+  }
+};
+template <int NP, bool RELU>
+struct JPart {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const size_t lds = ((size_t)NP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
+    return launch("cproj_bwd_part", nfp::cproj_bwd_part<NP, RELU>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
+                  dim3(nfp::cp_part_threads<NP>()), lds, st, k, (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
+  }
+};
+template <int NP, bool RELU>
+struct JMaps {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const int npt = (k.P + 63) / 64;
+    return launch("cproj_bwd_maps", nfp::cproj_bwd_maps<NP, RELU>, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st,
+                  k, npt);
+  }
+};
+
 }  // namespace
 }  // namespace nfp_host
 
@@ -787,9 +1129,101 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
     k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
     rc = cpool_by_np<LPart>(NP, k, st);
     if (rc == NFP_OK)
-      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
+      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
   }
   if (rc == NFP_OK && grad_maps != nullptr) rc = cpool_by_np<LMaps>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
+  if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
+  return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
+}
+
+int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                      float* scratch, int64_t scratch_floats, void* hip_stream) {
+  const char* what = "nfp_cproj_forward";
+  if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
+  if (!w || !gamma || !beta || (B > 0 && (!maps || !out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
+  if ((running_mean == nullptr) != (running_var == nullptr) || (!training && running_mean == nullptr))
+    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", what);
+  if (!(eps >= 0.0) || !(momentum == momentum)) return fail(NFP_E_INVALID, "%s: eps = %g, momentum = %g", what, eps, momentum);
+  if (training) {
+    if (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D))
+      return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
+                  (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
+    if (B > 0 && (scratch == nullptr || scratch_floats < nfp_cproj_scratch_floats(B, N, P, D, 0)))
+      return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cproj_scratch_floats is %lld", what,
+                  (long long)(scratch ? scratch_floats : 0), (long long)nfp_cproj_scratch_floats(B, N, P, D, 0));
+  }
+  if (B == 0) return NFP_OK;
+  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
+  const int NP = cpool_np(N);
+  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.outv = out;
+  k.eps = (float)eps, k.eps64 = eps, k.mom = momentum;
+  hipStream_t st = (hipStream_t)hip_stream;
+  snprintf(g_variant, sizeof(g_variant), "cproj_fwd<%s,%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
+           relu ? "relu" : "lin");
+  int rc = NFP_OK;
+  if (training) {
+    k.part_w = scratch, k.part = scratch, k.stats_w = saved, k.stats = saved, k.rm_w = running_mean, k.rv_w = running_var;
+    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
+    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
+    if (rc == NFP_OK)
+      rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k);
+  } else {
+    k.rm = running_mean, k.rv = running_var;
+  }
+  k.CH = cproj_fwd_chunk(NP, B, P, D), k.CHs = cpool_stride(k.CH), k.nc = (int)((P + k.CH - 1) / k.CH);   // (cproj_fwd's own)
+  if (rc == NFP_OK) rc = cproj_by_np<JFwd>(NP, relu != 0, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream) {
+  const char* what = "nfp_cproj_backward";
+  if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
+  if (!w || !gamma || !beta || (B > 0 && (!maps || !grad_out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
+  if (!training && (running_mean == nullptr || running_var == nullptr))
+    return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", what);
+  if (!(eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", what, eps);
+  if (training && (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D)))
+    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
+                (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
+  const bool params = grad_w != nullptr || grad_gamma != nullptr || grad_beta != nullptr;
+  if (!params && grad_maps == nullptr) return NFP_OK;
+  const bool sums = params || training;   // (train-mode grad_maps needs k and Q: the batch sums)
+  if (sums && B > 0 && (scratch == nullptr || scratch_floats < nfp_cproj_scratch_floats(B, N, P, D, 1)))
+    return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cproj_scratch_floats is %lld", what,
+                (long long)(scratch ? scratch_floats : 0), (long long)nfp_cproj_scratch_floats(B, N, P, D, 1));
+  if (B == 0) return NFP_OK;
+  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
+  const int NP = cpool_np(N);
+  k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                 // cproj_bwd_part's passes
+  k.ipw = cproj_upw(B, P, D), k.S = cproj_slices(B, P, D);               // ... and how many of them a workgroup takes
+  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.gov = grad_out, k.stats = saved;
+  k.eps = (float)eps, k.eps64 = eps;
+  if (!training) k.rm = running_mean, k.rv = running_var;
+  k.gm = grad_maps, k.gw = grad_w, k.gg = grad_gamma, k.gb = grad_beta;
+  hipStream_t st = (hipStream_t)hip_stream;
+  snprintf(g_variant, sizeof(g_variant), "cproj_bwd<%s,%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
+           relu ? "relu" : "lin");
+  int rc = NFP_OK;
+  if (sums) {
+    k.part_w = scratch, k.part = scratch;
+    k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
+    rc = cproj_by_np<JPart>(NP, relu != 0, k, st);
+    if (rc == NFP_OK)
+      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
+  }
+  if (rc == NFP_OK && grad_maps != nullptr) rc = cproj_by_np<JMaps>(NP, relu != 0, k, st);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }

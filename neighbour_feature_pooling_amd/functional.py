@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _abi
-from ._host import attention_pool_host, compress_pool_host, nfp_host
+from ._host import attention_pool_host, compress_map_host, compress_pool_host, nfp_host
 
 
 @dataclass(frozen=True)
@@ -1208,3 +1208,161 @@ def nfp_compress_pool(maps, weight, bn, training=None):
     if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
         return compress_pool_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps)
     return nfp_compress_pool_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps)
+
+
+# ---- the same projection with the map kept — include/nfp.h: nfp_cproj_* (csrc/nfp_cpool.hip, the cproj kernels) ------------
+# What cproj_hip_serves takes by default — the classes scripts/bench_insert.py measured faster than the composition beyond
+# the run-to-run spread on an MI355X: with at most 8 maps, the forward that keeps no state for a backward on
+# running statistics (every row: 1.9x to 4.0x), and the train-mode step from 64 images of 54 x 54 map pixels up
+# ([64,8,54,54] -> 24: 1.49x, -> 64 without the ReLU: 1.41x, [64,8,110,110] -> 16: 2.13x).  The smaller train-mode rows
+# lost (0.64x to 0.96x), and so did the 24-map step (0.42x): the composition's.
+CPROJ_ROUTED_MAPS = 8
+CPROJ_ROUTED_TRAIN_PIXELS = 64 * 54 * 54      # B * P of the smallest train-mode row that won
+
+
+def cproj_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu):
+    """(out [B,D,...] in the maps' dtype, saved) from nfp_cproj_forward on dense CUDA maps [B,N,...] and float32 w [D,N],
+    gamma, beta [D] — cpool_forward_call's arguments and `saved`, plus `relu`."""
+    L = _abi.load()
+    B, N, P, D = _cpool_sizes(maps, w)
+    dev = maps.device
+    with _on_device(dev):
+        out = torch.empty((B, D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev)
+        ns = int(L.nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
+        nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 0)) if use_batch_stats else 0
+        saved = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
+        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
+        _abi.check(L.nfp_cproj_forward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
+                                       maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                       rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
+                                       float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
+                                       scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev)))
+    return out, saved
+
+
+def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, relu, grad_out, want):
+    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cproj_backward, grad_out
+    [B,D,...] in the maps' dtype — None for each gradient `want` (four flags) leaves out: a NULL pointer in the library,
+    neither computed nor written."""
+    L = _abi.load()
+    B, N, P, D = _cpool_sizes(maps, w)
+    dev = maps.device
+    go = grad_out.to(maps.dtype).contiguous()
+    with _on_device(dev):
+        gm = torch.empty_like(maps) if want[0] else None
+        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
+        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
+        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None
+        sums = use_batch_stats or want[1] or want[2] or want[3]
+        nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 1)) if sums else 0
+        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        _abi.check(L.nfp_cproj_backward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
+                                        maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                        None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv), float(eps),
+                                        ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(), ptr(gm), ptr(gw),
+                                        ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev)))
+    return gm, gw, gg, gb
+
+
+class _CProjHip(torch.autograd.Function):
+    """out [B,D,...] in the maps' dtype of dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the
+    backward: the maps, the three parameters and the O(N*N + D) statistics — not the output, which the caller may modify in
+    place (ReLU(inplace=True) behind it, `out += identity`): the backward recomputes the pre-activation from the maps.
+    `stats`, need_grad: as _CPoolHip."""
+
+    @staticmethod
+    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, relu, need_grad):
+        out, saved = cproj_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps, relu)
+        if need_grad:
+            ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
+            ctx.stats, ctx.use_batch_stats, ctx.eps, ctx.relu = stats, use_batch_stats, eps, relu
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        maps, w, gamma, beta = ctx.saved_tensors[:4]
+        saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        gm, gw, gg, gb = cproj_backward_call(maps, w, gamma, beta, ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats,
+                                             ctx.eps, ctx.relu, grad_out, ctx.needs_input_grad[:4])
+        return gm, gw, gg, gb, None, None, None, None, None, None
+
+
+def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, need_grad=True):
+    """The cproj kernels can serve dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] with N * P and D * P below 2^31
+    per image and D <= 2^22, under an affine BatchNorm with a float momentum, outside torch.compile and torch.autocast.  Of
+    those they take, by default, what measured faster than the composition (CPROJ_ROUTED_MAPS and
+    CPROJ_ROUTED_TRAIN_PIXELS above): at most 8 maps, and either a forward on running statistics that no
+    backward follows, or batch statistics over B * P >= 64 * 54 * 54 map pixels; a backward on running statistics was not
+    measured.  NFP_CPROJ_TORCH (read at call time) is the A/B switch: "1" the torch composition everywhere, "0" the HIP
+    kernels wherever they can serve."""
+    env = os.environ.get("NFP_CPROJ_TORCH")
+    if env == "1":
+        return False
+    can = (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
+           and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
+           and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
+    if not can:
+        return False
+    B, N = maps.shape[:2]
+    P = maps.numel() // (B * N)
+    if N * P >= 2 ** 31 or weight.shape[0] * P >= 2 ** 31 or weight.shape[0] > 2 ** 22:
+        return False
+    if env == "0":
+        return True
+    if N > CPROJ_ROUTED_MAPS:
+        return False
+    return B * P >= CPROJ_ROUTED_TRAIN_PIXELS if use_batch_stats else not need_grad
+
+
+def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5,
+                             relu=True):
+    """`nfp_compress_map` on loose tensors: maps [B,N,H,W] (or [B,N,P]) -> [B,D,H,W] ([B,D,P]) =
+    [relu](batch_norm(conv1x1(maps))), the arguments those of nfp_compress_pool_tensors plus `relu`.  Where
+    `cproj_hip_serves`, three HIP launches forward and at most three backward: the [B,D,H,W] result is stored once, and the
+    backward reads grad_out twice and nothing else of that size — autograd keeps the maps, the parameters and O(N*N + D)
+    statistics, so the result may be modified in place (include/nfp.h: nfp_cproj_*; float32 arithmetic, the result rounded
+    once to the maps' dtype).  Everything else — by default also what measured slower, see cproj_hip_serves — is
+    `_host.compress_map_host`."""
+    if maps.dim() < 3:
+        raise RuntimeError(f"nfp_compress_map expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
+    if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
+        raise RuntimeError(f"nfp_compress_map: {maps.shape[1]} maps need a 1x1 conv weight [D,{maps.shape[1]},1,1], got "
+                           f"{tuple(weight.shape)}")
+    if not use_batch_stats and (running_mean is None or running_var is None):
+        raise RuntimeError("nfp_compress_map: without batch statistics the running mean and variance are required")
+    host = lambda: compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps,  # noqa: E731
+                                     relu)
+    need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (maps, weight, gamma, beta))
+    if not cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad):
+        return host()
+    B, N = maps.shape[:2]
+    D = weight.shape[0]
+    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
+    f32 = lambda t: t if t.dtype == torch.float32 else t.float()     # noqa: E731
+    rm, rv = running_mean, running_var
+    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+        return host()
+    return _CProjHip.apply(maps, f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous(),
+                           (rm, rv), bool(use_batch_stats), float(momentum), float(eps), bool(relu), need_grad)
+
+
+def nfp_compress_map(maps, weight, bn, relu=True, training=None):
+    """The projection behind the NFP maps where the network carries on from the projected map: NFPInsert's nfp_proj
+    (models/mobilenetv3.py:346-350) and, with relu=False, NFPBottleneck's bn2(conv2(.)) (models/nfp_heads.py:270-272).
+    maps [B,N,H,W] -> [B,D,H,W] = [relu](bn(conv1x1(maps))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its
+    nn.BatchNorm2d — whose mode (`training`: None = bn.training), running statistics and num_batches_tracked are used and
+    updated exactly as bn.forward does.  See nfp_compress_map_tensors."""
+    training = bn.training if training is None else bool(training)
+    factor = 0.0 if bn.momentum is None else bn.momentum
+    if training and bn.track_running_stats and bn.num_batches_tracked is not None:      # nn.modules.batchnorm._BatchNorm.forward
+        bn.num_batches_tracked.add_(1)
+        factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+    use_batch_stats = training or (bn.running_mean is None and bn.running_var is None)
+    track = not training or bn.track_running_stats
+    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
+    if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
+        return compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
+    return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu)

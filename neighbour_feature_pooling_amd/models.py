@@ -290,3 +290,32 @@ class MultiStageNFPNet(nn.Module):
                        for f, layer in zip(feats, self.nfps)], dim=1)   # [B, 40]
         head = self.conv_head(feats[-1]).mean((2, 3))
         return self.fc(head * self.nfp_proj(v))
+
+
+class NFPInsertNet(nn.Module):
+    """models/mobilenetv3.py::MOBILENETV3_NFP_INSERT (306-378) over the local backbone: NFP inside the trunk.  Behind block
+    `nfp_insert_idx` of timm's seven `blocks` — which end at features[3, 5, 8, 12, 14, 17, 20] here, with 16 / 24 / 40 / 80 /
+    112 / 160 / 960 channels — an NFPInsert (NFPPooling(**nfp_kwargs), then a 1x1 conv + BN + ReLU back to the stage's
+    channel count) replaces the feature map; the rest of the trunk follows, then the 960 -> 1280 head conv + Hardswish, GAP
+    and fc.  With the class defaults (padding 0) the map shrinks by 2R at the insert."""
+    BLOCK_ENDS = (3, 5, 8, 12, 14, 17, 20)            # indices into backbone.features
+    BLOCK_CHANNELS = (16, 24, 40, 80, 112, 160, 960)
+
+    def __init__(self, num_classes=10, num_input_channels=3, nfp_insert_idx=1, nfp_kwargs=None, head_width=1280):
+        super().__init__()
+        from .nfp import NFPInsert
+        if isinstance(nfp_insert_idx, bool) or not isinstance(nfp_insert_idx, int) or not 0 <= nfp_insert_idx <= 6:
+            raise ValueError(f"nfp_insert_idx must be between 0 and 6 (inclusive), got {nfp_insert_idx!r}")
+        self.nfp_insert_idx = nfp_insert_idx
+        self.backbone = MobileNetV3LargeFeatures(in_chans=num_input_channels)
+        self.insert = NFPInsert(self.BLOCK_CHANNELS[nfp_insert_idx], **(nfp_kwargs or {}))
+        self.conv_head = nn.Sequential(nn.Conv2d(960, head_width, 1), nn.Hardswish(inplace=True))   # timm: conv_head + act2
+        self.fc = nn.Linear(head_width, num_classes)
+
+    def forward(self, x):
+        at = self.BLOCK_ENDS[self.nfp_insert_idx]
+        for i, layer in enumerate(self.backbone.features):
+            x = layer(x)
+            if i == at:
+                x = self.insert(x)
+        return self.fc(self.conv_head(x).mean((2, 3)))

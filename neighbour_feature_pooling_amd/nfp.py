@@ -13,8 +13,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
-from .functional import (NfpConfig, gap_servable, multi_radius_config, nfp, nfp_attention_pool, nfp_biased, nfp_multi_radius,
-                         nfp_valid, nfp_with_gap)
+from .functional import (NfpConfig, gap_servable, multi_radius_config, nfp, nfp_attention_pool, nfp_biased,
+                         nfp_compress_map, nfp_multi_radius, nfp_valid, nfp_with_gap)
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -260,11 +260,15 @@ class NFPBottleneck(nn.Module):
     (conv1 / bn1 / nfp.* / conv2 / bn2 / downsample.*); the RNG is consumed in the reference's order — conv1, bn1, the
     layer's two depthwise conv weights (drawn and dropped: NFPPooling(bias=False) holds no conv), the 5x5 probe, conv2,
     bn2, downsample — so the same seed gives bit-identical parameters.  On the GPU the layer runs the valid-map kernels
-    (functional.nfp_valid), forward and backward one launch each."""
+    (functional.nfp_valid), forward and backward one launch each.
+    fused_project=True (not in the reference; the default keeps the two ATen ops): bn2(conv2(.)) as one call of
+    functional.nfp_compress_map(relu=False) — on the GPU, where it serves, without the copies of the [B,out,H,W]
+    activation that conv2 and bn2 write, re-read and save."""
     expansion = 1
 
-    def __init__(self, in_channels: int, out_channels: int, stride=1):
+    def __init__(self, in_channels: int, out_channels: int, stride=1, *, fused_project=False):
         super().__init__()
+        self.fused_project = bool(fused_project)
         mid = out_channels // 4
         self.conv1 = nn.Conv2d(in_channels, mid, 1, bias=False, stride=stride)
         self.bn1 = nn.BatchNorm2d(mid)
@@ -294,8 +298,38 @@ class NFPBottleneck(nn.Module):
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = nfp_valid(out, self.nfp.config)
-        out = self.bn2(self.conv2(out))
+        if self.fused_project:
+            out = nfp_compress_map(out, self.conv2.weight, self.bn2, relu=False)
+        else:
+            out = self.bn2(self.conv2(out))
         identity = self._match(identity, out.shape[-1])
         identity = self.downsample(identity)
         out += identity
         return self.relu(out)
+
+
+class NFPInsert(nn.Module):
+    """The block models/mobilenetv3.py::MOBILENETV3_NFP_INSERT puts behind one stage of its trunk (mobilenetv3.py:345-353):
+        nfp = NFPPooling(in_channels, **nfp_kwargs)      nfp_proj = Conv2d(nfp.out_channels, C, 1, bias=False) -> BN -> ReLU
+        x -> nfp_proj(nfp(x))                            [B, in, H, W] -> [B, C, H', W']
+    C = out_channels (None: in_channels, as in the reference, where the result replaces the stage's feature map).  The
+    layer's keywords default to the class defaults, as there: Norm p = 1, padding 0, reflect — the map shrinks by 2R.
+    `nfp_proj` is the reference's nn.Sequential as parameter holder, with its state-dict keys (nfp_proj.0.weight,
+    nfp_proj.1.*); the RNG is consumed in the reference's order — the layer's two depthwise conv weights (drawn and
+    dropped), then the conv — so the same seed gives bit-identical parameters.  forward is one call of
+    functional.nfp_compress_map behind the layer: on the GPU, where it serves, the projected map is stored once and nothing
+    of its size is saved for the backward."""
+
+    def __init__(self, in_channels, out_channels=None, **nfp_kwargs):
+        super().__init__()
+        from .heads import _reference_layer_draws
+        out_channels = int(in_channels if out_channels is None else out_channels)
+        self.nfp = NFPPooling(in_channels=in_channels, **nfp_kwargs)
+        if not self.nfp.bias:       # (bias=True: the layer has built both convs itself)
+            _reference_layer_draws(self.nfp)
+        self.nfp_proj = nn.Sequential(nn.Conv2d(self.nfp.out_channels, out_channels, kernel_size=1, bias=False),
+                                      nn.BatchNorm2d(out_channels), nn.ReLU(inplace=True))
+        self.in_channels, self.out_channels = int(in_channels), out_channels
+
+    def forward(self, x):
+        return nfp_compress_map(self.nfp(x), self.nfp_proj[0].weight, self.nfp_proj[1])
