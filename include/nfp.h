@@ -352,6 +352,28 @@ int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream);
 
+/*
+ * The same two calls with a memory layout for the [B,D,P] activation — `out` in the forward, `grad_out` in the backward;
+ * the maps and grad_maps stay [B,N,P]:
+ *   NFP_ACT_NCHW  [b][d][p], element (b*D + d)*P + p: the calls above — the same kernels, the same bytes
+ *   NFP_ACT_NHWC  [b][p][d], element (b*P + p)*D + d: a channels-last [B,D,H,W] tensor, P = H*W
+ * The layout is the last argument, behind hip_stream; every other argument, length query (nfp_cproj_scratch_floats serves
+ * both layouts), refusal and launch count is as documented for nfp_cproj_forward / nfp_cproj_backward, and the two calls
+ * of one step need not use the same layout.  With NFP_ACT_NHWC every element of `out` has the bits the NCHW call stores
+ * for it, the parameter gradients are summed in the NCHW call's order, and no atomics are used.  nfp_last_variant names
+ * cproj_fwd<...,nhwc> / cproj_bwd<...,nhwc>.  Any other layout value: NFP_E_INVALID, launching nothing.  Additive to ABI 7.
+ */
+enum nfp_act_layout { NFP_ACT_NCHW = 0, NFP_ACT_NHWC = 1 };
+int nfp_cproj_forward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                          const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                          float* scratch, int64_t scratch_floats, void* hip_stream, int32_t out_layout);
+int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                           const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                           const float* running_var, double eps, const float* saved, int64_t saved_floats,
+                           const void* grad_out, void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta,
+                           float* scratch, int64_t scratch_floats, void* hip_stream, int32_t grad_out_layout);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

@@ -26,7 +26,9 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
            "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
-           "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward"]
+           "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward",
+           "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt"]
+ACT_NCHW, ACT_NHWC = 0, 1     # enum nfp_act_layout: out / grad_out of nfp_cproj_*_fmt
 
 
 class NfpDesc(ctypes.Structure):
@@ -125,6 +127,9 @@ def load():
                                         vp]
         L.nfp_cproj_backward.argtypes = [i32, i32, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp, vp, vp,
                                          vp, vp, i64, vp]
+    if hasattr(L, "nfp_cproj_forward_fmt"):     # (absent only from an older library loaded for an A/B run)
+        L.nfp_cproj_forward_fmt.argtypes = L.nfp_cproj_forward.argtypes + [i32]
+        L.nfp_cproj_backward_fmt.argtypes = L.nfp_cproj_backward.argtypes + [i32]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

@@ -40,6 +40,10 @@
 //                   [128 channels][64 pixels] tile of grad_out go to LDS with lanes along p (whole lines), and are read back
 //                   as a float4 per channel
 //   cproj_bwd_maps  cpool_bwd_maps with grad_out read per (channel, pixel), lanes along p, four channels' loads in flight
+// Channels-last out / grad_out, [b][p][d] (nfp_cproj_*_fmt, NFP_ACT_NHWC; the maps stay [B,N,P], the statistics kernels are
+// the same launches): cproj_fwd_nhwc — the same chain per element, lanes along the chunk's [p][d] range — and the NHWC
+// instantiations of cproj_bwd_part / cproj_bwd_maps, which bring their grad_out tile into LDS with d fastest and are the
+// NCHW kernels behind that: the same sums in the same order.
 #include "nfp_launch.h"
 
 #include <cmath>
@@ -684,10 +688,91 @@ __global__ void __launch_bounds__(kCjT) cproj_fwd(CpK k, int tiles) {
   }
 }
 
+// cproj_fwd for a channels-last out, [b][p][d]: the same grid, LDS and per-element chain — only who owns an element
+// changes.  The tile's share of the chunk is [ch][nd] with the channel fastest: element e = pl * nd + dl at
+// obase + pl * D + dl, so where the tile is all of D the chunk is one span of ch * D elements, and otherwise ch segments
+// of nd channels.  Lanes run along e: a wavefront's store covers whole segments (several pixels where D is small), the
+// rows of tb are read at an odd stride and the maps as broadcasts.
+// PAIR (bf16, out 4-byte aligned, and a single tile or an even D): a lane holds the two elements of an aligned dword and
+// stores them together.  With a single tile the pairs are laid over the span from its even address down (s: the span
+// starts on an odd element), so they may straddle two pixels' rows and the span's first and last element may stand
+// alone; with an even D every segment starts and ends on a pair.
+template <int NP, bool RELU, bool PAIR>
+__global__ void __launch_bounds__(kCjT) cproj_fwd_nhwc(CpK k, int tiles) {
+  constexpr int kTS = NP + 1;
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* tb = sm + NP * k.CHs;
+  const int tid = threadIdx.x;
+  const int bj = blockIdx.x / tiles, tile = blockIdx.x - bj * tiles;
+  const int b = bj / k.nc, j = bj - b * k.nc;
+  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
+  const int d0 = tile * kCjDT, nd = min(kCjDT, k.D - d0);
+  cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+  for (int i = tid; i < nd * kTS; i += kCjT) {
+    const int dl = i / kTS, n = i - dl * kTS;
+    float scale, shift;
+    cp_coef(k, d0 + dl, scale, shift);
+    tb[i] = n == NP ? shift : (n < k.N ? k.w[(long long)(d0 + dl) * k.N + n] * scale : 0.f);
+  }
+  __syncthreads();
+  const int CHs = k.CHs;
+  auto act = [&](int pl, int dl) {
+    const float* row = tb + dl * kTS;
+    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
+#pragma unroll
+    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * CHs + pl], a);
+    if (RELU) a = a < 0.f ? 0.f : a;
+    return a;
+  };
+  const int total = nd * ch;
+  const long long obase = ((long long)b * k.P + p0) * k.D + d0;
+  if (!PAIR) {
+    const int qT = kCjT / nd, rT = kCjT - qT * nd;   // a thread's next element is 256 further on
+    int pl = tid / nd, dl = tid - pl * nd;
+    for (int e = tid; e < total; e += kCjT) {
+      const float a = act(pl, dl);
+      const long long o = obase + (long long)pl * k.D + dl;
+      if (k.bf16)
+        ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
+      else
+        ((float*)k.outv)[o] = a;
+      dl += rT, pl += qT;
+      if (dl >= nd) dl -= nd, ++pl;
+    }
+  } else {
+    const int s = tiles == 1 ? (int)(obase & 1) : 0;
+    const int qT = 2 * kCjT / nd, rT = 2 * kCjT - qT * nd;   // a thread's next pair is 512 elements further on
+    int e0 = 2 * tid - s, pl = -1, dl = nd - 1;              // (e0 = -1: the element before the span)
+    if (e0 >= 0) pl = e0 / nd, dl = e0 - pl * nd;
+    for (; e0 < total; e0 += 2 * kCjT) {
+      int pl1 = pl, dl1 = dl + 1;
+      if (dl1 == nd) dl1 = 0, ++pl1;
+      const bool v0 = e0 >= 0, v1 = e0 + 1 < total;
+      const float a0 = v0 ? act(pl, dl) : 0.f, a1 = v1 ? act(pl1, dl1) : 0.f;
+      uint16_t* o = (uint16_t*)k.outv + (obase + (long long)pl * k.D + dl);
+      if (v0 && v1)
+        *(uint32_t*)o = f32_to_bf16x2(a0, a1);
+      else if (v0)
+        o[0] = f32_to_bf16(a0);
+      else
+        o[1] = f32_to_bf16(a1);
+      dl += rT, pl += qT;
+      if (dl >= nd) dl -= nd, ++pl;
+    }
+  }
+}
+
 // grid = (S, ceil(D / 128)), block = cp_part_threads: passes [s * upw, (s + 1) * upw) of the batch's B * nsub passes of 64
 // pixels.  LDS: sm[NP * 68], gl[128 * 68] (grad_out of the pass; at the end the join buffer red[128 * (NP + 1)]).
 // part_w: [S][D][N + 1], as cpool_bwd_part.
-template <int NP, bool RELU>
+// NHWC: grad_out is [b][p][d].  The tile goes into the same gl[dl * 68 + pl], read from global memory with d fastest: a
+// lane takes one channel at four neighbouring pixels — four loads that each run along d across the wavefront — and
+// stores them as one 16-byte row piece.  ds_write_b128 is served eight lanes at a time; eight neighbouring channels are
+// 8 * 68 floats apart, banks 4 * dl + {0..3} (mod 32): all 32 different.  (One pixel per lane, a dword each, puts the 32
+// lanes of a half on eight banks.)  Lanes cover the nd channels of the tile rounded up to a power of two, 8 at the
+// least; the rows beyond that are zeroed once.  Everything behind the staging is the NCHW kernel's, sum for sum.
+template <int NP, bool RELU, bool NHWC = false>
 __global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, int nsub, int upw) {
   constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
@@ -705,11 +790,27 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, i
     const int b = u / nsub, ps = (u - b * nsub) * kCjSP, npx = min(kCjSP, k.P - ps);
     if (u > u0) __syncthreads();   // (the previous pass has been read)
     cp_stage(k, NP, sm, b, ps, npx, !k.eval);
-    for (int i = tid; i < kCpDT * kCjSP; i += kT) {
-      const int dl = i >> 6, pl = i & 63, d = tile * kCpDT + dl;
-      float v = 0.f;
-      if (d < k.D && pl < npx) v = cj_load(k, k.gov, ((long long)b * k.D + d) * k.P + ps + pl);
-      gl[dl * kCjSS + pl] = v;
+    if constexpr (NHWC) {
+      const int nd = min(kCpDT, k.D - tile * kCpDT), lg = nd <= 8 ? 3 : 32 - __clz(nd - 1);
+      if (u == u0)
+        for (int i = (kCjSS << lg) + tid; i < kCpDT * kCjSS; i += kT) gl[i] = 0.f;
+      for (int i = tid; i < (kCjSP / 4) << lg; i += kT) {
+        const int dl = i & ((1 << lg) - 1), q = i >> lg, d = tile * kCpDT + dl;
+        const long long g0 = ((long long)b * k.P + ps + 4 * q) * k.D + d;
+        float4 v;
+        v.x = (d < k.D && 4 * q < npx) ? cj_load(k, k.gov, g0) : 0.f;
+        v.y = (d < k.D && 4 * q + 1 < npx) ? cj_load(k, k.gov, g0 + k.D) : 0.f;
+        v.z = (d < k.D && 4 * q + 2 < npx) ? cj_load(k, k.gov, g0 + 2LL * k.D) : 0.f;
+        v.w = (d < k.D && 4 * q + 3 < npx) ? cj_load(k, k.gov, g0 + 3LL * k.D) : 0.f;
+        *(float4*)(gl + dl * kCjSS + 4 * q) = v;
+      }
+    } else {
+      for (int i = tid; i < kCpDT * kCjSP; i += kT) {
+        const int dl = i >> 6, pl = i & 63, d = tile * kCpDT + dl;
+        float v = 0.f;
+        if (d < k.D && pl < npx) v = cj_load(k, k.gov, ((long long)b * k.D + d) * k.P + ps + pl);
+        gl[dl * kCjSS + pl] = v;
+      }
     }
     __syncthreads();
     const int nq = (npx + 3) >> 2;
@@ -769,13 +870,19 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, i
 
 // grid = B * ceil(P / 64), block = 512: cpool_bwd_maps with grad_out read per (channel, pixel).  LDS: red[NP * 64],
 // kql[N + N * N], tb[128][NP + 4] — a channel's scaled row, then its shift.
-template <int NP, bool RELU>
+// NHWC: grad_out is [b][p][d], where a lane's own loads would be D elements apart.  The block's [64 pixels][<= 128 d] tile
+// comes through LDS instead — gt[pl * 129 + dl], written with d fastest across the lanes (whole segments of global
+// memory, consecutive banks) and read by every lane from its own pixel's row (an odd stride: 32 banks).  The sums are the
+// NCHW kernel's, in its order.
+template <int NP, bool RELU, bool NHWC = false>
 __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
   constexpr int kTS = NP + 4;
+  constexpr int kGS = kCpMB + 1;
   __shared__ float red[NP * 64];
   __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
   __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
   __shared__ float cf[kCpMB];
+  __shared__ float gt[NHWC ? 64 * kGS : 1];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
   const bool live = p < k.P;
@@ -802,6 +909,13 @@ __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
   for (int dB = 0; dB < k.D; dB += kCpMB) {
     const int nd = min(kCpMB, k.D - dB);
     if (dB > 0) __syncthreads();   // (the previous block has been read)
+    if constexpr (NHWC) {
+      const int lg = nd <= 1 ? 0 : 32 - __clz(nd - 1);   // lanes cover nd rounded up to a power of two
+      for (int i = tid; i < 64 << lg; i += kCpT) {
+        const int dl = i & ((1 << lg) - 1), pl = i >> lg, pp = pt * 64 + pl;
+        if (dl < nd) gt[pl * kGS + dl] = pp < k.P ? cj_load(k, k.gov, ((long long)b * k.P + pp) * k.D + dB + dl) : 0.f;
+      }
+    }
     if (tid < nd) {
       float scale, shift;
       cp_coef(k, dB + tid, scale, shift);
@@ -819,7 +933,10 @@ __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int dl = dl0 + u * kCpW;
-        t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
+        if constexpr (NHWC)
+          t[u] = dl < nd ? gt[lane * kGS + dl] : 0.f;   // (zero beyond P)
+        else
+          t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -1036,6 +1153,41 @@ struct JMaps {
                   k, npt);
   }
 };
+// The channels-last forms (out / grad_out [b][p][d]): the same grids, LDS sizes and scratch.
+template <int NP, bool RELU>
+struct JFwdN {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
+    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
+    const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
+    // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
+    if (k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0))
+      return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+    return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+  }
+};
+template <int NP, bool RELU>
+struct JPartN {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const size_t lds = ((size_t)NP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
+    return launch("cproj_bwd_part_nhwc", nfp::cproj_bwd_part<NP, RELU, true>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
+                  dim3(nfp::cp_part_threads<NP>()), lds, st, k, (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
+  }
+};
+template <int NP, bool RELU>
+struct JMapsN {
+  static int go(const nfp::CpK& k, hipStream_t st) {
+    const int npt = (k.P + 63) / 64;
+    return launch("cproj_bwd_maps_nhwc", nfp::cproj_bwd_maps<NP, RELU, true>, dim3((unsigned)((long long)k.B * npt)),
+                  dim3(nfp::kCpT), 0, st, k, npt);
+  }
+};
+
+int cproj_layout(const char* what, int32_t layout) {
+  if (layout != NFP_ACT_NCHW && layout != NFP_ACT_NHWC)
+    return fail(NFP_E_INVALID, "%s: unknown layout %d (NFP_ACT_NCHW = 0, NFP_ACT_NHWC = 1)", what, layout);
+  return NFP_OK;
+}
 
 }  // namespace
 }  // namespace nfp_host
@@ -1141,11 +1293,12 @@ int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int
   return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
 }
 
-int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
-                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
-                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
-                      float* scratch, int64_t scratch_floats, void* hip_stream) {
-  const char* what = "nfp_cproj_forward";
+// nfp_cproj_forward / nfp_cproj_forward_fmt (`what`): layout = NFP_ACT_NCHW is the former, kernel for kernel.
+static int cproj_forward(const char* what, int32_t layout, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
+                         int32_t training, int32_t relu, const void* maps, const float* w, const float* gamma,
+                         const float* beta, float* running_mean, float* running_var, double momentum, double eps, void* out,
+                         float* saved, int64_t saved_floats, float* scratch, int64_t scratch_floats, void* hip_stream) {
+  if (int rc = cproj_layout(what, layout)) return rc;
   if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
   if (!w || !gamma || !beta || (B > 0 && (!maps || !out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
   if ((running_mean == nullptr) != (running_var == nullptr) || (!training && running_mean == nullptr))
@@ -1165,8 +1318,8 @@ int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
   k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.outv = out;
   k.eps = (float)eps, k.eps64 = eps, k.mom = momentum;
   hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cproj_fwd<%s,%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
-           relu ? "relu" : "lin");
+  snprintf(g_variant, sizeof(g_variant), "cproj_fwd<%s,%s,%s%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
+           relu ? "relu" : "lin", layout == NFP_ACT_NHWC ? ",nhwc" : "");
   int rc = NFP_OK;
   if (training) {
     k.part_w = scratch, k.part = scratch, k.stats_w = saved, k.stats = saved, k.rm_w = running_mean, k.rv_w = running_var;
@@ -1178,17 +1331,35 @@ int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
     k.rm = running_mean, k.rv = running_var;
   }
   k.CH = cproj_fwd_chunk(NP, B, P, D), k.CHs = cpool_stride(k.CH), k.nc = (int)((P + k.CH - 1) / k.CH);   // (cproj_fwd's own)
-  if (rc == NFP_OK) rc = cproj_by_np<JFwd>(NP, relu != 0, k, st);
+  if (rc == NFP_OK)
+    rc = layout == NFP_ACT_NHWC ? cproj_by_np<JFwdN>(NP, relu != 0, k, st) : cproj_by_np<JFwd>(NP, relu != 0, k, st);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
 
-int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
-                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
-                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
-                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
-                       int64_t scratch_floats, void* hip_stream) {
-  const char* what = "nfp_cproj_backward";
+int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                      float* scratch, int64_t scratch_floats, void* hip_stream) {
+  return cproj_forward("nfp_cproj_forward", NFP_ACT_NCHW, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
+                       running_var, momentum, eps, out, saved, saved_floats, scratch, scratch_floats, hip_stream);
+}
+
+int nfp_cproj_forward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                          const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                          float* scratch, int64_t scratch_floats, void* hip_stream, int32_t out_layout) {
+  return cproj_forward("nfp_cproj_forward_fmt", out_layout, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
+                       running_var, momentum, eps, out, saved, saved_floats, scratch, scratch_floats, hip_stream);
+}
+
+// nfp_cproj_backward / nfp_cproj_backward_fmt (`what`): layout, of grad_out, = NFP_ACT_NCHW is the former.
+static int cproj_backward(const char* what, int32_t layout, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
+                          int32_t training, int32_t relu, const void* maps, const float* w, const float* gamma,
+                          const float* beta, const float* running_mean, const float* running_var, double eps,
+                          const float* saved, int64_t saved_floats, const void* grad_out, void* grad_maps, float* grad_w,
+                          float* grad_gamma, float* grad_beta, float* scratch, int64_t scratch_floats, void* hip_stream) {
+  if (int rc = cproj_layout(what, layout)) return rc;
   if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
   if (!w || !gamma || !beta || (B > 0 && (!maps || !grad_out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
   if (!training && (running_mean == nullptr || running_var == nullptr))
@@ -1213,19 +1384,41 @@ int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
   if (!training) k.rm = running_mean, k.rv = running_var;
   k.gm = grad_maps, k.gw = grad_w, k.gg = grad_gamma, k.gb = grad_beta;
   hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cproj_bwd<%s,%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
-           relu ? "relu" : "lin");
+  snprintf(g_variant, sizeof(g_variant), "cproj_bwd<%s,%s,%s%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
+           relu ? "relu" : "lin", layout == NFP_ACT_NHWC ? ",nhwc" : "");
+  const bool nhwc = layout == NFP_ACT_NHWC;
   int rc = NFP_OK;
   if (sums) {
     k.part_w = scratch, k.part = scratch;
     k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
-    rc = cproj_by_np<JPart>(NP, relu != 0, k, st);
+    rc = nhwc ? cproj_by_np<JPartN>(NP, relu != 0, k, st) : cproj_by_np<JPart>(NP, relu != 0, k, st);
     if (rc == NFP_OK)
       rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
   }
-  if (rc == NFP_OK && grad_maps != nullptr) rc = cproj_by_np<JMaps>(NP, relu != 0, k, st);
+  if (rc == NFP_OK && grad_maps != nullptr)
+    rc = nhwc ? cproj_by_np<JMapsN>(NP, relu != 0, k, st) : cproj_by_np<JMaps>(NP, relu != 0, k, st);
   if (rc == NFP_OK) publish_variant();
   return rc;
+}
+
+int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream) {
+  return cproj_backward("nfp_cproj_backward", NFP_ACT_NCHW, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
+                        running_var, eps, saved, saved_floats, grad_out, grad_maps, grad_w, grad_gamma, grad_beta, scratch,
+                        scratch_floats, hip_stream);
+}
+
+int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                           const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                           const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
+                           void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                           int64_t scratch_floats, void* hip_stream, int32_t grad_out_layout) {
+  return cproj_backward("nfp_cproj_backward_fmt", grad_out_layout, B, N, P, D, dtype, training, relu, maps, w, gamma, beta,
+                        running_mean, running_var, eps, saved, saved_floats, grad_out, grad_maps, grad_w, grad_gamma, grad_beta,
+                        scratch, scratch_floats, hip_stream);
 }
 
 }  // extern "C"

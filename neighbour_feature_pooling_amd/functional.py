@@ -1218,36 +1218,64 @@ def nfp_compress_pool(maps, weight, bn, training=None):
 # lost (0.64x to 0.96x), and so did the 24-map step (0.42x): the composition's.
 CPROJ_ROUTED_MAPS = 8
 CPROJ_ROUTED_TRAIN_PIXELS = 64 * 54 * 54      # B * P of the smallest train-mode row that won
+# A channels-last result (memory_format=torch.channels_last) has its own measurement, scripts/bench_insert.py
+# --channels-last (float32 and bf16 alike), routed by the same rule: the forward on running statistics that no
+# backward follows won every row, the 24-map one included (1.5x to 5.7x); the train-mode step won with 8 maps from 256
+# images of 12 x 12 map pixels up ([256,8,12,12] -> 256 without the ReLU: 1.66x, [64,8,26,26] -> 40: 1.13x, up to 2.44x at
+# [64,8,110,110] -> 16) and lost or tied below that ([64,8,12,12] and [64,8,5,5]: 0.75x to 1.0x) and with 24 maps (0.50x).
+CPROJ_ROUTED_NHWC_EVAL_MAPS = 24
+CPROJ_ROUTED_NHWC_TRAIN_PIXELS = 256 * 12 * 12    # B * P of the smallest channels-last train-mode row that won
 
 
-def cproj_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu):
-    """(out [B,D,...] in the maps' dtype, saved) from nfp_cproj_forward on dense CUDA maps [B,N,...] and float32 w [D,N],
-    gamma, beta [D] — cpool_forward_call's arguments and `saved`, plus `relu`."""
+def _cproj_memory_format(memory_format, maps):
+    """True for torch.channels_last, False for torch.contiguous_format; ValueError for anything else and for channels_last
+    on maps that are not [B,N,H,W]."""
+    if memory_format == torch.contiguous_format:
+        return False
+    if memory_format != torch.channels_last:
+        raise ValueError(f"nfp_compress_map: memory_format must be torch.contiguous_format or torch.channels_last, got "
+                         f"{memory_format!r}")
+    if maps.dim() != 4:
+        raise ValueError(f"nfp_compress_map: memory_format=torch.channels_last needs [B,N,H,W] maps, got {tuple(maps.shape)}")
+    return True
+
+
+def cproj_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu, channels_last=False):
+    """(out [B,D,...] in the maps' dtype, saved) from nfp_cproj_forward_fmt on dense CUDA maps [B,N,...] and float32 w
+    [D,N], gamma, beta [D] — cpool_forward_call's arguments and `saved`, plus `relu`; channels_last: `out` [B,D,H,W] is
+    written channels-last (the maps stay NCHW)."""
     L = _abi.load()
     B, N, P, D = _cpool_sizes(maps, w)
     dev = maps.device
     with _on_device(dev):
-        out = torch.empty((B, D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev)
+        out = torch.empty((B, D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
         ns = int(L.nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
         nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 0)) if use_batch_stats else 0
         saved = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
         scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
-        _abi.check(L.nfp_cproj_forward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
-                                       maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                       rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
-                                       float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
-                                       scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev)))
+        _abi.check(L.nfp_cproj_forward_fmt(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
+                                           maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                           rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
+                                           float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
+                                           scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev),
+                                           _abi.ACT_NHWC if channels_last else _abi.ACT_NCHW))
     return out, saved
 
 
 def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, relu, grad_out, want):
     """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cproj_backward, grad_out
     [B,D,...] in the maps' dtype — None for each gradient `want` (four flags) leaves out: a NULL pointer in the library,
-    neither computed nor written."""
+    neither computed nor written.  The layout grad_out arrives in selects the kernels, whatever the forward wrote: NCHW-dense
+    (also where H = W = 1 or D = 1 make it both) the NCHW ones, channels-last-dense the channels-last ones, neither a
+    copy; anything else is made NCHW-dense first."""
     L = _abi.load()
     B, N, P, D = _cpool_sizes(maps, w)
     dev = maps.device
-    go = grad_out.to(maps.dtype).contiguous()
+    go = grad_out.to(maps.dtype)        # (preserve_format: a dense tensor keeps its layout)
+    nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
+    if not nhwc:
+        go = go.contiguous()
     with _on_device(dev):
         gm = torch.empty_like(maps) if want[0] else None
         gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
@@ -1257,11 +1285,12 @@ def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, ep
         nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 1)) if sums else 0
         scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
         ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
-        _abi.check(L.nfp_cproj_backward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
-                                        maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                        None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv), float(eps),
-                                        ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(), ptr(gm), ptr(gw),
-                                        ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev)))
+        _abi.check(L.nfp_cproj_backward_fmt(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
+                                            maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                            None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv),
+                                            float(eps), ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(),
+                                            ptr(gm), ptr(gw), ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev),
+                                            _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
     return gm, gw, gg, gb
 
 
@@ -1269,11 +1298,12 @@ class _CProjHip(torch.autograd.Function):
     """out [B,D,...] in the maps' dtype of dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the
     backward: the maps, the three parameters and the O(N*N + D) statistics — not the output, which the caller may modify in
     place (ReLU(inplace=True) behind it, `out += identity`): the backward recomputes the pre-activation from the maps.
-    `stats`, need_grad: as _CPoolHip."""
+    `stats`, need_grad: as _CPoolHip.  channels_last: the layout `out` is written in; the backward goes by its grad_out's."""
 
     @staticmethod
-    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, relu, need_grad):
-        out, saved = cproj_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps, relu)
+    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, relu, need_grad, channels_last=False):
+        out, saved = cproj_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps, relu,
+                                        channels_last)
         if need_grad:
             ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
             ctx.stats, ctx.use_batch_stats, ctx.eps, ctx.relu = stats, use_batch_stats, eps, relu
@@ -1286,17 +1316,19 @@ class _CProjHip(torch.autograd.Function):
         saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
         gm, gw, gg, gb = cproj_backward_call(maps, w, gamma, beta, ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats,
                                              ctx.eps, ctx.relu, grad_out, ctx.needs_input_grad[:4])
-        return gm, gw, gg, gb, None, None, None, None, None, None
+        return gm, gw, gg, gb, None, None, None, None, None, None, None
 
 
-def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, need_grad=True):
+def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, need_grad=True, channels_last=False):
     """The cproj kernels can serve dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] with N * P and D * P below 2^31
     per image and D <= 2^22, under an affine BatchNorm with a float momentum, outside torch.compile and torch.autocast.  Of
     those they take, by default, what measured faster than the composition (CPROJ_ROUTED_MAPS and
     CPROJ_ROUTED_TRAIN_PIXELS above): at most 8 maps, and either a forward on running statistics that no
     backward follows, or batch statistics over B * P >= 64 * 54 * 54 map pixels; a backward on running statistics was not
-    measured.  NFP_CPROJ_TORCH (read at call time) is the A/B switch: "1" the torch composition everywhere, "0" the HIP
-    kernels wherever they can serve."""
+    measured.  A channels_last result is routed by its own measurement (CPROJ_ROUTED_NHWC_* above): that forward with at
+    most 24 maps, or batch statistics with at most 8 maps over B * P >= 256 * 12 * 12 map pixels.
+    NFP_CPROJ_TORCH (read at call time) is the A/B switch for both layouts: "1" the torch composition everywhere, "0" the
+    HIP kernels wherever they can serve."""
     env = os.environ.get("NFP_CPROJ_TORCH")
     if env == "1":
         return False
@@ -1311,20 +1343,29 @@ def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, 
         return False
     if env == "0":
         return True
+    if channels_last:
+        if not use_batch_stats:
+            return N <= CPROJ_ROUTED_NHWC_EVAL_MAPS and not need_grad
+        return N <= CPROJ_ROUTED_MAPS and B * P >= CPROJ_ROUTED_NHWC_TRAIN_PIXELS
     if N > CPROJ_ROUTED_MAPS:
         return False
     return B * P >= CPROJ_ROUTED_TRAIN_PIXELS if use_batch_stats else not need_grad
 
 
 def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5,
-                             relu=True):
+                             relu=True, *, memory_format=torch.contiguous_format):
     """`nfp_compress_map` on loose tensors: maps [B,N,H,W] (or [B,N,P]) -> [B,D,H,W] ([B,D,P]) =
     [relu](batch_norm(conv1x1(maps))), the arguments those of nfp_compress_pool_tensors plus `relu`.  Where
     `cproj_hip_serves`, three HIP launches forward and at most three backward: the [B,D,H,W] result is stored once, and the
     backward reads grad_out twice and nothing else of that size — autograd keeps the maps, the parameters and O(N*N + D)
     statistics, so the result may be modified in place (include/nfp.h: nfp_cproj_*; float32 arithmetic, the result rounded
     once to the maps' dtype).  Everything else — by default also what measured slower, see cproj_hip_serves — is
-    `_host.compress_map_host`."""
+    `_host.compress_map_host`.
+    memory_format: torch.contiguous_format (the default) or torch.channels_last — the same [B,D,H,W] values, dense
+    channels-last, for a network that runs in that format: the kernels store them so and read a channels-last grad_out as
+    it comes, without a converting copy either way; the composition's result is converted.  It needs [B,N,H,W] maps, which
+    themselves stay NCHW; ValueError otherwise, and for any other value."""
+    channels_last = _cproj_memory_format(memory_format, maps)
     if maps.dim() < 3:
         raise RuntimeError(f"nfp_compress_map expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
     if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
@@ -1332,10 +1373,11 @@ def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_va
                            f"{tuple(weight.shape)}")
     if not use_batch_stats and (running_mean is None or running_var is None):
         raise RuntimeError("nfp_compress_map: without batch statistics the running mean and variance are required")
-    host = lambda: compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps,  # noqa: E731
-                                     relu)
+    def host():
+        y = compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps, relu)
+        return y.contiguous(memory_format=torch.channels_last) if channels_last else y
     need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (maps, weight, gamma, beta))
-    if not cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad):
+    if not cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad, channels_last):
         return host()
     B, N = maps.shape[:2]
     D = weight.shape[0]
@@ -1346,15 +1388,17 @@ def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_va
     if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
         return host()
     return _CProjHip.apply(maps, f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous(),
-                           (rm, rv), bool(use_batch_stats), float(momentum), float(eps), bool(relu), need_grad)
+                           (rm, rv), bool(use_batch_stats), float(momentum), float(eps), bool(relu), need_grad, channels_last)
 
 
-def nfp_compress_map(maps, weight, bn, relu=True, training=None):
+def nfp_compress_map(maps, weight, bn, relu=True, training=None, *, memory_format=torch.contiguous_format):
     """The projection behind the NFP maps where the network carries on from the projected map: NFPInsert's nfp_proj
     (models/mobilenetv3.py:346-350) and, with relu=False, NFPBottleneck's bn2(conv2(.)) (models/nfp_heads.py:270-272).
     maps [B,N,H,W] -> [B,D,H,W] = [relu](bn(conv1x1(maps))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its
     nn.BatchNorm2d — whose mode (`training`: None = bn.training), running statistics and num_batches_tracked are used and
-    updated exactly as bn.forward does.  See nfp_compress_map_tensors."""
+    updated exactly as bn.forward does.  memory_format: torch.contiguous_format or torch.channels_last, the layout of the
+    result.  See nfp_compress_map_tensors."""
+    channels_last = _cproj_memory_format(memory_format, maps)       # (refused before the step counter moves)
     training = bn.training if training is None else bool(training)
     factor = 0.0 if bn.momentum is None else bn.momentum
     if training and bn.track_running_stats and bn.num_batches_tracked is not None:      # nn.modules.batchnorm._BatchNorm.forward
@@ -1364,5 +1408,7 @@ def nfp_compress_map(maps, weight, bn, relu=True, training=None):
     track = not training or bn.track_running_stats
     rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
     if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
-        return compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
-    return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu)
+        y = compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
+        return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+    return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu,
+                                    memory_format=memory_format)

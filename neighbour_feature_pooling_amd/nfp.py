@@ -252,6 +252,18 @@ class SimilarityAwarePooling(nn.Module):
         return nfp_attention_pool(self.nfp(x), self.att_proj.weight, self.att_proj.bias)
 
 
+def _module_memory_format(memory_format, x):
+    """The memory_format a block hands nfp_compress_map for input x: torch.preserve_format follows x — channels-last exactly
+    when x is dense in that layout and not also NCHW-dense (H = W = 1 or one channel: both) —, the other two stand."""
+    if memory_format != torch.preserve_format:
+        return memory_format
+    follows = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+    return torch.channels_last if follows else torch.contiguous_format
+
+
+_MODULE_FORMATS = (torch.contiguous_format, torch.channels_last, torch.preserve_format)
+
+
 class NFPBottleneck(nn.Module):
     """Drop-in for models/nfp_heads.py::NFPBottleneck (nfp_heads.py:234-278, the second definition — the one Python keeps):
     a residual block with an unpadded cosine NFP layer between two 1x1 convs,
@@ -263,12 +275,22 @@ class NFPBottleneck(nn.Module):
     (functional.nfp_valid), forward and backward one launch each.
     fused_project=True (not in the reference; the default keeps the two ATen ops): bn2(conv2(.)) as one call of
     functional.nfp_compress_map(relu=False) — on the GPU, where it serves, without the copies of the [B,out,H,W]
-    activation that conv2 and bn2 write, re-read and save."""
+    activation that conv2 and bn2 write, re-read and save.
+    memory_format (with fused_project=True only; anything but the default without it is a ValueError): the layout the
+    projection writes, and so the block returns — torch.channels_last for a channels-last network, where `out += identity`
+    then adds like to like; torch.preserve_format: channels-last exactly when x is (dense in it and not also NCHW-dense)."""
     expansion = 1
 
-    def __init__(self, in_channels: int, out_channels: int, stride=1, *, fused_project=False):
+    def __init__(self, in_channels: int, out_channels: int, stride=1, *, fused_project=False,
+                 memory_format=torch.contiguous_format):
         super().__init__()
         self.fused_project = bool(fused_project)
+        if memory_format not in _MODULE_FORMATS:
+            raise ValueError(f"NFPBottleneck: memory_format must be torch.contiguous_format, torch.channels_last or "
+                             f"torch.preserve_format, got {memory_format!r}")
+        if memory_format != torch.contiguous_format and not self.fused_project:
+            raise ValueError("NFPBottleneck: memory_format applies to the fused projection; pass fused_project=True")
+        self.memory_format = memory_format
         mid = out_channels // 4
         self.conv1 = nn.Conv2d(in_channels, mid, 1, bias=False, stride=stride)
         self.bn1 = nn.BatchNorm2d(mid)
@@ -299,7 +321,8 @@ class NFPBottleneck(nn.Module):
         out = self.relu(self.bn1(self.conv1(x)))
         out = nfp_valid(out, self.nfp.config)
         if self.fused_project:
-            out = nfp_compress_map(out, self.conv2.weight, self.bn2, relu=False)
+            out = nfp_compress_map(out, self.conv2.weight, self.bn2, relu=False,
+                                   memory_format=_module_memory_format(self.memory_format, x))
         else:
             out = self.bn2(self.conv2(out))
         identity = self._match(identity, out.shape[-1])
@@ -318,10 +341,16 @@ class NFPInsert(nn.Module):
     nfp_proj.1.*); the RNG is consumed in the reference's order — the layer's two depthwise conv weights (drawn and
     dropped), then the conv — so the same seed gives bit-identical parameters.  forward is one call of
     functional.nfp_compress_map behind the layer: on the GPU, where it serves, the projected map is stored once and nothing
-    of its size is saved for the backward."""
+    of its size is saved for the backward.
+    memory_format (keyword only): the layout of the result — torch.contiguous_format, torch.channels_last, or
+    torch.preserve_format: channels-last exactly when x is (dense in it and not also NCHW-dense)."""
 
-    def __init__(self, in_channels, out_channels=None, **nfp_kwargs):
+    def __init__(self, in_channels, out_channels=None, *, memory_format=torch.contiguous_format, **nfp_kwargs):
         super().__init__()
+        if memory_format not in _MODULE_FORMATS:
+            raise ValueError(f"NFPInsert: memory_format must be torch.contiguous_format, torch.channels_last or "
+                             f"torch.preserve_format, got {memory_format!r}")
+        self.memory_format = memory_format
         from .heads import _reference_layer_draws
         out_channels = int(in_channels if out_channels is None else out_channels)
         self.nfp = NFPPooling(in_channels=in_channels, **nfp_kwargs)
@@ -332,4 +361,5 @@ class NFPInsert(nn.Module):
         self.in_channels, self.out_channels = int(in_channels), out_channels
 
     def forward(self, x):
-        return nfp_compress_map(self.nfp(x), self.nfp_proj[0].weight, self.nfp_proj[1])
+        return nfp_compress_map(self.nfp(x), self.nfp_proj[0].weight, self.nfp_proj[1],
+                                memory_format=_module_memory_format(self.memory_format, x))
