@@ -88,6 +88,11 @@ __device__ __forceinline__ void cp_coef(const CpK& k, int d, float& scale, float
   shift = k.eval ? k.beta[d] - scale * k.rm[d] : k.beta[d];
 }
 
+// element j of a tensor of the maps' dtype (the maps, or cproj's grad_out) as float32
+__device__ __forceinline__ float cj_load(const CpK& k, const void* p, long long j) {
+  return k.bf16 ? bf16_to_f32(((const uint16_t*)p)[j]) : ((const float*)p)[j];
+}
+
 // The chunk [p0, p0 + ch) of image b into sm[NP][CHs] as centred float32; rows n >= N and pixels >= ch are zero.
 __device__ __forceinline__ void cp_stage(const CpK& k, int NP, float* sm, int b, int p0, int ch, bool centre) {
   const long long base = (long long)b * k.N * k.P + p0;
@@ -96,8 +101,7 @@ __device__ __forceinline__ void cp_stage(const CpK& k, int NP, float* sm, int b,
     const int n = i / k.CHs, pl = i - n * k.CHs;
     float v = 0.f;
     if (n < k.N && pl < ch) {
-      const long long j = base + (long long)n * k.P + pl;
-      v = k.bf16 ? bf16_to_f32(((const uint16_t*)k.maps)[j]) : ((const float*)k.maps)[j];
+      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
       if (centre) v = (v - k.stats[n]) - k.stats[k.N + n];
     }
     sm[i] = v;
@@ -572,8 +576,7 @@ __global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
   for (int n = 0; n < NP; ++n) {
     float v = 0.f;
     if (n < N && live) {
-      const long long j = base + (long long)n * k.P;
-      v = k.bf16 ? bf16_to_f32(((const uint16_t*)k.maps)[j]) : ((const float*)k.maps)[j];
+      v = cj_load(k, k.maps, base + (long long)n * k.P);
       if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
     }
     c[n] = v;
@@ -642,10 +645,6 @@ constexpr int kCjT = 256;    // threads of cproj_fwd
 constexpr int kCjDT = 64;    // channels of D per workgroup of cproj_fwd
 constexpr int kCjSP = 64;    // pixels per pass of cproj_bwd_part
 constexpr int kCjSS = 68;    // floats between two rows of a pass in LDS: 16-byte rows, an odd number of 16-byte slots
-
-__device__ __forceinline__ float cj_load(const CpK& k, const void* p, long long j) {
-  return k.bf16 ? bf16_to_f32(((const uint16_t*)p)[j]) : ((const float*)p)[j];
-}
 
 // grid = B * nc * tiles (the tile fastest), block = 256; k.CH / k.CHs / k.nc are this kernel's own chunks (cproj_fwd_chunk).
 // LDS: sm[NP * CHs], tb[64][NP + 1] — the scaled row of a channel, then its shift.
@@ -1119,67 +1118,52 @@ int cproj_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int
   return NFP_OK;
 }
 
-template <template <int, bool> class F, typename... A>
-int cproj_by_np(int NP, bool relu, A... a) {
+template <template <int, bool, bool> class F, int NP, typename... A>
+int cproj_by_flags(bool relu, bool nhwc, A... a) {
+  if (relu) return nhwc ? F<NP, true, true>::go(a...) : F<NP, true, false>::go(a...);
+  return nhwc ? F<NP, false, true>::go(a...) : F<NP, false, false>::go(a...);
+}
+template <template <int, bool, bool> class F, typename... A>
+int cproj_by_np(int NP, bool relu, bool nhwc, A... a) {
   switch (NP) {
-    case 8: return relu ? F<8, true>::go(a...) : F<8, false>::go(a...);
-    case 16: return relu ? F<16, true>::go(a...) : F<16, false>::go(a...);
-    case 24: return relu ? F<24, true>::go(a...) : F<24, false>::go(a...);
-    default: return relu ? F<32, true>::go(a...) : F<32, false>::go(a...);
+    case 8: return cproj_by_flags<F, 8>(relu, nhwc, a...);
+    case 16: return cproj_by_flags<F, 16>(relu, nhwc, a...);
+    case 24: return cproj_by_flags<F, 24>(relu, nhwc, a...);
+    default: return cproj_by_flags<F, 32>(relu, nhwc, a...);
   }
 }
-template <int NP, bool RELU>
+// NHWC: the channels-last forms (out / grad_out [b][p][d]) — the same grids, LDS sizes and scratch.
+template <int NP, bool RELU, bool NHWC>
 struct JFwd {
   static int go(const nfp::CpK& k, hipStream_t st) {
     const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
     const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
-    return launch("cproj_fwd", nfp::cproj_fwd<NP, RELU>, dim3((unsigned)((long long)k.B * k.nc * tiles)), dim3(nfp::kCjT), lds, st,
-                  k, tiles);
+    const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
+    if constexpr (!NHWC) {
+      return launch("cproj_fwd", nfp::cproj_fwd<NP, RELU>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+    } else {
+      // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
+      if (k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0))
+        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+      return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+    }
   }
 };
-template <int NP, bool RELU>
+template <int NP, bool RELU, bool NHWC>
 struct JPart {
   static int go(const nfp::CpK& k, hipStream_t st) {
     const size_t lds = ((size_t)NP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
-    return launch("cproj_bwd_part", nfp::cproj_bwd_part<NP, RELU>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
-                  dim3(nfp::cp_part_threads<NP>()), lds, st, k, (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
+    return launch(NHWC ? "cproj_bwd_part_nhwc" : "cproj_bwd_part", nfp::cproj_bwd_part<NP, RELU, NHWC>,
+                  dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)), dim3(nfp::cp_part_threads<NP>()), lds, st, k,
+                  (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
   }
 };
-template <int NP, bool RELU>
+template <int NP, bool RELU, bool NHWC>
 struct JMaps {
   static int go(const nfp::CpK& k, hipStream_t st) {
     const int npt = (k.P + 63) / 64;
-    return launch("cproj_bwd_maps", nfp::cproj_bwd_maps<NP, RELU>, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st,
-                  k, npt);
-  }
-};
-// The channels-last forms (out / grad_out [b][p][d]): the same grids, LDS sizes and scratch.
-template <int NP, bool RELU>
-struct JFwdN {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
-    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
-    const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
-    // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
-    if (k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0))
-      return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
-    return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
-  }
-};
-template <int NP, bool RELU>
-struct JPartN {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const size_t lds = ((size_t)NP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
-    return launch("cproj_bwd_part_nhwc", nfp::cproj_bwd_part<NP, RELU, true>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
-                  dim3(nfp::cp_part_threads<NP>()), lds, st, k, (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
-  }
-};
-template <int NP, bool RELU>
-struct JMapsN {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const int npt = (k.P + 63) / 64;
-    return launch("cproj_bwd_maps_nhwc", nfp::cproj_bwd_maps<NP, RELU, true>, dim3((unsigned)((long long)k.B * npt)),
-                  dim3(nfp::kCpT), 0, st, k, npt);
+    return launch(NHWC ? "cproj_bwd_maps_nhwc" : "cproj_bwd_maps", nfp::cproj_bwd_maps<NP, RELU, NHWC>,
+                  dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st, k, npt);
   }
 };
 
@@ -1187,6 +1171,168 @@ int cproj_layout(const char* what, int32_t layout) {
   if (layout != NFP_ACT_NCHW && layout != NFP_ACT_NHWC)
     return fail(NFP_E_INVALID, "%s: unknown layout %d (NFP_ACT_NCHW = 0, NFP_ACT_NHWC = 1)", what, layout);
   return NFP_OK;
+}
+
+// ---- one host path for both kinds ----
+// What an extern "C" entry asks for.  kind: the pooled tail (nfp_cpool_*: out [B,D] float32, always with the ReLU) or the
+// projection with the map kept (nfp_cproj_*: out / grad_out [B,D,P] in the maps' dtype, `relu` and `layout` the caller's).
+// A forward fills rm_w .. saved_w, a backward rm .. gb; the other direction's fields stay zero.
+enum CpKind { kCpPool, kCpProj };
+struct CpCall {
+  const char* what;   // the entry's name, at the head of every message
+  CpKind kind;
+  int32_t layout, relu;
+  int32_t B, N;
+  int64_t P;
+  int32_t D, dtype, training;
+  const void* maps;
+  const float *w, *gamma, *beta;
+  double eps;
+  int64_t saved_floats;
+  float* scratch;
+  int64_t scratch_floats;
+  void* stream;
+  float *rm_w, *rv_w;   // forward
+  double momentum;
+  void* out;
+  float* saved_w;
+  const float *rm, *rv, *saved;   // backward
+  const void* go;
+  void* gm;
+  float *gw, *gg, *gb;
+};
+
+// The refusals both directions share, in order: layout, sizes, pointers (io: the forward's out, the backward's grad_out)
+int cp_check(const CpCall& c, const void* io) {
+  if (c.kind == kCpProj)
+    if (int rc = cproj_layout(c.what, c.layout)) return rc;
+  if (int rc = (c.kind == kCpProj ? cproj_args : cpool_args)(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training)) return rc;
+  if (!c.w || !c.gamma || !c.beta || (c.B > 0 && (!c.maps || !io))) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
+  return NFP_OK;
+}
+int cp_check_scratch(const CpCall& c, int backward) {
+  const bool proj = c.kind == kCpProj;
+  const int64_t need = (proj ? nfp_cproj_scratch_floats : nfp_cpool_scratch_floats)(c.B, c.N, c.P, c.D, backward);
+  if (c.B > 0 && (c.scratch == nullptr || c.scratch_floats < need))
+    return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, %s is %lld", c.what, (long long)(c.scratch ? c.scratch_floats : 0),
+                proj ? "nfp_cproj_scratch_floats" : "nfp_cpool_scratch_floats", (long long)need);
+  return NFP_OK;
+}
+nfp::CpK cp_k(const CpCall& c) {
+  nfp::CpK k = cpool_k(c.B, c.N, c.P, c.D, c.dtype, c.training);
+  k.maps = c.maps, k.w = c.w, k.gamma = c.gamma, k.beta = c.beta;
+  k.eps = (float)c.eps, k.eps64 = c.eps;
+  return k;
+}
+void cp_variant(const CpCall& c, const char* dir) {
+  const char *dt = c.dtype == NFP_BF16 ? "bf16" : "f32", *mode = c.training ? "train" : "eval";
+  if (c.kind == kCpPool)
+    snprintf(g_variant, sizeof(g_variant), "cpool_%s<%s,%s>", dir, dt, mode);
+  else
+    snprintf(g_variant, sizeof(g_variant), "cproj_%s<%s,%s,%s%s>", dir, dt, mode, c.relu ? "relu" : "lin",
+             c.layout == NFP_ACT_NHWC ? ",nhwc" : "");
+}
+// cpool_moments + cpool_finish: the train-mode statistics of either kind
+int launch_stats(const nfp::CpK& k, int NP, hipStream_t st) {
+  const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
+  int rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
+  if (rc == NFP_OK)
+    rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st,
+                k);
+  return rc;
+}
+
+int cp_forward(const CpCall& c) {
+  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
+  if (int rc = cp_check(c, c.out)) return rc;
+  if ((c.rm_w == nullptr) != (c.rv_w == nullptr) || (!c.training && c.rm_w == nullptr))
+    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", c.what);
+  if (!(c.eps >= 0.0) || !(c.momentum == c.momentum))
+    return fail(NFP_E_INVALID, "%s: eps = %g, momentum = %g", c.what, c.eps, c.momentum);
+  if (c.training) {
+    if (c.saved_w == nullptr || c.saved_floats < nfp_cpool_saved_floats(c.N, c.D))
+      return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", c.what,
+                  (long long)(c.saved_w ? c.saved_floats : 0), (long long)nfp_cpool_saved_floats(c.N, c.D));
+    if (int rc = cp_check_scratch(c, 0)) return rc;
+  }
+  if (c.B == 0) return NFP_OK;
+  nfp::CpK k = cp_k(c);
+  const int NP = cpool_np(c.N);
+  k.mom = c.momentum;
+  if (proj)
+    k.outv = c.out;
+  else
+    k.out = (float*)c.out;
+  hipStream_t st = (hipStream_t)c.stream;
+  cp_variant(c, "fwd");
+  int rc = NFP_OK;
+  if (c.training) {
+    k.part_w = c.scratch, k.part = c.scratch, k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
+    rc = launch_stats(k, NP, st);
+  } else {
+    k.rm = c.rm_w, k.rv = c.rv_w;
+  }
+  if (proj)   // (cproj_fwd's own chunks)
+    k.CH = cproj_fwd_chunk(NP, c.B, c.P, c.D), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
+  if (rc == NFP_OK) rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LFwd>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int cp_backward(const CpCall& c) {
+  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
+  if (int rc = cp_check(c, c.go)) return rc;
+  if (!c.training && (c.rm == nullptr || c.rv == nullptr))
+    return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", c.what);
+  if (!(c.eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", c.what, c.eps);
+  if (c.training && (c.saved == nullptr || c.saved_floats < nfp_cpool_saved_floats(c.N, c.D)))
+    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", c.what,
+                (long long)(c.saved ? c.saved_floats : 0), (long long)nfp_cpool_saved_floats(c.N, c.D));
+  const bool params = c.gw != nullptr || c.gg != nullptr || c.gb != nullptr;
+  if (!params && c.gm == nullptr) return NFP_OK;
+  const bool sums = params || c.training;   // (train-mode grad_maps needs k and Q: the batch sums)
+  if (sums)
+    if (int rc = cp_check_scratch(c, 1)) return rc;
+  if (c.B == 0) return NFP_OK;
+  nfp::CpK k = cp_k(c);
+  const int NP = cpool_np(c.N);
+  if (proj) {
+    k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                   // cproj_bwd_part's passes
+    k.ipw = cproj_upw(c.B, c.P, c.D), k.S = cproj_slices(c.B, c.P, c.D);     // ... and how many of them a workgroup takes
+  }
+  if (proj)
+    k.gov = c.go;
+  else
+    k.go = (const float*)c.go;
+  k.stats = c.saved;
+  if (!c.training) k.rm = c.rm, k.rv = c.rv;
+  k.gm = c.gm, k.gw = c.gw, k.gg = c.gg, k.gb = c.gb;
+  hipStream_t st = (hipStream_t)c.stream;
+  cp_variant(c, "bwd");
+  int rc = NFP_OK;
+  if (sums) {
+    k.part_w = c.scratch, k.part = c.scratch;
+    k.kq_w = c.scratch + (int64_t)k.S * c.D * (c.N + 1), k.kq = k.kq_w;
+    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LPart>(NP, k, st);
+    if (rc == NFP_OK)
+      rc = proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
+                : launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
+  }
+  if (rc == NFP_OK && c.gm != nullptr) rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LMaps>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+// ... with the direction's own arguments filled in behind the entry's leading fields
+int cp_forward(CpCall c, float* running_mean, float* running_var, double momentum, void* out, float* saved) {
+  c.rm_w = running_mean, c.rv_w = running_var, c.momentum = momentum, c.out = out, c.saved_w = saved;
+  return cp_forward(c);
+}
+int cp_backward(CpCall c, const float* running_mean, const float* running_var, const float* saved, const void* grad_out,
+                void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta) {
+  c.rm = running_mean, c.rv = running_var, c.saved = saved, c.go = grad_out;
+  c.gm = grad_maps, c.gw = grad_w, c.gg = grad_gamma, c.gb = grad_beta;
+  return cp_backward(c);
 }
 
 }  // namespace
@@ -1206,44 +1352,20 @@ int64_t nfp_cpool_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int
   return std::max<int64_t>(1, backward ? cpool_bwd_scratch(B, N, D) : cpool_fwd_scratch(B, N, P));
 }
 
+int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
+  if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
+  return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
+}
+
+// The six entries: a CpCall of the leading fields, in order, and cp_forward / cp_backward with the direction's own.
+
 int nfp_cpool_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
                       const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
                       double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
                       int64_t scratch_floats, void* hip_stream) {
-  const char* what = "nfp_cpool_forward";
-  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
-  if (!w || !gamma || !beta || (B > 0 && (!maps || !out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
-  if ((running_mean == nullptr) != (running_var == nullptr) || (!training && running_mean == nullptr))
-    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", what);
-  if (!(eps >= 0.0) || !(momentum == momentum)) return fail(NFP_E_INVALID, "%s: eps = %g, momentum = %g", what, eps, momentum);
-  if (training) {
-    if (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D))
-      return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
-                  (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
-    if (B > 0 && (scratch == nullptr || scratch_floats < nfp_cpool_scratch_floats(B, N, P, D, 0)))
-      return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cpool_scratch_floats is %lld", what,
-                  (long long)(scratch ? scratch_floats : 0), (long long)nfp_cpool_scratch_floats(B, N, P, D, 0));
-  }
-  if (B == 0) return NFP_OK;
-  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
-  const int NP = cpool_np(N);
-  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.out = out;
-  k.eps = (float)eps, k.eps64 = eps, k.mom = momentum;
-  hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cpool_fwd<%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval");
-  int rc = NFP_OK;
-  if (training) {
-    k.part_w = scratch, k.part = scratch, k.stats_w = saved, k.stats = saved, k.rm_w = running_mean, k.rv_w = running_var;
-    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
-    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
-    if (rc == NFP_OK)
-      rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k);
-  } else {
-    k.rm = running_mean, k.rv = running_var;
-  }
-  if (rc == NFP_OK) rc = cpool_by_np<LFwd>(NP, k, st);
-  if (rc == NFP_OK) publish_variant();
-  return rc;
+  const CpCall c{"nfp_cpool_forward", kCpPool, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
 int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
@@ -1251,164 +1373,18 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        const float* running_var, double eps, const float* saved, int64_t saved_floats, const float* grad_out,
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream) {
-  const char* what = "nfp_cpool_backward";
-  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
-  if (!w || !gamma || !beta || (B > 0 && (!maps || !grad_out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
-  if (!training && (running_mean == nullptr || running_var == nullptr))
-    return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", what);
-  if (!(eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", what, eps);
-  if (training && (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D)))
-    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
-                (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
-  const bool params = grad_w != nullptr || grad_gamma != nullptr || grad_beta != nullptr;
-  if (!params && grad_maps == nullptr) return NFP_OK;
-  const bool sums = params || training;   // (train-mode grad_maps needs k and Q: the batch sums)
-  if (sums && B > 0 && (scratch == nullptr || scratch_floats < nfp_cpool_scratch_floats(B, N, P, D, 1)))
-    return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cpool_scratch_floats is %lld", what,
-                (long long)(scratch ? scratch_floats : 0), (long long)nfp_cpool_scratch_floats(B, N, P, D, 1));
-  if (B == 0) return NFP_OK;
-  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
-  const int NP = cpool_np(N);
-  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.go = grad_out, k.stats = saved;
-  k.eps = (float)eps, k.eps64 = eps;
-  if (!training) k.rm = running_mean, k.rv = running_var;
-  k.gm = grad_maps, k.gw = grad_w, k.gg = grad_gamma, k.gb = grad_beta;
-  hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cpool_bwd<%s,%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval");
-  int rc = NFP_OK;
-  if (sums) {
-    k.part_w = scratch, k.part = scratch;
-    k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
-    rc = cpool_by_np<LPart>(NP, k, st);
-    if (rc == NFP_OK)
-      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
-  }
-  if (rc == NFP_OK && grad_maps != nullptr) rc = cpool_by_np<LMaps>(NP, k, st);
-  if (rc == NFP_OK) publish_variant();
-  return rc;
-}
-
-int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
-  if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
-  return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
-}
-
-// nfp_cproj_forward / nfp_cproj_forward_fmt (`what`): layout = NFP_ACT_NCHW is the former, kernel for kernel.
-static int cproj_forward(const char* what, int32_t layout, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
-                         int32_t training, int32_t relu, const void* maps, const float* w, const float* gamma,
-                         const float* beta, float* running_mean, float* running_var, double momentum, double eps, void* out,
-                         float* saved, int64_t saved_floats, float* scratch, int64_t scratch_floats, void* hip_stream) {
-  if (int rc = cproj_layout(what, layout)) return rc;
-  if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
-  if (!w || !gamma || !beta || (B > 0 && (!maps || !out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
-  if ((running_mean == nullptr) != (running_var == nullptr) || (!training && running_mean == nullptr))
-    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", what);
-  if (!(eps >= 0.0) || !(momentum == momentum)) return fail(NFP_E_INVALID, "%s: eps = %g, momentum = %g", what, eps, momentum);
-  if (training) {
-    if (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D))
-      return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
-                  (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
-    if (B > 0 && (scratch == nullptr || scratch_floats < nfp_cproj_scratch_floats(B, N, P, D, 0)))
-      return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cproj_scratch_floats is %lld", what,
-                  (long long)(scratch ? scratch_floats : 0), (long long)nfp_cproj_scratch_floats(B, N, P, D, 0));
-  }
-  if (B == 0) return NFP_OK;
-  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
-  const int NP = cpool_np(N);
-  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.outv = out;
-  k.eps = (float)eps, k.eps64 = eps, k.mom = momentum;
-  hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cproj_fwd<%s,%s,%s%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
-           relu ? "relu" : "lin", layout == NFP_ACT_NHWC ? ",nhwc" : "");
-  int rc = NFP_OK;
-  if (training) {
-    k.part_w = scratch, k.part = scratch, k.stats_w = saved, k.stats = saved, k.rm_w = running_mean, k.rv_w = running_var;
-    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
-    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
-    if (rc == NFP_OK)
-      rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k);
-  } else {
-    k.rm = running_mean, k.rv = running_var;
-  }
-  k.CH = cproj_fwd_chunk(NP, B, P, D), k.CHs = cpool_stride(k.CH), k.nc = (int)((P + k.CH - 1) / k.CH);   // (cproj_fwd's own)
-  if (rc == NFP_OK)
-    rc = layout == NFP_ACT_NHWC ? cproj_by_np<JFwdN>(NP, relu != 0, k, st) : cproj_by_np<JFwd>(NP, relu != 0, k, st);
-  if (rc == NFP_OK) publish_variant();
-  return rc;
-}
-
-int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
-                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
-                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
-                      float* scratch, int64_t scratch_floats, void* hip_stream) {
-  return cproj_forward("nfp_cproj_forward", NFP_ACT_NCHW, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
-                       running_var, momentum, eps, out, saved, saved_floats, scratch, scratch_floats, hip_stream);
+  const CpCall c{"nfp_cpool_backward", kCpPool, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
 int nfp_cproj_forward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
                           const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
                           float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
                           float* scratch, int64_t scratch_floats, void* hip_stream, int32_t out_layout) {
-  return cproj_forward("nfp_cproj_forward_fmt", out_layout, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
-                       running_var, momentum, eps, out, saved, saved_floats, scratch, scratch_floats, hip_stream);
-}
-
-// nfp_cproj_backward / nfp_cproj_backward_fmt (`what`): layout, of grad_out, = NFP_ACT_NCHW is the former.
-static int cproj_backward(const char* what, int32_t layout, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
-                          int32_t training, int32_t relu, const void* maps, const float* w, const float* gamma,
-                          const float* beta, const float* running_mean, const float* running_var, double eps,
-                          const float* saved, int64_t saved_floats, const void* grad_out, void* grad_maps, float* grad_w,
-                          float* grad_gamma, float* grad_beta, float* scratch, int64_t scratch_floats, void* hip_stream) {
-  if (int rc = cproj_layout(what, layout)) return rc;
-  if (int rc = cproj_args(what, B, N, P, D, dtype, training)) return rc;
-  if (!w || !gamma || !beta || (B > 0 && (!maps || !grad_out))) return fail(NFP_E_INVALID, "%s: null tensor pointer", what);
-  if (!training && (running_mean == nullptr || running_var == nullptr))
-    return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", what);
-  if (!(eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", what, eps);
-  if (training && (saved == nullptr || saved_floats < nfp_cpool_saved_floats(N, D)))
-    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpool_saved_floats is %lld", what,
-                (long long)(saved ? saved_floats : 0), (long long)nfp_cpool_saved_floats(N, D));
-  const bool params = grad_w != nullptr || grad_gamma != nullptr || grad_beta != nullptr;
-  if (!params && grad_maps == nullptr) return NFP_OK;
-  const bool sums = params || training;   // (train-mode grad_maps needs k and Q: the batch sums)
-  if (sums && B > 0 && (scratch == nullptr || scratch_floats < nfp_cproj_scratch_floats(B, N, P, D, 1)))
-    return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, nfp_cproj_scratch_floats is %lld", what,
-                (long long)(scratch ? scratch_floats : 0), (long long)nfp_cproj_scratch_floats(B, N, P, D, 1));
-  if (B == 0) return NFP_OK;
-  nfp::CpK k = cpool_k(B, N, P, D, dtype, training);
-  const int NP = cpool_np(N);
-  k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                 // cproj_bwd_part's passes
-  k.ipw = cproj_upw(B, P, D), k.S = cproj_slices(B, P, D);               // ... and how many of them a workgroup takes
-  k.maps = maps, k.w = w, k.gamma = gamma, k.beta = beta, k.gov = grad_out, k.stats = saved;
-  k.eps = (float)eps, k.eps64 = eps;
-  if (!training) k.rm = running_mean, k.rv = running_var;
-  k.gm = grad_maps, k.gw = grad_w, k.gg = grad_gamma, k.gb = grad_beta;
-  hipStream_t st = (hipStream_t)hip_stream;
-  snprintf(g_variant, sizeof(g_variant), "cproj_bwd<%s,%s,%s%s>", k.bf16 ? "bf16" : "f32", training ? "train" : "eval",
-           relu ? "relu" : "lin", layout == NFP_ACT_NHWC ? ",nhwc" : "");
-  const bool nhwc = layout == NFP_ACT_NHWC;
-  int rc = NFP_OK;
-  if (sums) {
-    k.part_w = scratch, k.part = scratch;
-    k.kq_w = scratch + (int64_t)k.S * D * (N + 1), k.kq = k.kq_w;
-    rc = nhwc ? cproj_by_np<JPartN>(NP, relu != 0, k, st) : cproj_by_np<JPart>(NP, relu != 0, k, st);
-    if (rc == NFP_OK)
-      rc = launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
-  }
-  if (rc == NFP_OK && grad_maps != nullptr)
-    rc = nhwc ? cproj_by_np<JMapsN>(NP, relu != 0, k, st) : cproj_by_np<JMaps>(NP, relu != 0, k, st);
-  if (rc == NFP_OK) publish_variant();
-  return rc;
-}
-
-int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
-                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
-                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
-                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
-                       int64_t scratch_floats, void* hip_stream) {
-  return cproj_backward("nfp_cproj_backward", NFP_ACT_NCHW, B, N, P, D, dtype, training, relu, maps, w, gamma, beta, running_mean,
-                        running_var, eps, saved, saved_floats, grad_out, grad_maps, grad_w, grad_gamma, grad_beta, scratch,
-                        scratch_floats, hip_stream);
+  const CpCall c{"nfp_cproj_forward_fmt", kCpProj, out_layout, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
 int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
@@ -1416,9 +1392,28 @@ int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t d
                            const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
                            void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                            int64_t scratch_floats, void* hip_stream, int32_t grad_out_layout) {
-  return cproj_backward("nfp_cproj_backward_fmt", grad_out_layout, B, N, P, D, dtype, training, relu, maps, w, gamma, beta,
-                        running_mean, running_var, eps, saved, saved_floats, grad_out, grad_maps, grad_w, grad_gamma, grad_beta,
-                        scratch, scratch_floats, hip_stream);
+  const CpCall c{"nfp_cproj_backward_fmt", kCpProj, grad_out_layout, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
+// nfp_cproj_forward / nfp_cproj_backward: the NCHW call under its own name
+int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                      const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
+                      float* scratch, int64_t scratch_floats, void* hip_stream) {
+  const CpCall c{"nfp_cproj_forward", kCpProj, NFP_ACT_NCHW, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_forward(c, running_mean, running_var, momentum, out, saved);
+}
+
+int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, int32_t relu,
+                       const void* maps, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
+                       void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
+                       int64_t scratch_floats, void* hip_stream) {
+  const CpCall c{"nfp_cproj_backward", kCpProj, NFP_ACT_NCHW, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
+}
 }  // extern "C"

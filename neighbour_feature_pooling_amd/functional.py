@@ -1066,9 +1066,13 @@ def nfp_valid(x, cfg):
     return _NfpValidHip.apply(x, layout, cfg, need_grad)
 
 
-# ---- the heads' compress-BN-ReLU-GAP tail — include/nfp.h: nfp_cpool_* (csrc/nfp_cpool.hip) --------------------------------
+# ---- the heads' compress-BN-ReLU-GAP tail — include/nfp.h: nfp_cpool_* (csrc/nfp_cpool.hip) — and the same projection
+# ---- with the map kept — nfp_cproj_* (the cproj kernels): one call path, one autograd node and one set of checks for both
 CPOOL_MAX_MAPS = 32     # csrc/nfp_cpool.hip: kCpMaxN (a lane keeps two weight rows in registers)
 CPOOL_ROUTED_MAPS = 8   # what cpool_hip_serves takes by default: the maps counts that measured faster than the composition
+# the two kinds' library calls: (forward, backward, the scratch length query)
+_CP_ENTRIES = {"pool": ("nfp_cpool_forward", "nfp_cpool_backward", "nfp_cpool_scratch_floats"),
+               "proj": ("nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt", "nfp_cproj_scratch_floats")}
 
 
 def _cpool_sizes(maps, w):
@@ -1076,73 +1080,149 @@ def _cpool_sizes(maps, w):
     return B, N, maps.numel() // max(B * N, 1), w.shape[0]
 
 
-def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps):
-    """(out [B,D] float32, saved) from nfp_cpool_forward on dense CUDA maps [B,N,...] and float32 w [D,N], gamma, beta [D].
-    use_batch_stats: train-mode statistics, the running ones (float32 [D], or both None) updated by the same call; `saved`
-    is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics)."""
-    L = _abi.load()
-    B, N, P, D = _cpool_sizes(maps, w)
-    dev = maps.device
-    with _on_device(dev):
-        out = torch.empty(B, D, dtype=torch.float32, device=dev)
-        ns = int(L.nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
-        nscr = int(L.nfp_cpool_scratch_floats(B, N, P, D, 0)) if use_batch_stats else 0
-        saved = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
-        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
-        _abi.check(L.nfp_cpool_forward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), maps.data_ptr(),
-                                       w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                       rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
-                                       float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
-                                       scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev)))
-    return out, saved
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
-def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want):
-    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cpool_backward — None for each
-    gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
+def _cp_invoke(kind, backward, maps, w, gamma, beta, use_batch_stats, relu, nhwc, need_scratch, middle):
+    """One call of a _CP_ENTRIES function, on the maps' device — the one place its argument list is built: the sizes, dtype
+    and mode (proj: relu), the maps and parameters, `middle` (the direction's own arguments), the scratch with its length,
+    the stream (proj: the layout of out / grad_out)."""
     L = _abi.load()
     B, N, P, D = _cpool_sizes(maps, w)
+    proj = kind == "proj"
+    nscr = int(getattr(L, _CP_ENTRIES[kind][2])(B, N, P, D, int(backward))) if need_scratch else 0
+    scratch = torch.empty(nscr, dtype=torch.float32, device=maps.device) if nscr else None
+    args = [B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats))] + ([int(bool(relu))] if proj else [])
+    args += [maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *middle, _ptr(scratch), nscr,
+             _raw_stream(maps.device)]
+    args += [_abi.ACT_NHWC if nhwc else _abi.ACT_NCHW] if proj else []
+    _abi.check(getattr(L, _CP_ENTRIES[kind][int(backward)])(*args))
+
+
+def _cp_forward_call(kind, out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu=True, nhwc=False):
+    """The forward of `kind` into `out`; returns `saved`, the O(N*N + D) state the backward reads (None in eval)."""
+    _, N, _, D = _cpool_sizes(maps, w)
+    with _on_device(maps.device):
+        ns = int(_abi.load().nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
+        saved = torch.empty(ns, dtype=torch.float32, device=maps.device) if ns else None
+        _cp_invoke(kind, False, maps, w, gamma, beta, use_batch_stats, relu, nhwc, use_batch_stats,
+                   [_ptr(rm), _ptr(rv), float(momentum), float(eps), out.data_ptr(), _ptr(saved), ns])
+    return saved
+
+
+def _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, go, want, relu=True, nhwc=False):
+    """(grad_maps, grad_w, grad_gamma, grad_beta) of `kind` under the dense grad_out `go` — None for each gradient `want`
+    (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
+    _, N, _, D = _cpool_sizes(maps, w)
     dev = maps.device
-    go = grad_out.contiguous().float()
     with _on_device(dev):
         gm = torch.empty_like(maps) if want[0] else None
         gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
         gg = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
         gb = torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None
         sums = use_batch_stats or want[1] or want[2] or want[3]
-        nscr = int(L.nfp_cpool_scratch_floats(B, N, P, D, 1)) if sums else 0
-        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
-        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
-        _abi.check(L.nfp_cpool_backward(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), maps.data_ptr(),
-                                        w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                        None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv), float(eps),
-                                        ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(), ptr(gm), ptr(gw),
-                                        ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev)))
+        _cp_invoke(kind, True, maps, w, gamma, beta, use_batch_stats, relu, nhwc, sums,
+                   [None if use_batch_stats else _ptr(rm), None if use_batch_stats else _ptr(rv), float(eps), _ptr(saved),
+                    saved.numel() if saved is not None else 0, go.data_ptr(), _ptr(gm), _ptr(gw), _ptr(gg), _ptr(gb)])
     return gm, gw, gg, gb
 
 
-class _CPoolHip(torch.autograd.Function):
-    """out [B,D] float32 of dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the backward: the maps,
-    the three parameters and the O(N*N + D) statistics — nothing of the size of the [B,D,P] activation.  `stats` = (rm, rv),
-    the running statistics or (None, None): buffers the forward kernel updates in place, handed over outside autograd's
-    view.  need_grad: some input requires a gradient and grad mode is on, sampled by the caller."""
+def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps):
+    """(out [B,D] float32, saved) from nfp_cpool_forward on dense CUDA maps [B,N,...] and float32 w [D,N], gamma, beta [D].
+    use_batch_stats: train-mode statistics, the running ones (float32 [D], or both None) updated by the same call; `saved`
+    is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics)."""
+    with _on_device(maps.device):
+        out = torch.empty(maps.shape[0], w.shape[0], dtype=torch.float32, device=maps.device)
+    return out, _cp_forward_call("pool", out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps)
+
+
+def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want):
+    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cpool_backward — None for each
+    gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
+    return _cp_backward_call("pool", maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out.contiguous().float(), want)
+
+
+class _CpHip(torch.autograd.Function):
+    """What the nodes of both kinds share, on dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the
+    backward: the maps, the three parameters and the O(N*N + D) statistics — nothing of the size of the [B,D,P]
+    activation, and not the output.  `stats` = (rm, rv), the running statistics or (None, None): buffers the forward kernel
+    updates in place, handed over outside autograd's view.  need_grad: some input requires a gradient and grad mode is on,
+    sampled by the caller."""
+
+    @staticmethod
+    def _save(ctx, maps, w, gamma, beta, saved, stats, use_batch_stats, eps):
+        ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
+        ctx.stats, ctx.use_batch_stats, ctx.eps = stats, use_batch_stats, eps
+
+    @staticmethod
+    def _state(ctx):
+        """The leading arguments of c*_backward_call: (maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps)."""
+        saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        return (*ctx.saved_tensors[:4], ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats, ctx.eps)
+
+
+class _CPoolHip(_CpHip):
+    """out [B,D] float32."""
 
     @staticmethod
     def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, need_grad):
         out, saved = cpool_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps)
         if need_grad:
-            ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
-            ctx.stats, ctx.use_batch_stats, ctx.eps = stats, use_batch_stats, eps
+            _CpHip._save(ctx, maps, w, gamma, beta, saved, stats, use_batch_stats, eps)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        maps, w, gamma, beta = ctx.saved_tensors[:4]
-        saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        gm, gw, gg, gb = cpool_backward_call(maps, w, gamma, beta, ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats,
-                                             ctx.eps, grad_out, ctx.needs_input_grad[:4])
-        return gm, gw, gg, gb, None, None, None, None, None
+        return (*cpool_backward_call(*_CpHip._state(ctx), grad_out, ctx.needs_input_grad[:4]), None, None, None, None, None)
+
+
+def _cp_can_serve(maps, gamma, beta, momentum):
+    """What both kinds' kernels can serve: dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] under an affine BatchNorm
+    with a float momentum, outside torch.compile and torch.autocast."""
+    return (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
+            and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
+            and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
+
+
+def _cp_check_args(name, maps, weight, use_batch_stats, running_mean, running_var):
+    if maps.dim() < 3:
+        raise RuntimeError(f"{name} expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
+    if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
+        raise RuntimeError(f"{name}: {maps.shape[1]} maps need a 1x1 conv weight [D,{maps.shape[1]},1,1], got "
+                           f"{tuple(weight.shape)}")
+    if not use_batch_stats and (running_mean is None or running_var is None):
+        raise RuntimeError(f"{name}: without batch statistics the running mean and variance are required")
+
+
+def _cp_prepare(maps, weight, gamma, beta, rm, rv, use_batch_stats):
+    """What a served call hands its node: float32, contiguous (w [D,N], gamma, beta) — or None where the running statistics
+    are not float32 and contiguous, which is the host composition's.  ValueError as F.batch_norm raises it for a single
+    value per channel in training."""
+    B, N = maps.shape[:2]
+    D = weight.shape[0]
+    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
+    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+        return None
+    f32 = lambda t: t if t.dtype == torch.float32 else t.float()     # noqa: E731
+    return f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous()
+
+
+def _bn_call_mode(bn, training):
+    """(use_batch_stats, rm, rv, factor) of one call of `bn` in mode `training`, as nn.modules.batchnorm._BatchNorm.forward
+    decides them — num_batches_tracked moved on by it.  factor: None with a float bn.momentum; with momentum=None the
+    cumulative average's factor, a function of the step count (the composition's to apply)."""
+    factor = 0.0 if bn.momentum is None else None
+    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if bn.momentum is None:
+            factor = 1.0 / float(bn.num_batches_tracked)
+    use_batch_stats = training or (bn.running_mean is None and bn.running_var is None)
+    track = not training or bn.track_running_stats
+    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
+    return use_batch_stats, rm, rv, factor
 
 
 def cpool_hip_serves(maps, gamma, beta, momentum):
@@ -1154,10 +1234,7 @@ def cpool_hip_serves(maps, gamma, beta, momentum):
     env = os.environ.get("NFP_CPOOL_TORCH")
     if env == "1":
         return False
-    can = (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
-           and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
-           and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
-    return can and (env == "0" or maps.shape[1] <= CPOOL_ROUTED_MAPS)
+    return _cp_can_serve(maps, gamma, beta, momentum) and (env == "0" or maps.shape[1] <= CPOOL_ROUTED_MAPS)
 
 
 def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5):
@@ -1168,26 +1245,14 @@ def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_v
     statistics instead (eval).  Where `cpool_hip_serves`, three HIP launches forward and at most three backward that never form
     the [B,D,H,W] activation (include/nfp.h: nfp_cpool_*; float32 arithmetic, the result cast once to the maps' dtype);
     everything else — by default also more than 8 maps, see cpool_hip_serves — is `_host.compress_pool_host`."""
-    if maps.dim() < 3:
-        raise RuntimeError(f"nfp_compress_pool expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
-    if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
-        raise RuntimeError(f"nfp_compress_pool: {maps.shape[1]} maps need a 1x1 conv weight [D,{maps.shape[1]},1,1], got "
-                           f"{tuple(weight.shape)}")
-    if not use_batch_stats and (running_mean is None or running_var is None):
-        raise RuntimeError("nfp_compress_pool: without batch statistics the running mean and variance are required")
-    if not cpool_hip_serves(maps, gamma, beta, momentum):
-        return compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps)
-    B, N = maps.shape[:2]
-    D = weight.shape[0]
-    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
-    f32 = lambda t: t if t is None or t.dtype == torch.float32 else t.float()     # noqa: E731
-    rm, rv = running_mean, running_var
-    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+    _cp_check_args("nfp_compress_pool", maps, weight, use_batch_stats, running_mean, running_var)
+    prepared = cpool_hip_serves(maps, gamma, beta, momentum) and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var,
+                                                                             use_batch_stats)
+    if not prepared:
         return compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps)
     need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (maps, weight, gamma, beta))
-    out = _CPoolHip.apply(maps, f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous(),
-                          (rm, rv), bool(use_batch_stats), float(momentum), float(eps), need_grad)
+    out = _CPoolHip.apply(maps, *prepared, (running_mean, running_var), bool(use_batch_stats), float(momentum), float(eps),
+                          need_grad)
     return out if out.dtype == maps.dtype else out.to(maps.dtype)
 
 
@@ -1197,20 +1262,12 @@ def nfp_compress_pool(maps, weight, bn, training=None):
     GAP(relu(bn(conv1x1(maps)))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its nn.BatchNorm2d — whose mode
     (`training`: None = bn.training), running statistics and num_batches_tracked are used and updated exactly as
     bn.forward does.  See nfp_compress_pool_tensors."""
-    training = bn.training if training is None else bool(training)
-    factor = 0.0 if bn.momentum is None else bn.momentum
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:      # nn.modules.batchnorm._BatchNorm.forward
-        bn.num_batches_tracked.add_(1)
-        factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
-    use_batch_stats = training or (bn.running_mean is None and bn.running_var is None)
-    track = not training or bn.track_running_stats
-    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
-    if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
+    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, bn.training if training is None else bool(training))
+    if factor is not None:
         return compress_pool_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps)
     return nfp_compress_pool_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps)
 
 
-# ---- the same projection with the map kept — include/nfp.h: nfp_cproj_* (csrc/nfp_cpool.hip, the cproj kernels) ------------
 # What cproj_hip_serves takes by default — the classes scripts/bench_insert.py measured faster than the composition beyond
 # the run-to-run spread on an MI355X (DESIGN 4g): with at most 8 maps, the forward that keeps no state for a backward on
 # running statistics (every row: 1.9x to 4.0x), and the train-mode step from 64 images of 54 x 54 map pixels up
@@ -1244,79 +1301,44 @@ def cproj_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, 
     """(out [B,D,...] in the maps' dtype, saved) from nfp_cproj_forward_fmt on dense CUDA maps [B,N,...] and float32 w
     [D,N], gamma, beta [D] — cpool_forward_call's arguments and `saved`, plus `relu`; channels_last: `out` [B,D,H,W] is
     written channels-last (the maps stay NCHW)."""
-    L = _abi.load()
-    B, N, P, D = _cpool_sizes(maps, w)
-    dev = maps.device
-    with _on_device(dev):
-        out = torch.empty((B, D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev,
+    with _on_device(maps.device):
+        out = torch.empty((maps.shape[0], w.shape[0]) + tuple(maps.shape[2:]), dtype=maps.dtype, device=maps.device,
                           memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-        ns = int(L.nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
-        nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 0)) if use_batch_stats else 0
-        saved = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
-        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
-        _abi.check(L.nfp_cproj_forward_fmt(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
-                                           maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                           rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
-                                           float(momentum), float(eps), out.data_ptr(), saved.data_ptr() if ns else None, ns,
-                                           scratch.data_ptr() if nscr else None, nscr, _raw_stream(dev),
-                                           _abi.ACT_NHWC if channels_last else _abi.ACT_NCHW))
-    return out, saved
+    return out, _cp_forward_call("proj", out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu, channels_last)
 
 
 def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, relu, grad_out, want):
-    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cproj_backward, grad_out
+    """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cproj_backward_fmt, grad_out
     [B,D,...] in the maps' dtype — None for each gradient `want` (four flags) leaves out: a NULL pointer in the library,
     neither computed nor written.  The layout grad_out arrives in selects the kernels, whatever the forward wrote: NCHW-dense
     (also where H = W = 1 or D = 1 make it both) the NCHW ones, channels-last-dense the channels-last ones, neither a
     copy; anything else is made NCHW-dense first."""
-    L = _abi.load()
-    B, N, P, D = _cpool_sizes(maps, w)
-    dev = maps.device
     go = grad_out.to(maps.dtype)        # (preserve_format: a dense tensor keeps its layout)
     nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
     if not nhwc:
         go = go.contiguous()
-    with _on_device(dev):
-        gm = torch.empty_like(maps) if want[0] else None
-        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
-        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
-        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None
-        sums = use_batch_stats or want[1] or want[2] or want[3]
-        nscr = int(L.nfp_cproj_scratch_floats(B, N, P, D, 1)) if sums else 0
-        scratch = torch.empty(nscr, dtype=torch.float32, device=dev) if nscr else None
-        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
-        _abi.check(L.nfp_cproj_backward_fmt(B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats)), int(bool(relu)),
-                                            maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                            None if use_batch_stats else ptr(rm), None if use_batch_stats else ptr(rv),
-                                            float(eps), ptr(saved), saved.numel() if saved is not None else 0, go.data_ptr(),
-                                            ptr(gm), ptr(gw), ptr(gg), ptr(gb), ptr(scratch), nscr, _raw_stream(dev),
-                                            _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
-    return gm, gw, gg, gb
+    return _cp_backward_call("proj", maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, go, want, relu, nhwc)
 
 
-class _CProjHip(torch.autograd.Function):
-    """out [B,D,...] in the maps' dtype of dense CUDA maps and float32 (w [D,N], gamma [D], beta [D]).  Saved for the
-    backward: the maps, the three parameters and the O(N*N + D) statistics — not the output, which the caller may modify in
-    place (ReLU(inplace=True) behind it, `out += identity`): the backward recomputes the pre-activation from the maps.
-    `stats`, need_grad: as _CPoolHip.  channels_last: the layout `out` is written in; the backward goes by its grad_out's."""
+class _CProjHip(_CpHip):
+    """out [B,D,...] in the maps' dtype, which the caller may modify in place (ReLU(inplace=True) behind it,
+    `out += identity`): the backward recomputes the pre-activation from the maps.  channels_last: the layout `out` is
+    written in; the backward goes by its grad_out's."""
 
     @staticmethod
     def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, relu, need_grad, channels_last=False):
         out, saved = cproj_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps, relu,
                                         channels_last)
         if need_grad:
-            ctx.save_for_backward(maps, w, gamma, beta, *([saved] if saved is not None else []))
-            ctx.stats, ctx.use_batch_stats, ctx.eps, ctx.relu = stats, use_batch_stats, eps, relu
+            _CpHip._save(ctx, maps, w, gamma, beta, saved, stats, use_batch_stats, eps)
+            ctx.relu = relu
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        maps, w, gamma, beta = ctx.saved_tensors[:4]
-        saved = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        gm, gw, gg, gb = cproj_backward_call(maps, w, gamma, beta, ctx.stats[0], ctx.stats[1], saved, ctx.use_batch_stats,
-                                             ctx.eps, ctx.relu, grad_out, ctx.needs_input_grad[:4])
-        return gm, gw, gg, gb, None, None, None, None, None, None, None
+        grads = cproj_backward_call(*_CpHip._state(ctx), ctx.relu, grad_out, ctx.needs_input_grad[:4])
+        return (*grads, None, None, None, None, None, None, None)
 
 
 def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, need_grad=True, channels_last=False):
@@ -1330,12 +1352,7 @@ def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, 
     NFP_CPROJ_TORCH (read at call time) is the A/B switch for both layouts: "1" the torch composition everywhere, "0" the
     HIP kernels wherever they can serve."""
     env = os.environ.get("NFP_CPROJ_TORCH")
-    if env == "1":
-        return False
-    can = (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
-           and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
-           and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
-    if not can:
+    if env == "1" or not _cp_can_serve(maps, gamma, beta, momentum):
         return False
     B, N = maps.shape[:2]
     P = maps.numel() // (B * N)
@@ -1366,29 +1383,15 @@ def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_va
     it comes, without a converting copy either way; the composition's result is converted.  It needs [B,N,H,W] maps, which
     themselves stay NCHW; ValueError otherwise, and for any other value."""
     channels_last = _cproj_memory_format(memory_format, maps)
-    if maps.dim() < 3:
-        raise RuntimeError(f"nfp_compress_map expects [B,N,H,W] (or [B,N,P]) maps, got {tuple(maps.shape)}")
-    if weight.dim() < 2 or weight.shape[1] != maps.shape[1] or weight.numel() != weight.shape[0] * maps.shape[1]:
-        raise RuntimeError(f"nfp_compress_map: {maps.shape[1]} maps need a 1x1 conv weight [D,{maps.shape[1]},1,1], got "
-                           f"{tuple(weight.shape)}")
-    if not use_batch_stats and (running_mean is None or running_var is None):
-        raise RuntimeError("nfp_compress_map: without batch statistics the running mean and variance are required")
-    def host():
+    _cp_check_args("nfp_compress_map", maps, weight, use_batch_stats, running_mean, running_var)
+    need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (maps, weight, gamma, beta))
+    prepared = (cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad, channels_last)
+                and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats))
+    if not prepared:
         y = compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps, relu)
         return y.contiguous(memory_format=torch.channels_last) if channels_last else y
-    need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (maps, weight, gamma, beta))
-    if not cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad, channels_last):
-        return host()
-    B, N = maps.shape[:2]
-    D = weight.shape[0]
-    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
-    f32 = lambda t: t if t.dtype == torch.float32 else t.float()     # noqa: E731
-    rm, rv = running_mean, running_var
-    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
-        return host()
-    return _CProjHip.apply(maps, f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(), f32(beta).contiguous(),
-                           (rm, rv), bool(use_batch_stats), float(momentum), float(eps), bool(relu), need_grad, channels_last)
+    return _CProjHip.apply(maps, *prepared, (running_mean, running_var), bool(use_batch_stats), float(momentum), float(eps),
+                           bool(relu), need_grad, channels_last)
 
 
 def nfp_compress_map(maps, weight, bn, relu=True, training=None, *, memory_format=torch.contiguous_format):
@@ -1399,15 +1402,8 @@ def nfp_compress_map(maps, weight, bn, relu=True, training=None, *, memory_forma
     updated exactly as bn.forward does.  memory_format: torch.contiguous_format or torch.channels_last, the layout of the
     result.  See nfp_compress_map_tensors."""
     channels_last = _cproj_memory_format(memory_format, maps)       # (refused before the step counter moves)
-    training = bn.training if training is None else bool(training)
-    factor = 0.0 if bn.momentum is None else bn.momentum
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:      # nn.modules.batchnorm._BatchNorm.forward
-        bn.num_batches_tracked.add_(1)
-        factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
-    use_batch_stats = training or (bn.running_mean is None and bn.running_var is None)
-    track = not training or bn.track_running_stats
-    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
-    if bn.momentum is None:     # (a cumulative average, its factor a function of the step count: the composition's)
+    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, bn.training if training is None else bool(training))
+    if factor is not None:
         y = compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
         return y.contiguous(memory_format=torch.channels_last) if channels_last else y
     return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu,
