@@ -323,6 +323,28 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        int64_t scratch_floats, void* hip_stream);
 
 /*
+ * The same tail for 1 <= N <= 96 maps (csrc/nfp_cpool.hip, the cpw kernels): the heads at R = 3 (48 maps), R = 4 (80) and
+ * R_list = (1, 2, 3) (80).  The weight rows of 64 channels and the chunk's centred maps sit in LDS and a lane owns a small
+ * tile of outputs, so nothing in registers grows with N.  Arguments, formulas, `saved` (nfp_cpool_saved_floats(N, D) floats,
+ * the same layout) and every convention and refusal are those of nfp_cpool_* above, with these differences:
+ *   N         up to 96; NFP_E_UNSUPPORTED above
+ *   scratch   nfp_cpool_wide_scratch_floats(B, N, P, D, backward) floats; the forward's must be 8-byte aligned
+ *   launches  forward 5 in training (moments, mu, Sigma, var, main) and 1 in eval; backward at most 3, skipped as above
+ * nfp_last_variant names cpool_wide_fwd<f32|bf16,train|eval,nK> / cpool_wide_bwd<...>, K = N rounded up to 16.  The results
+ * are not bitwise those of nfp_cpool_* (other sums, other orders); two runs of these entries agree bitwise.  Additive to ABI 7.
+ */
+int64_t nfp_cpool_wide_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward);
+int nfp_cpool_wide_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                           const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                           double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
+                           int64_t scratch_floats, void* hip_stream);
+int nfp_cpool_wide_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                            const float* w, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, double eps, const float* saved, int64_t saved_floats,
+                            const float* grad_out, void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta,
+                            float* scratch, int64_t scratch_floats, void* hip_stream);
+
+/*
  * The same projection with the map kept (csrc/nfp_cpool.hip, the cproj kernels) — NFPInsert's nfp_proj
  * (models/mobilenetv3.py:346-350: Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU) and NFPBottleneck's bn2(conv2(.))
  * (models/nfp_heads.py:270-272, relu = 0):

@@ -27,7 +27,8 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
            "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
            "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward",
-           "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt"]
+           "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt",
+           "nfp_cpool_wide_scratch_floats", "nfp_cpool_wide_forward", "nfp_cpool_wide_backward"]
 ACT_NCHW, ACT_NHWC = 0, 1     # enum nfp_act_layout: out / grad_out of nfp_cproj_*_fmt
 
 
@@ -130,6 +131,11 @@ def load():
     if hasattr(L, "nfp_cproj_forward_fmt"):     # (absent only from an older library loaded for an A/B run)
         L.nfp_cproj_forward_fmt.argtypes = L.nfp_cproj_forward.argtypes + [i32]
         L.nfp_cproj_backward_fmt.argtypes = L.nfp_cproj_backward.argtypes + [i32]
+    if hasattr(L, "nfp_cpool_wide_forward"):    # (absent only from an older library loaded for an A/B run)
+        L.nfp_cpool_wide_scratch_floats.argtypes = L.nfp_cpool_scratch_floats.argtypes
+        L.nfp_cpool_wide_scratch_floats.restype = i64
+        L.nfp_cpool_wide_forward.argtypes = L.nfp_cpool_forward.argtypes
+        L.nfp_cpool_wide_backward.argtypes = L.nfp_cpool_backward.argtypes
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

@@ -982,6 +982,560 @@ __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
   }
 }
 
+// ---- the wide form: 1 <= N <= 96 maps (nfp_cpool_wide_*) --------------------------------------------------------------------
+// The kernels above keep a lane's weight rows, its T sums or a pixel's c_n in registers: a cost that grows with N and ends at
+// 32 maps.  Here the rows of a block of 64 channels and the chunk's centred maps both sit in LDS, and a lane owns a small
+// tile of outputs: nothing in registers grows with N beyond N' / 16 <= 6 accumulators per owned row (N' = N rounded up to 16).
+// The formulas, the saved state (2N + N^2 + D floats) and the layouts of the partial sums are the ones above.
+//   cpw_moments     cpool_moments with the Gram as 4 x 4 register tiles of (n, n2) pairs, each pair's sum in pixel order
+//   cpw_mu          one workgroup: mu in float64 from the chunks' anchors (eight slices of consecutive chunks, in order)
+//   cpw_sigma       one workgroup per 64 (n, n2) pairs: cpool_finish's join of the chunks in float64, four slices in order
+//   cpw_var         one workgroup per 16 channels: w_d^T Sigma w_d in float64, the rows of Sigma dealt to sixteen slices
+//                   joined in order; inv_d and the running statistics
+//   cpw_fwd         one workgroup per (image, 64 channels): a lane owns 4 channels x 4 pixels of pre-activations, summed
+//                   over n from two ds_read_b128 (the rows transposed, tb[n][d]; the maps sm[n][p]); the sixteen pixel
+//                   slots joined in order
+//   cpw_bwd_part    the same pre-activations over a slice of the batch, ga written to LDS as [p][d]; then T_dn as a second
+//                   product, a lane owning 4 channels x N'/16 maps, summed over the pixels in order (no join)
+//   cpw_bwd_reduce  cpool_bwd_reduce with its tables sized by N
+//   cpw_bwd_maps    one workgroup per 64 pixels of an image: per block of 64 channels the pre-activations as in cpw_fwd, the
+//                   masked G_bd / P to LDS as [d][p]; then sum_d s_d w_dn ga_dp, a lane owning 4 pixels x N'/16 maps, summed
+//                   over d in order; then - k - Q c from LDS
+// Every a_bdp is one chain — the shift, then the maps in order (cw_preact) — in all three kernels: the same bits, the same mask.
+constexpr int kWT = 256;          // threads of every wide kernel but cpw_mu
+constexpr int kWDT = 64;          // channels of D per workgroup / per LDS block
+constexpr int kWRS = kWDT + 4;    // floats between two maps' rows of the transposed table: 16-byte rows, an odd number of slots
+constexpr int kWMaxN = 96;
+constexpr int kWJ = kWMaxN / 16;  // maps per lane of the second products
+constexpr int kWBudget = 16384;   // floats of LDS the chunk's maps and ga may take together (cpw_chunk)
+constexpr int kWMuT = 1024;       // threads of cpw_mu
+
+// tb[n * 68 + dl] = s_d w_dn and sh[dl] of the 64 channels from d0 (zero beyond D and N); cf: 64 floats of scratch.
+// The caller has a barrier before (tb is free) and after.
+__device__ __forceinline__ void cw_rows(const CpK& k, int NP, int d0, float* tb, float* sh, float* cf) {
+  const int tid = threadIdx.x;
+  if (tid < kWDT) {
+    float scale = 0.f, shift = 0.f;
+    if (d0 + tid < k.D) cp_coef(k, d0 + tid, scale, shift);
+    cf[tid] = scale;
+    sh[tid] = shift;
+  }
+  __syncthreads();
+  for (int i = tid; i < kWDT * NP; i += kWT) {
+    const int dl = i / NP, n = i - dl * NP, d = d0 + dl;
+    tb[n * kWRS + dl] = (d < k.D && n < k.N) ? k.w[(long long)d * k.N + n] * cf[dl] : 0.f;
+  }
+}
+
+// a of channels 4 dg .. 4 dg + 3 at the pixels 4 q .. 4 q + 3 of sm (rows rs floats apart): the shift first, then the maps
+// in order
+__device__ __forceinline__ void cw_preact(const float* tb, const float* sh, const float* sm, int rs, int NP, int dg, int q,
+                                          float (&a)[4][4]) {
+  const float4 s4 = *(const float4*)(sh + 4 * dg);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[0][j] = s4.x, a[1][j] = s4.y, a[2][j] = s4.z, a[3][j] = s4.w;
+  const float* tp = tb + 4 * dg;
+  const float* cp = sm + 4 * q;
+#pragma unroll 4
+  for (int n = 0; n < NP; ++n) {
+    const float4 w = *(const float4*)(tp + n * kWRS);
+    const float4 c = *(const float4*)(cp + n * rs);
+    const float wv[4] = {w.x, w.y, w.z, w.w}, cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[i][j] = fmaf(wv[i], cv[j], a[i][j]);
+  }
+}
+
+// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP].  part_w: per chunk [a (N), r (N), Gram (N * N)].
+__global__ void __launch_bounds__(kWT) cpw_moments(CpK k, int NP) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* anchor = sm + NP * k.CHs;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kWT >> 6;
+  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
+  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
+  const int N = k.N;
+  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
+  cp_stage(k, NP, sm, b, p0, ch, false);
+  __syncthreads();
+  for (int n = wv; n < N; n += nw) {
+    float s = 0.f;
+    for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
+    s = cp_wave_sum(s);
+    if (lane == 0) anchor[n] = s / (float)ch;
+  }
+  __syncthreads();
+  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
+    const float an = anchor[n];
+    float s = 0.f;
+    for (int pl = lane; pl < ch; pl += 64) {
+      const float c = sm[n * k.CHs + pl] - an;
+      sm[n * k.CHs + pl] = c;
+      s += c;
+    }
+    s = cp_wave_sum(s);
+    if (lane == 0) {
+      outp[n] = an;
+      outp[N + n] = s / (float)ch;
+    }
+  }
+  __syncthreads();
+  const int nq = (ch + 3) >> 2, NT = NP >> 2;
+  for (int t = tid; t < NT * NT; t += kWT) {
+    const int tn = t / NT, tm = t - tn * NT;
+    const float4* ra = (const float4*)(sm + 4 * tn * k.CHs);
+    const float4* rb = (const float4*)(sm + 4 * tm * k.CHs);
+    const int qs = k.CHs >> 2;
+    float g[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) g[i][jj] = 0.f;
+    for (int q = 0; q < nq; ++q) {
+      float4 x[4], y[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x[i] = ra[i * qs + q], y[i] = rb[i * qs + q];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          float v = g[i][jj];
+          v = fmaf(x[i].x, y[jj].x, v);
+          v = fmaf(x[i].y, y[jj].y, v);
+          v = fmaf(x[i].z, y[jj].z, v);
+          v = fmaf(x[i].w, y[jj].w, v);
+          g[i][jj] = v;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int n = 4 * tn + i, n2 = 4 * tm + jj;
+        if (n < N && n2 < N) outp[2 * N + n * N + n2] = g[i][jj];
+      }
+  }
+}
+
+// pixels of chunk c (chunk j of its image)
+__device__ __forceinline__ double cw_count(const CpK& k, int j) {
+  return j == k.nc - 1 ? (double)(k.P - (k.nc - 1) * k.CH) : (double)k.CH;
+}
+
+// grid = 1, block = 1024: thread (n = tid % 128, slice = tid / 128).  mu64: N doubles.
+__global__ void __launch_bounds__(kWMuT) cpw_mu(CpK k, double* mu64) {
+  __shared__ double red[kWMuT];
+  const int tid = threadIdx.x, N = k.N, K = k.B * k.nc, rec = 2 * N + N * N;
+  const int n = tid & 127, sl = tid >> 7, Kc = (K + 7) / 8;
+  const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
+  double s = 0.0;
+  if (n < N) {
+    int j = c0 % k.nc;
+#pragma unroll 4
+    for (int c = c0; c < c1; ++c) {
+      const float* r = k.part + (long long)c * rec;
+      s += cw_count(k, j) * ((double)r[n] + (double)r[N + n]);
+      if (++j == k.nc) j = 0;
+    }
+  }
+  red[tid] = s;
+  __syncthreads();
+  if (tid < N) {
+    double t = red[tid];
+    for (int i = 1; i < 8; ++i) t += red[i * 128 + tid];
+    t /= k.M;
+    mu64[tid] = t;
+    const float hi = (float)t;
+    k.stats_w[tid] = hi;
+    k.stats_w[N + tid] = (float)(t - (double)hi);
+  }
+}
+
+// grid = ceil(N^2 / 64), block = 256: thread (pair = 64 blockIdx + tid % 64, slice = tid / 64).  sig64: N * N doubles.
+__global__ void __launch_bounds__(kWT) cpw_sigma(CpK k, const double* mu64, double* sig64) {
+  __shared__ double red[kWT];
+  const int tid = threadIdx.x, N = k.N, NN = N * N, K = k.B * k.nc, rec = 2 * N + NN;
+  const int pl = tid & 63, sl = tid >> 6, pr = blockIdx.x * 64 + pl, Kc = (K + 3) / 4;
+  double s = 0.0;
+  if (pr < NN) {
+    const int n = pr / N, n2 = pr - n * N;
+    const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
+    const double m1 = mu64[n], m2 = mu64[n2];
+    int j = c0 % k.nc;
+#pragma unroll 4
+    for (int c = c0; c < c1; ++c) {
+      const float* r = k.part + (long long)c * rec;
+      const double d1 = (double)r[n] - m1, d2 = (double)r[n2] - m2, r1 = r[N + n], r2 = r[N + n2];
+      s += (double)r[2 * N + pr] + cw_count(k, j) * (r1 * d2 + d1 * r2 + d1 * d2);
+      if (++j == k.nc) j = 0;
+    }
+  }
+  red[tid] = s;
+  __syncthreads();
+  if (tid < 64 && pr < NN) {
+    const double t = (((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid]) / k.M;
+    sig64[pr] = t;
+    k.stats_w[2 * N + pr] = (float)t;
+  }
+}
+
+// grid = ceil(D / 16), block = 256: thread (channel = 16 blockIdx + tid % 16, slice = tid / 16) takes the rows
+// n = slice, slice + 16, ... of Sigma.
+__global__ void __launch_bounds__(kWT) cpw_var(CpK k, const double* mu64, const double* sig64) {
+  __shared__ double wl[kWMaxN * 16];   // [n][dl]
+  __shared__ double red[kWT];
+  const int tid = threadIdx.x, N = k.N, dl = tid & 15, sl = tid >> 4, d0 = blockIdx.x * 16;
+  for (int i = tid; i < 16 * N; i += kWT) {
+    const int dd = i / N, n = i - dd * N;
+    wl[n * 16 + dd] = d0 + dd < k.D ? (double)k.w[(long long)(d0 + dd) * N + n] : 0.0;
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int n = sl; n < N; n += 16) {
+    const double* row = sig64 + n * N;
+    double v = 0.0;
+#pragma unroll 4
+    for (int n2 = 0; n2 < N; ++n2) v += row[n2] * wl[n2 * 16 + dl];
+    acc += wl[n * 16 + dl] * v;
+  }
+  red[tid] = acc;
+  __syncthreads();
+  const int d = d0 + tid;
+  if (tid >= 16 || d >= k.D) return;
+  double var = red[tid], mean = 0.0;
+  for (int i = 1; i < 16; ++i) var += red[i * 16 + tid];
+  for (int n = 0; n < N; ++n) mean += wl[n * 16 + tid] * mu64[n];
+  var = var > 0.0 ? var : 0.0;
+  k.stats_w[2 * N + N * N + d] = (float)(1.0 / sqrt(var + k.eps64));
+  if (k.rm_w != nullptr) {
+    k.rm_w[d] = (float)((1.0 - k.mom) * (double)k.rm_w[d] + k.mom * mean);
+    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (k.M / (k.M - 1.0)));
+  }
+}
+
+// grid = (B, ceil(D / 64)), block = 256: thread (dg = tid % 16: four channels, qs = tid / 16: a slot of pixel quads).
+// LDS: tb[NP * 68], sh[64], cf[64], sm[NP * CHs], red[16 * 64].
+__global__ void __launch_bounds__(kWT) cpw_fwd(CpK k, int NP) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* tb = cp_lds;
+  float* sh = tb + NP * kWRS;
+  float* cf = sh + kWDT;
+  float* sm = cf + kWDT;
+  float* red = sm + NP * k.CHs;
+  const int tid = threadIdx.x, dg = tid & 15, qs = tid >> 4;
+  const int b = blockIdx.x, d0 = blockIdx.y * kWDT;
+  cw_rows(k, NP, d0, tb, sh, cf);
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int p0 = 0; p0 < k.P; p0 += k.CH) {
+    const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
+    if (p0 > 0) __syncthreads();   // (the previous chunk has been read)
+    cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+    __syncthreads();
+    for (int q = qs; q < nq; q += 16) {
+      float a[4][4];
+      cw_preact(tb, sh, sm, k.CHs, NP, dg, q, a);
+      const int nv = min(4, ch - 4 * q);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nv) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) s[i] += fmaxf(a[i][j], 0.f);
+        }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[qs * kWDT + 4 * dg + i] = s[i];
+  __syncthreads();
+  const int d = d0 + tid;
+  if (tid < kWDT && d < k.D) {
+    float t = red[tid];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += red[w * kWDT + tid];
+    k.out[(long long)b * k.D + d] = t / (float)k.P;
+  }
+}
+
+// grid = (S, ceil(D / 64)), block = 256: images [s * ipw, (s + 1) * ipw) of the batch.  Thread (dg, qs) as in cpw_fwd for
+// the pre-activations; (dg: four channels, ns = tid / 16: the maps ns, ns + 16, ...) for T.
+// LDS: tb[NP * 68], sh[64], cf[64], gp[64] (G_bd / P of the image), sm[NP * CHs], ga[CHs * 68] ([p][d]).
+// part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
+__global__ void __launch_bounds__(kWT) cpw_bwd_part(CpK k, int NP) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* tb = cp_lds;
+  float* sh = tb + NP * kWRS;
+  float* cf = sh + kWDT;
+  float* gp = cf + kWDT;
+  float* sm = gp + kWDT;
+  float* ga = sm + NP * k.CHs;
+  const int tid = threadIdx.x, dg = tid & 15, qs = tid >> 4, ns = qs, nj = NP >> 4;
+  const int sl = blockIdx.x, d0 = blockIdx.y * kWDT;
+  cw_rows(k, NP, d0, tb, sh, cf);
+  float T[4][kWJ], gbs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < kWJ; ++j) T[i][j] = 0.f;
+  const int b1 = min(k.B, (sl + 1) * k.ipw);
+  for (int b = sl * k.ipw; b < b1; ++b) {
+    // (every thread is behind the barrier that follows the last read of gp)
+    if (tid < kWDT) gp[tid] = d0 + tid < k.D ? k.go[(long long)b * k.D + d0 + tid] / (float)k.P : 0.f;
+    for (int p0 = 0; p0 < k.P; p0 += k.CH) {
+      const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
+      __syncthreads();   // (the previous chunk's sm and ga have been read; the first time: tb is written)
+      cp_stage(k, NP, sm, b, p0, ch, !k.eval);
+      __syncthreads();
+      const float4 g4 = *(const float4*)(gp + 4 * dg);
+      for (int q = qs; q < nq; q += 16) {
+        float a[4][4];
+        cw_preact(tb, sh, sm, k.CHs, NP, dg, q, a);
+        const int nv = min(4, ch - 4 * q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float4 v;
+          v.x = (j < nv && a[0][j] > 0.f) ? g4.x : 0.f;
+          v.y = (j < nv && a[1][j] > 0.f) ? g4.y : 0.f;
+          v.z = (j < nv && a[2][j] > 0.f) ? g4.z : 0.f;
+          v.w = (j < nv && a[3][j] > 0.f) ? g4.w : 0.f;
+          *(float4*)(ga + (4 * q + j) * kWRS + 4 * dg) = v;
+        }
+      }
+      __syncthreads();
+      for (int q = 0; q < nq; ++q) {
+        float4 gv[4], cv[kWJ];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) gv[jj] = *(const float4*)(ga + (4 * q + jj) * kWRS + 4 * dg);
+#pragma unroll
+        for (int j = 0; j < kWJ; ++j)
+          if (j < nj) cv[j] = *(const float4*)(sm + (ns + 16 * j) * k.CHs + 4 * q);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const float g[4] = {gv[jj].x, gv[jj].y, gv[jj].z, gv[jj].w};
+          if (ns == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) gbs[i] += g[i];
+          }
+#pragma unroll
+          for (int j = 0; j < kWJ; ++j)
+            if (j < nj) {
+              const float c = jj == 0 ? cv[j].x : jj == 1 ? cv[j].y : jj == 2 ? cv[j].z : cv[j].w;
+#pragma unroll
+              for (int i = 0; i < 4; ++i) T[i][j] = fmaf(g[i], c, T[i][j]);
+            }
+        }
+      }
+    }
+  }
+  const int N1 = k.N + 1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int d = d0 + 4 * dg + i;
+    if (d >= k.D) continue;
+    float* row = k.part_w + ((long long)sl * k.D + d) * N1;
+#pragma unroll
+    for (int j = 0; j < kWJ; ++j)
+      if (j < nj && ns + 16 * j < k.N) row[ns + 16 * j] = T[i][j];
+    if (ns == 0) row[k.N] = gbs[i];
+  }
+}
+
+// grid = ceil(D / 32), block = 256.  LDS: Tl[32 * (N + 1)], wl[32 * N], sg[N * N].
+// kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
+__global__ void __launch_bounds__(kWT) cpw_bwd_reduce(CpK k) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
+  const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
+  float* Tl = cp_lds;
+  float* wl = Tl + kCpRT * N1;
+  float* sg = wl + kCpRT * N;
+  const long long stride = (long long)k.D * N1;
+  for (int i = tid; i < kCpRT * N1; i += kWT) {
+    const int dl = i / N1;
+    float acc = 0.f;
+    if (d0 + dl < k.D) {
+      const float* src = k.part + (long long)d0 * N1 + i;
+      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[min(sl0 + u, k.S - 1) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (sl0 + u < k.S) acc += v[u];
+      }
+    }
+    Tl[i] = acc;
+  }
+  for (int i = tid; i < kCpRT * N; i += kWT) {
+    const int dl = i / N;
+    wl[i] = d0 + dl < k.D ? k.w[(long long)d0 * N + i] : 0.f;
+  }
+  if (!k.eval)
+    for (int i = tid; i < NN; i += kWT) sg[i] = k.stats[2 * N + i];
+  __syncthreads();
+  if (tid < kCpRT) {
+    const int d = d0 + tid;
+    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
+    if (d < k.D) {
+      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
+      c1 = k.gamma[d] * inv;
+      const float gb = Tl[tid * N1 + N];
+      float dot = 0.f;
+      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * N + n], Tl[tid * N1 + n], dot);
+      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
+      if (!k.eval) {
+        e = c1 * (gb / (float)k.M);
+        f = c1 * (gg * inv / (float)k.M);
+      }
+      if (k.gg != nullptr) k.gg[d] = gg;
+      if (k.gb != nullptr) k.gb[d] = gb;
+    }
+    el[tid] = e;
+    fl[tid] = f;
+    ggl[tid] = gg;
+    c1l[tid] = c1;
+    invl[tid] = inv;
+  }
+  __syncthreads();
+  if (k.gw != nullptr)
+    for (int i = tid; i < kCpRT * N; i += kWT) {
+      const int dl = i / N, n = i - dl * N, d = d0 + dl;
+      if (d >= k.D) continue;
+      float t = Tl[dl * N1 + n];
+      if (!k.eval) {
+        float sw = 0.f;
+        for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * N + n2], sw);
+        t -= ggl[dl] * invl[dl] * sw;
+      }
+      k.gw[(long long)d * N + n] = c1l[dl] * t;
+    }
+  if (k.eval || k.kq_w == nullptr) return;
+  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
+  for (int i = tid; i < N + NN; i += kWT) {
+    float s = 0.f;
+    if (i < N) {
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * N + i], el[dl], s);
+    } else {
+      const int n = (i - N) / N, n2 = (i - N) - n * N;
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * N + n], wl[dl * N + n2], s);
+    }
+    kq[i] = s;
+  }
+}
+
+// grid = B * ceil(P / 64), block = 256: the 64 pixels from pt * 64 of image b.  Thread (dg = tid % 16, q = tid / 16) for
+// the pre-activations of a block of 64 channels; (pq = tid % 16: four pixels, ns = tid / 16: the maps ns, ns + 16, ...) for
+// the sums over d.
+// LDS: cl[NP * 68] (c_n of the pixels), sh[64], cf[64], gp[64], tb[NP * 68], tt[64 * 68] (the masked G_bd / P, [d][p]);
+// after the last block tb and tt together hold k and Q (N + N * N <= 68 N' + 4352 up to 107 maps).
+__global__ void __launch_bounds__(kWT) cpw_bwd_maps(CpK k, int NP, int npt) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* cl = cp_lds;
+  float* sh = cl + NP * kWRS;
+  float* cf = sh + kWDT;
+  float* gp = cf + kWDT;
+  float* tb = gp + kWDT;
+  float* tt = tb + NP * kWRS;
+  float* kql = tb;
+  const int tid = threadIdx.x, dg = tid & 15, q = tid >> 4, pq = dg, ns = q, nj = NP >> 4;
+  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p0 = pt * 64, N = k.N, NN = N * N;
+  const int npx = min(64, k.P - p0);
+  const long long base = (long long)b * N * k.P + p0;
+  for (int i = tid; i < NP * 64; i += kWT) {
+    const int n = i >> 6, pl = i & 63;
+    float v = 0.f;
+    if (n < N && pl < npx) {
+      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
+      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
+    }
+    cl[n * kWRS + pl] = v;
+  }
+  float g[4][kWJ];   // [pixel][map]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < kWJ; ++j) g[i][j] = 0.f;
+  for (int dB = 0; dB < k.D; dB += kWDT) {
+    __syncthreads();   // (the previous block has been read; the first time: cl is written)
+    if (tid < kWDT) gp[tid] = dB + tid < k.D ? k.go[(long long)b * k.D + dB + tid] / (float)k.P : 0.f;
+    cw_rows(k, NP, dB, tb, sh, cf);
+    __syncthreads();
+    {
+      float a[4][4];
+      cw_preact(tb, sh, cl, kWRS, NP, dg, q, a);
+      const float4 g4 = *(const float4*)(gp + 4 * dg);
+      const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float4 v;
+        v.x = a[i][0] > 0.f ? gv[i] : 0.f;
+        v.y = a[i][1] > 0.f ? gv[i] : 0.f;
+        v.z = a[i][2] > 0.f ? gv[i] : 0.f;
+        v.w = a[i][3] > 0.f ? gv[i] : 0.f;
+        *(float4*)(tt + (4 * dg + i) * kWRS + 4 * q) = v;
+      }
+    }
+    __syncthreads();
+    for (int d4 = 0; d4 < kWDT; d4 += 4) {
+      float4 tv[4], wv[kWJ];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) tv[i] = *(const float4*)(tt + (d4 + i) * kWRS + 4 * pq);
+#pragma unroll
+      for (int j = 0; j < kWJ; ++j)
+        if (j < nj) wv[j] = *(const float4*)(tb + (ns + 16 * j) * kWRS + d4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float t[4] = {tv[i].x, tv[i].y, tv[i].z, tv[i].w};
+#pragma unroll
+        for (int j = 0; j < kWJ; ++j)
+          if (j < nj) {
+            const float w = i == 0 ? wv[j].x : i == 1 ? wv[j].y : i == 2 ? wv[j].z : wv[j].w;
+#pragma unroll
+            for (int px = 0; px < 4; ++px) g[px][j] = fmaf(w, t[px], g[px][j]);
+          }
+      }
+    }
+  }
+  if (!k.eval) {
+    __syncthreads();   // (tb and tt have been read: k and Q take their place)
+    for (int i = tid; i < N + NN; i += kWT) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
+      kql[i] = s;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < kWJ; ++j) {
+    const int n = ns + 16 * j;
+    if (j >= nj || n >= N) continue;
+    float v[4] = {g[0][j], g[1][j], g[2][j], g[3][j]};
+    if (!k.eval) {
+      float qc[4] = {kql[n], kql[n], kql[n], kql[n]};
+      for (int n2 = 0; n2 < N; ++n2) {
+        const float qv = kql[N + n * N + n2];
+        const float4 c = *(const float4*)(cl + n2 * kWRS + 4 * pq);
+        qc[0] = fmaf(qv, c.x, qc[0]);
+        qc[1] = fmaf(qv, c.y, qc[1]);
+        qc[2] = fmaf(qv, c.z, qc[2]);
+        qc[3] = fmaf(qv, c.w, qc[3]);
+      }
+#pragma unroll
+      for (int px = 0; px < 4; ++px) v[px] -= qc[px];
+    }
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      if (4 * pq + px >= npx) continue;
+      const long long o = base + (long long)n * k.P + 4 * pq + px;
+      if (k.bf16)
+        ((uint16_t*)k.gm)[o] = f32_to_bf16(v[px]);
+      else
+        ((float*)k.gm)[o] = v[px];
+    }
+  }
+}
+
 }  // namespace
 }  // namespace nfp
 
@@ -1014,16 +1568,35 @@ int cpool_slices(int B, int D) {
   return (B + ipw - 1) / ipw;
 }
 
-int cpool_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
+// ---- the wide form's sizes ----
+int cpw_np(int N) { return (N + 15) & ~15; }
+// pixels per chunk: the whole image where its maps and ga fit kWBudget floats of LDS beside the rows, else a multiple of 64
+// (64 at 64 maps and more, 128 at 32 and 48, 192 at 16)
+int cpw_chunk(int NP, long long P) {
+  return (int)std::min<long long>(P, std::max(64, (nfp::kWBudget / (NP + nfp::kWRS)) & ~63));
+}
+int cpw_tiles(int D) { return (D + nfp::kWDT - 1) / nfp::kWDT; }
+// images per workgroup of cpw_bwd_part: about 512 workgroups, at most one per image
+int cpw_ipw(int B, int D) {
+  const int want = std::min(B, std::max(1, 512 / cpw_tiles(D)));
+  return (B + want - 1) / want;
+}
+int cpw_slices(int B, int D) {
+  const int ipw = cpw_ipw(B, D);
+  return (B + ipw - 1) / ipw;
+}
+
+int cpool_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training, bool wide = false) {
+  const int maxN = wide ? nfp::kWMaxN : nfp::kCpMaxN;
   if (B < 0 || N < 1 || P < 1 || D < 1)
     return fail(NFP_E_INVALID, "%s: B = %d, N = %d, P = %lld, D = %d", what, B, N, (long long)P, D);
   if (dtype != NFP_F32 && dtype != NFP_BF16) return fail(NFP_E_INVALID, "%s: unknown dtype %d", what, dtype);
-  if (N > nfp::kCpMaxN) return fail(NFP_E_UNSUPPORTED, "%s: N = %d maps (more than %d) has no kernel", what, N, nfp::kCpMaxN);
+  if (N > maxN) return fail(NFP_E_UNSUPPORTED, "%s: N = %d maps (more than %d) has no kernel", what, N, maxN);
   if ((long long)N * P >= (1LL << 31))
     return fail(NFP_E_UNSUPPORTED, "%s: an image of N * P = %lld map elements (2^31 and more) has no kernel", what,
                 (long long)N * P);
   if (D > (1 << 22)) return fail(NFP_E_UNSUPPORTED, "%s: D = %d (more than 2^22) has no kernel", what, D);
-  const long long nc = (P + cpool_chunk(cpool_np(N), P) - 1) / cpool_chunk(cpool_np(N), P);
+  const long long ch = wide ? cpw_chunk(cpw_np(N), P) : cpool_chunk(cpool_np(N), P), nc = (P + ch - 1) / ch;
   if ((long long)B * std::max<long long>(nc, (P + 63) / 64) >= (1LL << 31))
     return fail(NFP_E_UNSUPPORTED, "%s: B = %d images of P = %lld pixels make 2^31 workgroups and more", what, B, (long long)P);
   if (training && B > 0 && (long long)B * P < 2)
@@ -1083,6 +1656,15 @@ int64_t cpool_fwd_scratch(int32_t B, int32_t N, int64_t P) {
 }
 int64_t cpool_bwd_scratch(int32_t B, int32_t N, int32_t D) {
   return (int64_t)cpool_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
+}
+// the wide forward: the chunks' records, then (from an even float on) mu and Sigma as doubles
+int64_t cpw_fwd_records(int32_t B, int32_t N, int64_t P) {
+  const int ch = cpw_chunk(cpw_np(N), P);
+  return ((int64_t)B * ((P + ch - 1) / ch) * (2 * N + N * N) + 1) & ~(int64_t)1;
+}
+int64_t cpw_fwd_scratch(int32_t B, int32_t N, int64_t P) { return cpw_fwd_records(B, N, P) + 2 * ((int64_t)N + (int64_t)N * N); }
+int64_t cpw_bwd_scratch(int32_t B, int32_t N, int32_t D) {
+  return (int64_t)cpw_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
 }
 
 // ---- cproj ----
@@ -1177,7 +1759,8 @@ int cproj_layout(const char* what, int32_t layout) {
 // What an extern "C" entry asks for.  kind: the pooled tail (nfp_cpool_*: out [B,D] float32, always with the ReLU) or the
 // projection with the map kept (nfp_cproj_*: out / grad_out [B,D,P] in the maps' dtype, `relu` and `layout` the caller's).
 // A forward fills rm_w .. saved_w, a backward rm .. gb; the other direction's fields stay zero.
-enum CpKind { kCpPool, kCpProj };
+// kCpWide: the pooled tail through the wide kernels (nfp_cpool_wide_*: up to 96 maps).
+enum CpKind { kCpPool, kCpProj, kCpWide };
 struct CpCall {
   const char* what;   // the entry's name, at the head of every message
   CpKind kind;
@@ -1206,28 +1789,39 @@ struct CpCall {
 int cp_check(const CpCall& c, const void* io) {
   if (c.kind == kCpProj)
     if (int rc = cproj_layout(c.what, c.layout)) return rc;
-  if (int rc = (c.kind == kCpProj ? cproj_args : cpool_args)(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training)) return rc;
+  if (int rc = c.kind == kCpProj ? cproj_args(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training)
+                                 : cpool_args(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training, c.kind == kCpWide))
+    return rc;
   if (!c.w || !c.gamma || !c.beta || (c.B > 0 && (!c.maps || !io))) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
   return NFP_OK;
 }
 int cp_check_scratch(const CpCall& c, int backward) {
-  const bool proj = c.kind == kCpProj;
-  const int64_t need = (proj ? nfp_cproj_scratch_floats : nfp_cpool_scratch_floats)(c.B, c.N, c.P, c.D, backward);
+  const auto query = c.kind == kCpProj ? nfp_cproj_scratch_floats
+                     : c.kind == kCpWide ? nfp_cpool_wide_scratch_floats : nfp_cpool_scratch_floats;
+  const char* name = c.kind == kCpProj ? "nfp_cproj_scratch_floats"
+                     : c.kind == kCpWide ? "nfp_cpool_wide_scratch_floats" : "nfp_cpool_scratch_floats";
+  const int64_t need = query(c.B, c.N, c.P, c.D, backward);
   if (c.B > 0 && (c.scratch == nullptr || c.scratch_floats < need))
     return fail(NFP_E_INVALID, "%s: scratch holds %lld floats, %s is %lld", c.what, (long long)(c.scratch ? c.scratch_floats : 0),
-                proj ? "nfp_cproj_scratch_floats" : "nfp_cpool_scratch_floats", (long long)need);
+                name, (long long)need);
   return NFP_OK;
 }
 nfp::CpK cp_k(const CpCall& c) {
   nfp::CpK k = cpool_k(c.B, c.N, c.P, c.D, c.dtype, c.training);
   k.maps = c.maps, k.w = c.w, k.gamma = c.gamma, k.beta = c.beta;
   k.eps = (float)c.eps, k.eps64 = c.eps;
+  if (c.kind == kCpWide) {   // (the wide kernels' own chunks and slices)
+    k.CH = cpw_chunk(cpw_np(c.N), c.P), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
+    k.ipw = cpw_ipw(std::max(c.B, 1), c.D), k.S = cpw_slices(std::max(c.B, 1), c.D);
+  }
   return k;
 }
 void cp_variant(const CpCall& c, const char* dir) {
   const char *dt = c.dtype == NFP_BF16 ? "bf16" : "f32", *mode = c.training ? "train" : "eval";
   if (c.kind == kCpPool)
     snprintf(g_variant, sizeof(g_variant), "cpool_%s<%s,%s>", dir, dt, mode);
+  else if (c.kind == kCpWide)
+    snprintf(g_variant, sizeof(g_variant), "cpool_wide_%s<%s,%s,n%d>", dir, dt, mode, cpw_np(c.N));
   else
     snprintf(g_variant, sizeof(g_variant), "cproj_%s<%s,%s,%s%s>", dir, dt, mode, c.relu ? "relu" : "lin",
              c.layout == NFP_ACT_NHWC ? ",nhwc" : "");
@@ -1240,6 +1834,40 @@ int launch_stats(const nfp::CpK& k, int NP, hipStream_t st) {
     rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st,
                 k);
   return rc;
+}
+
+// ---- the wide kernels' launches ----
+// cpw_moments, cpw_mu, cpw_sigma, cpw_var: the train-mode statistics; scratch as cpw_fwd_scratch lays it out
+int cpw_launch_stats(const nfp::CpK& k, int NP, float* scratch, hipStream_t st) {
+  double* mu64 = (double*)(scratch + cpw_fwd_records(k.B, k.N, k.P));
+  double* sig64 = mu64 + k.N;
+  const int NN = k.N * k.N;
+  int rc = launch("cpw_moments", nfp::cpw_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kWT),
+                  ((size_t)NP * k.CHs + NP) * sizeof(float), st, k, NP);
+  if (rc == NFP_OK) rc = launch("cpw_mu", nfp::cpw_mu, dim3(1), dim3(nfp::kWMuT), 0, st, k, mu64);
+  if (rc == NFP_OK)
+    rc = launch("cpw_sigma", nfp::cpw_sigma, dim3((unsigned)((NN + 63) / 64)), dim3(nfp::kWT), 0, st, k, (const double*)mu64, sig64);
+  if (rc == NFP_OK)
+    rc = launch("cpw_var", nfp::cpw_var, dim3((unsigned)((k.D + 15) / 16)), dim3(nfp::kWT), 0, st, k, (const double*)mu64,
+                (const double*)sig64);
+  return rc;
+}
+int cpw_launch_fwd(const nfp::CpK& k, int NP, hipStream_t st) {
+  const size_t lds = ((size_t)NP * nfp::kWRS + 2 * nfp::kWDT + (size_t)NP * k.CHs + 16 * nfp::kWDT) * sizeof(float);
+  return launch("cpw_fwd", nfp::cpw_fwd, dim3((unsigned)k.B, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+}
+int cpw_launch_part(const nfp::CpK& k, int NP, hipStream_t st) {
+  const size_t lds = ((size_t)NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)(NP + nfp::kWRS) * k.CHs) * sizeof(float);
+  return launch("cpw_bwd_part", nfp::cpw_bwd_part, dim3((unsigned)k.S, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+}
+int cpw_launch_reduce(const nfp::CpK& k, hipStream_t st) {
+  const size_t lds = ((size_t)nfp::kCpRT * (2 * k.N + 1) + (size_t)k.N * k.N) * sizeof(float);
+  return launch("cpw_bwd_reduce", nfp::cpw_bwd_reduce, dim3((unsigned)k.ntr), dim3(nfp::kWT), lds, st, k);
+}
+int cpw_launch_maps(const nfp::CpK& k, int NP, hipStream_t st) {
+  const int npt = (k.P + 63) / 64;
+  const size_t lds = ((size_t)2 * NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)nfp::kWDT * nfp::kWRS) * sizeof(float);
+  return launch("cpw_bwd_maps", nfp::cpw_bwd_maps, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kWT), lds, st, k, NP, npt);
 }
 
 int cp_forward(const CpCall& c) {
@@ -1257,7 +1885,8 @@ int cp_forward(const CpCall& c) {
   }
   if (c.B == 0) return NFP_OK;
   nfp::CpK k = cp_k(c);
-  const int NP = cpool_np(c.N);
+  const bool wide = c.kind == kCpWide;
+  const int NP = wide ? cpw_np(c.N) : cpool_np(c.N);
   k.mom = c.momentum;
   if (proj)
     k.outv = c.out;
@@ -1268,13 +1897,14 @@ int cp_forward(const CpCall& c) {
   int rc = NFP_OK;
   if (c.training) {
     k.part_w = c.scratch, k.part = c.scratch, k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
-    rc = launch_stats(k, NP, st);
+    rc = wide ? cpw_launch_stats(k, NP, c.scratch, st) : launch_stats(k, NP, st);
   } else {
     k.rm = c.rm_w, k.rv = c.rv_w;
   }
   if (proj)   // (cproj_fwd's own chunks)
     k.CH = cproj_fwd_chunk(NP, c.B, c.P, c.D), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
-  if (rc == NFP_OK) rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LFwd>(NP, k, st);
+  if (rc == NFP_OK)
+    rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_fwd(k, NP, st) : cpool_by_np<LFwd>(NP, k, st);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
@@ -1295,7 +1925,8 @@ int cp_backward(const CpCall& c) {
     if (int rc = cp_check_scratch(c, 1)) return rc;
   if (c.B == 0) return NFP_OK;
   nfp::CpK k = cp_k(c);
-  const int NP = cpool_np(c.N);
+  const bool wide = c.kind == kCpWide;
+  const int NP = wide ? cpw_np(c.N) : cpool_np(c.N);
   if (proj) {
     k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                   // cproj_bwd_part's passes
     k.ipw = cproj_upw(c.B, c.P, c.D), k.S = cproj_slices(c.B, c.P, c.D);     // ... and how many of them a workgroup takes
@@ -1313,12 +1944,13 @@ int cp_backward(const CpCall& c) {
   if (sums) {
     k.part_w = c.scratch, k.part = c.scratch;
     k.kq_w = c.scratch + (int64_t)k.S * c.D * (c.N + 1), k.kq = k.kq_w;
-    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LPart>(NP, k, st);
+    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_part(k, NP, st) : cpool_by_np<LPart>(NP, k, st);
     if (rc == NFP_OK)
-      rc = proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
+      rc = wide ? cpw_launch_reduce(k, st) : proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
                 : launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
   }
-  if (rc == NFP_OK && c.gm != nullptr) rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LMaps>(NP, k, st);
+  if (rc == NFP_OK && c.gm != nullptr)
+    rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_maps(k, NP, st) : cpool_by_np<LMaps>(NP, k, st);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
@@ -1352,12 +1984,17 @@ int64_t nfp_cpool_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int
   return std::max<int64_t>(1, backward ? cpool_bwd_scratch(B, N, D) : cpool_fwd_scratch(B, N, P));
 }
 
+int64_t nfp_cpool_wide_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
+  if (B < 1 || N < 1 || N > nfp::kWMaxN || P < 1 || D < 1) return 1;
+  return std::max<int64_t>(1, backward ? cpw_bwd_scratch(B, N, D) : cpw_fwd_scratch(B, N, P));
+}
+
 int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
   if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
   return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
 }
 
-// The six entries: a CpCall of the leading fields, in order, and cp_forward / cp_backward with the direction's own.
+// The eight entries: a CpCall of the leading fields, in order, and cp_forward / cp_backward with the direction's own.
 
 int nfp_cpool_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
                       const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -1374,6 +2011,25 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream) {
   const CpCall c{"nfp_cpool_backward", kCpPool, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
+}
+
+int nfp_cpool_wide_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                           const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                           double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
+                           int64_t scratch_floats, void* hip_stream) {
+  const CpCall c{"nfp_cpool_wide_forward", kCpWide, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
+                 saved_floats, scratch, scratch_floats, hip_stream};
+  return cp_forward(c, running_mean, running_var, momentum, out, saved);
+}
+
+int nfp_cpool_wide_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
+                            const float* w, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, double eps, const float* saved, int64_t saved_floats,
+                            const float* grad_out, void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta,
+                            float* scratch, int64_t scratch_floats, void* hip_stream) {
+  const CpCall c{"nfp_cpool_wide_backward", kCpWide, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
                  saved_floats, scratch, scratch_floats, hip_stream};
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }

@@ -1070,8 +1070,15 @@ def nfp_valid(x, cfg):
 # ---- with the map kept — nfp_cproj_* (the cproj kernels): one call path, one autograd node and one set of checks for both
 CPOOL_MAX_MAPS = 32     # csrc/nfp_cpool.hip: kCpMaxN (a lane keeps two weight rows in registers)
 CPOOL_ROUTED_MAPS = 8   # what cpool_hip_serves takes by default: the maps counts that measured faster than the composition
-# the two kinds' library calls: (forward, backward, the scratch length query)
+CPOOL_WIDE_MAX_MAPS = 96    # csrc/nfp_cpool.hip: kWMaxN (the cpw kernels: rows and maps in LDS, a tile of outputs per lane)
+# What cpool_wide_serves takes by default: the (maps, B * P) classes scripts/bench_heads.py measured faster than the
+# composition beyond the run-to-run spread on an MI355X ("The wide form") — none: [64,48,7,7] 0.35x, [256,48,7,7]
+# 0.60x, [256,80,7,7] 0.42x, [64,48,14,14] 0.49x (-> 512, train-mode forward + backward, graph-timed), so 33 to 96 maps reach
+# the wide kernels with NFP_CPOOL_TORCH=0 only.
+CPOOL_WIDE_ROUTED_CLASSES = ()      # ((min maps, max maps, min B * P), ...)
+# the three kinds' library calls: (forward, backward, the scratch length query)
 _CP_ENTRIES = {"pool": ("nfp_cpool_forward", "nfp_cpool_backward", "nfp_cpool_scratch_floats"),
+               "wide": ("nfp_cpool_wide_forward", "nfp_cpool_wide_backward", "nfp_cpool_wide_scratch_floats"),
                "proj": ("nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt", "nfp_cproj_scratch_floats")}
 
 
@@ -1128,19 +1135,21 @@ def _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats
     return gm, gw, gg, gb
 
 
-def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps):
+def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, kind="pool"):
     """(out [B,D] float32, saved) from nfp_cpool_forward on dense CUDA maps [B,N,...] and float32 w [D,N], gamma, beta [D].
     use_batch_stats: train-mode statistics, the running ones (float32 [D], or both None) updated by the same call; `saved`
-    is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics)."""
+    is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics).
+    kind="wide": nfp_cpool_wide_forward (up to 96 maps), the same arguments and `saved`."""
     with _on_device(maps.device):
         out = torch.empty(maps.shape[0], w.shape[0], dtype=torch.float32, device=maps.device)
-    return out, _cp_forward_call("pool", out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps)
+    return out, _cp_forward_call(kind, out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps)
 
 
-def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want):
+def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want, kind="pool"):
     """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cpool_backward — None for each
-    gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
-    return _cp_backward_call("pool", maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out.contiguous().float(), want)
+    gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written.  kind="wide":
+    nfp_cpool_wide_backward, on the `saved` of a wide forward."""
+    return _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out.contiguous().float(), want)
 
 
 class _CpHip(torch.autograd.Function):
@@ -1163,26 +1172,28 @@ class _CpHip(torch.autograd.Function):
 
 
 class _CPoolHip(_CpHip):
-    """out [B,D] float32."""
+    """out [B,D] float32; kind: "pool" or "wide"."""
 
     @staticmethod
-    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, need_grad):
-        out, saved = cpool_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps)
+    def forward(ctx, maps, w, gamma, beta, stats, use_batch_stats, momentum, eps, need_grad, kind):
+        out, saved = cpool_forward_call(maps, w, gamma, beta, stats[0], stats[1], use_batch_stats, momentum, eps, kind)
         if need_grad:
             _CpHip._save(ctx, maps, w, gamma, beta, saved, stats, use_batch_stats, eps)
+            ctx.kind = kind
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        return (*cpool_backward_call(*_CpHip._state(ctx), grad_out, ctx.needs_input_grad[:4]), None, None, None, None, None)
+        grads = cpool_backward_call(*_CpHip._state(ctx), grad_out, ctx.needs_input_grad[:4], ctx.kind)
+        return (*grads, None, None, None, None, None, None)
 
 
-def _cp_can_serve(maps, gamma, beta, momentum):
-    """What both kinds' kernels can serve: dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] under an affine BatchNorm
-    with a float momentum, outside torch.compile and torch.autocast."""
+def _cp_can_serve(maps, gamma, beta, momentum, max_maps=CPOOL_MAX_MAPS):
+    """What the kernels of every kind can serve: dense CUDA float32 / bfloat16 maps [B >= 1, N <= max_maps, ...] under an affine
+    BatchNorm with a float momentum, outside torch.compile and torch.autocast."""
     return (not torch.compiler.is_compiling() and maps.is_cuda and not torch.is_autocast_enabled("cuda")
-            and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= CPOOL_MAX_MAPS
+            and maps.dtype in _DTYPES and maps.is_contiguous() and maps.shape[0] > 0 and 1 <= maps.shape[1] <= max_maps
             and maps.numel() > 0 and gamma is not None and beta is not None and isinstance(momentum, float))
 
 
@@ -1229,12 +1240,34 @@ def cpool_hip_serves(maps, gamma, beta, momentum):
     """The HIP tail can serve dense CUDA float32 / bfloat16 maps [B >= 1, N <= 32, ...] under an affine BatchNorm with a float
     momentum, outside torch.compile and torch.autocast.  Of those it takes, by default, the ones with at most 8 maps: with 32
     maps it measured slower than the torch composition ([256,32,7,7] -> 512: 327 against 185 us graph-timed), and
-    16 and 24 maps run the same register-heavy forms and were not measured.  NFP_CPOOL_TORCH (read at call time) is the A/B
+    16 and 24 maps run the same register-heavy forms (measured since: 161 against 157 and 248 against 167 us).  NFP_CPOOL_TORCH (read at call time) is the A/B
     switch: "1" the torch composition everywhere, "0" the HIP tail wherever it can serve."""
     env = os.environ.get("NFP_CPOOL_TORCH")
     if env == "1":
         return False
     return _cp_can_serve(maps, gamma, beta, momentum) and (env == "0" or maps.shape[1] <= CPOOL_ROUTED_MAPS)
+
+
+def cpool_wide_serves(maps, gamma, beta, momentum):
+    """The wide HIP tail (nfp_cpool_wide_*) can serve what cpool_hip_serves describes with up to 96 maps.  It is asked after
+    cpool_hip_serves has declined, and takes by default the classes of CPOOL_WIDE_ROUTED_CLASSES (none so far), so 33 to 96
+    maps run it under NFP_CPOOL_TORCH=0 and the composition otherwise.  NFP_CPOOL_WIDE=1 (read at call time, for
+    measurement): 9 to 32 maps run the wide form too, wherever the tail is served — it is then asked first."""
+    env = os.environ.get("NFP_CPOOL_TORCH")
+    if env == "1" or not _cp_can_serve(maps, gamma, beta, momentum, CPOOL_WIDE_MAX_MAPS):
+        return False
+    N, M = maps.shape[1], maps.numel() // maps.shape[1]
+    return env == "0" or any(lo <= N <= hi and M >= m for lo, hi, m in CPOOL_WIDE_ROUTED_CLASSES)
+
+
+def _cpool_kind(maps, gamma, beta, momentum):
+    """"pool", "wide" or None (the composition) for one call of the tail."""
+    hip = cpool_hip_serves(maps, gamma, beta, momentum)
+    if hip and not (os.environ.get("NFP_CPOOL_WIDE") == "1" and maps.shape[1] > CPOOL_ROUTED_MAPS):
+        return "pool"
+    if hip or cpool_wide_serves(maps, gamma, beta, momentum):
+        return "wide"
+    return None
 
 
 def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5):
@@ -1244,15 +1277,17 @@ def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_v
     F.batch_norm takes; None, a cumulative average, is the caller's to resolve.  use_batch_stats=False reads the running
     statistics instead (eval).  Where `cpool_hip_serves`, three HIP launches forward and at most three backward that never form
     the [B,D,H,W] activation (include/nfp.h: nfp_cpool_*; float32 arithmetic, the result cast once to the maps' dtype);
-    everything else — by default also more than 8 maps, see cpool_hip_serves — is `_host.compress_pool_host`."""
+    where it does not and `cpool_wide_serves` (33 to 96 maps under NFP_CPOOL_TORCH=0), the wide kernels: five launches
+    forward, at most three backward (nfp_cpool_wide_*); everything else — by default also more than 8 maps, see
+    cpool_hip_serves — is `_host.compress_pool_host`."""
     _cp_check_args("nfp_compress_pool", maps, weight, use_batch_stats, running_mean, running_var)
-    prepared = cpool_hip_serves(maps, gamma, beta, momentum) and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var,
-                                                                             use_batch_stats)
+    kind = _cpool_kind(maps, gamma, beta, momentum)
+    prepared = kind and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats)
     if not prepared:
         return compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps)
     need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (maps, weight, gamma, beta))
     out = _CPoolHip.apply(maps, *prepared, (running_mean, running_var), bool(use_batch_stats), float(momentum), float(eps),
-                          need_grad)
+                          need_grad, kind)
     return out if out.dtype == maps.dtype else out.to(maps.dtype)
 
 
