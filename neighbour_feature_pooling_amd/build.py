@@ -10,8 +10,12 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libnfp_hip.so")
-# the library's translation units, compiled in parallel: every csrc/*.hip (tests/test_sap_host.py holds the list to that)
-SOURCES = ["nfp_hip.hip", "nfp_tile.hip", "nfp_bias.hip", "nfp_attpool.hip", "nfp_valid.hip", "nfp_cpool.hip"]
+# the library's translation units, compiled in parallel: every csrc/*.hip (tests/test_sap_host.py holds the list to that),
+# longest compile first, so that the short ones fill the workers the long ones leave
+SOURCES = ["nfp_table_bwd.hip", "nfp_generic.hip", "nfp_tile_bwd.hip", "nfp_table_fwd.hip", "nfp_tile_fwd.hip",
+           "nfp_cpool.hip", "nfp_valid.hip", "nfp_bias.hip", "nfp_hip.hip", "nfp_attpool.hip"]
+# compile jobs per library: build_hip() runs the product and the LDS-poison build side by side, together 16
+MAX_JOBS = 8
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,
 # which costs more issue time than it saves at two wavefronts per SIMD (headline forward 5.31 -> 5.10 us,
 # [256,512,7,7] forward 7.8 -> 7.5 us; scripts/ab_flags.py)
@@ -48,7 +52,7 @@ def compile_hip(out_lib, extra_flags=(), verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
             return obj
-        with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+        with cf.ThreadPoolExecutor(max_workers=min(MAX_JOBS, len(SOURCES))) as ex:
             objs = list(ex.map(one, SOURCES))
         cmd = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc", "-o", out_lib] + objs
         if verbose:

@@ -82,6 +82,10 @@ __host__ __device__ inline uint32_t band_head_chunk(int Cc, int lg, int R, int T
 __host__ __device__ inline uint32_t bwd_head_geom(int P, int mode, int unit, int G, int T) {
   return (uint32_t)P | ((uint32_t)mode << 10) | ((uint32_t)(unit != 0) << 12) | ((uint32_t)G << 13) | ((uint32_t)(T >> 6) << 22);
 }
+#ifndef NFP_BWD_THREADS
+#define NFP_BWD_THREADS 512
+#endif
+constexpr int kBwdThreads = NFP_BWD_THREADS;  // backward keeps (2R+1)^2 weights + offsets + staged x in registers
 constexpr int kTicketWords = 4096;              // (batches beyond it: no counters — make_kp)
 constexpr int kTicketBytes = kTicketWords * 4;
 

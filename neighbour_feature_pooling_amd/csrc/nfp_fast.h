@@ -34,16 +34,13 @@ namespace nfp {
 #ifndef NFP_RB
 #define NFP_RB 3
 #endif
-#ifndef NFP_BWD_THREADS
-#define NFP_BWD_THREADS 512
-#endif
 #ifndef NFP_UNROLL_B
 #define NFP_UNROLL_B 1
 #endif
 constexpr int kRB = NFP_RB;  // NCHW staging: 4x4 blocks per thread per chunk
 constexpr int kRN = 4;    // channels-last staging: slots per thread per chunk
 constexpr int kRS = 6;    // NCHW staging by pixel rows (StagedRows): slots per thread per chunk
-constexpr int kBwdThreads = NFP_BWD_THREADS;  // backward keeps (2R+1)^2 weights + offsets + staged x in registers
+// (kBwdThreads, the backward's workgroup size and the table kernels' pixel bound: nfp_common.h — the dispatcher reads it too)
 
 // exact i / d for 0 <= i, quotient < 2048 (d >= 1): float multiply instead of the ~20-instruction
 // integer division sequence
@@ -669,7 +666,7 @@ struct L_BRQ {
 // for every p, and every grad_x[b,c,p] also receives ggap[b,c]/P (adjoint of the two means).
 // POOL = kPoolGap (nfp_common.h): the head's pass — grad_out IS a map, read as the plain backward reads it, and every
 // grad_x[b,c,p] also receives ggap[b,c]/P where the pooled mode adds it.
-// ROWS: the x chunk staged by pixel rows (StagedRows above) instead of 4 x 4 blocks; the launcher's choice (nfp_hip.hip).
+// ROWS: the x chunk staged by pixel rows (StagedRows above) instead of 4 x 4 blocks; the launcher's choice (nfp_table_bwd.hip).
 // MF: float32 grad_out / out beside bf16 x / grad_x (nfp_desc.map_f32: the torch.autocast call); vector phase B only.
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, int GEMM = 0,   // GEMM: 0 vector phase B, 1 / 2 matrix cores
           bool ROWS = false, bool MF = false>

@@ -30,7 +30,7 @@ template <> struct NCoef<NFP_GFC> { static constexpr int v = 3; };
 template <> struct NCoef<NFP_SMITH> { static constexpr int v = 3; };
 template <> struct NCoef<NFP_PEARSON> { static constexpr int v = 5; };
 
-// LDS word offsets of the tables (host: launch_bwd_gather in nfp_hip.hip)
+// LDS word offsets of the tables (host: launch_bwd_gather in nfp_generic.hip)
 struct GatherLds {
   int ON;          // O * N pairs
   int cf;          // float [NC][ON]  coefficient k of pair j = n*O + o at cf + k*ON + j

@@ -2,13 +2,10 @@
 //
 // Stands in for models/pooling/nfp.py::NFPPooling.forward (nfp.py:132-134) and its
 // autograd backward.  gfx950 only; no CPU path lives here — the library fails
-// loudly (NFP_E_HIP / NFP_E_UNSUPPORTED) rather than fall back.
+// loudly (NFP_E_HIP / NFP_E_UNSUPPORTED) rather than fall back.  The kernels and their launchers live in the other units,
+// behind the interfaces of nfp_launch.h; this one launches fill_workspace alone.
 #include "nfp_launch.h"
-#include "nfp_fast.h"
-#include "nfp_band.h"
-#include "nfp_gather.h"
-#include "nfp_mfma.h"
-#include "nfp_direct.h"
+#include "nfp_tables.h"
 
 using namespace nfp;
 using namespace nfp_host;
@@ -94,7 +91,7 @@ int make_kp(const nfp_desc* d, KP* g) {
   g->zero0 = d->measure == NFP_RMSE ? 0 : 1;
   if (!(g->stride == 1 && g->dil == 1 && g->pad == g->R && g->mode != NFP_PAD_CIRCULAR && (g->R == 1 || g->R == 2) &&
         g->P <= kBwdThreads && g->P >= 4))
-    g->ws = nullptr;   // (not a table geometry — fast_geometry below: its workspace holds the counters alone)
+    g->ws = nullptr;   // (not a table geometry — nfp_launch.h::fast_geometry: its workspace holds the counters alone)
   // index arithmetic of the general kernels: coordinates in 15 bits, pair indices in 31
   if (d->H > 32767 || d->W > 32767 || (int64_t)g->P > (1 << 26) || (int64_t)g->N * g->O >= (1LL << 31) || d->B > 65535)
     return fail(NFP_E_UNSUPPORTED, "feature map [%d,%d,%d,%d] with k = %d exceeds the index range of the kernels", d->B,
@@ -102,587 +99,21 @@ int make_kp(const nfp_desc* d, KP* g) {
   return NFP_OK;
 }
 
-// ---- generic launches -----------------------------------------------------------------------
-// Forward of nfp_gather.h (fwd_pairs): one workgroup per (image, tile of outputs); declines only when not even
-// one channel quad of the map fits next to its tables, then the chunked scalar kernel below serves the call.
-bool force_scalar_fwd() { return g_sw.fwd_scalar.load(std::memory_order_relaxed) != 0; }
-
-template <int M, int NN>
-int launch_fwd_pairs_t(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
-  constexpr int T = 512;
-  const int Q = (g.C + 3) / 4;
-  // output tiles: every CU busy at small batch; at most T outputs per tile, whole output rows when there are
-  // several tiles per image anyway (a tile stages only the input rows it reads)
-  int tiles = (256 + g.B - 1) / g.B;
-  if (tiles > (g.O + 7) / 8) tiles = (g.O + 7) / 8;
-  if (tiles < 1) tiles = 1;
-  PairsLds L;
-  L.Ot = (g.O + tiles - 1) / tiles;
-  if (L.Ot > T) L.Ot = g.Wo <= T ? (T / g.Wo) * g.Wo : T;
-  tiles = (g.O + L.Ot - 1) / L.Ot;
-  // rows of x a tile can read: its output rows through stride / dilation, plus what padding folds back in
-  // (inside that window when pad <= R*dilation; circular wraps and over-padding may reach anywhere)
-  int rows = g.H;
-  if (g.mode != NFP_PAD_CIRCULAR && g.pad <= g.R * g.dil) {
-    const int orows = std::min(g.Ho, (L.Ot + g.Wo - 2) / g.Wo + 1);  // a tile may start and end mid-row
-    rows = std::min(g.H, (orows - 1) * g.stride + 2 * g.R * g.dil + 1);
-  }
-  L.PSm = rows * g.W + 1;
-  L.G = T / L.Ot;
-  if (L.G > Q) L.G = Q;
-  L.Gs = T / (L.PSm - 1);
-  if (L.Gs > 16) L.Gs = 16;
-  if (L.Gs > Q) L.Gs = Q;
-  if (L.Gs < 1) L.Gs = 1;
-  long long w = 0;
-  L.st = (int)w;  w += 2LL * L.PSm;
-  L.piv = (int)w; w += L.PSm;
-  L.mm = (int)w;  w += 2;
-  L.tap = (int)w; w += ((long long)(g.N + 1) * L.Ot + 1) / 2;
-  L.red = (int)w; w += std::max((long long)L.G * NN * L.Ot, 2LL * L.Gs * (L.PSm - 1));
-  w = (w + 3) & ~3LL;
-  L.xs = (int)w;
-  const long long quad_bytes = (long long)L.PSm * 16, room = (long long)kLdsMax - w * 4;
-  if (room < quad_bytes) return kNotApplicable;
-  long long Cq = room / quad_bytes;
-  if (Cq > Q) Cq = Q;
-  if (Cq < Q) {  // several chunks: make them even
-    const long long nch = (Q + Cq - 1) / Cq;
-    Cq = (Q + nch - 1) / nch;
-  }
-  L.Cq = (int)Cq;
-  // wavefronts for the index tables vs the first slab: balance ~350*k clk per pass of 64 (output, kernel row)
-  // items against ~2.5 B/clk of staging per wavefront (measured on MI355X, scripts/diag_stamps.py)
-  double best = 1e30;
-  L.Tt = 64;
-  for (int nt = 1; nt <= 4; ++nt) {
-    const double tt = (double)((L.Ot * g.k + 64 * nt - 1) / (64 * nt)) * 350.0 * g.k;
-    const double ts = (double)Cq * (double)quad_bytes / ((T / 64 - nt) * 2.5);
-    if (std::max(tt, ts) < best) {
-      best = std::max(tt, ts);
-      L.Tt = 64 * nt;
-    }
-  }
-  const size_t lds = (size_t)w * 4 + (size_t)Cq * quad_bytes;
-  snprintf(g_variant, sizeof(g_variant), "fwd_pairs");
-  return launch("fwd_pairs", fwd_pairs<M, NN>, dim3(g.B, tiles), dim3(T), lds, st, g, L, x, out, saved);
-}
-
-template <int M>
-int launch_fwd_pairs(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
-  if (force_scalar_fwd() || g.P > 65534) return kNotApplicable;
-  return g.N <= 8 ? launch_fwd_pairs_t<M, 8>(g, x, out, saved, st) : launch_fwd_pairs_t<M, 24>(g, x, out, saved, st);
-}
-
-template <int M>
-int launch_fwd_generic(KP g, const void* x, void* out, float* saved, hipStream_t st) {
-  if (int rc = launch_fwd_pairs<M>(g, x, out, saved, st); rc != kNotApplicable) return rc;
-  // last resort (nfp_direct.h): no LDS tables, any map size
-  snprintf(g_variant, sizeof(g_variant), "fwd_direct");
-  return launch("fwd_direct", fwd_direct<M>, dim3((unsigned)((g.O + 255) / 256), (g.N + kGroup - 1) / kGroup, g.B), dim3(256),
-                0, st, g, x, out, saved);
-}
-
-// Gather-form backward (nfp_gather.h): tables + one slab of >= QB channel quads must fit in LDS and the
-// packed 16-bit indices must hold; otherwise the LDS-atomic kernel below serves the call.
-bool force_atomic() { return g_sw.bwd_atomic.load(std::memory_order_relaxed) != 0; }
-// tests: NFP_BWD_BANDS=n sends every call through the banded kernel with >= n bands
-int force_bands() { return g_sw.bwd_bands.load(std::memory_order_relaxed); }
-
-#ifndef NFP_GATHER_WGS
-#define NFP_GATHER_WGS 512
-#endif
-#ifndef NFP_GATHER_QB
-#define NFP_GATHER_QB 4
-#endif
-#ifndef NFP_GATHER_SLAB_KB
-#define NFP_GATHER_SLAB_KB 48
-#endif
-
-template <int M>
-int launch_bwd_gather(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st) {
-  constexpr int QB = NFP_GATHER_QB, NC = NCoef<M>::v;
-  const long long ON = (long long)g.O * g.N;
-  // index ranges the packed tables hold (nfp_gather.h)
-  if (force_atomic() || force_bands() > 0 || ON > 65535 || g.P > 65534 || g.k > 15 || g.pad > 8 || g.H >= 16383 ||
-      g.W >= 16383 || (long long)(g.H + g.W) * (2 * g.pad + 1) * g.k >= (1 << 20))
-    return kNotApplicable;
-  auto folds = [&](int n) {  // padded coordinates that can fold onto one coordinate of an axis of size n
-    if (g.pad == 0 || g.mode == NFP_PAD_ZEROS) return 1;
-    if (g.mode == NFP_PAD_REPLICATE) return n == 1 ? 2 * g.pad + 1 : g.pad + 1;
-    return 3;
-  };
-  GatherLds L;
-  L.ON = (int)ON;
-  L.capY = g.k * folds(g.H);
-  L.capX = g.k * folds(g.W);
-  long long w = 0;
-  L.cf = (int)w;  w += (long long)NC * L.ON;
-  L.nbq = (int)w; w += (L.ON + 1) / 2;
-  w = (w + 1) & ~1LL;  // uint2 lists
-  L.yl = (int)w;  w += 2LL * g.H * L.capY;
-  L.xl = (int)w;  w += 2LL * g.W * L.capX;
-  L.yc = (int)w;  w += g.H;
-  L.xc = (int)w;  w += g.W;
-  w = (w + 1) & ~1LL;
-  L.sl = (int)w;  w += 2LL * (g.H + g.W) * (2 * g.pad + 1) * g.k;
-  w = (w + 3) & ~3LL;
-  if (w * 4 > kLdsMax) return kNotApplicable;
-  L.xs = (int)w;
-  L.Ts = NFP_GATHER_T / 4;  // a quarter of the threads stage
-  const size_t table_bytes = (size_t)w * 4, quad_bytes = (size_t)(g.P + 1) * 16;
-  if (table_bytes + QB * quad_bytes > (size_t)kLdsMax) return kNotApplicable;
-  const int Q = (g.C + 3) / 4;
-  // channel split: enough workgroups to fill the chip at small batch, whole QB blocks per workgroup
-  int S = (NFP_GATHER_WGS + g.B - 1) / g.B;
-  const int maxS = (Q + QB - 1) / QB;
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  L.Qwg = (((Q + S - 1) / S) + QB - 1) / QB * QB;
-  S = (Q + L.Qwg - 1) / L.Qwg;
-  // slab: what the workgroup needs, capped by a budget that keeps several workgroups per CU, then by LDS
-  size_t budget = (size_t)NFP_GATHER_SLAB_KB * 1024;
-  if (budget < QB * quad_bytes) budget = QB * quad_bytes;
-  if (budget > (size_t)kLdsMax - table_bytes) budget = (size_t)kLdsMax - table_bytes;
-  int Cq = (int)(budget / quad_bytes) / QB * QB;
-  if (Cq > L.Qwg) Cq = L.Qwg;
-  L.Cq = Cq;
-  const size_t lds = table_bytes + (size_t)Cq * quad_bytes;
-  snprintf(g_variant, sizeof(g_variant), "bwd_gather");
-  return launch("bwd_gather", bwd_gather<M, QB>, dim3(g.B, S), dim3(NFP_GATHER_T), lds, st, g, L, x, go, out, saved, gx);
-}
-
-// Banded variant for maps whose whole-image tables exceed LDS (nfp_gather.h::bwd_gather_banded).
-template <int M>
-int launch_bwd_gather_banded(const KP& g, const void* x, const void* go, const void* out, const float* saved,
-                             void* gx, hipStream_t st) {
-  constexpr int QB = NFP_GATHER_QB, NC = NCoef<M>::v;
-  if (force_atomic() || g.k > 15 || g.pad > 8 || g.H >= 16383 || g.W >= 16383 ||
-      (long long)(g.H + g.W) * (2 * g.pad + 1) * g.k >= (1 << 20))
-    return kNotApplicable;
-  auto folds = [&](int n) {
-    if (g.pad == 0 || g.mode == NFP_PAD_ZEROS) return 1;
-    if (g.mode == NFP_PAD_REPLICATE) return n == 1 ? 2 * g.pad + 1 : g.pad + 1;
-    return 3;
-  };
-  const bool local = g.mode != NFP_PAD_CIRCULAR && g.pad <= g.R * g.dil;  // an output reads near its centre only
-  const int reach = 2 * g.R * g.dil, nslot = (2 * g.pad + 1) * g.k, Q = (g.C + 3) / 4;
-  BandLds L;
-  L.capY = g.k * folds(g.H);
-  L.capX = g.k * folds(g.W);
-  long long w = 0;
-  size_t table_bytes = 0, quad_bytes = 0, slot_bytes = 0;
-  int bands = 0;
-  const int nb0 = local ? std::min(std::max(force_bands(), 1), g.H) : 1;
-  for (int nb = nb0; nb <= g.H; nb = local ? nb + 1 : g.H + 1) {
-    const int RB = (g.H + nb - 1) / nb;
-    const int orows = local ? std::min(g.Ho, (RB - 1 + reach) / g.stride + 2) : g.Ho;
-    const int wrows = local ? std::min(g.H, RB + reach) : g.H;
-    const long long ONm = (long long)g.N * orows * g.Wo, PSm = (long long)wrows * g.W + 1;
-    if (PSm > 65535) continue;
-    w = 0;
-    L.cf = (int)w;  w += NC * ONm;
-    L.nbq = (int)w; w += (ONm + 1) / 2;
-    w = (w + 1) & ~1LL;
-    L.yl = (int)w;  w += 2LL * RB * L.capY;
-    L.xl = (int)w;  w += 2LL * g.W * L.capX;
-    L.yc = (int)w;  w += RB;
-    L.xc = (int)w;  w += g.W;
-    L.mm = (int)w;  w += 4;
-    w = (w + 3) & ~3LL;
-    table_bytes = (size_t)w * 4;
-    quad_bytes = (size_t)PSm * 16;
-    slot_bytes = (size_t)(RB + g.W) * nslot * 8;
-    // tables may take half of LDS; the rest is the slab (at least one block of QB quads) or the slots
-    if (table_bytes <= (size_t)kLdsMax / 2 && table_bytes + std::max(QB * quad_bytes, slot_bytes) <= (size_t)kLdsMax) {
-      L.RB = RB;
-      L.ONm = (int)ONm;
-      L.PSm = (int)PSm;
-      L.xs = (int)w;
-      bands = (g.H + RB - 1) / RB;
-      break;
-    }
-  }
-  if (bands == 0) return kNotApplicable;
-  int S = (NFP_GATHER_WGS + g.B * bands - 1) / (g.B * bands);
-  const int maxS = (Q + QB - 1) / QB;
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  L.Qwg = (((Q + S - 1) / S) + QB - 1) / QB * QB;
-  S = (Q + L.Qwg - 1) / L.Qwg;
-  size_t room = (size_t)kLdsMax - table_bytes;
-  int Cq = (int)(room / quad_bytes) / QB * QB;
-  if (Cq > L.Qwg) Cq = L.Qwg;
-  L.Cq = Cq;
-  const size_t lds = table_bytes + std::max((size_t)Cq * quad_bytes, slot_bytes);
-  snprintf(g_variant, sizeof(g_variant), "bwd_gather_banded");
-  return launch("bwd_gather_banded", bwd_gather_banded<M, QB>, dim3(g.B, S, bands), dim3(512), lds, st, g, L, x, go, out,
-                saved, gx);
-}
-
-template <int M>
-int launch_bwd_generic(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                       hipStream_t st) {
-  if (int rc = launch_bwd_gather<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
-  if (int rc = launch_bwd_gather_banded<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
-  // last resort (nfp_direct.h): no LDS tables, any map size, still one writer per element in a fixed order
-  snprintf(g_variant, sizeof(g_variant), "bwd_direct");
-  return launch("bwd_direct", bwd_direct<M>, dim3((unsigned)((g.P + 255) / 256), (g.C + kDirectCB - 1) / kDirectCB, g.B),
-                dim3(256), 0, st, g, x, go, out, saved, gx);
-}
-
-// ---- fast-path launches (nfp_fast.h) ----------------------------------------------------------
-#ifndef NFP_FWD_SLAB_KB
-#define NFP_FWD_SLAB_KB 128
-#endif
-#ifndef NFP_BWD_SLAB_KB
-#define NFP_BWD_SLAB_KB 60
-#endif
-constexpr int kSlabBudgetBwd = NFP_BWD_SLAB_KB * 1024;
-
-
-// Geometry of the hot path: "same" maps (stride 1, dilation 1, pad = R) small enough for one workgroup per image.
-// These are the descriptors that have workspace tables (nfp_tables.h).
-bool fast_geometry(const KP& g) {
-  if (g.stride != 1 || g.dil != 1 || g.pad != g.R || g.mode == NFP_PAD_CIRCULAR) return false;
-  if (g.R != 1 && g.R != 2) return false;
-  return g.P <= kBwdThreads && g.P >= 4;
-}
-
-// Which calls the hot-path kernels serve; everything else runs on the generic kernels.
-// sym: also the five measures of nfp_measures.h::kSymTerm (plain single-radius maps only: their callers pass it)
-bool fast_ok(const KP& g, const void* x, const void* gx, bool sym = false) {
-  if (force_generic()) return false;
-  if (!fast_geometry(g) || (g.C & 3)) return false;
-  if (!hot_measure(g) && !hot_l1(g) && !(sym && hot_sym(g))) return false;
-  const bool nhwc = g.sC == 1 && g.sW == g.C && g.sH == (long long)g.W * g.C;
-  if (!g.contig && !nhwc) return false;
-  if (!g.contig) {  // vector loads of 4 channels need natural alignment
-    const uintptr_t m = g.dtype == NFP_F32 ? 15 : 7;
-    const int es = g.dtype == NFP_F32 ? 4 : 2;
-    if (((uintptr_t)x & m) || ((uintptr_t)gx & m) || ((g.sB * es) & m) || ((g.gB * es) & m)) return false;
-  }
-  return true;
-}
-
-
-// channels per LDS chunk: bounded by the slab budget and by what one staging round-set can carry
-int chunk_channels(const KP& g, int total, int T, int G, bool nhwc, int budget) {
-  int ncq = budget / (nfp::bwd_row_slots(g.P, nhwc) * 16);
-  if (nhwc) {
-    if (ncq > kRN * G) ncq = kRN * G;
-  } else {  // ceil(P/4) blocks per channel row, the last one overlapping (nfp_fast.h: StagedOvl)
-    const int NQb = (g.P + 3) >> 2;
-    if (ncq > (kRB * T) / NQb) ncq = (kRB * T) / NQb;
-  }
-  if (ncq > 2047) ncq = 2047;  // fast_div quotient bound
-  if (ncq < 1) ncq = 1;
-  int cmax = 4 * ncq;
-  int nch = (total + cmax - 1) / cmax;
-  return round4((total + nch - 1) / nch);
-}
-
-// Row-banded forward (nfp_band.h): needs the descriptor's workspace tables.
-#ifndef NFP_BAND_WGS
-#define NFP_BAND_WGS 256
-#endif
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
-int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                      float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
-  constexpr int NF = Win<R>::NF;
-  int nb = std::min(g.H, (NFP_BAND_WGS + g.B - 1) / g.B);   // bands per image so that >= NFP_BAND_WGS workgroups exist
-  // two workgroups per CU overlap each other's load and sum phases — worth it while a band's R halo rows stay a small
-  // part of what it stages (14x14, k = 3 at B = 256: 12.8 -> 10.8 us; not 7x7: 7.3 -> 8.2 us)
-  nb = std::max(nb, std::min((2 * NFP_BAND_WGS + g.B - 1) / g.B, g.H / (6 * g.R)));
-  // The pooled outputs are sums over the whole image.  One workgroup per image writes them itself; several bands per image
-  // write partial sums that a second launch (pool_fold) joins.  Measured at [64,512,7,7] (profiles/r03_i_fused_callers.jsonl):
-  // four bands + fold 9.5 us against 8.1 us for one band — the second launch costs more than the bands save — so the table
-  // kernels keep one band (-DNFP_POOL_BANDS=1 builds the other arm; the row-band kernels of nfp_tile.h, whose maps do not
-  // fit one workgroup, always fold).
-#ifndef NFP_POOL_BANDS
-#define NFP_POOL_BANDS 0
-#endif
-  // Round 4: with the workspace's arrival counters the last band to finish folds them all inside the SAME launch
-  // (nfp_common.h::pool_last_band): the bands come back.  Without counters: one band, as before.
-  if (POOL && (part == nullptr || !(NFP_POOL_BANDS || g.tickets != nullptr))) nb = 1;
-  const int rb = (g.H + nb - 1) / nb;
-  nb = (g.H + rb - 1) / rb;
-  const int psm = std::min(g.P, (rb + g.R) * g.W);          // most pixels a band stages
-  // channel groups: a power of two (adjacent lanes, joined by DPP), as many as kBandT threads and C allow, <= 32
-  // (up to one workgroup per CU, latency counts: all the threads a workgroup may have.  Beyond one workgroup per CU latency no longer counts and every extra thread's index work is paid for: half the
-  // threads on half-size slabs, two workgroups per CU; from four workgroups per CU on, a quarter — four 256-thread
-  // workgroups overlap each other's load / sum phases better than two of 512: [4096,512,7,7] cold 91.5 -> 85.4 us, [1024,…]
-  // 27.5 -> 26.2; an eighth is no better.  -DNFP_BAND_SAT_SHIFT=1 builds the old arm)
-#ifndef NFP_BAND_SAT_SHIFT
-#define NFP_BAND_SAT_SHIFT 2
-#endif
-  // (a band of more pixels than a quarter workgroup has threads stays at two per CU — the registers of 104-VGPR wavefronts
-  // hold 1024 threads per CU, whatever the slabs: [2048,64,20,20] 63 vs 73 us)
-  const long long nwg = (long long)g.B * nb;
-  const int sat = nwg > 256 ? ((nwg >= 1024 && psm <= (kBandT >> NFP_BAND_SAT_SHIFT)) ? NFP_BAND_SAT_SHIFT : 1) : 0;
-  const int tcap = kBandT >> sat;
-  int lg = 0;
-  while (lg < 5 && (2 << lg) * psm <= tcap && (2 << lg) <= g.C / 4) ++lg;
-  g.G = 1 << lg;
-  g.Tc = lg;
-  const int T = ((g.G * psm + 63) / 64) * 64;
-  const int nqb = (psm + 3) / 4 + 1, ppb = ((psm + 3 + 8) & ~3) + 4;   // blocks / slots per slab row, alignment slack and
-                                                                       // the bank padding of band_row_slots included
-  // up to one workgroup per CU the whole band is staged at once; beyond that, half-size slabs let two workgroups share a
-  // CU and overlap each other's load / sum phases ([4096,512,7,7]: 91 vs 118 us)
-  const int budget = (NFP_FWD_SLAB_KB * 1024) >> sat;
-  int ncq = budget / (ppb * 16);
-  ncq = std::min(ncq, NHWC ? kBandRN * g.G : (kBandRB * T) / nqb);
-  if (ncq < 1) return kNotApplicable;
-  const int total = g.C / 4, nch = (total + ncq - 1) / ncq;
-  g.Cc = 4 * ((total + nch - 1) / nch);
-#ifndef NFP_BAND_PF
-#define NFP_BAND_PF 1
-#endif
-  // (measured, profiles/r04_a_…: [4096,512,7,7] forward 84.8 -> 83.1 us cold, 81.6 -> 80.0 resident; k = 5 loses 1-3 %:
-  // its sums already hide the next chunk's latency behind four times the LDS reads)
-  g.pf = (NFP_BAND_PF && nch > 1 && Win<R>::RAD == 1) ? 1 : 0;
-  const size_t slab = (size_t)(g.Cc / 4) * ppb * 16;
-  const size_t tail = (size_t)psm * (NF + 1) * 4 + (POOL == kPoolBoth ? (size_t)Win<R>::N * psm * 4 : 0);   // Tt (+ pooled-map staging)
-  const size_t lds = slab + tail;
-  if (lds > (size_t)kLdsMax) return kNotApplicable;
-  snprintf(g_variant, sizeof(g_variant), "fwd_band<R%s,%s,%s,%s%s>x%d", R == 12 ? "1+2" : (R == 1 ? "1" : "2"), hot_name(g),
-           MF ? "mix" : (BF ? "bf16" : "f32"), NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
-  if (nb_out) *nb_out = nb;
-  // the kernel's preloadable head (nfp_common.h): what stands in front of its first x request
-  const uint32_t sB_lo = (uint32_t)((unsigned long long)g.sB & 0xFFFFFFFFull), sB_hi = (uint32_t)((unsigned long long)g.sB >> 32);
-  const uint32_t hchunk = nfp::band_head_chunk(g.Cc, lg, g.R, T), hgeom = nfp::band_head_geom(g.H, g.W, rb);
-  // (NCHW staging: always the 4 x 4 blocks here.  The pixel-row form bwd_fast takes — launch_bwd_fast_t — was built for this
-  // kernel too and measured no faster at the headline shape, 4.80 -> 4.86 us: profiles/r05_b_nchw_row_staging_ab.txt)
-  auto go = [&](auto kernel) {
-    if constexpr (NHWC)
-      return launch("fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk, hgeom, out, saved,
-                    gap, nfpm, part, g);
-    else
-      return launch_staged(false, "fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk,
-                           hgeom, out, saved, gap, nfpm, part, g);
-  };
-  // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — pool_forward_rm)
-  if constexpr (M != kSymTerm)
-  if (g.unit || g.gfc || g.d2s != 1.f)   // DotProduct / GFC / RMSE: the finalize with the run-time constants
-    return go(fwd_band<R, M, BF, NHWC, POOL, true, MF>);
-  return go(fwd_band<R, M, BF, NHWC, POOL, false, MF>);
-}
-
-template <int R, int M, int POOL = kPoolNone>
-int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                    float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
-  if (g.ws == nullptr) return kNotApplicable;
-  return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
-    return launch_fwd_band_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, gap, nfpm, part, nb_out);
-  });
-}
-
-// LDS of bwd_fast's phase A: tables that live to the end of the kernel (Wt, Dt, two norm factors per pixel), and
-// the per-pair values, which are dead once Wt is built (nfp_fast.h::bwd_fast)
-size_t bwd_fixed_bytes(const KP& g, int K2) { return ((size_t)(2 * g.P * K2 + 2 * g.P) * 4 + 15) & ~(size_t)15; }
-size_t bwd_pair_bytes(const KP& g, int M, int N) {
-  return ((size_t)((M == NFP_COSINE ? 2 : 1) * (N * g.P + 1)) * 4 + 15) & ~(size_t)15;   // (+ the zero an empty list entry reads)
-}
-constexpr size_t kEarlyBudget = 96 * 1024;  // slab beside the pair values (committed during phase A) up to this much LDS
-
-template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
-int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
-  constexpr int N = Win<R>::N, K2 = Win<R>::K2;
-#ifndef NFP_BWD_WGS
-#define NFP_BWD_WGS 256
-#endif
-  int S = (NFP_BWD_WGS + g.B - 1) / g.B;  // channel blocks per image so that >= NFP_BWD_WGS workgroups exist
-  // ... and twice as many while a workgroup's block stays large ([256,960,7,7]: 22.9 -> 21.5 us, [256,192,14,14]: 21.3 ->
-  // 20.2 us; not [256,512,7,7]: 13.8 -> 14.0 us): phase A is repeated per block, the streaming part is what splits.
-  // k = 3 only: a 5x5 window's phase A is a third of the kernel ([256,192,14,14] L2 k = 5 f32: 41.0 -> 49.6 us split)
-  if (K2 <= 9 && (long long)g.C * g.P / S >= 32768 && (long long)g.B * S < 2 * NFP_BWD_WGS)
-    S = (2 * NFP_BWD_WGS + g.B - 1) / g.B;
-  if (S > g.C / 4) S = g.C / 4;
-  if (S < 1) S = 1;
-  g.Cwg = round4((g.C + S - 1) / S);
-  S = (g.C + g.Cwg - 1) / g.Cwg;
-  // From four workgroups per CU on (k = 3): quarter-size workgroups, four per CU (128 registers: 1024 threads per CU
-  // either way) — they overlap each other's phases better than two of 512: [4096,64,7,7] 45 -> 33 us, [4096,512,7,7] 176 ->
-  // 168, [1024,256,14,14] 100 -> 94.  Not k = 5: its 13-entry-per-pixel phase A on 256 threads doubles the kernel
-  // ([2048,192,14,14] 290 -> 486 us).  (-DNFP_BWD_SAT_T=512 builds the old arm.)
-#ifndef NFP_BWD_SAT_T
-#define NFP_BWD_SAT_T 256
-#endif
-#ifndef NFP_BWD_SAT_SLAB
-#define NFP_BWD_SAT_SLAB 2
-#endif
-  // (channels-last, lanes along a pixel's channel groups since round 4: a quarter-size workgroup has G = 5 groups at 7x7 —
-  // 80-byte runs of a 2 KB pixel; with 512 threads G = 10: [4096,512,7,7] 209 -> 147 us, [1024,512,7,7] 45 -> 38; narrow
-  // pixels keep the quarter size: [4096,64,7,7] 27 vs 32 us — profiles/r04_p_…)
-  const bool satb = K2 <= 9 && (long long)g.B * S >= 1024 && g.P <= NFP_BWD_SAT_T && NFP_BWD_SAT_T < kBwdThreads &&
-                    !(NHWC && g.C > 128);
-  g.G = (satb ? NFP_BWD_SAT_T : kBwdThreads) / g.P;
-  if (g.G < 1) g.G = 1;
-  if (g.G > g.Cwg / 4) g.G = g.Cwg / 4;
-  int T = ((g.P * g.G + 63) / 64) * 64;
-  // large batches (one workgroup per image, several images per CU over time): fewer, larger chunks win
-  const int bbudget = satb ? NFP_BWD_SAT_SLAB * kSlabBudgetBwd / 2 : ((S == 1 && g.B > 256) ? 2 * kSlabBudgetBwd : kSlabBudgetBwd);
-  g.Cc = chunk_channels(g, g.Cwg, T, g.G, NHWC, bbudget);
-  g.G = even_groups(g.Cc / 4, g.G);
-  T = ((g.P * g.G + 63) / 64) * 64;
-  g.Cc = chunk_channels(g, g.Cwg, T, g.G, NHWC, bbudget);
-  const size_t fixed = bwd_fixed_bytes(g, K2), pairs = bwd_pair_bytes(g, M, N);
-  const size_t slab = (size_t)(g.Cc / 4) * nfp::bwd_row_slots(g.P, NHWC) * 16;
-  g.early = fixed + pairs + slab <= kEarlyBudget ? 1 : 0;
-  const size_t lds = g.early ? fixed + pairs + slab : fixed + std::max(pairs, slab);
-  if (lds > (size_t)kLdsMax) return kNotApplicable;  // tables + slab do not fit: the generic kernels serve it
-  snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%s,%s,%s,%s%s>", R == 12 ? "1+2" : (R == 1 ? "1" : "2"),
-           hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"), NHWC ? "nhwc" : "nchw", pool_tag(POOL));
-  // NCHW staging form (nfp_fast.h: StagedRows).  By pixel rows for ONE class: float32, k = 3, plain maps, the cosine and L2
-  // instantiations (with their dot / gfc / rmse riders; Norm p = 1 and the symmetric-term measures keep the blocks: an
-  // instantiation more each for measures no in-tree model uses), a single chunk (Cc covers the workgroup's channels), at
-  // most one workgroup per CU (beyond that latency no longer counts) and at most kRS slots per thread.  Everything else:
-  // 4 x 4 blocks, as before.  NFP_STAGE_BLOCKS=1 forces the blocks; the two forms agree bitwise.
-  // (the slot bound is this change's own, a register budget: kRS slots are 24 staging registers against the blocks' 48;
-  // a single-chunk launch beyond it — [128,512,7,7]: 64 quads on 10 groups, 7 slots — keeps the blocks)
-  const uint32_t hgeom = nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T);
-  if constexpr (R == 1 && !BF && !NHWC && POOL == kPoolNone && (M == NFP_COSINE || M == NFP_NORM)) {
-    if (!satb && g.Cc >= g.Cwg && ceil_div(g.Cwg / 4, g.G) <= nfp::kRS && !g_sw.stage_blocks.load(std::memory_order_relaxed))
-      return launch_staged(true, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, true>, dim3(g.B, S), dim3(T), lds, st, x, go, out,
-                           saved, g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
-  }
-  if constexpr (!NHWC)
-    return launch_staged(false, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
-                         g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
-  else
-    return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws, hgeom,
-                  g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
-}
-
-// Matrix-core forward (nfp_mfma.h): bf16, dense channels-last, C a multiple of 16.
-bool mfma_enabled() { return g_sw.mfma.load(std::memory_order_relaxed) != 0; }
-
-template <int R, int M>
-int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                    float* nfpm = nullptr) {
-  if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 15) || g.P > 512) return kNotApplicable;
-  if (mixed_maps(g)) return kNotApplicable;   // (the Gram-form L2 loses digits a float32 map would show: DESIGN §4)
-  if (g.unit || g.gfc || g.d2s != 1.f) return kNotApplicable;   // (DotProduct / GFC / RMSE: the vector kernels' run-time constants)
-  if (!g.contig && (((uintptr_t)x & 15) || ((g.sB * 2) & 15))) return kNotApplicable;  // 16-byte fragment loads
-  const int nt = (g.P + 31) / 32, D = std::min(nt - 1, (g.R * g.W + g.R + 31) / 32);
-  const size_t tiles = (((size_t)nt * (D + 1) * 32 * kGramLd + 3) & ~(size_t)3) * 4;
-  const size_t image = (size_t)g.P * (g.C / 8 + 1) * 16;
-  if (tiles > (size_t)kLdsMax) return kNotApplicable;
-  if (g.contig && tiles + image > (size_t)kLdsMax) return kNotApplicable;  // NCHW is transposed through LDS only
-  if (tiles + (size_t)g.P * 8 > (size_t)kLdsMax) return kNotApplicable;  // (the norm tables reuse the image's words)
-  // the pooled variant takes its sums from the LDS image and stages the map values in it afterwards; GAP(x) alone (gap set,
-  // nfpm null: nfp_gap_forward) needs the LDS image too, and nothing behind it
-  if (gap != nullptr && nfpm == nullptr && tiles + image > (size_t)kLdsMax) return kNotApplicable;
-  if (nfpm != nullptr && (tiles + image > (size_t)kLdsMax || image < (size_t)(2 + Win<R>::N) * g.P * 4)) return kNotApplicable;
-  snprintf(g_variant, sizeof(g_variant), "fwd_gram<R%d,%s,bf16,%s%s>", R, hot_name(g),
-           g.contig ? "nchw" : "nhwc", nfpm != nullptr ? ",pool" : (gap != nullptr ? ",gap" : ""));
-  if (g.contig)
-    return launch("fwd_gram", fwd_gram<R, M, true, true>, dim3(g.B), dim3(1024), tiles + image, st, g, x, out, saved, D, g.ws,
-                  gap, nfpm);
-  if (tiles + image <= (size_t)kLdsMax)
-    return launch("fwd_gram", fwd_gram<R, M, true>, dim3(g.B), dim3(1024), tiles + image, st, g, x, out, saved, D, g.ws, gap,
-                  nfpm);
-  return launch("fwd_gram", fwd_gram<R, M, false>, dim3(g.B), dim3(1024), tiles + (size_t)g.P * 8, st, g, x, out, saved, D, g.ws,
-                (float*)nullptr, (float*)nullptr);
-}
-
-// Phase B of the backward on the matrix cores (nfp_fast.h::bwd_gemm_phase): bf16 storage, C a multiple of 32.
-template <int R, int M, bool NHWC, int POOL = kPoolNone>
-int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
-  constexpr int N = Win<R>::N, K2 = Win<R>::K2;
-  if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 31) || mixed_maps(g)) return kNotApplicable;
-  if (NHWC && (((uintptr_t)x & 15) || ((g.sB * 2) & 15) || ((uintptr_t)gx & 15) || ((g.gB * 2) & 15)))
-    return kNotApplicable;  // 16-byte staging loads and grad_x stores
-  int S = (NFP_BWD_WGS + g.B - 1) / g.B;  // channel blocks per image, whole 32-channel tiles each
-  if (S > g.C / 32) S = g.C / 32;
-  if (S < 1) S = 1;
-  g.Cwg = ((g.C / 32 + S - 1) / S) * 32;
-  S = (g.C + g.Cwg - 1) / g.Cwg;
-  // NCHW rows that are not 8-byte aligned (H*W % 4 != 0) are staged and stored 2 bytes at a time: that only pays
-  // while the batch is small enough for the channel split (measured: 7.2 vs 8.4 us at B = 64, 16.1 vs 14.0 at 256)
-  if (!NHWC && (g.P & 3) && S < 2) return kNotApplicable;
-  // the matrix-core variant keeps nothing of x in registers, so it may run 16 wavefronts: that pays when phase A has
-  // thousands of table entries to build (k = 5 at 14x14: 36 -> 29.5 us), not at 7x7 with k = 3 (7.2 -> 7.7 us)
-  g.G = (g.P * K2 > 2048 ? 1024 : kBwdThreads) / g.P;
-  if (g.G < 1) g.G = 1;
-  if (g.G > g.Cwg / 4) g.G = g.Cwg / 4;
-  int T = ((g.P * g.G + 63) / 64) * 64;
-  // phase A of this variant is loop-free (nfp_fast.h): one round of pair values, at most kGemmPre gather rounds
-  const int NJ = Win<R>::RAD >= 2 ? Win<R>::NF + 1 : K2, NE = g.P * NJ, NO = N * g.P;
-  if (NE > nfp::kGemmPre * T || NO > 8 * T) T = 1024;
-  if (NE > nfp::kGemmPre * T || NO > 8 * T) return kNotApplicable;
-  g.Cc = g.Cwg;
-  const int band = g.R * g.W + g.R, KW = nfp::gemm_kw(band);
-  const size_t xq = (size_t)((((g.P + 15) >> 4 << 1) + 1) | 1), wq = (size_t)((2 * KW + 1) | 1);
-  // row tiles whose densified weights sit in LDS together (fewer rounds of zero / scatter / barrier): all that fit
-  const int nt = (g.P + 31) / 32;
-  // LDS of this variant (nfp_fast.h::bwd_fast, GEMM): Wt | ipn | dfn live to the end; Dt and the pair values are dead once
-  // the diagonal is folded — the operand images lie over both
-  const size_t xt = (size_t)g.Cwg * xq * 16, wd1 = (size_t)2 * 32 * wq * 16;
-  const size_t fixed = ((size_t)(g.P * K2 + 2 * g.P) * 4 + 15) & ~(size_t)15, dtb = ((size_t)g.P * K2 * 4 + 15) & ~(size_t)15;
-  const size_t ggb = POOL != kPoolNone ? (size_t)g.Cwg * 4 : 0;   // grad(GAP(x)) of the block, staged behind Wd
-  int rt = fixed + xt + ggb < (size_t)kLdsMax ? (int)(((size_t)kLdsMax - fixed - xt - ggb) / wd1) : 0;
-  rt = std::min(rt, nt);
-  // Second form (round 4): Wd of ALL row tiles, written by phase A itself, x in chunks of `ctr` channel tiles (about one output
-  // tile per wavefront and chunk), two buffers — where that fits
-  // (measured, profiles/r04_zb_…: 17.4 -> 16.2 us at config 5, where the first form takes two rounds; where the first form
-  // holds every row tile in ONE round — 7 x 7 maps — it stays: 10.2 vs 12.2 us at [256,512,7,7], 5.96 vs 6.5 at [64,512,7,7])
-  if (const int g3 = g_sw.gemm3.load(std::memory_order_relaxed); g3 == 2 || (g3 == 1 && rt < nt)) {
-    const int nw = T / 64, nct = g.Cwg / 32;
-    int ctr = std::max(1, std::min(nct, nw / nt));
-    const int nch = (nct + ctr - 1) / ctr;
-    ctr = (nct + nch - 1) / nch;   // even chunks
-    const size_t fixed3 = ((size_t)(3 * g.P + (POOL != kPoolNone ? g.Cwg : 0)) * 4 + 15) & ~(size_t)15;
-    const size_t xtc = (size_t)32 * ctr * xq * 16;
-    const size_t lds3 = fixed3 + (size_t)nt * wd1 + std::max((size_t)(nch > 1 ? 2 : 1) * xtc, bwd_pair_bytes(g, M, N) + dtb);
-    if (lds3 <= (size_t)kLdsMax) {
-      g.Tc = ctr;
-      g.early = 0;
-      snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma2%s>", R, hot_name(g), NHWC ? "nhwc" : "nchw",
-               pool_tag(POOL));
-      return launch("bwd_fast_mfma2", bwd_fast<R, M, true, NHWC, POOL, 2>, dim3(g.B, S), dim3(T), lds3, st, x, go, out, saved,
-                    g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
-    }
-  }
-  if (rt >= 2 && rt < nt) rt = (nt + ((nt + rt - 1) / rt) - 1) / ((nt + rt - 1) / rt);  // even rounds
-  if (rt < std::min(2, nt)) return kNotApplicable;
-  g.Tc = rt;
-  const size_t images = xt + (size_t)rt * wd1 + ggb;
-  const size_t lds = fixed + std::max(dtb + bwd_pair_bytes(g, M, N), images);
-  g.early = 0;
-  if (lds > (size_t)kLdsMax) return kNotApplicable;
-  snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma%s>", R, hot_name(g),
-           NHWC ? "nhwc" : "nchw", pool_tag(POOL));
-  return launch("bwd_fast_mfma", bwd_fast<R, M, true, NHWC, POOL, 1>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
-                g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
-}
-
-// The table backward: phase B on the matrix cores where that form exists (bf16 maps, one radius, cosine / L2) and applies,
-// else the vector (VALU) form, which serves every radius spec.  (float32 maps beside bf16 x: the vector form — the
-// matrix-core backward stages grad_out / out under an LDS budget sized for 2-byte values.)
-template <int R, int M, int POOL = kPoolNone>
-int launch_bwd_fast(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                    hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
-  return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
-    if constexpr (bf() && !mf() && R != 12 && (M == NFP_COSINE || M == NFP_NORM))
-      if (int rc = launch_bwd_gemm_t<R, M, nhwc(), POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm); rc != kNotApplicable)
-        return rc;
-    return launch_bwd_fast_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, ggap, gnfpm);
-  });
-}
-
 }  // namespace
 
 #ifdef NFP_STAMPS
-extern "C" int nfp_debug_set_stamp_buffer_tile(void* dev_ptr);
+// (every unit whose kernels stamp has its own copy of the device-side stamp pointer, and a setter for it; this unit's
+// kernels — fill_workspace — do not stamp)
+extern "C" int nfp_debug_set_stamp_buffer_generic(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_table_fwd(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_table_bwd(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_tile_fwd(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_tile_bwd(void* dev_ptr);
 extern "C" int nfp_debug_set_stamp_buffer(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  if (int rc = nfp_debug_set_stamp_buffer_tile(dev_ptr)) return rc;
-  return hip_ok(hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)), "set stamp buffer");
+  for (auto set : {nfp_debug_set_stamp_buffer_generic, nfp_debug_set_stamp_buffer_table_fwd, nfp_debug_set_stamp_buffer_table_bwd,
+                   nfp_debug_set_stamp_buffer_tile_fwd, nfp_debug_set_stamp_buffer_tile_bwd})
+    if (int rc = set(dev_ptr)) return rc;
+  return NFP_OK;
 }
 #endif
 
@@ -740,17 +171,11 @@ int hot_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t
     if (int rc = tile_forward(g, x, out, saved, st, false, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
   // (Geman / Canberra / Hellinger / Jeffrey / squared chord / chi-squared 1 share the kSymTerm instantiation)
   if (fast_ok(g, x, x, true)) {
-    const int rc = with_radius(g, [&](auto r) {
-      return with_hot<true>(g, [&](auto m) {
-        constexpr int R = decltype(r)::value, M = decltype(m)::value;
-        if constexpr (M == NFP_COSINE || M == NFP_NORM)   // the matrix-core forward has these two forms alone
-          if (int rc = launch_fwd_gram<R, M>(g, x, out, saved, st); rc != kNotApplicable) return rc;
-        return launch_fwd_band<R, M>(g, x, out, saved, st);
-      });
-    });
-    if (rc != kNotApplicable) return rc;
+    // (the matrix-core forward has the cosine and L2 forms alone)
+    if (int rc = table_fwd_gram(g, x, out, saved, st, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = table_fwd_band(g, x, out, saved, st, kPoolNone, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
   }
-  // maps above the table kernels' 512 pixels, or a descriptor without its tables: the row-band kernels (nfp_tile.hip)
+  // maps above the table kernels' 512 pixels, or a descriptor without its tables: the row-band kernels (nfp_tile_fwd.hip)
   if (int rc = tile_forward(g, x, out, saved, st, false, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
   return kNotApplicable;
 }
@@ -788,10 +213,7 @@ int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void
     if (g.ws == nullptr || !fast_ok(g, x, x))
       return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
                   "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = with_hot<true>(g, [&](auto m) {
-      if constexpr (m() == kSymTerm) return kNotApplicable;   // (fast_ok above has refused these)
-      else return launch_fwd_band<12, m()>(g, x, out, saved, st);
-    });
+    const int rc = table_fwd_band(g, x, out, saved, st, kPoolNone, nullptr, nullptr, nullptr, nullptr);
     return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path forward") : rc;
   }
   if (int rc = hot_forward(g, x, out, saved, st); rc != kNotApplicable) return rc;
@@ -804,14 +226,12 @@ int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void
     // float32 maps: DotProduct's hot-path kernels write the raw dots (round 4; bf16 maps keep float32 dots in the scratch, which
     // only the any-geometry kernels write)
     int rc = g.dtype == NFP_F32 ? hot_forward(gd, x, dots, nullptr, st) : kNotApplicable;
-    if (rc == kNotApplicable) rc = launch_fwd_generic<NFP_DOT>(gd, x, dots, nullptr, st);
+    if (rc == kNotApplicable) rc = generic_forward(gd, x, dots, nullptr, st);
     if (rc) return rc;
-    const long long n = (long long)g.B * g.O;
     variant_suffix("+attn_softmax");
-    return launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                  (const float*)dots, out);
+    return attn_softmax_forward(g, dots, out, st);
   }
-  const int rc = with_measure(g, [&](auto m) { return launch_fwd_generic<m()>(g, x, out, saved, st); });
+  const int rc = generic_forward(g, x, out, saved, st);
   if (rc == kNotApplicable)
     return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine mixes batch elements in the reference, "
                 "nfp.py:359-374) has no HIP kernel", g.measure);
@@ -833,10 +253,7 @@ int hot_backward(const KP& g, const void* x, const void* grad_out, const void* o
   // k = 5 97.5 vs 101.9 us, [256,64,20,20] 37.5 vs 41.4; at 7 x 7 the table kernel: [64,512,7,7] 10.1-12.3 vs 18.2-22.5 us —
   // profiles/r04_zd_…; the forward stays on the tables up to 512 pixels: 52.7 vs 66.8 us at [256,192,14,14])
   if (g.ws != nullptr && fast_ok(g, x, grad_x, true) && !(hot_sym(g) && !(NFP_SYM_TABLE_BWD && g.P < 196))) {
-    const int rc = with_radius(g, [&](auto r) {
-      return with_hot<true>(g, [&](auto m) { return launch_bwd_fast<decltype(r)::value, m()>(g, x, grad_out, out, saved, grad_x, st); });
-    });
-    if (rc != kNotApplicable) return rc;
+    if (int rc = table_backward(g, x, grad_out, out, saved, grad_x, st, kPoolNone, nullptr, nullptr); rc != kNotApplicable) return rc;
   }
   if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
   return kNotApplicable;
@@ -855,19 +272,13 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
     if (g.ws == nullptr || !fast_ok(g, x, grad_x))
       return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
                   "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = with_hot<true>(g, [&](auto m) {
-      if constexpr (m() == kSymTerm) return kNotApplicable;   // (fast_ok above has refused these)
-      else return launch_bwd_fast<12, m()>(g, x, grad_out, out, saved, grad_x, st);
-    });
+    const int rc = table_backward(g, x, grad_out, out, saved, grad_x, st, kPoolNone, nullptr, nullptr);
     return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path backward") : rc;
   }
   if (int rc = hot_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   if (g.measure == NFP_ATTENTION) {
     float* gd = const_cast<float*>(saved);  // scratch handed over by nfp_forward's caller (nfp_saved_floats)
-    const long long n = (long long)g.B * g.O;
-    if (int rc = launch("attn_softmax_bwd", attn_softmax_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                        grad_out, out, gd))
-      return rc;
+    if (int rc = attn_softmax_backward(g, grad_out, out, gd, st)) return rc;
     KP gdot = as_dot(g);
     gdot.odtype = g.odtype;
     gdot.godtype = NFP_F32;
@@ -876,27 +287,26 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
     if (g.dtype == NFP_F32) {
       if (int rc = hot_backward(gdot, x, gd, out, nullptr, grad_x, st); rc != kNotApplicable) return rc;
     }
-    return launch_bwd_generic<NFP_DOT>(gdot, x, gd, out, nullptr, grad_x, st);
+    return generic_backward(gdot, x, gd, out, nullptr, grad_x, st);
   }
-  const int rc = with_measure(g, [&](auto m) { return launch_bwd_generic<m()>(g, x, grad_out, out, saved, grad_x, st); });
+  const int rc = generic_backward(g, x, grad_out, out, saved, grad_x, st);
   if (rc == kNotApplicable) return fail(NFP_E_UNSUPPORTED, "measure %d (SharpenedCosine) has no HIP kernel", g.measure);
   return rc;
 }
 
 // Floats of scratch behind the per-pixel state in `saved` that the row-band pooled forward needs: every band's share of
-// the two pooled sums (nfp_tile.h::fwd_tile<POOL> -> pool_fold).  Set by pool_forward_rm (also in plan mode).
+// the two pooled sums (nfp_tile.h::fwd_tile<POOL> -> pool_fold).  Set by pool_forward / gap_forward (also in plan mode).
 thread_local long long t_pool_scratch = 0;
 
-template <int R, int M>
-int pool_forward_rm(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
+int pool_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
   t_pool_scratch = 0;
   if (g.ws != nullptr && fast_ok(g, x, x)) {
     // the matrix-core forward where it applies, as in nfp_forward (it declines float32 storage itself)
-    if (int rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nfpm); rc != kNotApplicable) return rc;
+    if (int rc = table_fwd_gram(g, x, out_map, saved, st, gap, nfpm); rc != kNotApplicable) return rc;
     // row bands at small batches: each band's share of the pooled sums goes to the scratch behind the norms
     float* part = saved != nullptr ? saved + (long long)stats_of(g.measure) * g.B * g.P : nullptr;
     int nb = 1;
-    const int rc = launch_fwd_band<R, M, kPoolBoth>(g, x, out_map, saved, st, gap, nfpm, part, &nb);
+    const int rc = table_fwd_band(g, x, out_map, saved, st, kPoolBoth, gap, nfpm, part, &nb);
     if (rc == NFP_OK && nb > 1) {
       t_pool_scratch = (long long)g.B * nb * (g.C + g.N);
       if (g.tickets != nullptr) return rc;   // (the last band to arrive folded them inside the launch)
@@ -916,11 +326,10 @@ int pool_forward_rm(const KP& g, const void* x, void* out_map, float* saved, hip
   variant_suffix("+pool_fold");
   return tile_pool_fold(g, part, gap, nfpm, nb, st);
 }
-template <int R, int M>
-int pool_backward_rm(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
+int pool_backward(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
                      const float* ggap, const float* gnfpm) {
   if (g.ws != nullptr && fast_ok(g, x, gx))
-    if (int rc = launch_bwd_fast<R, M, kPoolBoth>(g, x, nullptr, out_map, saved, gx, st, ggap, gnfpm); rc != kNotApplicable) return rc;
+    if (int rc = table_backward(g, x, nullptr, out_map, saved, gx, st, kPoolBoth, ggap, gnfpm); rc != kNotApplicable) return rc;
   return tile_backward(g, x, nullptr, out_map, saved, gx, st, kPoolBoth, ggap, gnfpm);
 }
 
@@ -932,8 +341,7 @@ int pool_backward_rm(const KP& g, const void* x, const void* out_map, const floa
 // R = 12 (radii 1 and 2 from one pass, MultiRadiusNFPHead): the table kernels alone — the two-radius window has no
 // matrix-core and no row-band form, so bf16 runs on the vector kernels (as nfp_forward's) and maps above 512 pixels are
 // not served; one band per image (no counters on this path), so no pool_fold launch either.
-template <int R, int M>
-int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
+int gap_forward(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
   t_pool_scratch = 0;
   g.tickets = nullptr;
   g.pool_gap = g.pool_map = 1;
@@ -942,10 +350,10 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
   KP gfold = g;
   gfold.N = 0;   // (rows of C floats: pool_fold joins the channel sums alone)
   if (g.ws != nullptr && fast_ok(g, x, x)) {
-    if constexpr (R != 12)
-      if (int rc = launch_fwd_gram<R, M>(g, x, out_map, saved, st, gap, nullptr); rc != kNotApplicable) return rc;
+    if (g.rs != 12)
+      if (int rc = table_fwd_gram(g, x, out_map, saved, st, gap, nullptr); rc != kNotApplicable) return rc;
     int nb = 1;
-    const int rc = launch_fwd_band<R, M, kPoolGap>(g, x, out_map, saved, st, gap, nullptr, part, &nb);
+    const int rc = table_fwd_band(g, x, out_map, saved, st, kPoolGap, gap, nullptr, part, &nb);
     if (rc == NFP_OK && nb > 1) {
       t_pool_scratch = (long long)g.B * nb * g.C;
       variant_suffix("+pool_fold");
@@ -953,45 +361,20 @@ int gap_forward_rm(KP g, const void* x, void* out_map, float* saved, hipStream_t
     }
     if (rc != kNotApplicable) return rc;
   }
-  if (R == 12 || !tile_ok(g, x, x)) return kNotApplicable;
+  if (g.rs == 12 || !tile_ok(g, x, x)) return kNotApplicable;
   int nb = 0;
   if (int rc = tile_forward(g, x, out_map, saved, st, kPoolGap, part, &nb, gap, nullptr); rc != NFP_OK) return rc;
   t_pool_scratch = (long long)g.B * nb * g.C;
   variant_suffix("+pool_fold");
   return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
 }
-template <int R, int M>
-int gap_backward_rm(KP g, const void* x, const void* go, const void* out_map, const float* saved, void* gx, hipStream_t st,
+int gap_backward(KP g, const void* x, const void* go, const void* out_map, const float* saved, void* gx, hipStream_t st,
                     const float* ggap) {
   g.pool_gap = ggap != nullptr ? 1 : 0;   // NULL: GAP(x) took no part in the loss — nothing is added, nothing is read
   if (g.ws != nullptr && fast_ok(g, x, gx))
-    if (int rc = launch_bwd_fast<R, M, kPoolGap>(g, x, go, out_map, saved, gx, st, ggap, nullptr); rc != kNotApplicable) return rc;
-  if (R == 12) return kNotApplicable;
+    if (int rc = table_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr); rc != kNotApplicable) return rc;
+  if (g.rs == 12) return kNotApplicable;
   return tile_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr);
-}
-
-// the four of them by the descriptor's radius and family; the gap calls also take radii (1, 2) together (inner_R = 1)
-int pool_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
-  return with_radius(g, [&](auto r) {
-    return with_hot(g, [&](auto m) { return pool_forward_rm<decltype(r)::value, m()>(g, x, out_map, saved, st, gap, nfpm); });
-  });
-}
-int pool_backward(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
-                  const float* ggap, const float* gnfpm) {
-  return with_radius(g, [&](auto r) {
-    return with_hot(g, [&](auto m) { return pool_backward_rm<decltype(r)::value, m()>(g, x, out_map, saved, gx, st, ggap, gnfpm); });
-  });
-}
-int gap_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
-  return with_radius<true>(g, [&](auto r) {
-    return with_hot(g, [&](auto m) { return gap_forward_rm<decltype(r)::value, m()>(g, x, out_map, saved, st, gap); });
-  });
-}
-int gap_backward(const KP& g, const void* x, const void* go, const void* out_map, const float* saved, void* gx,
-                 hipStream_t st, const float* ggap) {
-  return with_radius<true>(g, [&](auto r) {
-    return with_hot(g, [&](auto m) { return gap_backward_rm<decltype(r)::value, m()>(g, x, go, out_map, saved, gx, st, ggap); });
-  });
 }
 
 }  // namespace
@@ -1324,10 +707,8 @@ int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias,
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.measure == NFP_ATTENTION) {
     if (int rc = bias_forward(as_dot(g), dw, x, centre_bias, neighbour_bias, nullptr, nullptr, saved, st)) return rc;
-    const long long n = (long long)g.B * g.O;
     variant_suffix("+attn_softmax");
-    return finish(launch("attn_softmax_fwd", attn_softmax_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                         (const float*)saved, out), "nfp_bias_forward");
+    return finish(attn_softmax_forward(g, saved, out, st), "nfp_bias_forward");
   }
   return finish(bias_forward(g, dw, x, centre_bias, neighbour_bias, out, saved, nullptr, st), "nfp_bias_forward");
 }
@@ -1352,14 +733,12 @@ int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.measure == NFP_ATTENTION) {
     // gradient with respect to the dots behind the scratch's coefficient and partial-sum parts, then DotProduct's backward
-    const long long bno = (long long)g.B * g.N * g.O, n = (long long)g.B * g.O;
+    const long long bno = (long long)g.B * g.N * g.O;
     KP gdot = as_dot(g);
     gdot.godtype = NFP_F32;
     float* gd = scratch + bno * bias_coef_floats(gdot) + (long long)g.B * g.C * (g.N + 1);
     if (g.B > 0)
-      if (int rc = launch("attn_softmax_bwd", attn_softmax_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, grad_out,
-                          out, gd))
-        return rc;
+      if (int rc = attn_softmax_backward(g, grad_out, out, gd, st)) return rc;
     const int rc = bias_backward(gdot, dw, x, centre_bias, neighbour_bias, gd, saved, nullptr, grad_x, grad_centre_bias,
                                  grad_neighbour_bias, scratch, st);
     if (rc == NFP_OK) variant_suffix("+attn_softmax");

@@ -1,7 +1,8 @@
-// nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI,
-// table kernels, any-geometry kernels; nfp_tile.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
+// nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI and
+// dispatch; nfp_generic.hip: the any-geometry kernels; nfp_table_fwd.hip / nfp_table_bwd.hip: the table kernels;
+// nfp_tile_fwd.hip / nfp_tile_bwd.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
 // nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_cpool.hip: the heads'
-// compress-BN-ReLU-GAP tail).  Separate
+// compress-BN-ReLU-GAP tail), and the interface of each unit's launchers to the dispatcher (below).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 //
 // Also the one home of "descriptor field -> kernel template argument": with_radius, with_hot, with_measure, with_storage and
@@ -248,6 +249,56 @@ inline const char* hot_name(const KP& g) {
 // launchers (Attention's float32 dots never reach them with bf16 storage).
 inline bool mixed_maps(const KP& g) { return g.dtype == NFP_BF16 && g.odtype == NFP_F32; }
 inline bool force_generic() { return g_sw.force_generic.load(std::memory_order_relaxed) != 0; }
+// the matrix-core kernels (nfp_mfma.h::fwd_gram, nfp_fast.h::bwd_gemm_phase): NFP_MFMA=0 turns them off
+inline bool mfma_enabled() { return g_sw.mfma.load(std::memory_order_relaxed) != 0; }
+
+// Geometry of the hot path: "same" maps (stride 1, dilation 1, pad = R) small enough for one workgroup per image.
+// These are the descriptors that have workspace tables (nfp_tables.h).
+inline bool fast_geometry(const KP& g) {
+  if (g.stride != 1 || g.dil != 1 || g.pad != g.R || g.mode == NFP_PAD_CIRCULAR) return false;
+  if (g.R != 1 && g.R != 2) return false;
+  return g.P <= kBwdThreads && g.P >= 4;
+}
+
+// Which calls the hot-path kernels serve; everything else runs on the generic kernels.
+// sym: also the five measures of nfp_measures.h::kSymTerm (plain single-radius maps only: their callers pass it)
+inline bool fast_ok(const KP& g, const void* x, const void* gx, bool sym = false) {
+  if (force_generic()) return false;
+  if (!fast_geometry(g) || (g.C & 3)) return false;
+  if (!hot_measure(g) && !hot_l1(g) && !(sym && hot_sym(g))) return false;
+  const bool nhwc = g.sC == 1 && g.sW == g.C && g.sH == (long long)g.W * g.C;
+  if (!g.contig && !nhwc) return false;
+  if (!g.contig) {  // vector loads of 4 channels need natural alignment
+    const uintptr_t m = g.dtype == NFP_F32 ? 15 : 7;
+    const int es = g.dtype == NFP_F32 ? 4 : 2;
+    if (((uintptr_t)x & m) || ((uintptr_t)gx & m) || ((g.sB * es) & m) || ((g.gB * es) & m)) return false;
+  }
+  return true;
+}
+
+// ... and the row-band kernels (nfp_tile.h): "same" maps of any size, no tables
+inline bool tile_geometry(const KP& g) {
+  if (g.stride != 1 || g.dil != 1 || g.pad != g.R || g.mode == NFP_PAD_CIRCULAR || g.rs == 12) return false;
+  if (g.R != 1 && g.R != 2) return false;
+  // one thread per padded position: the smallest band (R + 1 rows and its halo) must fit a workgroup
+  if (g.W < 2 * g.R + 2 || g.H < g.R + 1) return false;
+  return (g.W + 2 * g.R) * (3 * g.R + 1) <= 1024;
+}
+inline bool tile_ok(const KP& g, const void* x, const void* gx) {
+  if (force_generic() || !tile_geometry(g) || (g.C & 3)) return false;
+  if (!hot_measure(g) && !hot_l1(g) && !hot_sym(g)) return false;
+  const bool nhwc = g.sC == 1 && g.sW == g.C && g.sH == (long long)g.W * g.C;
+  if (!g.contig && !nhwc) return false;
+  const int es = g.dtype == NFP_F32 ? 4 : 2;
+  // 32-bit buffer offsets inside an image, and room for the "reads zero" offset (nfp_tile.h::Oob)
+  if ((long long)std::max(g.C, g.N) * g.P * es >= 0x7ffffff0LL) return false;
+  if (mixed_maps(g) && (long long)g.N * g.P * 4 >= 0x7ffffff0LL) return false;   // (float32 maps beside bf16 x)
+  if (!g.contig) {
+    const uintptr_t m = g.dtype == NFP_F32 ? 15 : 7;
+    if (((uintptr_t)x & m) || ((uintptr_t)gx & m) || ((g.sB * es) & m) || ((g.gB * es) & m)) return false;
+  }
+  return true;
+}
 inline int round4(int v) { return (v + 3) & ~3; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline const char* pool_tag(int pool) { return pool == nfp::kPoolBoth ? ",pool" : (pool == nfp::kPoolGap ? ",gap" : ""); }
@@ -284,6 +335,13 @@ int with_hot(const KP& g, F&& f) {
     if (hot_sym(g)) return f(Int<kSymTerm>{});
   }
   return hot_product(g) ? f(Int<NFP_COSINE>{}) : f(Int<NFP_NORM>{});
+}
+
+// the fused tail of the launch: none, nfp_pool_* (both pooled sums) or nfp_gap_* (GAP(x) beside the maps)
+template <typename F>
+int with_pool(int pool, F&& f) {
+  if (pool == nfp::kPoolGap) return f(Int<nfp::kPoolGap>{});
+  return pool ? f(Int<nfp::kPoolBoth>{}) : f(Int<nfp::kPoolNone>{});
 }
 
 // every measure with a Meas<> of its own, Norm by its order; Attention and SharpenedCosine (the caller's): kNotApplicable.
@@ -337,11 +395,35 @@ int with_storage_mixed(const KP& g, F&& f) {
     return kNotApplicable;
 }
 
-// ---- the row-band kernels of nfp_tile.h (defined in nfp_tile.hip) -------------------------------------------------------
+// ---- the any-geometry kernels of nfp_gather.h / nfp_direct.h (nfp_generic.hip) -------------------------------------------
+// fwd_pairs, else fwd_direct; bwd_gather, bwd_gather_banded, else bwd_direct — by with_measure: NFP_OK, an NFP_E_* code, or
+// kNotApplicable for the measures with_measure leaves to the caller.  Attention arrives as its DotProduct block
+// (nfp_hip.hip::as_dot); its softmax over the neighbours is the two launches below.
+int generic_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st);
+int generic_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st);
+int attn_softmax_forward(const KP& g, const float* dots, void* out, hipStream_t st);
+int attn_softmax_backward(const KP& g, const void* go, const void* out, float* gd, hipStream_t st);
+
+// ---- the table kernels of nfp_mfma.h / nfp_band.h (nfp_table_fwd.hip) and nfp_fast.h (nfp_table_bwd.hip) ------------------
+// Each returns NFP_OK, kNotApplicable or an NFP_E_* code; g_variant names the launch.  The caller has asked fast_ok; the
+// radius (12: g.rs), the family (with_hot<true>) and the tail (pool, as below) select the instantiation.  Those that exist:
+// plain maps for every family, but not kSymTerm with radius 12; the pooled and gap tails for the cosine and L2 families
+// alone, and kPoolBoth not with radius 12.  fwd_gram and the matrix-core backward: cosine / L2, one radius (its tail is
+// a run-time option of fwd_gram: gap, nfpm or both null).
+template <int R, int M, int POOL>
+constexpr bool kHasTable = POOL == nfp::kPoolNone ? !(R == 12 && M == kSymTerm)
+                                                  : (M == NFP_COSINE || M == NFP_NORM) && !(R == 12 && POOL == nfp::kPoolBoth);
+int table_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap, float* nfpm);
+int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* gap, float* nfpm,
+                   float* part, int* nb);
+// (the matrix-core form first where it exists and applies, else the vector form)
+int table_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
+                   int pool, const float* ggap, const float* gnfpm);
+
+// ---- the row-band kernels of nfp_tile.h (nfp_tile_fwd.hip, nfp_tile_bwd.hip; shared sizing: nfp_tile_launch.h) ------------
 // Each returns NFP_OK, kNotApplicable (this descriptor is not theirs / does not fit) or an NFP_E_* code; g_variant names
 // the launch.  pool: nfp::kPoolNone / kPoolBoth (the fused nfp_pooling tail) / kPoolGap (GAP(x) beside the maps); part = scratch
 // for the bands' partial sums, rows of C + N floats (kPoolGap: C); *nb = rows per image.
-bool tile_ok(const KP& g, const void* x, const void* gx);
 int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
                  float* gap, float* nfpm);
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,

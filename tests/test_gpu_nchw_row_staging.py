@@ -9,7 +9,7 @@ keeps its blocks: nfp_plan says `stage=blocks` for it under either value of the 
 
 Every case runs forward and backward under both values of the switch and asserts that the default arm matches the
 oracle, that its `out` and `grad_x` are bit-identical to the block arm's, and that nfp_plan names the form each arm
-launched.  A backward workgroup owns Cwg channels = Cwg / 4 quads, on G channel groups (csrc/nfp_hip.hip:
+launched.  A backward workgroup owns Cwg channels = Cwg / 4 quads, on G channel groups (csrc/nfp_table_bwd.hip:
 launch_bwd_fast_t); a thread stages ceil(quads / G) slots.  Small batches split the channels down to one quad per
 workgroup, so the small shapes — P % 4 != 0, the smallest map, H != W, one quad, 129 quads (a last workgroup of one quad
 beside two-quad ones), the padding modes, L2 and a VAR measure, a batch stride that is not C * P — run ONE slot per

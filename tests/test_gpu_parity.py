@@ -1504,7 +1504,7 @@ def _load_script(name):
 
 
 def test_random_stress_of_the_table_kernels_at_large_batches(dev):
-    """Batches of 1024+ images run quarter-size workgroups, four per CU, in both passes (csrc/nfp_hip.hip): random small
+    """Batches of 1024+ images run quarter-size workgroups, four per CU, in both passes (csrc/nfp_table_*.hip): random small
     maps, every hot measure incl. Norm p = 1, padding modes, layouts, storage types, plain and pooled, against the
     float64 formulation — NaN patterns included.  scripts/stress_big_batch.py is the long form."""
     import random

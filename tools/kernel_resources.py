@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy of every kernel of one translation unit, from hipcc's resource-usage remarks.
-usage: python tools/kernel_resources.py csrc/nfp_tile.hip [name-filter]"""
+usage: python tools/kernel_resources.py csrc/nfp_tile_fwd.hip [name-filter]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
