@@ -396,6 +396,61 @@ int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t d
                            const void* grad_out, void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta,
                            float* scratch, int64_t scratch_floats, void* hip_stream, int32_t grad_out_layout);
 
+/*
+ * The train-mode step of nfp_cpool_* / nfp_cproj_*_fmt in stages, for BatchNorm statistics taken over the batches of
+ * several ranks (nn.SyncBatchNorm): the caller gathers a small record between the stages, by whatever collective it has —
+ * this library makes none.  A rank is any holder of a share of the batch; B, P and the maps are the rank's own, N and D
+ * everyone's.  kind: NFP_CP_POOL (out [B,D] float32, the ReLU always; relu and the layout are ignored) or NFP_CP_PROJ
+ * (out / grad_out [B,D,P] in the maps' dtype, `relu` and the layout the caller's).  Up to 32 maps; the wide form has no
+ * staged calls.
+ *   nfp_cpsync_moments   the rank's record, float64 [n, mu (N), S (N*N)] = nfp_cpsync_record_doubles(N) doubles: its count
+ *                        n = B*P of values per map, their mean, their scatter about that mean (not divided).  scratch:
+ *                        nfp_cpool_scratch_floats(B, N, P, 1, 0) floats.  2 launches (moments, the join); B = 0 writes the
+ *                        zero record with the join alone
+ *   nfp_cpsync_forward   `records`: the records of `world` ranks, row r rank r's, the same rows in the same order on every
+ *                        rank.  They are joined in rank order in float64 — M = sum n_r, mu = sum n_r mu_r / M,
+ *                        Sigma = sum_r (S_r + n_r d_r d_r') / M with d_r = mu_r - mu — and from there on everything is as in
+ *                        nfp_cpool_forward: inv_d, the running statistics (updated with the counts' sum M, so they come out
+ *                        bitwise equal on every rank) and `saved`, then the rank's rows of `out`.  `saved` holds
+ *                        nfp_cpsync_saved_floats(N, D) = 2N + 2 N*N + D + 1 floats: nfp_cpool_saved_floats' layout, then
+ *                        (float)M, then what Sigma [N*N] loses as a float (the backward's grad_w reads both).
+ *                        global_count: sum n_r where the caller knows it on the host, else 0; it is only checked (the
+ *                        kernels use the records' own counts).  2 launches (the join, the main kernel); B = 0 the join alone
+ *   nfp_cpsync_reduce    the rank's grad_w, grad_gamma, grad_beta (each may be NULL; their sum over the ranks is the batch's
+ *                        gradient) and its row [k (N), Q (N*N)] = nfp_cpsync_kq_floats(N) floats, with M the count over all
+ *                        ranks.  scratch: nfp_cpool_scratch_floats / nfp_cproj_scratch_floats (B, N, P, D, 1).  3 launches;
+ *                        B = 0 one, which writes zeros
+ *   nfp_cpsync_maps      `kq_rows`: the rows of `world` ranks, summed in rank order; grad_maps [B,N,P] of the rank.  1
+ *                        launch; B = 0 none
+ * With world = 1 the stages compute what the one-call entries do, with another summation order in the statistics (the
+ * results agree to float32 rounding, not bitwise).  No atomics: two runs agree bitwise.  nfp_last_variant names
+ * cpsync_moments<f32|bf16> and cpsync_fwd|bwd_reduce|bwd_maps<pool|proj,relu|proj,lin,f32|bf16[,nhwc]>.
+ * NFP_E_INVALID, before any HIP call: a NULL required pointer, a short buffer (every buffer comes with its length),
+ * records not 8-byte aligned, world < 1, an unknown kind, dtype or layout, B < 0, N < 1, P < 1, D < 1, a negative eps or
+ * global_count.  NFP_E_UNSUPPORTED: N > 32, the size limits of nfp_cpool_* / nfp_cproj_*, global_count = 1 (or below this
+ * rank's own count).  A rank's own B*P may be 0 or 1.  Additive to ABI 7.
+ */
+enum nfp_cp_kind { NFP_CP_POOL = 0, NFP_CP_PROJ = 1 };
+int64_t nfp_cpsync_record_doubles(int32_t N);
+int64_t nfp_cpsync_kq_floats(int32_t N);
+int64_t nfp_cpsync_saved_floats(int32_t N, int32_t D);
+int nfp_cpsync_moments(int32_t B, int32_t N, int64_t P, int32_t dtype, const void* maps, double* record, int64_t record_doubles,
+                       float* scratch, int64_t scratch_floats, void* hip_stream);
+int nfp_cpsync_forward(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                       const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                       double momentum, double eps, const double* records, int32_t world, int64_t records_doubles,
+                       int64_t global_count, void* out, float* saved, int64_t saved_floats, void* hip_stream,
+                       int32_t out_layout);
+int nfp_cpsync_reduce(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                      const float* w, const float* gamma, const float* beta, double eps, const float* saved,
+                      int64_t saved_floats, const void* grad_out, float* grad_w, float* grad_gamma, float* grad_beta,
+                      float* kq_row, int64_t kq_floats, float* scratch, int64_t scratch_floats, void* hip_stream,
+                      int32_t grad_out_layout);
+int nfp_cpsync_maps(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                    const float* w, const float* gamma, const float* beta, double eps, const float* saved, int64_t saved_floats,
+                    const void* grad_out, const float* kq_rows, int32_t world, int64_t kq_floats, void* grad_maps,
+                    void* hip_stream, int32_t grad_out_layout);
+
 /* Telemetry: kernels enqueued by this process so far (tests use it to prove
  * the HIP path, not a fallback, produced a result). */
 uint64_t nfp_launch_count(void);

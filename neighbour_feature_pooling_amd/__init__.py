@@ -17,6 +17,8 @@ Drop-in for the reference's NFP hot path:
     NFPInsert                        <- the nfp + nfp_proj block of models/mobilenetv3.py::MOBILENETV3_NFP_INSERT (345-353)
     nfp_compress_map                 its projection [relu](bn(conv1x1(maps))) as one op that keeps the map (models.NFPInsertNet:
                                         the whole net; NFPBottleneck(fused_project=True): the same op without the ReLU)
+                                     (both ops follow an nn.SyncBatchNorm across the ranks of its process group: README,
+                                        "SyncBatchNorm in the fused tails")
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
 from .functional import (NfpConfig, nfp_attention_pool, nfp_compress_map, nfp_compress_map_tensors, nfp_compress_pool,

@@ -28,8 +28,11 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
            "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward",
            "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt",
-           "nfp_cpool_wide_scratch_floats", "nfp_cpool_wide_forward", "nfp_cpool_wide_backward"]
+           "nfp_cpool_wide_scratch_floats", "nfp_cpool_wide_forward", "nfp_cpool_wide_backward",
+           "nfp_cpsync_record_doubles", "nfp_cpsync_kq_floats", "nfp_cpsync_saved_floats", "nfp_cpsync_moments",
+           "nfp_cpsync_forward", "nfp_cpsync_reduce", "nfp_cpsync_maps"]
 ACT_NCHW, ACT_NHWC = 0, 1     # enum nfp_act_layout: out / grad_out of nfp_cproj_*_fmt
+CP_POOL, CP_PROJ = 0, 1       # enum nfp_cp_kind: the first argument of nfp_cpsync_forward / _reduce / _maps
 
 
 class NfpDesc(ctypes.Structure):
@@ -136,6 +139,16 @@ def load():
         L.nfp_cpool_wide_scratch_floats.restype = i64
         L.nfp_cpool_wide_forward.argtypes = L.nfp_cpool_forward.argtypes
         L.nfp_cpool_wide_backward.argtypes = L.nfp_cpool_backward.argtypes
+    if hasattr(L, "nfp_cpsync_forward"):        # (absent only from an older library loaded for an A/B run)
+        i32, f64 = ctypes.c_int32, ctypes.c_double
+        L.nfp_cpsync_record_doubles.argtypes = L.nfp_cpsync_kq_floats.argtypes = [i32]
+        L.nfp_cpsync_saved_floats.argtypes = [i32, i32]
+        L.nfp_cpsync_record_doubles.restype = L.nfp_cpsync_kq_floats.restype = L.nfp_cpsync_saved_floats.restype = i64
+        L.nfp_cpsync_moments.argtypes = [i32, i32, i64, i32, vp, vp, i64, vp, i64, vp]
+        head = [i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp]      # kind, B, N, P, D, dtype, relu, maps, w, gamma, beta
+        L.nfp_cpsync_forward.argtypes = head + [vp, vp, f64, f64, vp, i32, i64, i64, vp, vp, i64, vp, i32]
+        L.nfp_cpsync_reduce.argtypes = head + [f64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i32]
+        L.nfp_cpsync_maps.argtypes = head + [f64, vp, i64, vp, vp, i32, i64, vp, vp, i32]
     if L.nfp_abi_version() != ABI_VERSION:
         raise NfpError(f"libnfp_hip.so ABI {L.nfp_abi_version()} != binding {ABI_VERSION}; rebuild")
     _lib = L

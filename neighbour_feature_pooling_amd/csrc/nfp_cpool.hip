@@ -44,6 +44,15 @@
 // the same launches): cproj_fwd_nhwc — the same chain per element, lanes along the chunk's [p][d] range — and the NHWC
 // instantiations of cproj_bwd_part / cproj_bwd_maps, which bring their grad_out tile into LDS with d fastest and are the
 // NCHW kernels behind that: the same sums in the same order.
+//
+// Statistics over the batches of several ranks (nn.SyncBatchNorm) — nfp_cpsync_*: the same step in four stages around two
+// gathers the caller makes.  The main forward, *_bwd_part and *_bwd_maps kernels above serve unchanged; what is added:
+//   cps_record      cpool_finish's join of the rank's chunks, kept as a float64 record [count, mean, scatter about it]
+//   cps_finish      cpool_finish on the records of all ranks, joined in rank order (within plus between, exact); leaves the
+//                   global count and Sigma's second float behind inv for the backward
+//   cpool_bwd_reduce<., SYNC>  divides by that count, and forms Sigma w from both floats
+//   cps_kq_row      the workgroups' shares of k, Q summed into the rank's row; *_bwd_maps then read the ranks' rows
+//   cps_zero        a rank without an image: a zero row, zero parameter gradients
 #include "nfp_launch.h"
 
 #include <cmath>
@@ -182,13 +191,12 @@ __global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
   }
 }
 
-// grid = ceil(D / 1024), block = 1024; every workgroup joins the chunks itself (the same sums in the same order).  The chunks
-// are dealt to slices of consecutive chunks — 32 slices for mu, 1024 / N^2 for Sigma — whose sums are joined in slice order:
-// one thread walking all B * nc chunks is a chain of dependent global loads (measured: 100 us at 64 chunks).
-__global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
-  __shared__ double mu[kCpMaxN];
-  __shared__ double sig[kCpMaxN * kCpMaxN];   // [32][32], zero beyond N
-  __shared__ double red[kCpFT];
+// The join of a rank's B * nc chunk records, by the 1024 threads of a workgroup (red[1024], mu[32], sig[32][32], zero beyond
+// N).  The chunks are dealt to slices of consecutive chunks — 32 slices for mu, 1024 / N^2 for Sigma — whose sums are joined
+// in slice order: one thread walking all B * nc chunks is a chain of dependent global loads (measured: 100 us at 64 chunks).
+// RECORD (cps_record): sig keeps the scatter about mu undivided, and a rank without a chunk has mu = 0.
+template <bool RECORD>
+__device__ __forceinline__ void cp_join_chunks(const CpK& k, double* mu, double* sig, double* red) {
   const int tid = threadIdx.x, N = k.N, NN = N * N, K = k.B * k.nc, rec = 2 * N + NN;
   const int last = k.P - (k.nc - 1) * k.CH;   // pixels of an image's last chunk
   {
@@ -211,7 +219,7 @@ __global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
     if (tid < N) {
       double t = red[tid];
       for (int i = 1; i < 32; ++i) t += red[i * 32 + tid];
-      mu[tid] = t / k.M;
+      mu[tid] = RECORD && K == 0 ? 0.0 : t / k.M;
     }
     __syncthreads();
   }
@@ -237,10 +245,16 @@ __global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
     if (tid < NN) {
       double t = red[tid];
       for (int i = 1; i < nsl; ++i) t += red[i * NN + tid];
-      sig[n * kCpMaxN + n2] = t / k.M;
+      sig[n * kCpMaxN + n2] = RECORD ? t : t / k.M;
     }
     __syncthreads();
   }
+}
+
+// What follows mu and Sigma over M values per channel: they go to stats_w (workgroup 0), and channel d = blockIdx.x * 1024 +
+// tid gets w_d' Sigma w_d, inv_d and its running statistics.
+__device__ __forceinline__ void cp_finish_channels(const CpK& k, const double* mu, const double* sig, double M) {
+  const int tid = threadIdx.x, N = k.N, NN = N * N;
   if (blockIdx.x == 0) {
     if (tid < N) {
       const float hi = (float)mu[tid];
@@ -270,7 +284,98 @@ __global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
   k.stats_w[2 * N + NN + d] = (float)(1.0 / sqrt(var + k.eps64));
   if (k.rm_w != nullptr) {
     k.rm_w[d] = (float)((1.0 - k.mom) * (double)k.rm_w[d] + k.mom * mean);
-    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (k.M / (k.M - 1.0)));
+    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (M / (M - 1.0)));
+  }
+}
+
+// grid = ceil(D / 1024), block = 1024; every workgroup joins the chunks itself (the same sums in the same order).
+__global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
+  __shared__ double mu[kCpMaxN];
+  __shared__ double sig[kCpMaxN * kCpMaxN];   // [32][32], zero beyond N
+  __shared__ double red[kCpFT];
+  cp_join_chunks<false>(k, mu, sig, red);
+  cp_finish_channels(k, mu, sig, k.M);
+}
+
+// ---- the statistics across ranks (nfp_cpsync_*) ----------------------------------------------------------------------------
+// A rank's record, float64: [n, mu (N), S (N * N)] — its count of values per map, their mean, and their scatter about that
+// mean, not divided.  grid = 1, block = 1024: cpool_finish's join of the rank's chunk records; a rank without an image
+// (B = 0: no chunk) writes n = 0, mu = 0, S = 0.
+__global__ void __launch_bounds__(kCpFT) cps_record(CpK k, double* rec) {
+  __shared__ double mu[kCpMaxN];
+  __shared__ double sig[kCpMaxN * kCpMaxN];
+  __shared__ double red[kCpFT];
+  cp_join_chunks<true>(k, mu, sig, red);
+  const int tid = threadIdx.x, N = k.N, NN = N * N;
+  if (tid == 0) rec[0] = k.M;
+  if (tid < N) rec[1 + tid] = mu[tid];
+  if (tid < NN) rec[1 + N + tid] = sig[(tid / N) * kCpMaxN + tid % N];
+}
+
+// grid = ceil(D / 1024), block = 1024: cpool_finish over the records of `world` ranks instead of one rank's chunks, joined
+// in rank order by every workgroup (the same sums in the same order on every rank that holds the same records):
+//   M = sum n_r      mu = sum n_r mu_r / M      Sigma = sum_r (S_r + n_r d_r d_r') / M,  d_r = mu_r - mu
+// stats_w takes more than cpool_finish writes, behind inv [D]: (float)M, the count the backward divides by, and what
+// Sigma [N * N] loses as a float.  Ranks whose means lie far apart put the variance into the between-rank term — every
+// entry of Sigma large, the differences between them small — and grad_w, a difference of T and Sigma w, needs both floats
+// (means of +-100 at unit spread: 1.1e-4 of max|grad_w| with one, measured).
+__global__ void __launch_bounds__(kCpFT) cps_finish(CpK k, const double* recs, int world) {
+  __shared__ double mu[kCpMaxN];
+  __shared__ double sig[kCpMaxN * kCpMaxN];
+  const int tid = threadIdx.x, N = k.N, NN = N * N, rec = 1 + N + NN;
+  double M = 0.0;   // (every thread: the same loads, the same order)
+  for (int r = 0; r < world; ++r) M += recs[(long long)r * rec];
+  sig[tid] = 0.0;
+  if (tid < N) {
+    double s = 0.0;
+    for (int r = 0; r < world; ++r) s += recs[(long long)r * rec] * recs[(long long)r * rec + 1 + tid];
+    mu[tid] = s / M;
+  }
+  __syncthreads();
+  if (tid < NN) {
+    const int n = tid / N, n2 = tid - n * N;
+    const double m1 = mu[n], m2 = mu[n2];
+    double s = 0.0;
+    for (int r = 0; r < world; ++r) {
+      const double* R = recs + (long long)r * rec;
+      const double d1 = R[1 + n] - m1, d2 = R[1 + n2] - m2;
+      s += R[1 + N + tid] + R[0] * (d1 * d2);
+    }
+    sig[n * kCpMaxN + n2] = s / M;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0) {
+    float* tail = k.stats_w + 2 * N + NN + k.D;
+    if (tid == 0) tail[0] = (float)M;
+    if (tid < NN) {
+      const double s = sig[(tid / N) * kCpMaxN + tid % N];
+      tail[1 + tid] = (float)(s - (double)(float)s);
+    }
+  }
+  cp_finish_channels(k, mu, sig, M);
+}
+
+// A rank's row [k (N), Q (N * N)]: the shares of cpool_bwd_reduce's workgroups, summed in workgroup order as the *_bwd_maps
+// kernels sum them.  Those kernels then read the ranks' rows where they read the workgroups' shares.  grid = 1, block = 256.
+__global__ void __launch_bounds__(kCpMT) cps_kq_row(CpK k, float* row) {
+  const int L = k.N + k.N * k.N;
+  for (int i = threadIdx.x; i < L; i += kCpMT) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * L + i];
+    row[i] = s;
+  }
+}
+
+// What a rank without an image contributes backward: a zero row and zero parameter gradients (those that are asked for).
+// grid-stride, block = 256.
+__global__ void __launch_bounds__(kCpMT) cps_zero(CpK k, float* row) {
+  const long long L = k.N + k.N * k.N, DN = (long long)k.D * k.N, end = L > DN ? L : DN;
+  for (long long i = (long long)blockIdx.x * kCpMT + threadIdx.x; i < end; i += (long long)gridDim.x * kCpMT) {
+    if (i < L) row[i] = 0.f;
+    if (i < DN && k.gw != nullptr) k.gw[i] = 0.f;
+    if (i < k.D && k.gg != nullptr) k.gg[i] = 0.f;
+    if (i < k.D && k.gb != nullptr) k.gb[i] = 0.f;
   }
 }
 
@@ -432,7 +537,9 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
 // grid = ceil(D / 32), block = 256.  kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
 // LIVE (the cproj backward, whose S reaches 512): loads are issued only from the element rounds and lanes that hold an
 // element; the sums and their order are the same in both forms.
-template <bool LIVE>
+// SYNC (nfp_cpsync_reduce): the slices are one rank's, and e and f divide by the count over all ranks, which cps_finish
+// left behind inv in stats.
+template <bool LIVE, bool SYNC = false>
 __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
   __shared__ float Tl[kCpRT * (kCpMaxN + 1)];
   __shared__ float wl[kCpRT * kCpMaxN];
@@ -511,8 +618,9 @@ __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
       for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * kCpMaxN + n], Tl[tid * (kCpMaxN + 1) + n], dot);
       gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
       if (!k.eval) {
-        e = c1 * (gb / (float)k.M);
-        f = c1 * (gg * inv / (float)k.M);
+        const float M = SYNC ? cp_inv(k)[k.D] : (float)k.M;
+        e = c1 * (gb / M);
+        f = c1 * (gg * inv / M);
       }
       if (k.gg != nullptr) k.gg[d] = gg;
       if (k.gb != nullptr) k.gb[d] = gb;
@@ -531,7 +639,14 @@ __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
       float t = Tl[dl * (kCpMaxN + 1) + n];
       if (!k.eval) {
         float sw = 0.f;
-        for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * kCpMaxN + n2], sw);
+        if constexpr (SYNC) {   // Sigma as cps_finish left it, two floats an entry, summed in float64
+          const float* lo = cp_inv(k) + k.D + 1;
+          double s64 = 0.0;
+          for (int n2 = 0; n2 < N; ++n2) s64 += ((double)sg[n * N + n2] + (double)lo[n * N + n2]) * (double)wl[dl * kCpMaxN + n2];
+          sw = (float)s64;
+        } else {
+          for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * kCpMaxN + n2], sw);
+        }
         t -= ggl[dl] * invl[dl] * sw;
       }
       k.gw[(long long)d * N + n] = c1l[dl] * t;
@@ -1783,14 +1898,16 @@ struct CpCall {
   const void* go;
   void* gm;
   float *gw, *gg, *gb;
+  int32_t sync;   // nfp_cpsync_*: the statistics are those of all ranks, so this rank's B * P may be 0 or 1
 };
 
 // The refusals both directions share, in order: layout, sizes, pointers (io: the forward's out, the backward's grad_out)
 int cp_check(const CpCall& c, const void* io) {
   if (c.kind == kCpProj)
     if (int rc = cproj_layout(c.what, c.layout)) return rc;
-  if (int rc = c.kind == kCpProj ? cproj_args(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training)
-                                 : cpool_args(c.what, c.B, c.N, c.P, c.D, c.dtype, c.training, c.kind == kCpWide))
+  const int own = c.training && !c.sync;   // (the statistics come from this call's maps alone)
+  if (int rc = c.kind == kCpProj ? cproj_args(c.what, c.B, c.N, c.P, c.D, c.dtype, own)
+                                 : cpool_args(c.what, c.B, c.N, c.P, c.D, c.dtype, own, c.kind == kCpWide))
     return rc;
   if (!c.w || !c.gamma || !c.beta || (c.B > 0 && (!c.maps || !io))) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
   return NFP_OK;
@@ -1967,6 +2084,143 @@ int cp_backward(CpCall c, const float* running_mean, const float* running_var, c
   return cp_backward(c);
 }
 
+// ---- the staged calls of a step whose statistics span ranks (nfp_cpsync_*) ----
+int64_t cps_record_len(int32_t N) { return 1 + (int64_t)N + (int64_t)N * N; }
+int64_t cps_row_len(int32_t N) { return (int64_t)N + (int64_t)N * N; }
+
+// What the four calls of a kind share behind cp_check: the kind itself, eps, and `saved` with its length
+int cps_check(const CpCall& c, int32_t kind, const void* io, const float* saved) {
+  if (kind != NFP_CP_POOL && kind != NFP_CP_PROJ)
+    return fail(NFP_E_INVALID, "%s: unknown kind %d (NFP_CP_POOL = 0, NFP_CP_PROJ = 1)", c.what, kind);
+  if (int rc = cp_check(c, io)) return rc;
+  if (!(c.eps >= 0.0)) return fail(NFP_E_INVALID, "%s: eps = %g", c.what, c.eps);
+  if (saved == nullptr || c.saved_floats < nfp_cpsync_saved_floats(c.N, c.D))
+    return fail(NFP_E_INVALID, "%s: saved holds %lld floats, nfp_cpsync_saved_floats is %lld", c.what,
+                (long long)(saved ? c.saved_floats : 0), (long long)nfp_cpsync_saved_floats(c.N, c.D));
+  return NFP_OK;
+}
+// `world` gathered rows of `len` elements each, behind a pointer aligned to `align` bytes
+int cps_rows(const char* what, const char* name, const void* p, int32_t world, int64_t have, int64_t len, size_t align) {
+  if (world < 1) return fail(NFP_E_INVALID, "%s: world = %d ranks", what, world);
+  if (p == nullptr || have < (int64_t)world * len)
+    return fail(NFP_E_INVALID, "%s: %s holds %lld elements, %d ranks need %lld", what, name, (long long)(p ? have : 0), world,
+                (long long)world * len);
+  if ((uintptr_t)p % align != 0) return fail(NFP_E_INVALID, "%s: %s is not aligned to %zu bytes", what, name, align);
+  return NFP_OK;
+}
+void cps_variant(const CpCall& c, const char* stage) {
+  snprintf(g_variant, sizeof(g_variant), "cpsync_%s<%s,%s%s>", stage, c.kind == kCpPool ? "pool" : c.relu ? "proj,relu" : "proj,lin",
+           c.dtype == NFP_BF16 ? "bf16" : "f32", c.kind == kCpProj && c.layout == NFP_ACT_NHWC ? ",nhwc" : "");
+}
+
+int cps_moments(const CpCall& c, double* record, int64_t record_doubles) {
+  if (int rc = cpool_args(c.what, c.B, c.N, c.P, 1, c.dtype, 0)) return rc;
+  if (c.B > 0 && c.maps == nullptr) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
+  if (int rc = cps_rows(c.what, "record", record, 1, record_doubles, cps_record_len(c.N), sizeof(double))) return rc;
+  if (int rc = cp_check_scratch(c, 0)) return rc;
+  nfp::CpK k = cpool_k(c.B, c.N, c.P, 1, c.dtype, 1);
+  k.maps = c.maps, k.part_w = c.scratch, k.part = c.scratch;
+  hipStream_t st = (hipStream_t)c.stream;
+  snprintf(g_variant, sizeof(g_variant), "cpsync_moments<%s>", c.dtype == NFP_BF16 ? "bf16" : "f32");
+  const int NP = cpool_np(c.N);
+  int rc = NFP_OK;
+  if (c.B > 0) {
+    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
+    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
+  }
+  if (rc == NFP_OK) rc = launch("cps_record", nfp::cps_record, dim3(1), dim3(nfp::kCpFT), 0, st, k, record);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int cps_forward(const CpCall& c, int32_t kind, const double* records, int32_t world, int64_t records_doubles,
+                int64_t global_count) {
+  const bool proj = c.kind == kCpProj;
+  if (int rc = cps_check(c, kind, c.out, c.saved_w)) return rc;
+  if ((c.rm_w == nullptr) != (c.rv_w == nullptr))
+    return fail(NFP_E_INVALID, "%s: running_mean and running_var come together", c.what);
+  if (!(c.momentum == c.momentum)) return fail(NFP_E_INVALID, "%s: momentum = %g", c.what, c.momentum);
+  if (int rc = cps_rows(c.what, "records", records, world, records_doubles, cps_record_len(c.N), sizeof(double))) return rc;
+  if (global_count < 0) return fail(NFP_E_INVALID, "%s: global_count = %lld", c.what, (long long)global_count);
+  if (global_count == 1 || (global_count > 0 && global_count < (int64_t)c.B * c.P))
+    return fail(NFP_E_UNSUPPORTED, "%s: train-mode statistics need 2 values per channel over all ranks and no fewer than this "
+                "rank's %lld, got global_count = %lld", c.what, (long long)c.B * (long long)c.P, (long long)global_count);
+  nfp::CpK k = cp_k(c);
+  const int NP = cpool_np(c.N);
+  k.mom = c.momentum;
+  k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
+  if (proj)
+    k.outv = c.out;
+  else
+    k.out = (float*)c.out;
+  hipStream_t st = (hipStream_t)c.stream;
+  cps_variant(c, "fwd");
+  int rc = launch("cps_finish", nfp::cps_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k,
+                  records, (int)world);
+  if (proj && c.B > 0)   // (cproj_fwd's own chunks)
+    k.CH = cproj_fwd_chunk(NP, c.B, c.P, c.D), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
+  if (rc == NFP_OK && c.B > 0)
+    rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, c.layout == NFP_ACT_NHWC, k, st) : cpool_by_np<LFwd>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int cps_reduce(const CpCall& c, int32_t kind, float* kq_row, int64_t kq_floats) {
+  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
+  if (int rc = cps_check(c, kind, c.go, c.saved)) return rc;
+  if (int rc = cps_rows(c.what, "kq_row", kq_row, 1, kq_floats, cps_row_len(c.N), sizeof(float))) return rc;
+  if (int rc = cp_check_scratch(c, 1)) return rc;
+  nfp::CpK k = cp_k(c);
+  const int NP = cpool_np(c.N);
+  k.stats = c.saved, k.gw = c.gw, k.gg = c.gg, k.gb = c.gb;
+  hipStream_t st = (hipStream_t)c.stream;
+  cps_variant(c, "bwd_reduce");
+  int rc;
+  if (c.B == 0) {
+    const long long n = std::max<long long>((long long)c.D * c.N, cps_row_len(c.N));
+    rc = launch("cps_zero", nfp::cps_zero, dim3((unsigned)std::min<long long>(1024, (n + nfp::kCpMT - 1) / nfp::kCpMT)),
+                dim3(nfp::kCpMT), 0, st, k, kq_row);
+  } else {
+    if (proj) {
+      k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                   // cproj_bwd_part's passes
+      k.ipw = cproj_upw(c.B, c.P, c.D), k.S = cproj_slices(c.B, c.P, c.D);     // ... and how many of them a workgroup takes
+      k.gov = c.go;
+    } else {
+      k.go = (const float*)c.go;
+    }
+    k.part_w = c.scratch, k.part = c.scratch;
+    k.kq_w = c.scratch + (int64_t)k.S * c.D * (c.N + 1), k.kq = k.kq_w;
+    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LPart>(NP, k, st);
+    if (rc == NFP_OK)
+      rc = proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true, true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
+                : launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false, true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
+    if (rc == NFP_OK) rc = launch("cps_kq_row", nfp::cps_kq_row, dim3(1), dim3(nfp::kCpMT), 0, st, k, kq_row);
+  }
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
+int cps_maps(const CpCall& c, int32_t kind, const float* kq_rows, int32_t world, int64_t kq_floats) {
+  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
+  if (int rc = cps_check(c, kind, c.go, c.saved)) return rc;
+  if (int rc = cps_rows(c.what, "kq_rows", kq_rows, world, kq_floats, cps_row_len(c.N), sizeof(float))) return rc;
+  if (c.B > 0 && c.gm == nullptr) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
+  if (c.B == 0) return NFP_OK;
+  nfp::CpK k = cp_k(c);
+  const int NP = cpool_np(c.N);
+  k.stats = c.saved, k.gm = c.gm;
+  if (proj)
+    k.gov = c.go;
+  else
+    k.go = (const float*)c.go;
+  k.kq = kq_rows, k.ntr = world;   // (the ranks' rows, summed in rank order where the workgroups' shares are)
+  hipStream_t st = (hipStream_t)c.stream;
+  cps_variant(c, "bwd_maps");
+  const int rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LMaps>(NP, k, st);
+  if (rc == NFP_OK) publish_variant();
+  return rc;
+}
+
 }  // namespace
 }  // namespace nfp_host
 
@@ -2071,5 +2325,57 @@ int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
   const CpCall c{"nfp_cproj_backward", kCpProj, NFP_ACT_NCHW, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
                  saved_floats, scratch, scratch_floats, hip_stream};
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
+}
+
+// ---- nfp_cpsync_*: a CpCall in training mode with `sync` set; the pooled kind is always NCHW with the ReLU ----
+
+int64_t nfp_cpsync_record_doubles(int32_t N) { return N < 1 ? 1 : cps_record_len(N); }
+int64_t nfp_cpsync_kq_floats(int32_t N) { return N < 1 ? 1 : cps_row_len(N); }
+int64_t nfp_cpsync_saved_floats(int32_t N, int32_t D) {
+  if (N < 1 || D < 1) return 1;
+  return nfp_cpool_saved_floats(N, D) + 1 + (int64_t)N * N;
+}
+
+int nfp_cpsync_moments(int32_t B, int32_t N, int64_t P, int32_t dtype, const void* maps, double* record, int64_t record_doubles,
+                       float* scratch, int64_t scratch_floats, void* hip_stream) {
+  CpCall c{"nfp_cpsync_moments", kCpPool, NFP_ACT_NCHW, 1, B, N, P, 1, dtype, 1, maps, nullptr, nullptr, nullptr, 0.0, 0, scratch,
+           scratch_floats, hip_stream};
+  c.sync = 1;
+  return cps_moments(c, record, record_doubles);
+}
+
+int nfp_cpsync_forward(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                       const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                       double momentum, double eps, const double* records, int32_t world, int64_t records_doubles,
+                       int64_t global_count, void* out, float* saved, int64_t saved_floats, void* hip_stream,
+                       int32_t out_layout) {
+  const bool proj = kind == NFP_CP_PROJ;
+  CpCall c{"nfp_cpsync_forward", proj ? kCpProj : kCpPool, proj ? out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype, 1,
+           maps, w, gamma, beta, eps, saved_floats, nullptr, 0, hip_stream};
+  c.sync = 1, c.rm_w = running_mean, c.rv_w = running_var, c.momentum = momentum, c.out = out, c.saved_w = saved;
+  return cps_forward(c, kind, records, world, records_doubles, global_count);
+}
+
+int nfp_cpsync_reduce(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                      const float* w, const float* gamma, const float* beta, double eps, const float* saved,
+                      int64_t saved_floats, const void* grad_out, float* grad_w, float* grad_gamma, float* grad_beta,
+                      float* kq_row, int64_t kq_floats, float* scratch, int64_t scratch_floats, void* hip_stream,
+                      int32_t grad_out_layout) {
+  const bool proj = kind == NFP_CP_PROJ;
+  CpCall c{"nfp_cpsync_reduce", proj ? kCpProj : kCpPool, proj ? grad_out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype,
+           1, maps, w, gamma, beta, eps, saved_floats, scratch, scratch_floats, hip_stream};
+  c.sync = 1, c.saved = saved, c.go = grad_out, c.gw = grad_w, c.gg = grad_gamma, c.gb = grad_beta;
+  return cps_reduce(c, kind, kq_row, kq_floats);
+}
+
+int nfp_cpsync_maps(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu, const void* maps,
+                    const float* w, const float* gamma, const float* beta, double eps, const float* saved, int64_t saved_floats,
+                    const void* grad_out, const float* kq_rows, int32_t world, int64_t kq_floats, void* grad_maps,
+                    void* hip_stream, int32_t grad_out_layout) {
+  const bool proj = kind == NFP_CP_PROJ;
+  CpCall c{"nfp_cpsync_maps", proj ? kCpProj : kCpPool, proj ? grad_out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype, 1,
+           maps, w, gamma, beta, eps, saved_floats, nullptr, 0, hip_stream};
+  c.sync = 1, c.saved = saved, c.go = grad_out, c.gm = grad_maps;
+  return cps_maps(c, kind, kq_rows, world, kq_floats);
 }
 }  // extern "C"

@@ -1270,7 +1270,8 @@ def _cpool_kind(maps, gamma, beta, momentum):
     return None
 
 
-def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5):
+def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5,
+                              *, process_group=None):
     """`nfp_compress_pool` on loose tensors: maps [B,N,H,W] (or [B,N,P]) -> [B,D] = GAP(relu(batch_norm(conv1x1(maps)))), the
     1x1 conv given by weight ([D,N,1,1] or [D,N]), the BatchNorm by gamma / beta [D] (None: affine=False), its running
     statistics (updated in place when use_batch_stats; both None: not tracked) and `momentum` — the exponential factor
@@ -1279,8 +1280,12 @@ def nfp_compress_pool_tensors(maps, weight, gamma, beta, running_mean, running_v
     the [B,D,H,W] activation (include/nfp.h: nfp_cpool_*; float32 arithmetic, the result cast once to the maps' dtype);
     where it does not and `cpool_wide_serves` (33 to 96 maps under NFP_CPOOL_TORCH=0), the wide kernels: five launches
     forward, at most three backward (nfp_cpool_wide_*); everything else — by default also more than 8 maps, see
-    cpool_hip_serves — is `_host.compress_pool_host`."""
+    cpool_hip_serves — is `_host.compress_pool_host`.
+    process_group: a torch.distributed group of more than one rank over whose batches the batch statistics are taken
+    (`_cp_sync_tensors_call`); None, a one-rank group or use_batch_stats=False: this rank's alone, as above."""
     _cp_check_args("nfp_compress_pool", maps, weight, use_batch_stats, running_mean, running_var)
+    if _cp_sync_applies(process_group, use_batch_stats):
+        return _cp_sync_tensors_call("pool", maps, weight, gamma, beta, running_mean, running_var, momentum, eps, process_group)
     kind = _cpool_kind(maps, gamma, beta, momentum)
     prepared = kind and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats)
     if not prepared:
@@ -1296,8 +1301,14 @@ def nfp_compress_pool(maps, weight, bn, training=None):
     MultiRadiusNFPHead 98-102,114-115; AdaptiveFusionNFP 301-305,323-324): maps [B,N,H,W] -> [B,D] =
     GAP(relu(bn(conv1x1(maps)))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its nn.BatchNorm2d — whose mode
     (`training`: None = bn.training), running statistics and num_batches_tracked are used and updated exactly as
-    bn.forward does.  See nfp_compress_pool_tensors."""
-    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, bn.training if training is None else bool(training))
+    bn.forward does.  An nn.SyncBatchNorm takes its batch statistics over every rank of its process group where
+    SyncBatchNorm.forward would (cp_sync_group): see "SyncBatchNorm in the two tails" below.
+    See nfp_compress_pool_tensors."""
+    training = bn.training if training is None else bool(training)
+    group = cp_sync_group(bn, training)         # (asked before the step counter moves)
+    if group is not None:
+        return _cp_sync_module_call("pool", maps, weight, bn, training, group)
+    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, training)
     if factor is not None:
         return compress_pool_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps)
     return nfp_compress_pool_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps)
@@ -1405,7 +1416,7 @@ def cproj_hip_serves(maps, weight, gamma, beta, momentum, use_batch_stats=True, 
 
 
 def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum=0.1, eps=1e-5,
-                             relu=True, *, memory_format=torch.contiguous_format):
+                             relu=True, *, memory_format=torch.contiguous_format, process_group=None):
     """`nfp_compress_map` on loose tensors: maps [B,N,H,W] (or [B,N,P]) -> [B,D,H,W] ([B,D,P]) =
     [relu](batch_norm(conv1x1(maps))), the arguments those of nfp_compress_pool_tensors plus `relu`.  Where
     `cproj_hip_serves`, three HIP launches forward and at most three backward: the [B,D,H,W] result is stored once, and the
@@ -1416,9 +1427,13 @@ def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_va
     memory_format: torch.contiguous_format (the default) or torch.channels_last — the same [B,D,H,W] values, dense
     channels-last, for a network that runs in that format: the kernels store them so and read a channels-last grad_out as
     it comes, without a converting copy either way; the composition's result is converted.  It needs [B,N,H,W] maps, which
-    themselves stay NCHW; ValueError otherwise, and for any other value."""
+    themselves stay NCHW; ValueError otherwise, and for any other value.
+    process_group: as in nfp_compress_pool_tensors."""
     channels_last = _cproj_memory_format(memory_format, maps)
     _cp_check_args("nfp_compress_map", maps, weight, use_batch_stats, running_mean, running_var)
+    if _cp_sync_applies(process_group, use_batch_stats):
+        return _cp_sync_tensors_call("proj", maps, weight, gamma, beta, running_mean, running_var, momentum, eps, process_group,
+                                     relu, channels_last)
     need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (maps, weight, gamma, beta))
     prepared = (cproj_hip_serves(maps, weight, gamma, beta, momentum, bool(use_batch_stats), need_grad, channels_last)
                 and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats))
@@ -1435,11 +1450,256 @@ def nfp_compress_map(maps, weight, bn, relu=True, training=None, *, memory_forma
     maps [B,N,H,W] -> [B,D,H,W] = [relu](bn(conv1x1(maps))), `weight` the 1x1 conv's ([D,N,1,1], no bias) and `bn` its
     nn.BatchNorm2d — whose mode (`training`: None = bn.training), running statistics and num_batches_tracked are used and
     updated exactly as bn.forward does.  memory_format: torch.contiguous_format or torch.channels_last, the layout of the
-    result.  See nfp_compress_map_tensors."""
+    result.  An nn.SyncBatchNorm synchronises as in nfp_compress_pool.  See nfp_compress_map_tensors."""
     channels_last = _cproj_memory_format(memory_format, maps)       # (refused before the step counter moves)
-    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, bn.training if training is None else bool(training))
+    training = bn.training if training is None else bool(training)
+    group = cp_sync_group(bn, training)
+    if group is not None:
+        return _cp_sync_module_call("proj", maps, weight, bn, training, group, relu, channels_last)
+    use_batch_stats, rm, rv, factor = _bn_call_mode(bn, training)
     if factor is not None:
         y = compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
         return y.contiguous(memory_format=torch.channels_last) if channels_last else y
     return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu,
                                     memory_format=memory_format)
+
+
+# ---- SyncBatchNorm in the two tails — include/nfp.h: nfp_cpsync_* (DESIGN 4h) ----
+# The batch statistics of the tail come from the mean and covariance of the N maps, so a rank hands the others 1 + N + N*N
+# float64 numbers forward (its count, mean and scatter) and N + N*N float32 backward (its share of k and Q) — and gets every
+# rank's back, joined in rank order by the same kernel from the same bits on all of them.
+def cp_sync_group(bn, training=None):
+    """The process group over whose ranks one call of `bn` in mode `training` (None: bn.training) takes its batch
+    statistics, or None where the call is rank-local — the rule of nn.SyncBatchNorm.forward: an nn.SyncBatchNorm, in
+    training mode, torch.distributed available and initialised, and more than one rank in bn.process_group (None: WORLD)."""
+    if not isinstance(bn, torch.nn.SyncBatchNorm):
+        return None
+    dist = torch.distributed
+    if not (bn.training if training is None else training) or not dist.is_available() or not dist.is_initialized():
+        return None
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group if dist.get_world_size(group) > 1 else None
+
+
+def _cp_sync_applies(process_group, use_batch_stats):
+    """cp_sync_group's rule for the loose-tensor forms, which are handed the group."""
+    return bool(process_group is not None and use_batch_stats and torch.distributed.get_world_size(process_group) > 1)
+
+
+def cp_sync_serves(kind, maps, gamma, beta, momentum):
+    """The staged kernels (nfp_cpsync_*) take a call of `kind` ("pool" or "proj") whose statistics span a process group.
+    Every rank of the group must answer alike — ranks that disagree would enter different collectives and hang — so the
+    answer reads only what the ranks share: the device type, dtype and number of maps, affine parameters and a float
+    momentum, torch.compile / torch.autocast, and NFP_CPOOL_TORCH / NFP_CPROJ_TORCH ("1": the composition; "0": the
+    kernels up to 32 maps; unset: up to 8).  It never reads the local batch or map size: an empty rank, a rank with one
+    pixel and a rank with thousands take the same route, and the pixel-count thresholds of cproj_hip_serves do not apply.
+    For "proj" that default is a decision — the form that exchanges 73 + 72 numbers at 8 maps where SyncBatchNorm exchanges
+    2 D + 1 and 2 D — not a measurement: no run over more than one GPU has been made."""
+    env = os.environ.get("NFP_CPROJ_TORCH" if kind == "proj" else "NFP_CPOOL_TORCH")
+    if env == "1" or torch.compiler.is_compiling() or not maps.is_cuda or torch.is_autocast_enabled("cuda"):
+        return False
+    if maps.dtype not in _DTYPES or gamma is None or beta is None or not isinstance(momentum, float):
+        return False
+    return 1 <= maps.shape[1] <= (CPOOL_MAX_MAPS if env == "0" else CPOOL_ROUTED_MAPS)
+
+
+def _cps_sizes(maps, D):
+    """(B, N, P, D) of a rank's maps [B,N,...]; a rank without a value is B = 0 with one pixel."""
+    B, N = maps.shape[:2]
+    P = 1
+    for s in maps.shape[2:]:
+        P *= s
+    return (B, N, P, D) if P > 0 else (0, N, 1, D)
+
+
+def _cps_head(kind, maps, w, gamma, beta, relu):
+    B, N, P, D = _cps_sizes(maps, w.shape[0])
+    return [_abi.CP_PROJ if kind == "proj" else _abi.CP_POOL, B, N, P, D, _DTYPES[maps.dtype], int(bool(relu)), _ptr(maps),
+            w.data_ptr(), gamma.data_ptr(), beta.data_ptr()]
+
+
+def _ptr0(t):
+    return (t.data_ptr() or None) if t is not None else None
+
+
+def cp_sync_moments_call(maps):
+    """A rank's record from nfp_cpsync_moments: float64 [1 + N + N*N] — count, mean and scatter of its dense CUDA maps
+    [B,N,...], B = 0 included."""
+    L = _abi.load()
+    B, N, P, _ = _cps_sizes(maps, 1)
+    with _on_device(maps.device):
+        nr = int(L.nfp_cpsync_record_doubles(N))
+        record = torch.empty(nr, dtype=torch.float64, device=maps.device)
+        ns = int(L.nfp_cpool_scratch_floats(B, N, P, 1, 0)) if B else 0
+        scratch = torch.empty(ns, dtype=torch.float32, device=maps.device) if ns else None
+        _abi.check(L.nfp_cpsync_moments(B, N, P, _DTYPES[maps.dtype], _ptr0(maps), record.data_ptr(), nr, _ptr(scratch), ns,
+                                        _raw_stream(maps.device)))
+    return record
+
+
+def cp_sync_forward_call(kind, maps, w, gamma, beta, rm, rv, momentum, eps, records, relu=True, channels_last=False,
+                         global_count=0):
+    """(out, saved) from nfp_cpsync_forward: the rank's rows of the result — [B,D] float32 for "pool", [B,D,...] in the
+    maps' dtype for "proj" — under the statistics joined from `records` [world, 1 + N + N*N] (float64, row r rank r's),
+    and the state the backward reads.  rm / rv: the running statistics (float32 [D], or both None), updated in place."""
+    L = _abi.load()
+    B, N, P, D = _cps_sizes(maps, w.shape[0])
+    dev = maps.device
+    with _on_device(dev):
+        if kind == "proj":
+            out = torch.empty((maps.shape[0], D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev,
+                              memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+        else:
+            out = torch.empty(maps.shape[0], D, dtype=torch.float32, device=dev)
+        ns = int(L.nfp_cpsync_saved_floats(N, D))
+        saved = torch.empty(ns, dtype=torch.float32, device=dev)
+        records = records.contiguous()
+        _abi.check(L.nfp_cpsync_forward(*_cps_head(kind, maps, w, gamma, beta, relu), _ptr(rm), _ptr(rv), float(momentum),
+                                        float(eps), records.data_ptr(), records.shape[0], records.numel(), int(global_count),
+                                        _ptr0(out), saved.data_ptr(), ns, _raw_stream(dev),
+                                        _abi.ACT_NHWC if channels_last else _abi.ACT_NCHW))
+    return out, saved
+
+
+def _cps_grad_out(kind, maps, grad_out):
+    """(grad_out as the library reads it, whether that is channels-last): cpool_backward_call's / cproj_backward_call's."""
+    if kind != "proj":
+        return grad_out.contiguous().float(), False
+    go = grad_out.to(maps.dtype)
+    nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
+    return (go if nhwc else go.contiguous()), nhwc
+
+
+def cp_sync_reduce_call(kind, maps, w, gamma, beta, saved, eps, grad_out, want=(True, True, True), relu=True):
+    """(grad_w [D,N], grad_gamma [D], grad_beta [D], row) from nfp_cpsync_reduce: the rank's parameter gradients — None for
+    each `want` leaves out; their sum over the ranks is the batch's — and its row [N + N*N] of k and Q."""
+    L = _abi.load()
+    B, N, P, D = _cps_sizes(maps, w.shape[0])
+    dev = maps.device
+    go, nhwc = _cps_grad_out(kind, maps, grad_out)
+    with _on_device(dev):
+        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[0] else None
+        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[1] else None
+        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
+        nk = int(L.nfp_cpsync_kq_floats(N))
+        row = torch.empty(nk, dtype=torch.float32, device=dev)
+        ns = int(getattr(L, _CP_ENTRIES[kind][2])(B, N, P, D, 1)) if B else 0
+        scratch = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
+        _abi.check(L.nfp_cpsync_reduce(*_cps_head(kind, maps, w, gamma, beta, relu), float(eps), saved.data_ptr(), saved.numel(),
+                                       _ptr0(go), _ptr(gw), _ptr(gg), _ptr(gb), row.data_ptr(), nk, _ptr(scratch), ns,
+                                       _raw_stream(dev), _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
+    return gw, gg, gb, row
+
+
+def cp_sync_maps_call(kind, maps, w, gamma, beta, saved, eps, grad_out, rows, relu=True):
+    """grad_maps of the rank, in the maps' dtype, from nfp_cpsync_maps under `rows` [world, N + N*N] (row r rank r's)."""
+    L = _abi.load()
+    dev = maps.device
+    go, nhwc = _cps_grad_out(kind, maps, grad_out)
+    with _on_device(dev):
+        gm = torch.empty_like(maps)
+        rows = rows.contiguous()
+        _abi.check(L.nfp_cpsync_maps(*_cps_head(kind, maps, w, gamma, beta, relu), float(eps), saved.data_ptr(), saved.numel(),
+                                     _ptr0(go), rows.data_ptr(), rows.shape[0], rows.numel(), _ptr0(gm), _raw_stream(dev),
+                                     _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
+    return gm
+
+
+def _cps_gather(row, group):
+    """[world, len(row)]: every rank's `row`, row r rank r's — one all-reduce (SUM) of a zeroed buffer in which a rank fills
+    its own row.  Exact, since every other addend of an element is 0; the same bits on every rank; served by NCCL / RCCL and
+    by gloo for CUDA tensors.  Blocking, on the row's device and current stream."""
+    dist = torch.distributed
+    with _on_device(row.device):
+        buf = torch.zeros(dist.get_world_size(group), row.numel(), dtype=row.dtype, device=row.device)
+        buf[dist.get_rank(group)].copy_(row)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf
+
+
+class _CpSyncHip(torch.autograd.Function):
+    """_CPoolHip / _CProjHip in training mode with the statistics of every rank of `group`: moments -> gather -> finish and
+    the main forward; part and reduce -> gather -> grad_maps.  Both gathers are entered by every rank, whatever its batch
+    and whichever gradients it needs.  Saved: the maps, the parameters and the O(N*N + D) statistics."""
+
+    @staticmethod
+    def forward(ctx, maps, w, gamma, beta, stats, momentum, eps, relu, need_grad, kind, channels_last, group):
+        records = _cps_gather(cp_sync_moments_call(maps), group)
+        out, saved = cp_sync_forward_call(kind, maps, w, gamma, beta, stats[0], stats[1], momentum, eps, records, relu,
+                                          channels_last)
+        if need_grad:
+            ctx.save_for_backward(maps, w, gamma, beta, saved)
+            ctx.eps, ctx.relu, ctx.kind, ctx.group = eps, relu, kind, group
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        maps, w, gamma, beta, saved = ctx.saved_tensors
+        gw, gg, gb, row = cp_sync_reduce_call(ctx.kind, maps, w, gamma, beta, saved, ctx.eps, grad_out,
+                                              ctx.needs_input_grad[1:4], ctx.relu)
+        rows = _cps_gather(row, ctx.group)
+        gm = None
+        if ctx.needs_input_grad[0]:
+            gm = cp_sync_maps_call(ctx.kind, maps, w, gamma, beta, saved, ctx.eps, grad_out, rows, ctx.relu)
+        return (gm, gw, gg, gb, None, None, None, None, None, None, None, None)
+
+
+def _cp_sync_node_call(kind, maps, weight, gamma, beta, rm, rv, momentum, eps, group, relu, channels_last):
+    """The sync node on what cp_sync_serves took, or None where the running statistics are not float32 and contiguous."""
+    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+        return None
+    N, D = maps.shape[1], weight.shape[0]
+    f32 = lambda t: t if t.dtype == torch.float32 else t.float()     # noqa: E731
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (maps, weight, gamma, beta))
+    out = _CpSyncHip.apply(maps.contiguous(), f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(),
+                           f32(beta).contiguous(), (rm, rv), float(momentum), float(eps), bool(relu), need_grad, kind,
+                           channels_last, group)
+    return out if out.dtype == maps.dtype else out.to(maps.dtype)
+
+
+def _cp_sync_finish_composition(kind, y, maps, relu, channels_last):
+    y = torch.relu(y) if relu else y
+    if kind == "pool":
+        return y.mean((2, 3))
+    y = y if maps.dim() == 4 else y.reshape(maps.shape[0], y.shape[1], *maps.shape[2:])
+    return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+
+
+def _cp_conv(maps, weight):
+    B, N = maps.shape[:2]
+    return torch.nn.functional.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
+
+
+def _cp_sync_module_call(kind, maps, weight, bn, training, group, relu=True, channels_last=False):
+    """One call of the tail under `bn`, an nn.SyncBatchNorm that synchronises over `group` (cp_sync_group).  Where
+    cp_sync_serves, the staged kernels; else the composition with bn.forward itself on the conv's output, in the call's
+    mode: torch synchronises, and raises its own ValueError for CPU tensors."""
+    if cp_sync_serves(kind, maps, bn.weight, bn.bias, bn.momentum) and maps.dim() >= 3 and maps.shape[1] == weight.shape[1]:
+        rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+        out = _cp_sync_node_call(kind, maps, weight, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, group, relu, channels_last)
+        if out is not None:
+            _bn_call_mode(bn, training)          # (num_batches_tracked, once per call)
+            return out
+    was = bn.training
+    bn.training = training
+    try:
+        y = bn(_cp_conv(maps, weight))
+    finally:
+        bn.training = was
+    return _cp_sync_finish_composition(kind, y, maps, relu, channels_last)
+
+
+def _cp_sync_tensors_call(kind, maps, weight, gamma, beta, rm, rv, momentum, eps, group, relu=True, channels_last=False):
+    """The same on loose tensors (use_batch_stats, a group of more than one rank); the composition runs torch's own
+    SyncBatchNorm function on the conv's output."""
+    if cp_sync_serves(kind, maps, gamma, beta, momentum):
+        out = _cp_sync_node_call(kind, maps, weight, gamma, beta, rm, rv, momentum, eps, group, relu, channels_last)
+        if out is not None:
+            return out
+    if not maps.is_cuda:
+        raise ValueError("SyncBatchNorm expected input tensor to be on GPU or privateuseone")
+    from torch.nn.modules._functions import SyncBatchNorm as sync_batch_norm
+    y = sync_batch_norm.apply(_cp_conv(maps, weight), gamma, beta, rm, rv, eps, momentum, group,
+                              torch.distributed.get_world_size(group))
+    return _cp_sync_finish_composition(kind, y, maps, relu, channels_last)

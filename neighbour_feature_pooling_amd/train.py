@@ -74,6 +74,8 @@ def main():
                     "ranks share one GPU for rehearsal; RCCL refuses that)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1 without a launcher: start N ranks (one per GPU)")
     ap.add_argument("--print-launch", action="store_true", help="with --gpus N: print the launch command and exit")
+    ap.add_argument("--sync-bn", action="store_true", help="nn.SyncBatchNorm.convert_sync_batchnorm before the DDP wrap: "
+                    "BatchNorm statistics over every rank's batch (GPU ranks only; the fused compress tails join in)")
     a = ap.parse_args()
 
     from . import parallel
@@ -107,6 +109,10 @@ def main():
     torch.backends.cudnn.benchmark = bool(a.autotune)
     if a.channels_last:
         net = net.to(memory_format=torch.channels_last)
+    if a.sync_bn:
+        if a.cpu:
+            raise SystemExit("--sync-bn needs GPU ranks: nn.SyncBatchNorm refuses CPU tensors")
+        net = torch.nn.SyncBatchNorm.convert_sync_batchnorm(net)      # (a no-op for the statistics while world == 1)
     if world > 1:
         net = DDP(net, device_ids=None if a.cpu else [local], gradient_as_bucket_view=True)
     step, _ = make_step(net)
