@@ -119,16 +119,30 @@ def attention_pool_host(maps, w, b):
     return (m * att.unsqueeze(1)).sum(-1)
 
 
+def compress_conv(maps, weight):
+    """The 1x1 conv of the two compositions below: maps [B,N,H,W] (or [B,N,P], taken as [B,N,P,1]) under weight [D,N,1,1] or
+    [D,N] -> [B,D,H,W] ([B,D,P,1])."""
+    B, N = maps.shape[:2]
+    return F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
+
+
+def compress_finish(y, maps, relu, pool):
+    """... and what follows their BatchNorm on its output y: the ReLU where asked, then GAP -> [B,D] (pool), or the map in
+    the shape of `maps`."""
+    y = F.relu(y) if relu else y
+    if pool:
+        return y.mean((2, 3))
+    return y if maps.dim() == 4 else y.reshape(maps.shape[0], y.shape[1], *maps.shape[2:])
+
+
 def compress_pool_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps):
     """The tail the heads of models/nfp_heads.py share (NFPHead nfp_heads.py:28-32,42-43): GAP(relu(batch_norm(conv1x1(maps))))
     as the four ATen ops — conv2d, batch_norm, relu, mean — any dtype and device, under torch.compile and torch.autocast:
     maps [B,N,H,W] (or [B,N,P]) -> [B,D].  weight [D,N,1,1] or [D,N]; gamma / beta may be None (affine=False); the running
     statistics, where given, are updated in place by batch_norm when use_batch_stats (momentum: its exponential factor).
     Autograd differentiates."""
-    B, N = maps.shape[:2]
-    y = F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
-    y = F.batch_norm(y, running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
-    return F.relu(y).mean((2, 3))
+    y = F.batch_norm(compress_conv(maps, weight), running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
+    return compress_finish(y, maps, True, True)
 
 
 def compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps, relu=True):
@@ -137,8 +151,5 @@ def compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_
     ops, any dtype and device, under torch.compile and torch.autocast: maps [B,N,H,W] (or [B,N,P]) -> [B,D,H,W] ([B,D,P]).
     weight [D,N,1,1] or [D,N]; gamma / beta may be None (affine=False); the running statistics, where given, are updated in
     place by batch_norm when use_batch_stats (momentum: its exponential factor).  Autograd differentiates."""
-    B, N = maps.shape[:2]
-    y = F.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
-    y = F.batch_norm(y, running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
-    y = F.relu(y) if relu else y
-    return y if maps.dim() == 4 else y.reshape(B, weight.shape[0], *maps.shape[2:])
+    y = F.batch_norm(compress_conv(maps, weight), running_mean, running_var, gamma, beta, use_batch_stats, momentum, eps)
+    return compress_finish(y, maps, relu, False)

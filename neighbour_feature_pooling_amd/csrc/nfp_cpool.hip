@@ -53,1824 +53,19 @@
 //   cpool_bwd_reduce<., SYNC>  divides by that count, and forms Sigma w from both floats
 //   cps_kq_row      the workgroups' shares of k, Q summed into the rank's row; *_bwd_maps then read the ranks' rows
 //   cps_zero        a rank without an image: a zero row, zero parameter gradients
-#include "nfp_launch.h"
-
-#include <cmath>
-
-namespace nfp {
-namespace {
-
-constexpr int kCpT = 512;         // threads of cpool_fwd / cpool_bwd_part / cpool_bwd_maps: 8 wavefronts
-constexpr int kCpW = kCpT / 64;
-constexpr int kCpDT = 128;        // channels of D per workgroup: 64 lanes x 2
-constexpr int kCpBudget = 8192;   // floats of maps per chunk (32 KiB): with the join buffers a workgroup stays near 50 KiB
-constexpr int kCpMaxN = 32;
-constexpr int kCpRT = 32;         // channels of D per workgroup of cpool_bwd_reduce
-constexpr int kCpMT = 256;        // threads of cpool_moments / cpool_bwd_reduce
-constexpr int kCpFT = 1024;       // threads of cpool_finish
-constexpr int kCpMB = 128;        // channels of D per LDS block of cpool_bwd_maps
-
-struct CpK {
-  int B, N, P, CH, CHs, D, bf16, eval, S, ipw, nc, ntr;
-  float eps;
-  double eps64, mom, M;
-  const void* maps;
-  const float *w, *gamma, *beta, *rm, *rv, *stats, *go, *part, *kq;
-  float *out, *stats_w, *part_w, *kq_w, *rm_w, *rv_w, *gw, *gg, *gb;
-  void* gm;
-  const void* gov;   // cproj: grad_out [B,D,P] and out [B,D,P] in the maps' dtype
-  void* outv;
-};
-// stats (the forward's saved state, training): mu_hi [N], mu_lo [N], Sigma [N*N], inv [D]
-__device__ __forceinline__ const float* cp_inv(const CpK& k) { return k.stats + 2 * k.N + k.N * k.N; }
-
-__device__ __forceinline__ float cp_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// s_d = gamma_d inv_d and the shift of channel d (file comment)
-__device__ __forceinline__ void cp_coef(const CpK& k, int d, float& scale, float& shift) {
-  const float inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
-  scale = k.gamma[d] * inv;
-  shift = k.eval ? k.beta[d] - scale * k.rm[d] : k.beta[d];
-}
-
-// element j of a tensor of the maps' dtype (the maps, or cproj's grad_out) as float32
-__device__ __forceinline__ float cj_load(const CpK& k, const void* p, long long j) {
-  return k.bf16 ? bf16_to_f32(((const uint16_t*)p)[j]) : ((const float*)p)[j];
-}
-
-// The chunk [p0, p0 + ch) of image b into sm[NP][CHs] as centred float32; rows n >= N and pixels >= ch are zero.
-__device__ __forceinline__ void cp_stage(const CpK& k, int NP, float* sm, int b, int p0, int ch, bool centre) {
-  const long long base = (long long)b * k.N * k.P + p0;
-  const int total = NP * k.CHs;
-  for (int i = threadIdx.x; i < total; i += blockDim.x) {
-    const int n = i / k.CHs, pl = i - n * k.CHs;
-    float v = 0.f;
-    if (n < k.N && pl < ch) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
-      if (centre) v = (v - k.stats[n]) - k.stats[k.N + n];
-    }
-    sm[i] = v;
-  }
-}
-
-// ---- moments ---------------------------------------------------------------------------------------------------------------
-// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP], red[max(NP * NP, 256)].
-// part_w: per chunk [a (N), r (N), Gram (N * N)].
-__global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* anchor = sm + NP * k.CHs;
-  float* red = anchor + NP;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kCpMT >> 6;
-  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int N = k.N, NN = NP * NP;
-  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
-  cp_stage(k, NP, sm, b, p0, ch, false);
-  __syncthreads();
-  for (int n = wv; n < NP; n += nw) {
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
-    s = cp_wave_sum(s);
-    if (lane == 0) anchor[n] = s / (float)ch;
-  }
-  __syncthreads();
-  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
-    const float an = anchor[n];
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) {
-      const float c = sm[n * k.CHs + pl] - an;
-      sm[n * k.CHs + pl] = c;
-      s += c;
-    }
-    s = cp_wave_sum(s);
-    if (lane == 0) {
-      outp[n] = an;
-      outp[N + n] = s / (float)ch;
-    }
-  }
-  __syncthreads();
-  // Gram about the anchor: pair (n, n2) per thread, the pixels in quads; with fewer pairs than threads the quads are dealt
-  // to T / NN slices and joined in slice order
-  const int nq = (ch + 3) >> 2;
-  const int nsl = NN >= kCpMT ? 1 : kCpMT / NN;
-  for (int pr0 = 0; pr0 < NN; pr0 += kCpMT) {
-    const int pr = nsl > 1 ? tid % NN : pr0 + tid;
-    const int sl = nsl > 1 ? tid / NN : 0;
-    if (pr < NN && sl < nsl) {
-      const int n = pr / NP, n2 = pr - n * NP;
-      const float4* ra = (const float4*)(sm + n * k.CHs);
-      const float4* rb = (const float4*)(sm + n2 * k.CHs);
-      float g = 0.f;
-      for (int q = sl; q < nq; q += nsl) {
-        const float4 x = ra[q], y = rb[q];
-        g = fmaf(x.x, y.x, g);
-        g = fmaf(x.y, y.y, g);
-        g = fmaf(x.z, y.z, g);
-        g = fmaf(x.w, y.w, g);
-      }
-      if (nsl > 1) {
-        red[sl * NN + pr] = g;
-      } else if (n < N && n2 < N) {
-        outp[2 * N + n * N + n2] = g;
-      }
-    }
-  }
-  if (nsl > 1) {
-    __syncthreads();
-    if (tid < NN) {
-      const int n = tid / NP, n2 = tid - n * NP;
-      float g = red[tid];
-      for (int s = 1; s < nsl; ++s) g += red[s * NN + tid];
-      if (n < N && n2 < N) outp[2 * N + n * N + n2] = g;
-    }
-  }
-}
-
-// The join of a rank's B * nc chunk records, by the 1024 threads of a workgroup (red[1024], mu[32], sig[32][32], zero beyond
-// N).  The chunks are dealt to slices of consecutive chunks — 32 slices for mu, 1024 / N^2 for Sigma — whose sums are joined
-// in slice order: one thread walking all B * nc chunks is a chain of dependent global loads (measured: 100 us at 64 chunks).
-// RECORD (cps_record): sig keeps the scatter about mu undivided, and a rank without a chunk has mu = 0.
-template <bool RECORD>
-__device__ __forceinline__ void cp_join_chunks(const CpK& k, double* mu, double* sig, double* red) {
-  const int tid = threadIdx.x, N = k.N, NN = N * N, K = k.B * k.nc, rec = 2 * N + NN;
-  const int last = k.P - (k.nc - 1) * k.CH;   // pixels of an image's last chunk
-  {
-    const int n = tid & 31, sl = tid >> 5, Kc = (K + 31) / 32;
-    const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
-    double s = 0.0;
-    if (n < N) {
-      int j = c0 % k.nc;
-#pragma unroll 4
-      for (int c = c0; c < c1; ++c) {
-        const float* r = k.part + (long long)c * rec;
-        const double cnt = j == k.nc - 1 ? last : k.CH;
-        s += cnt * ((double)r[n] + (double)r[N + n]);
-        if (++j == k.nc) j = 0;
-      }
-    }
-    red[tid] = s;
-    sig[tid] = 0.0;
-    __syncthreads();
-    if (tid < N) {
-      double t = red[tid];
-      for (int i = 1; i < 32; ++i) t += red[i * 32 + tid];
-      mu[tid] = RECORD && K == 0 ? 0.0 : t / k.M;
-    }
-    __syncthreads();
-  }
-  {
-    const int nsl = kCpFT / NN, pr = tid % NN, sl = tid / NN, Kc = (K + nsl - 1) / nsl;
-    const int n = pr / N, n2 = pr - n * N;
-    if (sl < nsl) {
-      const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
-      const double m1 = mu[n], m2 = mu[n2];
-      double s = 0.0;
-      int j = c0 % k.nc;
-#pragma unroll 4
-      for (int c = c0; c < c1; ++c) {
-        const float* r = k.part + (long long)c * rec;
-        const double cnt = j == k.nc - 1 ? last : k.CH;
-        const double d1 = (double)r[n] - m1, d2 = (double)r[n2] - m2, r1 = r[N + n], r2 = r[N + n2];
-        s += (double)r[2 * N + pr] + cnt * (r1 * d2 + d1 * r2 + d1 * d2);
-        if (++j == k.nc) j = 0;
-      }
-      red[sl * NN + pr] = s;
-    }
-    __syncthreads();
-    if (tid < NN) {
-      double t = red[tid];
-      for (int i = 1; i < nsl; ++i) t += red[i * NN + tid];
-      sig[n * kCpMaxN + n2] = RECORD ? t : t / k.M;
-    }
-    __syncthreads();
-  }
-}
-
-// What follows mu and Sigma over M values per channel: they go to stats_w (workgroup 0), and channel d = blockIdx.x * 1024 +
-// tid gets w_d' Sigma w_d, inv_d and its running statistics.
-__device__ __forceinline__ void cp_finish_channels(const CpK& k, const double* mu, const double* sig, double M) {
-  const int tid = threadIdx.x, N = k.N, NN = N * N;
-  if (blockIdx.x == 0) {
-    if (tid < N) {
-      const float hi = (float)mu[tid];
-      k.stats_w[tid] = hi;
-      k.stats_w[N + tid] = (float)(mu[tid] - (double)hi);
-    }
-    if (tid < NN) k.stats_w[2 * N + tid] = (float)sig[(tid / N) * kCpMaxN + tid % N];
-  }
-  const int d = blockIdx.x * kCpFT + tid;
-  if (d >= k.D) return;
-  const float* wd = k.w + (long long)d * N;
-  double wr[kCpMaxN];   // (every index a constant below: registers)
-#pragma unroll
-  for (int n = 0; n < kCpMaxN; ++n) wr[n] = n < N ? (double)wd[n] : 0.0;
-  double var = 0.0, mean = 0.0;
-#pragma unroll
-  for (int n = 0; n < kCpMaxN; ++n) {
-    if (n < N) {   // (the same in every thread)
-      double v = 0.0;
-#pragma unroll
-      for (int n2 = 0; n2 < kCpMaxN; ++n2) v += sig[n * kCpMaxN + n2] * wr[n2];
-      var += wr[n] * v;
-      mean += wr[n] * mu[n];
-    }
-  }
-  var = var > 0.0 ? var : 0.0;
-  k.stats_w[2 * N + NN + d] = (float)(1.0 / sqrt(var + k.eps64));
-  if (k.rm_w != nullptr) {
-    k.rm_w[d] = (float)((1.0 - k.mom) * (double)k.rm_w[d] + k.mom * mean);
-    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (M / (M - 1.0)));
-  }
-}
-
-// grid = ceil(D / 1024), block = 1024; every workgroup joins the chunks itself (the same sums in the same order).
-__global__ void __launch_bounds__(kCpFT) cpool_finish(CpK k) {
-  __shared__ double mu[kCpMaxN];
-  __shared__ double sig[kCpMaxN * kCpMaxN];   // [32][32], zero beyond N
-  __shared__ double red[kCpFT];
-  cp_join_chunks<false>(k, mu, sig, red);
-  cp_finish_channels(k, mu, sig, k.M);
-}
-
-// ---- the statistics across ranks (nfp_cpsync_*) ----------------------------------------------------------------------------
-// A rank's record, float64: [n, mu (N), S (N * N)] — its count of values per map, their mean, and their scatter about that
-// mean, not divided.  grid = 1, block = 1024: cpool_finish's join of the rank's chunk records; a rank without an image
-// (B = 0: no chunk) writes n = 0, mu = 0, S = 0.
-__global__ void __launch_bounds__(kCpFT) cps_record(CpK k, double* rec) {
-  __shared__ double mu[kCpMaxN];
-  __shared__ double sig[kCpMaxN * kCpMaxN];
-  __shared__ double red[kCpFT];
-  cp_join_chunks<true>(k, mu, sig, red);
-  const int tid = threadIdx.x, N = k.N, NN = N * N;
-  if (tid == 0) rec[0] = k.M;
-  if (tid < N) rec[1 + tid] = mu[tid];
-  if (tid < NN) rec[1 + N + tid] = sig[(tid / N) * kCpMaxN + tid % N];
-}
-
-// grid = ceil(D / 1024), block = 1024: cpool_finish over the records of `world` ranks instead of one rank's chunks, joined
-// in rank order by every workgroup (the same sums in the same order on every rank that holds the same records):
-//   M = sum n_r      mu = sum n_r mu_r / M      Sigma = sum_r (S_r + n_r d_r d_r') / M,  d_r = mu_r - mu
-// stats_w takes more than cpool_finish writes, behind inv [D]: (float)M, the count the backward divides by, and what
-// Sigma [N * N] loses as a float.  Ranks whose means lie far apart put the variance into the between-rank term — every
-// entry of Sigma large, the differences between them small — and grad_w, a difference of T and Sigma w, needs both floats
-// (means of +-100 at unit spread: 1.1e-4 of max|grad_w| with one, measured).
-__global__ void __launch_bounds__(kCpFT) cps_finish(CpK k, const double* recs, int world) {
-  __shared__ double mu[kCpMaxN];
-  __shared__ double sig[kCpMaxN * kCpMaxN];
-  const int tid = threadIdx.x, N = k.N, NN = N * N, rec = 1 + N + NN;
-  double M = 0.0;   // (every thread: the same loads, the same order)
-  for (int r = 0; r < world; ++r) M += recs[(long long)r * rec];
-  sig[tid] = 0.0;
-  if (tid < N) {
-    double s = 0.0;
-    for (int r = 0; r < world; ++r) s += recs[(long long)r * rec] * recs[(long long)r * rec + 1 + tid];
-    mu[tid] = s / M;
-  }
-  __syncthreads();
-  if (tid < NN) {
-    const int n = tid / N, n2 = tid - n * N;
-    const double m1 = mu[n], m2 = mu[n2];
-    double s = 0.0;
-    for (int r = 0; r < world; ++r) {
-      const double* R = recs + (long long)r * rec;
-      const double d1 = R[1 + n] - m1, d2 = R[1 + n2] - m2;
-      s += R[1 + N + tid] + R[0] * (d1 * d2);
-    }
-    sig[n * kCpMaxN + n2] = s / M;
-  }
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    float* tail = k.stats_w + 2 * N + NN + k.D;
-    if (tid == 0) tail[0] = (float)M;
-    if (tid < NN) {
-      const double s = sig[(tid / N) * kCpMaxN + tid % N];
-      tail[1 + tid] = (float)(s - (double)(float)s);
-    }
-  }
-  cp_finish_channels(k, mu, sig, M);
-}
-
-// A rank's row [k (N), Q (N * N)]: the shares of cpool_bwd_reduce's workgroups, summed in workgroup order as the *_bwd_maps
-// kernels sum them.  Those kernels then read the ranks' rows where they read the workgroups' shares.  grid = 1, block = 256.
-__global__ void __launch_bounds__(kCpMT) cps_kq_row(CpK k, float* row) {
-  const int L = k.N + k.N * k.N;
-  for (int i = threadIdx.x; i < L; i += kCpMT) {
-    float s = 0.f;
-#pragma unroll 8
-    for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * L + i];
-    row[i] = s;
-  }
-}
-
-// What a rank without an image contributes backward: a zero row and zero parameter gradients (those that are asked for).
-// grid-stride, block = 256.
-__global__ void __launch_bounds__(kCpMT) cps_zero(CpK k, float* row) {
-  const long long L = k.N + k.N * k.N, DN = (long long)k.D * k.N, end = L > DN ? L : DN;
-  for (long long i = (long long)blockIdx.x * kCpMT + threadIdx.x; i < end; i += (long long)gridDim.x * kCpMT) {
-    if (i < L) row[i] = 0.f;
-    if (i < DN && k.gw != nullptr) k.gw[i] = 0.f;
-    if (i < k.D && k.gg != nullptr) k.gg[i] = 0.f;
-    if (i < k.D && k.gb != nullptr) k.gb[i] = 0.f;
-  }
-}
-
-// ---- lanes along d -----------------------------------------------------------------------------------------------------------
-// The two channels of a lane: d0 = tile * 128 + lane and d0 + 64.  ws = s_d w_d (zero beyond D and N), sh the shift.
-template <int NP>
-__device__ __forceinline__ void cp_rows(const CpK& k, int tile, int lane, float (&ws)[2][NP], float (&sh)[2]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int d = tile * kCpDT + lane + 64 * j;
-    float scale = 0.f;
-    sh[j] = 0.f;
-    if (d < k.D) cp_coef(k, d, scale, sh[j]);
-#pragma unroll
-    for (int n = 0; n < NP; ++n) ws[j][n] = (d < k.D && n < k.N) ? k.w[(long long)d * k.N + n] * scale : 0.f;
-  }
-}
-// a of the lane's two channels at the four pixels of quad q: the shift first, then the maps in order (cpool_bwd_maps forms
-// the same chain: the same bits, the same mask)
-template <int NP>
-__device__ __forceinline__ void cp_preact(const float* sm, int CHs, int q, const float (&ws)[2][NP], const float (&sh)[2],
-                                          float (&a)[2][4]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[j][i] = sh[j];
-#pragma unroll
-  for (int n = 0; n < NP; ++n) {
-    const float4 c = ((const float4*)(sm + n * CHs))[q];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      a[j][0] = fmaf(ws[j][n], c.x, a[j][0]);
-      a[j][1] = fmaf(ws[j][n], c.y, a[j][1]);
-      a[j][2] = fmaf(ws[j][n], c.z, a[j][2]);
-      a[j][3] = fmaf(ws[j][n], c.w, a[j][3]);
-    }
-  }
-}
-
-// grid = (B, ceil(D / 128)), block = 512.  LDS: sm[NP * CHs], red[8 * 128].
-template <int NP>
-__global__ void __launch_bounds__(kCpT) cpool_fwd(CpK k) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* red = sm + NP * k.CHs;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int b = blockIdx.x, tile = blockIdx.y;
-  float ws[2][NP], sh[2], s[2] = {0.f, 0.f};
-  cp_rows<NP>(k, tile, lane, ws, sh);
-  for (int p0 = 0; p0 < k.P; p0 += k.CH) {
-    const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
-    if (p0 > 0) __syncthreads();   // (the previous chunk has been read)
-    cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-    __syncthreads();
-    for (int q = wv; q < nq; q += kCpW) {
-      float a[2][4];
-      cp_preact<NP>(sm, k.CHs, q, ws, sh, a);
-      const int nv = min(4, ch - 4 * q);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < nv) {
-          s[0] += fmaxf(a[0][i], 0.f);
-          s[1] += fmaxf(a[1][i], 0.f);
-        }
-    }
-  }
-  red[wv * kCpDT + lane] = s[0];
-  red[wv * kCpDT + lane + 64] = s[1];
-  __syncthreads();
-  const int d = tile * kCpDT + tid;
-  if (tid < kCpDT && d < k.D) {
-    float t = red[tid];
-#pragma unroll
-    for (int w = 1; w < kCpW; ++w) t += red[w * kCpDT + tid];
-    k.out[(long long)b * k.D + d] = t / (float)k.P;
-  }
-}
-
-// grid = (S, ceil(D / 128)), block = cp_part_threads: images [s * ipw, (s + 1) * ipw) of the batch.  LDS: sm[NP * CHs],
-// red[128 * (NP + 1)].  part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
-// A lane keeps 2 * NP scaled weights and 2 * NP sums: above 24 maps that passes the 256 registers two wavefronts per SIMD
-// leave each (92 spilled at 512 threads), so those run four wavefronts, one per SIMD, with the whole file.
-template <int NP>
-constexpr int cp_part_threads() { return NP > 24 ? 256 : kCpT; }
-template <int NP>
-__global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
-  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* red = sm + NP * k.CHs;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int sl = blockIdx.x, tile = blockIdx.y;
-  float ws[2][NP], sh[2], T[2][NP], gbs[2] = {0.f, 0.f};
-  cp_rows<NP>(k, tile, lane, ws, sh);
-#pragma unroll
-  for (int n = 0; n < NP; ++n) T[0][n] = T[1][n] = 0.f;
-  const int b1 = min(k.B, (sl + 1) * k.ipw);
-  bool first = true;
-  for (int b = sl * k.ipw; b < b1; ++b) {
-    float gs[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int d = tile * kCpDT + lane + 64 * j;
-      gs[j] = d < k.D ? k.go[(long long)b * k.D + d] / (float)k.P : 0.f;
-    }
-    for (int p0 = 0; p0 < k.P; p0 += k.CH) {
-      const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
-      if (!first) __syncthreads();
-      first = false;
-      cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-      __syncthreads();
-      for (int q = wv; q < nq; q += kW) {
-        float a[2][4];
-        cp_preact<NP>(sm, k.CHs, q, ws, sh, a);
-        const int nv = min(4, ch - 4 * q);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            a[j][i] = (i < nv && a[j][i] > 0.f) ? gs[j] : 0.f;   // ga
-            gbs[j] += a[j][i];
-          }
-#pragma unroll
-        for (int n = 0; n < NP; ++n) {
-          const float4 c = ((const float4*)(sm + n * k.CHs))[q];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            float t = T[j][n];
-            t = fmaf(a[j][0], c.x, t);
-            t = fmaf(a[j][1], c.y, t);
-            t = fmaf(a[j][2], c.z, t);
-            t = fmaf(a[j][3], c.w, t);
-            T[j][n] = t;
-          }
-        }
-      }
-    }
-  }
-  // the eight wavefronts in order into red[dl][NP + 1] (every lane its own words)
-  for (int w = 0; w < kW; ++w) {
-    if (wv == w) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float* r = red + (lane + 64 * j) * (NP + 1);
-#pragma unroll
-        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
-        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
-      }
-    }
-    __syncthreads();
-  }
-  const int N1 = k.N + 1;
-  for (int i = tid; i < kCpDT * N1; i += kT) {
-    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
-    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
-  }
-}
-
-// grid = ceil(D / 32), block = 256.  kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
-// LIVE (the cproj backward, whose S reaches 512): loads are issued only from the element rounds and lanes that hold an
-// element; the sums and their order are the same in both forms.
-// SYNC (nfp_cpsync_reduce): the slices are one rank's, and e and f divide by the count over all ranks, which cps_finish
-// left behind inv in stats.
-template <bool LIVE, bool SYNC = false>
-__global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
-  __shared__ float Tl[kCpRT * (kCpMaxN + 1)];
-  __shared__ float wl[kCpRT * kCpMaxN];
-  __shared__ float sg[kCpMaxN * kCpMaxN];
-  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
-  const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
-  {
-    // a thread's elements (at most 5 of the 32 * (N + 1)) side by side, the slices in order: their loads are independent, so
-    // several are in flight — one element after the other is a chain of S dependent loads
-    constexpr int kE = (kCpRT * (kCpMaxN + 1) + kCpMT - 1) / kCpMT;
-    float acc[kE];
-    long long off[kE];
-#pragma unroll
-    for (int e = 0; e < kE; ++e) {
-      const int i = tid + e * kCpMT, dl = i / N1, j = i - dl * N1, d = d0 + dl;
-      acc[e] = 0.f;
-      off[e] = (i < kCpRT * N1 && d < k.D) ? (long long)d * N1 + j : -1;
-    }
-    const long long stride = (long long)k.D * N1;
-    if (!LIVE) {
-      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
-        float v[kE][8];
-#pragma unroll
-        for (int e = 0; e < kE; ++e)
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[e][u] = k.part[min(sl0 + u, k.S - 1) * stride + max(off[e], 0LL)];
-#pragma unroll
-        for (int e = 0; e < kE; ++e)
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
-      }
-    } else {
-      // the same, but only the ne element rounds that hold an element at all (2 of the 5 at N = 8) and only the lanes that
-      // hold one issue loads: with hundreds of slices the walk is bound by the loads one CU can issue (measured: 90 us over
-      // the 704 slices of cproj_bwd_part at [64,8,26,26] -> 40 with every lane of every round loading)
-      const int ne = (kCpRT * N1 + kCpMT - 1) / kCpMT;
-      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {
-        float v[kE][8];
-#pragma unroll
-        for (int e = 0; e < kE; ++e)
-          if (e < ne) {   // (the same in every thread)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[e][u] = off[e] >= 0 ? k.part[min(sl0 + u, k.S - 1) * stride + off[e]] : 0.f;
-          }
-#pragma unroll
-        for (int e = 0; e < kE; ++e)
-          if (e < ne) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-              if (sl0 + u < k.S && off[e] >= 0) acc[e] += v[e][u];
-          }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < kE; ++e) {
-      const int i = tid + e * kCpMT, dl = i / N1, j = i - dl * N1;
-      if (i < kCpRT * N1) Tl[dl * (kCpMaxN + 1) + (j < N ? j : kCpMaxN)] = acc[e];
-    }
-  }
-  for (int i = tid; i < kCpRT * N; i += kCpMT) {
-    const int dl = i / N, n = i - dl * N, d = d0 + dl;
-    wl[dl * kCpMaxN + n] = d < k.D ? k.w[(long long)d * N + n] : 0.f;
-  }
-  if (!k.eval)
-    for (int i = tid; i < NN; i += kCpMT) sg[i] = k.stats[2 * N + i];
-  __syncthreads();
-  if (tid < kCpRT) {
-    const int d = d0 + tid;
-    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
-    if (d < k.D) {
-      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
-      c1 = k.gamma[d] * inv;
-      const float gb = Tl[tid * (kCpMaxN + 1) + kCpMaxN];
-      float dot = 0.f;
-      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * kCpMaxN + n], Tl[tid * (kCpMaxN + 1) + n], dot);
-      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
-      if (!k.eval) {
-        const float M = SYNC ? cp_inv(k)[k.D] : (float)k.M;
-        e = c1 * (gb / M);
-        f = c1 * (gg * inv / M);
-      }
-      if (k.gg != nullptr) k.gg[d] = gg;
-      if (k.gb != nullptr) k.gb[d] = gb;
-    }
-    el[tid] = e;
-    fl[tid] = f;
-    ggl[tid] = gg;
-    c1l[tid] = c1;
-    invl[tid] = inv;
-  }
-  __syncthreads();
-  if (k.gw != nullptr)
-    for (int i = tid; i < kCpRT * N; i += kCpMT) {
-      const int dl = i / N, n = i - dl * N, d = d0 + dl;
-      if (d >= k.D) continue;
-      float t = Tl[dl * (kCpMaxN + 1) + n];
-      if (!k.eval) {
-        float sw = 0.f;
-        if constexpr (SYNC) {   // Sigma as cps_finish left it, two floats an entry, summed in float64
-          const float* lo = cp_inv(k) + k.D + 1;
-          double s64 = 0.0;
-          for (int n2 = 0; n2 < N; ++n2) s64 += ((double)sg[n * N + n2] + (double)lo[n * N + n2]) * (double)wl[dl * kCpMaxN + n2];
-          sw = (float)s64;
-        } else {
-          for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * kCpMaxN + n2], sw);
-        }
-        t -= ggl[dl] * invl[dl] * sw;
-      }
-      k.gw[(long long)d * N + n] = c1l[dl] * t;
-    }
-  if (k.eval || k.kq_w == nullptr) return;
-  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
-  for (int i = tid; i < N + NN; i += kCpMT) {
-    float s = 0.f;
-    if (i < N) {
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * kCpMaxN + i], el[dl], s);
-    } else {
-      const int n = (i - N) / N, n2 = (i - N) - n * N;
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * kCpMaxN + n], wl[dl * kCpMaxN + n2], s);
-    }
-    kq[i] = s;
-  }
-}
-
-// ---- lanes along p -----------------------------------------------------------------------------------------------------------
-// grid = B * ceil(P / 64), block = 512: the 64 pixels from pt * 64 of image b.  LDS: red[NP * 64], kql[N + N * N], the table
-// of a block of channels tb[128][NP + 4].
-template <int NP>
-__global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
-  constexpr int kTS = NP + 4;   // floats per channel of the block's table: the row, the shift, G_bd / P (16-byte rows)
-  __shared__ float red[NP * 64];
-  __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
-  __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
-  __shared__ float cf[kCpMB * 4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
-  const bool live = p < k.P;
-  if (!k.eval)
-    for (int i = tid; i < N + NN; i += kCpT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
-  float c[NP], g[NP];
-  const long long base = (long long)b * N * k.P + p;
-#pragma unroll
-  for (int n = 0; n < NP; ++n) {
-    float v = 0.f;
-    if (n < N && live) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    c[n] = v;
-    g[n] = 0.f;
-  }
-  // D in blocks of 128 channels: the block's rows s_d w_d, shifts and G_bd / P go to LDS with coalesced, independent loads
-  // first (fetched per channel inside the loop they were a chain of dependent global loads: 0.6 us per channel, measured),
-  // then every wavefront walks its channels of the block reading them as broadcasts
-  for (int dB = 0; dB < k.D; dB += kCpMB) {
-    const int nd = min(kCpMB, k.D - dB);
-    if (dB > 0) __syncthreads();   // (the previous block has been read)
-    if (tid < nd) {
-      float scale, shift;
-      cp_coef(k, dB + tid, scale, shift);
-      cf[tid * 4] = scale;
-      tb[tid * kTS + NP] = shift;
-      tb[tid * kTS + NP + 1] = k.go[(long long)b * k.D + dB + tid] / (float)k.P;
-    }
-    __syncthreads();
-    for (int i = tid; i < nd * NP; i += kCpT) {
-      const int dl = i / NP, n = i - dl * NP;
-      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl * 4] : 0.f;
-    }
-    __syncthreads();
-    for (int dl = wv; dl < nd; dl += kCpW) {
-      const float* row = tb + dl * kTS;
-      float wsn[NP];
-      float a = row[NP];
-#pragma unroll
-      for (int n = 0; n < NP; ++n) {
-        wsn[n] = row[n];
-        a = fmaf(wsn[n], c[n], a);
-      }
-      const float t = a > 0.f ? row[NP + 1] : 0.f;
-#pragma unroll
-      for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], t, g[n]);
-    }
-  }
-  for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
-    if (wv == w) {
-#pragma unroll
-      for (int n = 0; n < NP; ++n) red[n * 64 + lane] = w == 0 ? g[n] : red[n * 64 + lane] + g[n];
-    }
-    __syncthreads();
-  }
-  if (!live) return;
-  for (int n = wv; n < N; n += kCpW) {
-    float v = red[n * 64 + lane];
-    if (!k.eval) {
-      float qc = kql[n];
-#pragma unroll
-      for (int n2 = 0; n2 < NP; ++n2)
-        if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
-      v -= qc;
-    }
-    const long long j = base + (long long)n * k.P;
-    if (k.bf16)
-      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
-    else
-      ((float*)k.gm)[j] = v;
-  }
-}
-
-// ---- cproj: the projection with the map kept ------------------------------------------------------------------------------
-constexpr int kCjT = 256;    // threads of cproj_fwd
-constexpr int kCjDT = 64;    // channels of D per workgroup of cproj_fwd
-constexpr int kCjSP = 64;    // pixels per pass of cproj_bwd_part
-constexpr int kCjSS = 68;    // floats between two rows of a pass in LDS: 16-byte rows, an odd number of 16-byte slots
-
-// grid = B * nc * tiles (the tile fastest), block = 256; k.CH / k.CHs / k.nc are this kernel's own chunks (cproj_fwd_chunk).
-// LDS: sm[NP * CHs], tb[64][NP + 1] — the scaled row of a channel, then its shift.
-template <int NP, bool RELU>
-__global__ void __launch_bounds__(kCjT) cproj_fwd(CpK k, int tiles) {
-  constexpr int kTS = NP + 1;
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* tb = sm + NP * k.CHs;
-  const int tid = threadIdx.x;
-  const int bj = blockIdx.x / tiles, tile = blockIdx.x - bj * tiles;
-  const int b = bj / k.nc, j = bj - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int d0 = tile * kCjDT, nd = min(kCjDT, k.D - d0);
-  cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-  for (int i = tid; i < nd * kTS; i += kCjT) {
-    const int dl = i / kTS, n = i - dl * kTS;
-    float scale, shift;
-    cp_coef(k, d0 + dl, scale, shift);
-    tb[i] = n == NP ? shift : (n < k.N ? k.w[(long long)(d0 + dl) * k.N + n] * scale : 0.f);
-  }
-  __syncthreads();
-  // element e = dl * ch + pl of the chunk's [nd][ch] range; a thread's next one is 256 further on
-  const int total = nd * ch, qT = kCjT / ch, rT = kCjT - qT * ch;
-  int dl = tid / ch, pl = tid - dl * ch;
-  const long long obase = ((long long)b * k.D + d0) * k.P + p0;
-  for (int e = tid; e < total; e += kCjT) {
-    const float* row = tb + dl * kTS;
-    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
-#pragma unroll
-    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * k.CHs + pl], a);
-    if (RELU) a = a < 0.f ? 0.f : a;
-    const long long o = obase + (long long)dl * k.P + pl;
-    if (k.bf16)
-      ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
-    else
-      ((float*)k.outv)[o] = a;
-    pl += rT, dl += qT;
-    if (pl >= ch) pl -= ch, ++dl;
-  }
-}
-
-// cproj_fwd for a channels-last out, [b][p][d]: the same grid, LDS and per-element chain — only who owns an element
-// changes.  The tile's share of the chunk is [ch][nd] with the channel fastest: element e = pl * nd + dl at
-// obase + pl * D + dl, so where the tile is all of D the chunk is one span of ch * D elements, and otherwise ch segments
-// of nd channels.  Lanes run along e: a wavefront's store covers whole segments (several pixels where D is small), the
-// rows of tb are read at an odd stride and the maps as broadcasts.
-// PAIR (bf16, out 4-byte aligned, and a single tile or an even D): a lane holds the two elements of an aligned dword and
-// stores them together.  With a single tile the pairs are laid over the span from its even address down (s: the span
-// starts on an odd element), so they may straddle two pixels' rows and the span's first and last element may stand
-// alone; with an even D every segment starts and ends on a pair.
-template <int NP, bool RELU, bool PAIR>
-__global__ void __launch_bounds__(kCjT) cproj_fwd_nhwc(CpK k, int tiles) {
-  constexpr int kTS = NP + 1;
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* tb = sm + NP * k.CHs;
-  const int tid = threadIdx.x;
-  const int bj = blockIdx.x / tiles, tile = blockIdx.x - bj * tiles;
-  const int b = bj / k.nc, j = bj - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int d0 = tile * kCjDT, nd = min(kCjDT, k.D - d0);
-  cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-  for (int i = tid; i < nd * kTS; i += kCjT) {
-    const int dl = i / kTS, n = i - dl * kTS;
-    float scale, shift;
-    cp_coef(k, d0 + dl, scale, shift);
-    tb[i] = n == NP ? shift : (n < k.N ? k.w[(long long)(d0 + dl) * k.N + n] * scale : 0.f);
-  }
-  __syncthreads();
-  const int CHs = k.CHs;
-  auto act = [&](int pl, int dl) {
-    const float* row = tb + dl * kTS;
-    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
-#pragma unroll
-    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * CHs + pl], a);
-    if (RELU) a = a < 0.f ? 0.f : a;
-    return a;
-  };
-  const int total = nd * ch;
-  const long long obase = ((long long)b * k.P + p0) * k.D + d0;
-  if (!PAIR) {
-    const int qT = kCjT / nd, rT = kCjT - qT * nd;   // a thread's next element is 256 further on
-    int pl = tid / nd, dl = tid - pl * nd;
-    for (int e = tid; e < total; e += kCjT) {
-      const float a = act(pl, dl);
-      const long long o = obase + (long long)pl * k.D + dl;
-      if (k.bf16)
-        ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
-      else
-        ((float*)k.outv)[o] = a;
-      dl += rT, pl += qT;
-      if (dl >= nd) dl -= nd, ++pl;
-    }
-  } else {
-    const int s = tiles == 1 ? (int)(obase & 1) : 0;
-    const int qT = 2 * kCjT / nd, rT = 2 * kCjT - qT * nd;   // a thread's next pair is 512 elements further on
-    int e0 = 2 * tid - s, pl = -1, dl = nd - 1;              // (e0 = -1: the element before the span)
-    if (e0 >= 0) pl = e0 / nd, dl = e0 - pl * nd;
-    for (; e0 < total; e0 += 2 * kCjT) {
-      int pl1 = pl, dl1 = dl + 1;
-      if (dl1 == nd) dl1 = 0, ++pl1;
-      const bool v0 = e0 >= 0, v1 = e0 + 1 < total;
-      const float a0 = v0 ? act(pl, dl) : 0.f, a1 = v1 ? act(pl1, dl1) : 0.f;
-      uint16_t* o = (uint16_t*)k.outv + (obase + (long long)pl * k.D + dl);
-      if (v0 && v1)
-        *(uint32_t*)o = f32_to_bf16x2(a0, a1);
-      else if (v0)
-        o[0] = f32_to_bf16(a0);
-      else
-        o[1] = f32_to_bf16(a1);
-      dl += rT, pl += qT;
-      if (dl >= nd) dl -= nd, ++pl;
-    }
-  }
-}
-
-// grid = (S, ceil(D / 128)), block = cp_part_threads: passes [s * upw, (s + 1) * upw) of the batch's B * nsub passes of 64
-// pixels.  LDS: sm[NP * 68], gl[128 * 68] (grad_out of the pass; at the end the join buffer red[128 * (NP + 1)]).
-// part_w: [S][D][N + 1], as cpool_bwd_part.
-// NHWC: grad_out is [b][p][d].  The tile goes into the same gl[dl * 68 + pl], read from global memory with d fastest: a
-// lane takes one channel at four neighbouring pixels — four loads that each run along d across the wavefront — and
-// stores them as one 16-byte row piece.  ds_write_b128 is served eight lanes at a time; eight neighbouring channels are
-// 8 * 68 floats apart, banks 4 * dl + {0..3} (mod 32): all 32 different.  (One pixel per lane, a dword each, puts the 32
-// lanes of a half on eight banks.)  Lanes cover the nd channels of the tile rounded up to a power of two, 8 at the
-// least; the rows beyond that are zeroed once.  Everything behind the staging is the NCHW kernel's, sum for sum.
-template <int NP, bool RELU, bool NHWC = false>
-__global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, int nsub, int upw) {
-  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* gl = sm + NP * kCjSS;
-  float* red = gl;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int sl = blockIdx.x, tile = blockIdx.y;
-  float ws[2][NP], sh[2], T[2][NP], gbs[2] = {0.f, 0.f};
-  if (RELU) cp_rows<NP>(k, tile, lane, ws, sh);
-#pragma unroll
-  for (int n = 0; n < NP; ++n) T[0][n] = T[1][n] = 0.f;
-  const int units = k.B * nsub, u0 = sl * upw, u1 = min(units, u0 + upw);
-  for (int u = u0; u < u1; ++u) {
-    const int b = u / nsub, ps = (u - b * nsub) * kCjSP, npx = min(kCjSP, k.P - ps);
-    if (u > u0) __syncthreads();   // (the previous pass has been read)
-    cp_stage(k, NP, sm, b, ps, npx, !k.eval);
-    if constexpr (NHWC) {
-      const int nd = min(kCpDT, k.D - tile * kCpDT), lg = nd <= 8 ? 3 : 32 - __clz(nd - 1);
-      if (u == u0)
-        for (int i = (kCjSS << lg) + tid; i < kCpDT * kCjSS; i += kT) gl[i] = 0.f;
-      for (int i = tid; i < (kCjSP / 4) << lg; i += kT) {
-        const int dl = i & ((1 << lg) - 1), q = i >> lg, d = tile * kCpDT + dl;
-        const long long g0 = ((long long)b * k.P + ps + 4 * q) * k.D + d;
-        float4 v;
-        v.x = (d < k.D && 4 * q < npx) ? cj_load(k, k.gov, g0) : 0.f;
-        v.y = (d < k.D && 4 * q + 1 < npx) ? cj_load(k, k.gov, g0 + k.D) : 0.f;
-        v.z = (d < k.D && 4 * q + 2 < npx) ? cj_load(k, k.gov, g0 + 2LL * k.D) : 0.f;
-        v.w = (d < k.D && 4 * q + 3 < npx) ? cj_load(k, k.gov, g0 + 3LL * k.D) : 0.f;
-        *(float4*)(gl + dl * kCjSS + 4 * q) = v;
-      }
-    } else {
-      for (int i = tid; i < kCpDT * kCjSP; i += kT) {
-        const int dl = i >> 6, pl = i & 63, d = tile * kCpDT + dl;
-        float v = 0.f;
-        if (d < k.D && pl < npx) v = cj_load(k, k.gov, ((long long)b * k.D + d) * k.P + ps + pl);
-        gl[dl * kCjSS + pl] = v;
-      }
-    }
-    __syncthreads();
-    const int nq = (npx + 3) >> 2;
-    for (int q = wv; q < nq; q += kW) {
-      float ga[2][4];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float4 g4 = ((const float4*)(gl + (lane + 64 * j) * kCjSS))[q];   // (zero beyond npx and D)
-        ga[j][0] = g4.x, ga[j][1] = g4.y, ga[j][2] = g4.z, ga[j][3] = g4.w;
-      }
-      if (RELU) {
-        float a[2][4];
-        cp_preact<NP>(sm, kCjSS, q, ws, sh, a);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ga[j][i] = a[j][i] > 0.f ? ga[j][i] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) gbs[j] += ga[j][i];
-#pragma unroll
-      for (int n = 0; n < NP; ++n) {
-        const float4 c = ((const float4*)(sm + n * kCjSS))[q];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          float t = T[j][n];
-          t = fmaf(ga[j][0], c.x, t);
-          t = fmaf(ga[j][1], c.y, t);
-          t = fmaf(ga[j][2], c.z, t);
-          t = fmaf(ga[j][3], c.w, t);
-          T[j][n] = t;
-        }
-      }
-    }
-  }
-  __syncthreads();   // (gl has been read: red takes its place)
-  for (int w = 0; w < kW; ++w) {   // the wavefronts in order into red[dl][NP + 1] (every lane its own words)
-    if (wv == w) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float* r = red + (lane + 64 * j) * (NP + 1);
-#pragma unroll
-        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
-        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
-      }
-    }
-    __syncthreads();
-  }
-  const int N1 = k.N + 1;
-  for (int i = tid; i < kCpDT * N1; i += kT) {
-    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
-    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
-  }
-}
-
-// grid = B * ceil(P / 64), block = 512: cpool_bwd_maps with grad_out read per (channel, pixel).  LDS: red[NP * 64],
-// kql[N + N * N], tb[128][NP + 4] — a channel's scaled row, then its shift.
-// NHWC: grad_out is [b][p][d], where a lane's own loads would be D elements apart.  The block's [64 pixels][<= 128 d] tile
-// comes through LDS instead — gt[pl * 129 + dl], written with d fastest across the lanes (whole segments of global
-// memory, consecutive banks) and read by every lane from its own pixel's row (an odd stride: 32 banks).  The sums are the
-// NCHW kernel's, in its order.
-template <int NP, bool RELU, bool NHWC = false>
-__global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
-  constexpr int kTS = NP + 4;
-  constexpr int kGS = kCpMB + 1;
-  __shared__ float red[NP * 64];
-  __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
-  __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
-  __shared__ float cf[kCpMB];
-  __shared__ float gt[NHWC ? 64 * kGS : 1];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
-  const bool live = p < k.P;
-  if (!k.eval)
-    for (int i = tid; i < N + NN; i += kCpT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
-  float c[NP], g[NP];
-  const long long base = (long long)b * N * k.P + p;
-#pragma unroll
-  for (int n = 0; n < NP; ++n) {
-    float v = 0.f;
-    if (n < N && live) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    c[n] = v;
-    g[n] = 0.f;
-  }
-  const long long gbase = (long long)b * k.D * k.P + p;
-  for (int dB = 0; dB < k.D; dB += kCpMB) {
-    const int nd = min(kCpMB, k.D - dB);
-    if (dB > 0) __syncthreads();   // (the previous block has been read)
-    if constexpr (NHWC) {
-      const int lg = nd <= 1 ? 0 : 32 - __clz(nd - 1);   // lanes cover nd rounded up to a power of two
-      for (int i = tid; i < 64 << lg; i += kCpT) {
-        const int dl = i & ((1 << lg) - 1), pl = i >> lg, pp = pt * 64 + pl;
-        if (dl < nd) gt[pl * kGS + dl] = pp < k.P ? cj_load(k, k.gov, ((long long)b * k.P + pp) * k.D + dB + dl) : 0.f;
-      }
-    }
-    if (tid < nd) {
-      float scale, shift;
-      cp_coef(k, dB + tid, scale, shift);
-      cf[tid] = scale;
-      tb[tid * kTS + NP] = shift;
-    }
-    __syncthreads();
-    for (int i = tid; i < nd * NP; i += kCpT) {
-      const int dl = i / NP, n = i - dl * NP;
-      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl] : 0.f;
-    }
-    __syncthreads();
-    for (int dl0 = wv; dl0 < nd; dl0 += 4 * kCpW) {   // four channels' grad_out loads together, used in channel order
-      float t[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int dl = dl0 + u * kCpW;
-        if constexpr (NHWC)
-          t[u] = dl < nd ? gt[lane * kGS + dl] : 0.f;   // (zero beyond P)
-        else
-          t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int dl = dl0 + u * kCpW;
-        if (dl >= nd) break;   // (the same in every lane)
-        const float* row = tb + dl * kTS;
-        float wsn[NP];
-#pragma unroll
-        for (int n = 0; n < NP; ++n) wsn[n] = row[n];
-        float tu = t[u];
-        if (RELU) {
-          float a = row[NP];
-#pragma unroll
-          for (int n = 0; n < NP; ++n) a = fmaf(wsn[n], c[n], a);
-          tu = a > 0.f ? tu : 0.f;
-        }
-#pragma unroll
-        for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], tu, g[n]);
-      }
-    }
-  }
-  for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
-    if (wv == w) {
-#pragma unroll
-      for (int n = 0; n < NP; ++n) red[n * 64 + lane] = w == 0 ? g[n] : red[n * 64 + lane] + g[n];
-    }
-    __syncthreads();
-  }
-  if (!live) return;
-  for (int n = wv; n < N; n += kCpW) {
-    float v = red[n * 64 + lane];
-    if (!k.eval) {
-      float qc = kql[n];
-#pragma unroll
-      for (int n2 = 0; n2 < NP; ++n2)
-        if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
-      v -= qc;
-    }
-    const long long j = base + (long long)n * k.P;
-    if (k.bf16)
-      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
-    else
-      ((float*)k.gm)[j] = v;
-  }
-}
-
-// ---- the wide form: 1 <= N <= 96 maps (nfp_cpool_wide_*) --------------------------------------------------------------------
-// The kernels above keep a lane's weight rows, its T sums or a pixel's c_n in registers: a cost that grows with N and ends at
-// 32 maps.  Here the rows of a block of 64 channels and the chunk's centred maps both sit in LDS, and a lane owns a small
-// tile of outputs: nothing in registers grows with N beyond N' / 16 <= 6 accumulators per owned row (N' = N rounded up to 16).
-// The formulas, the saved state (2N + N^2 + D floats) and the layouts of the partial sums are the ones above.
-//   cpw_moments     cpool_moments with the Gram as 4 x 4 register tiles of (n, n2) pairs, each pair's sum in pixel order
-//   cpw_mu          one workgroup: mu in float64 from the chunks' anchors (eight slices of consecutive chunks, in order)
-//   cpw_sigma       one workgroup per 64 (n, n2) pairs: cpool_finish's join of the chunks in float64, four slices in order
-//   cpw_var         one workgroup per 16 channels: w_d^T Sigma w_d in float64, the rows of Sigma dealt to sixteen slices
-//                   joined in order; inv_d and the running statistics
-//   cpw_fwd         one workgroup per (image, 64 channels): a lane owns 4 channels x 4 pixels of pre-activations, summed
-//                   over n from two ds_read_b128 (the rows transposed, tb[n][d]; the maps sm[n][p]); the sixteen pixel
-//                   slots joined in order
-//   cpw_bwd_part    the same pre-activations over a slice of the batch, ga written to LDS as [p][d]; then T_dn as a second
-//                   product, a lane owning 4 channels x N'/16 maps, summed over the pixels in order (no join)
-//   cpw_bwd_reduce  cpool_bwd_reduce with its tables sized by N
-//   cpw_bwd_maps    one workgroup per 64 pixels of an image: per block of 64 channels the pre-activations as in cpw_fwd, the
-//                   masked G_bd / P to LDS as [d][p]; then sum_d s_d w_dn ga_dp, a lane owning 4 pixels x N'/16 maps, summed
-//                   over d in order; then - k - Q c from LDS
-// Every a_bdp is one chain — the shift, then the maps in order (cw_preact) — in all three kernels: the same bits, the same mask.
-constexpr int kWT = 256;          // threads of every wide kernel but cpw_mu
-constexpr int kWDT = 64;          // channels of D per workgroup / per LDS block
-constexpr int kWRS = kWDT + 4;    // floats between two maps' rows of the transposed table: 16-byte rows, an odd number of slots
-constexpr int kWMaxN = 96;
-constexpr int kWJ = kWMaxN / 16;  // maps per lane of the second products
-constexpr int kWBudget = 16384;   // floats of LDS the chunk's maps and ga may take together (cpw_chunk)
-constexpr int kWMuT = 1024;       // threads of cpw_mu
-
-// tb[n * 68 + dl] = s_d w_dn and sh[dl] of the 64 channels from d0 (zero beyond D and N); cf: 64 floats of scratch.
-// The caller has a barrier before (tb is free) and after.
-__device__ __forceinline__ void cw_rows(const CpK& k, int NP, int d0, float* tb, float* sh, float* cf) {
-  const int tid = threadIdx.x;
-  if (tid < kWDT) {
-    float scale = 0.f, shift = 0.f;
-    if (d0 + tid < k.D) cp_coef(k, d0 + tid, scale, shift);
-    cf[tid] = scale;
-    sh[tid] = shift;
-  }
-  __syncthreads();
-  for (int i = tid; i < kWDT * NP; i += kWT) {
-    const int dl = i / NP, n = i - dl * NP, d = d0 + dl;
-    tb[n * kWRS + dl] = (d < k.D && n < k.N) ? k.w[(long long)d * k.N + n] * cf[dl] : 0.f;
-  }
-}
-
-// a of channels 4 dg .. 4 dg + 3 at the pixels 4 q .. 4 q + 3 of sm (rows rs floats apart): the shift first, then the maps
-// in order
-__device__ __forceinline__ void cw_preact(const float* tb, const float* sh, const float* sm, int rs, int NP, int dg, int q,
-                                          float (&a)[4][4]) {
-  const float4 s4 = *(const float4*)(sh + 4 * dg);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) a[0][j] = s4.x, a[1][j] = s4.y, a[2][j] = s4.z, a[3][j] = s4.w;
-  const float* tp = tb + 4 * dg;
-  const float* cp = sm + 4 * q;
-#pragma unroll 4
-  for (int n = 0; n < NP; ++n) {
-    const float4 w = *(const float4*)(tp + n * kWRS);
-    const float4 c = *(const float4*)(cp + n * rs);
-    const float wv[4] = {w.x, w.y, w.z, w.w}, cv[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[i][j] = fmaf(wv[i], cv[j], a[i][j]);
-  }
-}
-
-// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP].  part_w: per chunk [a (N), r (N), Gram (N * N)].
-__global__ void __launch_bounds__(kWT) cpw_moments(CpK k, int NP) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* anchor = sm + NP * k.CHs;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kWT >> 6;
-  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int N = k.N;
-  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
-  cp_stage(k, NP, sm, b, p0, ch, false);
-  __syncthreads();
-  for (int n = wv; n < N; n += nw) {
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
-    s = cp_wave_sum(s);
-    if (lane == 0) anchor[n] = s / (float)ch;
-  }
-  __syncthreads();
-  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
-    const float an = anchor[n];
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) {
-      const float c = sm[n * k.CHs + pl] - an;
-      sm[n * k.CHs + pl] = c;
-      s += c;
-    }
-    s = cp_wave_sum(s);
-    if (lane == 0) {
-      outp[n] = an;
-      outp[N + n] = s / (float)ch;
-    }
-  }
-  __syncthreads();
-  const int nq = (ch + 3) >> 2, NT = NP >> 2;
-  for (int t = tid; t < NT * NT; t += kWT) {
-    const int tn = t / NT, tm = t - tn * NT;
-    const float4* ra = (const float4*)(sm + 4 * tn * k.CHs);
-    const float4* rb = (const float4*)(sm + 4 * tm * k.CHs);
-    const int qs = k.CHs >> 2;
-    float g[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) g[i][jj] = 0.f;
-    for (int q = 0; q < nq; ++q) {
-      float4 x[4], y[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) x[i] = ra[i * qs + q], y[i] = rb[i * qs + q];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          float v = g[i][jj];
-          v = fmaf(x[i].x, y[jj].x, v);
-          v = fmaf(x[i].y, y[jj].y, v);
-          v = fmaf(x[i].z, y[jj].z, v);
-          v = fmaf(x[i].w, y[jj].w, v);
-          g[i][jj] = v;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int n = 4 * tn + i, n2 = 4 * tm + jj;
-        if (n < N && n2 < N) outp[2 * N + n * N + n2] = g[i][jj];
-      }
-  }
-}
-
-// pixels of chunk c (chunk j of its image)
-__device__ __forceinline__ double cw_count(const CpK& k, int j) {
-  return j == k.nc - 1 ? (double)(k.P - (k.nc - 1) * k.CH) : (double)k.CH;
-}
-
-// grid = 1, block = 1024: thread (n = tid % 128, slice = tid / 128).  mu64: N doubles.
-__global__ void __launch_bounds__(kWMuT) cpw_mu(CpK k, double* mu64) {
-  __shared__ double red[kWMuT];
-  const int tid = threadIdx.x, N = k.N, K = k.B * k.nc, rec = 2 * N + N * N;
-  const int n = tid & 127, sl = tid >> 7, Kc = (K + 7) / 8;
-  const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
-  double s = 0.0;
-  if (n < N) {
-    int j = c0 % k.nc;
-#pragma unroll 4
-    for (int c = c0; c < c1; ++c) {
-      const float* r = k.part + (long long)c * rec;
-      s += cw_count(k, j) * ((double)r[n] + (double)r[N + n]);
-      if (++j == k.nc) j = 0;
-    }
-  }
-  red[tid] = s;
-  __syncthreads();
-  if (tid < N) {
-    double t = red[tid];
-    for (int i = 1; i < 8; ++i) t += red[i * 128 + tid];
-    t /= k.M;
-    mu64[tid] = t;
-    const float hi = (float)t;
-    k.stats_w[tid] = hi;
-    k.stats_w[N + tid] = (float)(t - (double)hi);
-  }
-}
-
-// grid = ceil(N^2 / 64), block = 256: thread (pair = 64 blockIdx + tid % 64, slice = tid / 64).  sig64: N * N doubles.
-__global__ void __launch_bounds__(kWT) cpw_sigma(CpK k, const double* mu64, double* sig64) {
-  __shared__ double red[kWT];
-  const int tid = threadIdx.x, N = k.N, NN = N * N, K = k.B * k.nc, rec = 2 * N + NN;
-  const int pl = tid & 63, sl = tid >> 6, pr = blockIdx.x * 64 + pl, Kc = (K + 3) / 4;
-  double s = 0.0;
-  if (pr < NN) {
-    const int n = pr / N, n2 = pr - n * N;
-    const int c0 = min(K, sl * Kc), c1 = min(K, c0 + Kc);
-    const double m1 = mu64[n], m2 = mu64[n2];
-    int j = c0 % k.nc;
-#pragma unroll 4
-    for (int c = c0; c < c1; ++c) {
-      const float* r = k.part + (long long)c * rec;
-      const double d1 = (double)r[n] - m1, d2 = (double)r[n2] - m2, r1 = r[N + n], r2 = r[N + n2];
-      s += (double)r[2 * N + pr] + cw_count(k, j) * (r1 * d2 + d1 * r2 + d1 * d2);
-      if (++j == k.nc) j = 0;
-    }
-  }
-  red[tid] = s;
-  __syncthreads();
-  if (tid < 64 && pr < NN) {
-    const double t = (((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid]) / k.M;
-    sig64[pr] = t;
-    k.stats_w[2 * N + pr] = (float)t;
-  }
-}
-
-// grid = ceil(D / 16), block = 256: thread (channel = 16 blockIdx + tid % 16, slice = tid / 16) takes the rows
-// n = slice, slice + 16, ... of Sigma.
-__global__ void __launch_bounds__(kWT) cpw_var(CpK k, const double* mu64, const double* sig64) {
-  __shared__ double wl[kWMaxN * 16];   // [n][dl]
-  __shared__ double red[kWT];
-  const int tid = threadIdx.x, N = k.N, dl = tid & 15, sl = tid >> 4, d0 = blockIdx.x * 16;
-  for (int i = tid; i < 16 * N; i += kWT) {
-    const int dd = i / N, n = i - dd * N;
-    wl[n * 16 + dd] = d0 + dd < k.D ? (double)k.w[(long long)(d0 + dd) * N + n] : 0.0;
-  }
-  __syncthreads();
-  double acc = 0.0;
-  for (int n = sl; n < N; n += 16) {
-    const double* row = sig64 + n * N;
-    double v = 0.0;
-#pragma unroll 4
-    for (int n2 = 0; n2 < N; ++n2) v += row[n2] * wl[n2 * 16 + dl];
-    acc += wl[n * 16 + dl] * v;
-  }
-  red[tid] = acc;
-  __syncthreads();
-  const int d = d0 + tid;
-  if (tid >= 16 || d >= k.D) return;
-  double var = red[tid], mean = 0.0;
-  for (int i = 1; i < 16; ++i) var += red[i * 16 + tid];
-  for (int n = 0; n < N; ++n) mean += wl[n * 16 + tid] * mu64[n];
-  var = var > 0.0 ? var : 0.0;
-  k.stats_w[2 * N + N * N + d] = (float)(1.0 / sqrt(var + k.eps64));
-  if (k.rm_w != nullptr) {
-    k.rm_w[d] = (float)((1.0 - k.mom) * (double)k.rm_w[d] + k.mom * mean);
-    k.rv_w[d] = (float)((1.0 - k.mom) * (double)k.rv_w[d] + k.mom * var * (k.M / (k.M - 1.0)));
-  }
-}
-
-// grid = (B, ceil(D / 64)), block = 256: thread (dg = tid % 16: four channels, qs = tid / 16: a slot of pixel quads).
-// LDS: tb[NP * 68], sh[64], cf[64], sm[NP * CHs], red[16 * 64].
-__global__ void __launch_bounds__(kWT) cpw_fwd(CpK k, int NP) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* tb = cp_lds;
-  float* sh = tb + NP * kWRS;
-  float* cf = sh + kWDT;
-  float* sm = cf + kWDT;
-  float* red = sm + NP * k.CHs;
-  const int tid = threadIdx.x, dg = tid & 15, qs = tid >> 4;
-  const int b = blockIdx.x, d0 = blockIdx.y * kWDT;
-  cw_rows(k, NP, d0, tb, sh, cf);
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int p0 = 0; p0 < k.P; p0 += k.CH) {
-    const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
-    if (p0 > 0) __syncthreads();   // (the previous chunk has been read)
-    cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-    __syncthreads();
-    for (int q = qs; q < nq; q += 16) {
-      float a[4][4];
-      cw_preact(tb, sh, sm, k.CHs, NP, dg, q, a);
-      const int nv = min(4, ch - 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (j < nv) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) s[i] += fmaxf(a[i][j], 0.f);
-        }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[qs * kWDT + 4 * dg + i] = s[i];
-  __syncthreads();
-  const int d = d0 + tid;
-  if (tid < kWDT && d < k.D) {
-    float t = red[tid];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) t += red[w * kWDT + tid];
-    k.out[(long long)b * k.D + d] = t / (float)k.P;
-  }
-}
-
-// grid = (S, ceil(D / 64)), block = 256: images [s * ipw, (s + 1) * ipw) of the batch.  Thread (dg, qs) as in cpw_fwd for
-// the pre-activations; (dg: four channels, ns = tid / 16: the maps ns, ns + 16, ...) for T.
-// LDS: tb[NP * 68], sh[64], cf[64], gp[64] (G_bd / P of the image), sm[NP * CHs], ga[CHs * 68] ([p][d]).
-// part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
-__global__ void __launch_bounds__(kWT) cpw_bwd_part(CpK k, int NP) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* tb = cp_lds;
-  float* sh = tb + NP * kWRS;
-  float* cf = sh + kWDT;
-  float* gp = cf + kWDT;
-  float* sm = gp + kWDT;
-  float* ga = sm + NP * k.CHs;
-  const int tid = threadIdx.x, dg = tid & 15, qs = tid >> 4, ns = qs, nj = NP >> 4;
-  const int sl = blockIdx.x, d0 = blockIdx.y * kWDT;
-  cw_rows(k, NP, d0, tb, sh, cf);
-  float T[4][kWJ], gbs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < kWJ; ++j) T[i][j] = 0.f;
-  const int b1 = min(k.B, (sl + 1) * k.ipw);
-  for (int b = sl * k.ipw; b < b1; ++b) {
-    // (every thread is behind the barrier that follows the last read of gp)
-    if (tid < kWDT) gp[tid] = d0 + tid < k.D ? k.go[(long long)b * k.D + d0 + tid] / (float)k.P : 0.f;
-    for (int p0 = 0; p0 < k.P; p0 += k.CH) {
-      const int ch = min(k.CH, k.P - p0), nq = (ch + 3) >> 2;
-      __syncthreads();   // (the previous chunk's sm and ga have been read; the first time: tb is written)
-      cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-      __syncthreads();
-      const float4 g4 = *(const float4*)(gp + 4 * dg);
-      for (int q = qs; q < nq; q += 16) {
-        float a[4][4];
-        cw_preact(tb, sh, sm, k.CHs, NP, dg, q, a);
-        const int nv = min(4, ch - 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float4 v;
-          v.x = (j < nv && a[0][j] > 0.f) ? g4.x : 0.f;
-          v.y = (j < nv && a[1][j] > 0.f) ? g4.y : 0.f;
-          v.z = (j < nv && a[2][j] > 0.f) ? g4.z : 0.f;
-          v.w = (j < nv && a[3][j] > 0.f) ? g4.w : 0.f;
-          *(float4*)(ga + (4 * q + j) * kWRS + 4 * dg) = v;
-        }
-      }
-      __syncthreads();
-      for (int q = 0; q < nq; ++q) {
-        float4 gv[4], cv[kWJ];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) gv[jj] = *(const float4*)(ga + (4 * q + jj) * kWRS + 4 * dg);
-#pragma unroll
-        for (int j = 0; j < kWJ; ++j)
-          if (j < nj) cv[j] = *(const float4*)(sm + (ns + 16 * j) * k.CHs + 4 * q);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const float g[4] = {gv[jj].x, gv[jj].y, gv[jj].z, gv[jj].w};
-          if (ns == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) gbs[i] += g[i];
-          }
-#pragma unroll
-          for (int j = 0; j < kWJ; ++j)
-            if (j < nj) {
-              const float c = jj == 0 ? cv[j].x : jj == 1 ? cv[j].y : jj == 2 ? cv[j].z : cv[j].w;
-#pragma unroll
-              for (int i = 0; i < 4; ++i) T[i][j] = fmaf(g[i], c, T[i][j]);
-            }
-        }
-      }
-    }
-  }
-  const int N1 = k.N + 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int d = d0 + 4 * dg + i;
-    if (d >= k.D) continue;
-    float* row = k.part_w + ((long long)sl * k.D + d) * N1;
-#pragma unroll
-    for (int j = 0; j < kWJ; ++j)
-      if (j < nj && ns + 16 * j < k.N) row[ns + 16 * j] = T[i][j];
-    if (ns == 0) row[k.N] = gbs[i];
-  }
-}
-
-// grid = ceil(D / 32), block = 256.  LDS: Tl[32 * (N + 1)], wl[32 * N], sg[N * N].
-// kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
-__global__ void __launch_bounds__(kWT) cpw_bwd_reduce(CpK k) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
-  const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
-  float* Tl = cp_lds;
-  float* wl = Tl + kCpRT * N1;
-  float* sg = wl + kCpRT * N;
-  const long long stride = (long long)k.D * N1;
-  for (int i = tid; i < kCpRT * N1; i += kWT) {
-    const int dl = i / N1;
-    float acc = 0.f;
-    if (d0 + dl < k.D) {
-      const float* src = k.part + (long long)d0 * N1 + i;
-      for (int sl0 = 0; sl0 < k.S; sl0 += 8) {   // eight slices' loads issued together, added in slice order
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = src[min(sl0 + u, k.S - 1) * stride];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (sl0 + u < k.S) acc += v[u];
-      }
-    }
-    Tl[i] = acc;
-  }
-  for (int i = tid; i < kCpRT * N; i += kWT) {
-    const int dl = i / N;
-    wl[i] = d0 + dl < k.D ? k.w[(long long)d0 * N + i] : 0.f;
-  }
-  if (!k.eval)
-    for (int i = tid; i < NN; i += kWT) sg[i] = k.stats[2 * N + i];
-  __syncthreads();
-  if (tid < kCpRT) {
-    const int d = d0 + tid;
-    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
-    if (d < k.D) {
-      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
-      c1 = k.gamma[d] * inv;
-      const float gb = Tl[tid * N1 + N];
-      float dot = 0.f;
-      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * N + n], Tl[tid * N1 + n], dot);
-      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
-      if (!k.eval) {
-        e = c1 * (gb / (float)k.M);
-        f = c1 * (gg * inv / (float)k.M);
-      }
-      if (k.gg != nullptr) k.gg[d] = gg;
-      if (k.gb != nullptr) k.gb[d] = gb;
-    }
-    el[tid] = e;
-    fl[tid] = f;
-    ggl[tid] = gg;
-    c1l[tid] = c1;
-    invl[tid] = inv;
-  }
-  __syncthreads();
-  if (k.gw != nullptr)
-    for (int i = tid; i < kCpRT * N; i += kWT) {
-      const int dl = i / N, n = i - dl * N, d = d0 + dl;
-      if (d >= k.D) continue;
-      float t = Tl[dl * N1 + n];
-      if (!k.eval) {
-        float sw = 0.f;
-        for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * N + n2], sw);
-        t -= ggl[dl] * invl[dl] * sw;
-      }
-      k.gw[(long long)d * N + n] = c1l[dl] * t;
-    }
-  if (k.eval || k.kq_w == nullptr) return;
-  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
-  for (int i = tid; i < N + NN; i += kWT) {
-    float s = 0.f;
-    if (i < N) {
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * N + i], el[dl], s);
-    } else {
-      const int n = (i - N) / N, n2 = (i - N) - n * N;
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * N + n], wl[dl * N + n2], s);
-    }
-    kq[i] = s;
-  }
-}
-
-// grid = B * ceil(P / 64), block = 256: the 64 pixels from pt * 64 of image b.  Thread (dg = tid % 16, q = tid / 16) for
-// the pre-activations of a block of 64 channels; (pq = tid % 16: four pixels, ns = tid / 16: the maps ns, ns + 16, ...) for
-// the sums over d.
-// LDS: cl[NP * 68] (c_n of the pixels), sh[64], cf[64], gp[64], tb[NP * 68], tt[64 * 68] (the masked G_bd / P, [d][p]);
-// after the last block tb and tt together hold k and Q (N + N * N <= 68 N' + 4352 up to 107 maps).
-__global__ void __launch_bounds__(kWT) cpw_bwd_maps(CpK k, int NP, int npt) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* cl = cp_lds;
-  float* sh = cl + NP * kWRS;
-  float* cf = sh + kWDT;
-  float* gp = cf + kWDT;
-  float* tb = gp + kWDT;
-  float* tt = tb + NP * kWRS;
-  float* kql = tb;
-  const int tid = threadIdx.x, dg = tid & 15, q = tid >> 4, pq = dg, ns = q, nj = NP >> 4;
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p0 = pt * 64, N = k.N, NN = N * N;
-  const int npx = min(64, k.P - p0);
-  const long long base = (long long)b * N * k.P + p0;
-  for (int i = tid; i < NP * 64; i += kWT) {
-    const int n = i >> 6, pl = i & 63;
-    float v = 0.f;
-    if (n < N && pl < npx) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    cl[n * kWRS + pl] = v;
-  }
-  float g[4][kWJ];   // [pixel][map]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < kWJ; ++j) g[i][j] = 0.f;
-  for (int dB = 0; dB < k.D; dB += kWDT) {
-    __syncthreads();   // (the previous block has been read; the first time: cl is written)
-    if (tid < kWDT) gp[tid] = dB + tid < k.D ? k.go[(long long)b * k.D + dB + tid] / (float)k.P : 0.f;
-    cw_rows(k, NP, dB, tb, sh, cf);
-    __syncthreads();
-    {
-      float a[4][4];
-      cw_preact(tb, sh, cl, kWRS, NP, dg, q, a);
-      const float4 g4 = *(const float4*)(gp + 4 * dg);
-      const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float4 v;
-        v.x = a[i][0] > 0.f ? gv[i] : 0.f;
-        v.y = a[i][1] > 0.f ? gv[i] : 0.f;
-        v.z = a[i][2] > 0.f ? gv[i] : 0.f;
-        v.w = a[i][3] > 0.f ? gv[i] : 0.f;
-        *(float4*)(tt + (4 * dg + i) * kWRS + 4 * q) = v;
-      }
-    }
-    __syncthreads();
-    for (int d4 = 0; d4 < kWDT; d4 += 4) {
-      float4 tv[4], wv[kWJ];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) tv[i] = *(const float4*)(tt + (d4 + i) * kWRS + 4 * pq);
-#pragma unroll
-      for (int j = 0; j < kWJ; ++j)
-        if (j < nj) wv[j] = *(const float4*)(tb + (ns + 16 * j) * kWRS + d4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float t[4] = {tv[i].x, tv[i].y, tv[i].z, tv[i].w};
-#pragma unroll
-        for (int j = 0; j < kWJ; ++j)
-          if (j < nj) {
-            const float w = i == 0 ? wv[j].x : i == 1 ? wv[j].y : i == 2 ? wv[j].z : wv[j].w;
-#pragma unroll
-            for (int px = 0; px < 4; ++px) g[px][j] = fmaf(w, t[px], g[px][j]);
-          }
-      }
-    }
-  }
-  if (!k.eval) {
-    __syncthreads();   // (tb and tt have been read: k and Q take their place)
-    for (int i = tid; i < N + NN; i += kWT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int j = 0; j < kWJ; ++j) {
-    const int n = ns + 16 * j;
-    if (j >= nj || n >= N) continue;
-    float v[4] = {g[0][j], g[1][j], g[2][j], g[3][j]};
-    if (!k.eval) {
-      float qc[4] = {kql[n], kql[n], kql[n], kql[n]};
-      for (int n2 = 0; n2 < N; ++n2) {
-        const float qv = kql[N + n * N + n2];
-        const float4 c = *(const float4*)(cl + n2 * kWRS + 4 * pq);
-        qc[0] = fmaf(qv, c.x, qc[0]);
-        qc[1] = fmaf(qv, c.y, qc[1]);
-        qc[2] = fmaf(qv, c.z, qc[2]);
-        qc[3] = fmaf(qv, c.w, qc[3]);
-      }
-#pragma unroll
-      for (int px = 0; px < 4; ++px) v[px] -= qc[px];
-    }
-#pragma unroll
-    for (int px = 0; px < 4; ++px) {
-      if (4 * pq + px >= npx) continue;
-      const long long o = base + (long long)n * k.P + 4 * pq + px;
-      if (k.bf16)
-        ((uint16_t*)k.gm)[o] = f32_to_bf16(v[px]);
-      else
-        ((float*)k.gm)[o] = v[px];
-    }
-  }
-}
-
-}  // namespace
-}  // namespace nfp
+//
+// The kernels are in nfp_cp_kernels.h; this file is the host path of all twelve launching entries.  An entry states its call
+// as a CpCall; behind the checks the call becomes a CpK (cp_fwd_k / cp_bwd_k) that a few steps fill further and launch from:
+//   forward   cp_local_stats | cps_rank_record | cps_joined_stats, then cp_main_forward
+//   backward  cp_sums, cps_rank_row, cp_grad_maps
+// cp_forward / cp_backward (one rank) and cps_moments / cps_forward / cps_reduce / cps_maps (several) are compositions of
+// those.  Which chunk, stride, passes and slices a kind launches with is decided in cp_chunks and cp_slices alone, and the
+// layout of the scratch in cp_records / cp_parts alone, for the steps and the nfp_*_scratch_floats queries alike.
+#include "nfp_cp_kernels.h"
 
 namespace nfp_host {
 namespace {
 
-int cpool_np(int N) { return (N + 7) & ~7; }
-// pixels per chunk: the whole image where it fits the budget, else a multiple of 64
-int cpool_chunk(int NP, long long P) {
-  long long ch = std::min<long long>(P, nfp::kCpBudget / NP);
-  if (ch < P) ch &= ~63LL;
-  return (int)ch;
-}
-// floats between two rows of the chunk in LDS: a multiple of 4 (16-byte reads) and an odd number of 16-byte slots, so
-// that sixteen rows at one quad (cpool_moments' Gram) fall on sixteen different slots
-int cpool_stride(int ch) {
-  int s = (ch + 3) & ~3;
-  if (((s >> 2) & 1) == 0) s += 4;
-  return s;
-}
-int cpool_tiles(int D) { return (D + nfp::kCpDT - 1) / nfp::kCpDT; }
-int cpool_rtiles(int D) { return (D + nfp::kCpRT - 1) / nfp::kCpRT; }
-// images per workgroup of cpool_bwd_part: about 512 workgroups, at most one per image
-int cpool_ipw(int B, int D) {
-  const int want = std::min(B, std::max(1, 512 / cpool_tiles(D)));
-  return (B + want - 1) / want;
-}
-int cpool_slices(int B, int D) {
-  const int ipw = cpool_ipw(B, D);
-  return (B + ipw - 1) / ipw;
-}
-
-// ---- the wide form's sizes ----
-int cpw_np(int N) { return (N + 15) & ~15; }
-// pixels per chunk: the whole image where its maps and ga fit kWBudget floats of LDS beside the rows, else a multiple of 64
-// (64 at 64 maps and more, 128 at 32 and 48, 192 at 16)
-int cpw_chunk(int NP, long long P) {
-  return (int)std::min<long long>(P, std::max(64, (nfp::kWBudget / (NP + nfp::kWRS)) & ~63));
-}
-int cpw_tiles(int D) { return (D + nfp::kWDT - 1) / nfp::kWDT; }
-// images per workgroup of cpw_bwd_part: about 512 workgroups, at most one per image
-int cpw_ipw(int B, int D) {
-  const int want = std::min(B, std::max(1, 512 / cpw_tiles(D)));
-  return (B + want - 1) / want;
-}
-int cpw_slices(int B, int D) {
-  const int ipw = cpw_ipw(B, D);
-  return (B + ipw - 1) / ipw;
-}
-
-int cpool_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training, bool wide = false) {
-  const int maxN = wide ? nfp::kWMaxN : nfp::kCpMaxN;
-  if (B < 0 || N < 1 || P < 1 || D < 1)
-    return fail(NFP_E_INVALID, "%s: B = %d, N = %d, P = %lld, D = %d", what, B, N, (long long)P, D);
-  if (dtype != NFP_F32 && dtype != NFP_BF16) return fail(NFP_E_INVALID, "%s: unknown dtype %d", what, dtype);
-  if (N > maxN) return fail(NFP_E_UNSUPPORTED, "%s: N = %d maps (more than %d) has no kernel", what, N, maxN);
-  if ((long long)N * P >= (1LL << 31))
-    return fail(NFP_E_UNSUPPORTED, "%s: an image of N * P = %lld map elements (2^31 and more) has no kernel", what,
-                (long long)N * P);
-  if (D > (1 << 22)) return fail(NFP_E_UNSUPPORTED, "%s: D = %d (more than 2^22) has no kernel", what, D);
-  const long long ch = wide ? cpw_chunk(cpw_np(N), P) : cpool_chunk(cpool_np(N), P), nc = (P + ch - 1) / ch;
-  if ((long long)B * std::max<long long>(nc, (P + 63) / 64) >= (1LL << 31))
-    return fail(NFP_E_UNSUPPORTED, "%s: B = %d images of P = %lld pixels make 2^31 workgroups and more", what, B, (long long)P);
-  if (training && B > 0 && (long long)B * P < 2)
-    return fail(NFP_E_UNSUPPORTED, "%s: train-mode statistics need B * P >= 2 values per channel", what);
-  return NFP_OK;
-}
-
-nfp::CpK cpool_k(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
-  nfp::CpK k;
-  memset(&k, 0, sizeof(k));
-  const int NP = cpool_np(N);
-  k.B = B, k.N = N, k.P = (int)P, k.D = D;
-  k.CH = cpool_chunk(NP, P), k.CHs = cpool_stride(k.CH);
-  k.nc = (int)((P + k.CH - 1) / k.CH);
-  k.bf16 = dtype == NFP_BF16, k.eval = !training;
-  k.ipw = cpool_ipw(std::max(B, 1), D), k.S = cpool_slices(std::max(B, 1), D), k.ntr = cpool_rtiles(D);
-  k.M = (double)B * (double)P;
-  return k;
-}
-
-template <template <int> class F, typename... A>
-int cpool_by_np(int NP, A... a) {
-  switch (NP) {
-    case 8: return F<8>::go(a...);
-    case 16: return F<16>::go(a...);
-    case 24: return F<24>::go(a...);
-    default: return F<32>::go(a...);
-  }
-}
-template <int NP>
-struct LFwd {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const size_t lds = ((size_t)NP * k.CHs + nfp::kCpW * nfp::kCpDT) * sizeof(float);
-    return launch("cpool_fwd", nfp::cpool_fwd<NP>, dim3((unsigned)k.B, (unsigned)cpool_tiles(k.D)), dim3(nfp::kCpT), lds, st, k);
-  }
-};
-template <int NP>
-struct LPart {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCpDT * (NP + 1)) * sizeof(float);
-    return launch("cpool_bwd_part", nfp::cpool_bwd_part<NP>, dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)),
-                  dim3(nfp::cp_part_threads<NP>()), lds, st, k);
-  }
-};
-template <int NP>
-struct LMaps {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const int npt = (k.P + 63) / 64;
-    return launch("cpool_bwd_maps", nfp::cpool_bwd_maps<NP>, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st, k,
-                  npt);
-  }
-};
-
-int64_t cpool_fwd_scratch(int32_t B, int32_t N, int64_t P) {
-  const int ch = cpool_chunk(cpool_np(N), P);
-  return (int64_t)B * ((P + ch - 1) / ch) * (2 * N + N * N);
-}
-int64_t cpool_bwd_scratch(int32_t B, int32_t N, int32_t D) {
-  return (int64_t)cpool_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
-}
-// the wide forward: the chunks' records, then (from an even float on) mu and Sigma as doubles
-int64_t cpw_fwd_records(int32_t B, int32_t N, int64_t P) {
-  const int ch = cpw_chunk(cpw_np(N), P);
-  return ((int64_t)B * ((P + ch - 1) / ch) * (2 * N + N * N) + 1) & ~(int64_t)1;
-}
-int64_t cpw_fwd_scratch(int32_t B, int32_t N, int64_t P) { return cpw_fwd_records(B, N, P) + 2 * ((int64_t)N + (int64_t)N * N); }
-int64_t cpw_bwd_scratch(int32_t B, int32_t N, int32_t D) {
-  return (int64_t)cpw_slices(std::max(B, 1), D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
-}
-
-// ---- cproj ----
-// pixels per workgroup of cproj_fwd: cpool_chunk, halved (down to 256) while the grid has fewer than 1024 workgroups
-int cproj_fwd_chunk(int NP, long long B, long long P, int D) {
-  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT;
-  long long ch = cpool_chunk(NP, P);
-  while (ch > 256 && B * ((P + ch - 1) / ch) * tiles < 1024) ch = std::max<long long>(256, (ch / 2) & ~63LL);
-  return (int)ch;
-}
-// passes of 64 pixels per workgroup of cproj_bwd_part: about 512 workgroups (every slice is read again by the few
-// workgroups of cpool_bwd_reduce), at most one per pass
-int cproj_upw(long long B, long long P, int D) {
-  const long long units = B * ((P + nfp::kCjSP - 1) / nfp::kCjSP);
-  const long long want = std::min<long long>(units, std::max(1, 512 / cpool_tiles(D)));
-  return (int)((units + want - 1) / want);
-}
-int cproj_slices(long long B, long long P, int D) {
-  const long long units = B * ((P + nfp::kCjSP - 1) / nfp::kCjSP), upw = cproj_upw(B, P, D);
-  return (int)((units + upw - 1) / upw);
-}
-int64_t cproj_bwd_scratch(int32_t B, int32_t N, int64_t P, int32_t D) {
-  return (int64_t)cproj_slices(std::max(B, 1), P, D) * D * (N + 1) + (int64_t)cpool_rtiles(D) * (N + N * N);
-}
-int cproj_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
-  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
-  if ((long long)D * P >= (1LL << 31))
-    return fail(NFP_E_UNSUPPORTED, "%s: an image of D * P = %lld output elements (2^31 and more) has no kernel", what,
-                (long long)D * P);
-  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT, ch = cproj_fwd_chunk(cpool_np(N), std::max(B, 1), P, D);
-  if ((long long)B * ((P + ch - 1) / ch) * tiles >= (1LL << 31))
-    return fail(NFP_E_UNSUPPORTED, "%s: B = %d, P = %lld, D = %d make 2^31 workgroups and more", what, B, (long long)P, D);
-  return NFP_OK;
-}
-
-template <template <int, bool, bool> class F, int NP, typename... A>
-int cproj_by_flags(bool relu, bool nhwc, A... a) {
-  if (relu) return nhwc ? F<NP, true, true>::go(a...) : F<NP, true, false>::go(a...);
-  return nhwc ? F<NP, false, true>::go(a...) : F<NP, false, false>::go(a...);
-}
-template <template <int, bool, bool> class F, typename... A>
-int cproj_by_np(int NP, bool relu, bool nhwc, A... a) {
-  switch (NP) {
-    case 8: return cproj_by_flags<F, 8>(relu, nhwc, a...);
-    case 16: return cproj_by_flags<F, 16>(relu, nhwc, a...);
-    case 24: return cproj_by_flags<F, 24>(relu, nhwc, a...);
-    default: return cproj_by_flags<F, 32>(relu, nhwc, a...);
-  }
-}
-// NHWC: the channels-last forms (out / grad_out [b][p][d]) — the same grids, LDS sizes and scratch.
-template <int NP, bool RELU, bool NHWC>
-struct JFwd {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
-    const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
-    const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
-    if constexpr (!NHWC) {
-      return launch("cproj_fwd", nfp::cproj_fwd<NP, RELU>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
-    } else {
-      // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
-      if (k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0))
-        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
-      return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<NP, RELU, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
-    }
-  }
-};
-template <int NP, bool RELU, bool NHWC>
-struct JPart {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const size_t lds = ((size_t)NP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
-    return launch(NHWC ? "cproj_bwd_part_nhwc" : "cproj_bwd_part", nfp::cproj_bwd_part<NP, RELU, NHWC>,
-                  dim3((unsigned)k.S, (unsigned)cpool_tiles(k.D)), dim3(nfp::cp_part_threads<NP>()), lds, st, k,
-                  (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
-  }
-};
-template <int NP, bool RELU, bool NHWC>
-struct JMaps {
-  static int go(const nfp::CpK& k, hipStream_t st) {
-    const int npt = (k.P + 63) / 64;
-    return launch(NHWC ? "cproj_bwd_maps_nhwc" : "cproj_bwd_maps", nfp::cproj_bwd_maps<NP, RELU, NHWC>,
-                  dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kCpT), 0, st, k, npt);
-  }
-};
-
-int cproj_layout(const char* what, int32_t layout) {
-  if (layout != NFP_ACT_NCHW && layout != NFP_ACT_NHWC)
-    return fail(NFP_E_INVALID, "%s: unknown layout %d (NFP_ACT_NCHW = 0, NFP_ACT_NHWC = 1)", what, layout);
-  return NFP_OK;
-}
-
-// ---- one host path for both kinds ----
 // What an extern "C" entry asks for.  kind: the pooled tail (nfp_cpool_*: out [B,D] float32, always with the ReLU) or the
 // projection with the map kept (nfp_cproj_*: out / grad_out [B,D,P] in the maps' dtype, `relu` and `layout` the caller's).
 // A forward fills rm_w .. saved_w, a backward rm .. gb; the other direction's fields stay zero.
@@ -1900,7 +95,167 @@ struct CpCall {
   float *gw, *gg, *gb;
   int32_t sync;   // nfp_cpsync_*: the statistics are those of all ranks, so this rank's B * P may be 0 or 1
 };
+// An entry's leading arguments as a CpCall — NCHW with the ReLU, which the projection's entries overwrite; everything
+// behind them zero, for the entry to fill by name
+CpCall cp_call(const char* what, CpKind kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training,
+               const void* maps, const float* w, const float* gamma, const float* beta) {
+  CpCall c{};
+  c.what = what, c.kind = kind, c.layout = NFP_ACT_NCHW, c.relu = 1;
+  c.B = B, c.N = N, c.P = P, c.D = D, c.dtype = dtype, c.training = training;
+  c.maps = maps, c.w = w, c.gamma = gamma, c.beta = beta;
+  return c;
+}
+// ... and the buffers every entry but nfp_cpsync_moments names behind them
+void cp_buffers(CpCall& c, double eps, int64_t saved_floats, float* scratch, int64_t scratch_floats, void* stream) {
+  c.eps = eps, c.saved_floats = saved_floats, c.scratch = scratch, c.scratch_floats = scratch_floats, c.stream = stream;
+}
+hipStream_t cp_stream(const CpCall& c) { return (hipStream_t)c.stream; }
 
+// ---- the sizes of each kind's kernels ----
+int cpool_np(int N) { return (N + 7) & ~7; }
+// pixels per chunk: the whole image where it fits the budget, else a multiple of 64
+int cpool_chunk(int NP, long long P) {
+  long long ch = std::min<long long>(P, nfp::kCpBudget / NP);
+  if (ch < P) ch &= ~63LL;
+  return (int)ch;
+}
+// floats between two rows of the chunk in LDS: a multiple of 4 (16-byte reads) and an odd number of 16-byte slots, so
+// that sixteen rows at one quad (cpool_moments' Gram) fall on sixteen different slots
+int cpool_stride(int ch) {
+  int s = (ch + 3) & ~3;
+  if (((s >> 2) & 1) == 0) s += 4;
+  return s;
+}
+int cpool_tiles(int D) { return (D + nfp::kCpDT - 1) / nfp::kCpDT; }
+int cpool_rtiles(int D) { return (D + nfp::kCpRT - 1) / nfp::kCpRT; }
+int cpw_np(int N) { return (N + 15) & ~15; }
+// pixels per chunk: the whole image where its maps and ga fit kWBudget floats of LDS beside the rows, else a multiple of 64
+// (64 at 64 maps and more, 128 at 32 and 48, 192 at 16)
+int cpw_chunk(int NP, long long P) {
+  return (int)std::min<long long>(P, std::max(64, (nfp::kWBudget / (NP + nfp::kWRS)) & ~63));
+}
+int cpw_tiles(int D) { return (D + nfp::kWDT - 1) / nfp::kWDT; }
+// pixels per workgroup of cproj_fwd: cpool_chunk, halved (down to 256) while the grid has fewer than 1024 workgroups
+int cproj_fwd_chunk(int NP, long long B, long long P, int D) {
+  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT;
+  long long ch = cpool_chunk(NP, P);
+  while (ch > 256 && B * ((P + ch - 1) / ch) * tiles < 1024) ch = std::max<long long>(256, (ch / 2) & ~63LL);
+  return (int)ch;
+}
+
+int cpool_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training, bool wide = false) {
+  const int maxN = wide ? nfp::kWMaxN : nfp::kCpMaxN;
+  if (B < 0 || N < 1 || P < 1 || D < 1)
+    return fail(NFP_E_INVALID, "%s: B = %d, N = %d, P = %lld, D = %d", what, B, N, (long long)P, D);
+  if (dtype != NFP_F32 && dtype != NFP_BF16) return fail(NFP_E_INVALID, "%s: unknown dtype %d", what, dtype);
+  if (N > maxN) return fail(NFP_E_UNSUPPORTED, "%s: N = %d maps (more than %d) has no kernel", what, N, maxN);
+  if ((long long)N * P >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: an image of N * P = %lld map elements (2^31 and more) has no kernel", what,
+                (long long)N * P);
+  if (D > (1 << 22)) return fail(NFP_E_UNSUPPORTED, "%s: D = %d (more than 2^22) has no kernel", what, D);
+  const long long ch = wide ? cpw_chunk(cpw_np(N), P) : cpool_chunk(cpool_np(N), P), nc = (P + ch - 1) / ch;
+  if ((long long)B * std::max<long long>(nc, (P + 63) / 64) >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: B = %d images of P = %lld pixels make 2^31 workgroups and more", what, B, (long long)P);
+  if (training && B > 0 && (long long)B * P < 2)
+    return fail(NFP_E_UNSUPPORTED, "%s: train-mode statistics need B * P >= 2 values per channel", what);
+  return NFP_OK;
+}
+int cproj_args(const char* what, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int training) {
+  if (int rc = cpool_args(what, B, N, P, D, dtype, training)) return rc;
+  if ((long long)D * P >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: an image of D * P = %lld output elements (2^31 and more) has no kernel", what,
+                (long long)D * P);
+  const long long tiles = (D + nfp::kCjDT - 1) / nfp::kCjDT, ch = cproj_fwd_chunk(cpool_np(N), std::max(B, 1), P, D);
+  if ((long long)B * ((P + ch - 1) / ch) * tiles >= (1LL << 31))
+    return fail(NFP_E_UNSUPPORTED, "%s: B = %d, P = %lld, D = %d make 2^31 workgroups and more", what, B, (long long)P, D);
+  return NFP_OK;
+}
+int cproj_layout(const char* what, int32_t layout) {
+  if (layout != NFP_ACT_NCHW && layout != NFP_ACT_NHWC)
+    return fail(NFP_E_INVALID, "%s: unknown layout %d (NFP_ACT_NCHW = 0, NFP_ACT_NHWC = 1)", what, layout);
+  return NFP_OK;
+}
+
+// ---- the launch shape of a call: decided here, once per direction ----
+int cp_np(const CpCall& c) { return c.kind == kCpWide ? cpw_np(c.N) : cpool_np(c.N); }
+// Forward, and every kernel that walks an image chunk by chunk: the pixels per chunk, the floats between two of its rows in
+// LDS and the chunks per image.  proj_fwd: cproj_fwd's own, finer chunks (the statistics ahead of it walk the pooled kind's).
+void cp_chunks(const CpCall& c, nfp::CpK& k, bool proj_fwd = false) {
+  const int NP = cp_np(c);
+  k.CH = c.kind == kCpWide ? cpw_chunk(NP, c.P) : proj_fwd ? cproj_fwd_chunk(NP, std::max(c.B, 1), c.P, c.D) : cpool_chunk(NP, c.P);
+  k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
+}
+// Backward: the units a workgroup of *_bwd_part takes — images; proj_part: cproj_bwd_part's passes of 64 pixels, which are
+// then its chunk — and the slices of the batch that makes: about 512 workgroups (every slice is read again by the few
+// workgroups of *_bwd_reduce), at most one per unit
+void cp_slices(const CpCall& c, nfp::CpK& k, bool proj_part = false) {
+  const long long B = std::max(c.B, 1), units = proj_part ? B * ((c.P + nfp::kCjSP - 1) / nfp::kCjSP) : B;
+  const long long want = std::min<long long>(units, std::max(1, 512 / (c.kind == kCpWide ? cpw_tiles(c.D) : cpool_tiles(c.D))));
+  k.ipw = (int)((units + want - 1) / want), k.S = (int)((units + k.ipw - 1) / k.ipw);
+  if (proj_part) k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;
+}
+// The call as every kernel reads it: sizes, dtype, mode, the maps and parameters, and the shape of the kernels that walk
+// whole images.  The projection's two kernels that walk otherwise get theirs from cp_chunks / cp_slices where they launch.
+nfp::CpK cp_k(const CpCall& c) {
+  nfp::CpK k;
+  memset(&k, 0, sizeof(k));
+  k.B = c.B, k.N = c.N, k.P = (int)c.P, k.D = c.D;
+  k.bf16 = c.dtype == NFP_BF16, k.eval = !c.training;
+  k.ntr = cpool_rtiles(c.D), k.M = (double)c.B * (double)c.P;
+  k.maps = c.maps, k.w = c.w, k.gamma = c.gamma, k.beta = c.beta;
+  k.eps = (float)c.eps, k.eps64 = c.eps;
+  cp_chunks(c, k), cp_slices(c, k);
+  return k;
+}
+// ... with what a forward adds: the result (the projection's in the maps' dtype), and the statistics it computes and the
+// running ones it updates (training) or reads (eval)
+nfp::CpK cp_fwd_k(const CpCall& c) {
+  nfp::CpK k = cp_k(c);
+  k.mom = c.momentum;
+  if (c.kind == kCpProj)
+    k.outv = c.out;
+  else
+    k.out = (float*)c.out;
+  if (c.training)
+    k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
+  else
+    k.rm = c.rm_w, k.rv = c.rv_w;
+  return k;
+}
+// ... and a backward: the saved statistics (eval: the running ones), the gradients wanted and, of a rank with images,
+// grad_out
+nfp::CpK cp_bwd_k(const CpCall& c) {
+  nfp::CpK k = cp_k(c);
+  k.stats = c.saved;
+  if (!c.training) k.rm = c.rm, k.rv = c.rv;
+  k.gm = c.gm, k.gw = c.gw, k.gg = c.gg, k.gb = c.gb;
+  if (c.B > 0) {
+    if (c.kind == kCpProj)
+      k.gov = c.go;
+    else
+      k.go = (const float*)c.go;
+  }
+  return k;
+}
+
+// ---- the scratch of a call, laid out once ----
+// Forward (training): a record [2 N + N*N] per chunk of the batch; wide: then, from an even float on, mu [N] and Sigma [N*N]
+// as doubles.  Backward: the slices' partials [S][D][N + 1], then the workgroups' shares of k, Q [ntr][N + N*N].
+int64_t cp_records(const CpCall& c, const nfp::CpK& k) {
+  const int64_t n = (int64_t)c.B * k.nc * (2 * c.N + c.N * c.N);
+  return c.kind == kCpWide ? (n + 1) & ~(int64_t)1 : n;
+}
+int64_t cp_parts(const nfp::CpK& k) { return (int64_t)k.S * k.D * (k.N + 1); }
+// what nfp_cpool_scratch_floats, nfp_cpool_wide_scratch_floats and nfp_cproj_scratch_floats answer for the sizes they serve
+int64_t cp_scratch_floats(CpKind kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
+  const CpCall c = cp_call("", kind, B, N, P, D, NFP_F32, 1, nullptr, nullptr, nullptr, nullptr);
+  nfp::CpK k = cp_k(c);
+  if (!backward) return std::max<int64_t>(1, cp_records(c, k) + (kind == kCpWide ? 2 * ((int64_t)N + (int64_t)N * N) : 0));
+  cp_slices(c, k, kind == kCpProj);
+  return std::max<int64_t>(1, cp_parts(k) + (int64_t)k.ntr * (N + N * N));
+}
+
+// ---- the checks ----
 // The refusals both directions share, in order: layout, sizes, pointers (io: the forward's out, the backward's grad_out)
 int cp_check(const CpCall& c, const void* io) {
   if (c.kind == kCpProj)
@@ -1923,16 +278,6 @@ int cp_check_scratch(const CpCall& c, int backward) {
                 name, (long long)need);
   return NFP_OK;
 }
-nfp::CpK cp_k(const CpCall& c) {
-  nfp::CpK k = cpool_k(c.B, c.N, c.P, c.D, c.dtype, c.training);
-  k.maps = c.maps, k.w = c.w, k.gamma = c.gamma, k.beta = c.beta;
-  k.eps = (float)c.eps, k.eps64 = c.eps;
-  if (c.kind == kCpWide) {   // (the wide kernels' own chunks and slices)
-    k.CH = cpw_chunk(cpw_np(c.N), c.P), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
-    k.ipw = cpw_ipw(std::max(c.B, 1), c.D), k.S = cpw_slices(std::max(c.B, 1), c.D);
-  }
-  return k;
-}
 void cp_variant(const CpCall& c, const char* dir) {
   const char *dt = c.dtype == NFP_BF16 ? "bf16" : "f32", *mode = c.training ? "train" : "eval";
   if (c.kind == kCpPool)
@@ -1943,22 +288,53 @@ void cp_variant(const CpCall& c, const char* dir) {
     snprintf(g_variant, sizeof(g_variant), "cproj_%s<%s,%s,%s%s>", dir, dt, mode, c.relu ? "relu" : "lin",
              c.layout == NFP_ACT_NHWC ? ",nhwc" : "");
 }
-// cpool_moments + cpool_finish: the train-mode statistics of either kind
-int launch_stats(const nfp::CpK& k, int NP, hipStream_t st) {
-  const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
-  int rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
-  if (rc == NFP_OK)
-    rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st,
-                k);
-  return rc;
+
+// ---- call fields -> kernel template arguments (as nfp_launch.h's with_* helpers) ----
+// the padded maps count of the pooled kind and the projection
+template <typename F>
+int with_np(const CpCall& c, F&& f) {
+  switch (cpool_np(c.N)) {
+    case 8: return f(Int<8>{});
+    case 16: return f(Int<16>{});
+    case 24: return f(Int<24>{});
+    default: return f(Int<32>{});
+  }
+}
+template <typename F>
+int with_flag(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+// the projection's f(RELU, NHWC) — NHWC: the channels-last forms (out / grad_out [b][p][d]), the same grids, LDS sizes and scratch
+template <typename F>
+int with_act(const CpCall& c, F&& f) {
+  return with_flag(c.relu != 0, [&](auto relu) {
+    return with_flag(c.layout == NFP_ACT_NHWC, [&](auto nhwc) { return f(relu, nhwc); });
+  });
 }
 
-// ---- the wide kernels' launches ----
-// cpw_moments, cpw_mu, cpw_sigma, cpw_var: the train-mode statistics; scratch as cpw_fwd_scratch lays it out
-int cpw_launch_stats(const nfp::CpK& k, int NP, float* scratch, hipStream_t st) {
-  double* mu64 = (double*)(scratch + cpw_fwd_records(k.B, k.N, k.P));
+// ---- the steps of a forward ----
+// cpool_moments: a record per chunk into the scratch (its caller has pointed k.part there)
+int cp_launch_moments(const CpCall& c, const nfp::CpK& k) {
+  const int NP = cp_np(c);
+  const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
+  return launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kCpMT), lds, cp_stream(c), k,
+                NP);
+}
+// The train-mode statistics of this call's maps alone: cpool_moments + cpool_finish; wide: cpw_moments, cpw_mu, cpw_sigma,
+// cpw_var
+int cp_local_stats(const CpCall& c, nfp::CpK& k) {
+  hipStream_t st = cp_stream(c);
+  k.part_w = c.scratch, k.part = c.scratch;
+  if (c.kind != kCpWide) {
+    int rc = cp_launch_moments(c, k);
+    if (rc == NFP_OK)
+      rc = launch("cpool_finish", nfp::cpool_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st,
+                  k);
+    return rc;
+  }
+  const int NP = cp_np(c), NN = k.N * k.N;
+  double* mu64 = (double*)(c.scratch + cp_records(c, k));
   double* sig64 = mu64 + k.N;
-  const int NN = k.N * k.N;
   int rc = launch("cpw_moments", nfp::cpw_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kWT),
                   ((size_t)NP * k.CHs + NP) * sizeof(float), st, k, NP);
   if (rc == NFP_OK) rc = launch("cpw_mu", nfp::cpw_mu, dim3(1), dim3(nfp::kWMuT), 0, st, k, mu64);
@@ -1969,26 +345,121 @@ int cpw_launch_stats(const nfp::CpK& k, int NP, float* scratch, hipStream_t st) 
                 (const double*)sig64);
   return rc;
 }
-int cpw_launch_fwd(const nfp::CpK& k, int NP, hipStream_t st) {
-  const size_t lds = ((size_t)NP * nfp::kWRS + 2 * nfp::kWDT + (size_t)NP * k.CHs + 16 * nfp::kWDT) * sizeof(float);
-  return launch("cpw_fwd", nfp::cpw_fwd, dim3((unsigned)k.B, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+// The rank's record for the other ranks: cpool_moments (where it has an image) + cps_record
+int cps_rank_record(const CpCall& c, nfp::CpK& k, double* record) {
+  k.part_w = c.scratch, k.part = c.scratch;
+  int rc = c.B > 0 ? cp_launch_moments(c, k) : NFP_OK;
+  if (rc == NFP_OK) rc = launch("cps_record", nfp::cps_record, dim3(1), dim3(nfp::kCpFT), 0, cp_stream(c), k, record);
+  return rc;
 }
-int cpw_launch_part(const nfp::CpK& k, int NP, hipStream_t st) {
-  const size_t lds = ((size_t)NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)(NP + nfp::kWRS) * k.CHs) * sizeof(float);
-  return launch("cpw_bwd_part", nfp::cpw_bwd_part, dim3((unsigned)k.S, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+// The statistics joined from every rank's record: cps_finish
+int cps_joined_stats(const CpCall& c, const nfp::CpK& k, const double* records, int32_t world) {
+  return launch("cps_finish", nfp::cps_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0,
+                cp_stream(c), k, records, (int)world);
 }
-int cpw_launch_reduce(const nfp::CpK& k, hipStream_t st) {
-  const size_t lds = ((size_t)nfp::kCpRT * (2 * k.N + 1) + (size_t)k.N * k.N) * sizeof(float);
-  return launch("cpw_bwd_reduce", nfp::cpw_bwd_reduce, dim3((unsigned)k.ntr), dim3(nfp::kWT), lds, st, k);
-}
-int cpw_launch_maps(const nfp::CpK& k, int NP, hipStream_t st) {
-  const int npt = (k.P + 63) / 64;
-  const size_t lds = ((size_t)2 * NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)nfp::kWDT * nfp::kWRS) * sizeof(float);
-  return launch("cpw_bwd_maps", nfp::cpw_bwd_maps, dim3((unsigned)((long long)k.B * npt)), dim3(nfp::kWT), lds, st, k, NP, npt);
+// The main forward under the statistics k names: cpool_fwd, cpw_fwd, or cproj_fwd / cproj_fwd_nhwc over chunks of their own
+int cp_main_forward(const CpCall& c, nfp::CpK& k) {
+  const int NP = cp_np(c);
+  hipStream_t st = cp_stream(c);
+  if (c.kind == kCpWide) {
+    const size_t lds = ((size_t)NP * nfp::kWRS + 2 * nfp::kWDT + (size_t)NP * k.CHs + 16 * nfp::kWDT) * sizeof(float);
+    return launch("cpw_fwd", nfp::cpw_fwd, dim3((unsigned)k.B, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+  }
+  if (c.kind == kCpPool) {
+    const size_t lds = ((size_t)NP * k.CHs + nfp::kCpW * nfp::kCpDT) * sizeof(float);
+    return with_np(c, [&](auto np) {
+      return launch("cpool_fwd", nfp::cpool_fwd<decltype(np)::value>, dim3((unsigned)k.B, (unsigned)cpool_tiles(k.D)),
+                    dim3(nfp::kCpT), lds, st, k);
+    });
+  }
+  cp_chunks(c, k, true);
+  const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
+  const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
+  const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
+  // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
+  const bool pair = k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0);
+  return with_np(c, [&](auto np) {
+    return with_act(c, [&](auto relu, auto nhwc) {
+      constexpr int kNP = decltype(np)::value;
+      constexpr bool kRelu = decltype(relu)::value;
+      if constexpr (!decltype(nhwc)::value)
+        return launch("cproj_fwd", nfp::cproj_fwd<kNP, kRelu>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+      else if (pair)
+        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<kNP, kRelu, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+      else
+        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<kNP, kRelu, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+    });
+  });
 }
 
+// ---- the steps of a backward (k sliced by cp_slices) ----
+// The batch sums: *_bwd_part writes every slice's partials, *_bwd_reduce joins them into the parameter gradients and the
+// workgroups' shares of k, Q behind them (cpool_bwd_reduce: LIVE = the projection, SYNC = the call's)
+int cp_sums(const CpCall& c, nfp::CpK& k) {
+  const int NP = cp_np(c);
+  hipStream_t st = cp_stream(c);
+  k.part_w = c.scratch, k.part = c.scratch;
+  k.kq_w = c.scratch + cp_parts(k), k.kq = k.kq_w;
+  if (c.kind == kCpWide) {
+    const size_t lds = ((size_t)NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)(NP + nfp::kWRS) * k.CHs) * sizeof(float);
+    const size_t lds_r = ((size_t)nfp::kCpRT * (2 * k.N + 1) + (size_t)k.N * k.N) * sizeof(float);
+    int rc = launch("cpw_bwd_part", nfp::cpw_bwd_part, dim3((unsigned)k.S, (unsigned)cpw_tiles(k.D)), dim3(nfp::kWT), lds, st, k, NP);
+    if (rc == NFP_OK) rc = launch("cpw_bwd_reduce", nfp::cpw_bwd_reduce, dim3((unsigned)k.ntr), dim3(nfp::kWT), lds_r, st, k);
+    return rc;
+  }
+  const dim3 grid((unsigned)k.S, (unsigned)cpool_tiles(k.D));
+  const int rc = with_np(c, [&](auto np) {
+    constexpr int kNP = decltype(np)::value;
+    const dim3 block(nfp::cp_part_threads<kNP>());
+    if (c.kind == kCpPool) {
+      const size_t lds = ((size_t)kNP * k.CHs + (size_t)nfp::kCpDT * (kNP + 1)) * sizeof(float);
+      return launch("cpool_bwd_part", nfp::cpool_bwd_part<kNP>, grid, block, lds, st, k);
+    }
+    const size_t lds = ((size_t)kNP + nfp::kCpDT) * nfp::kCjSS * sizeof(float);
+    return with_act(c, [&](auto relu, auto nhwc) {
+      constexpr bool kNhwc = decltype(nhwc)::value;
+      return launch(kNhwc ? "cproj_bwd_part_nhwc" : "cproj_bwd_part", nfp::cproj_bwd_part<kNP, decltype(relu)::value, kNhwc>, grid,
+                    block, lds, st, k, (k.P + nfp::kCjSP - 1) / nfp::kCjSP, k.ipw);
+    });
+  });
+  if (rc != NFP_OK) return rc;
+  return with_flag(c.kind == kCpProj, [&](auto live) {
+    return with_flag(c.sync != 0, [&](auto sync) {
+      return launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<decltype(live)::value, decltype(sync)::value>, dim3((unsigned)k.ntr),
+                    dim3(nfp::kCpMT), 0, st, k);
+    });
+  });
+}
+// The rank's row of k, Q for the other ranks: cps_kq_row sums the workgroups' shares; cps_zero for a rank without an image
+// (a zero row, zero parameter gradients)
+int cps_rank_row(const CpCall& c, const nfp::CpK& k, float* row) {
+  if (c.B > 0) return launch("cps_kq_row", nfp::cps_kq_row, dim3(1), dim3(nfp::kCpMT), 0, cp_stream(c), k, row);
+  const long long n = std::max<long long>((long long)c.D * c.N, (int64_t)c.N + (int64_t)c.N * c.N);
+  return launch("cps_zero", nfp::cps_zero, dim3((unsigned)std::min<long long>(1024, (n + nfp::kCpMT - 1) / nfp::kCpMT)),
+                dim3(nfp::kCpMT), 0, cp_stream(c), k, row);
+}
+// grad_maps, under the k, Q rows that k.kq / k.ntr name
+int cp_grad_maps(const CpCall& c, const nfp::CpK& k) {
+  const int NP = cp_np(c), npt = (k.P + 63) / 64;
+  hipStream_t st = cp_stream(c);
+  const dim3 grid((unsigned)((long long)k.B * npt));
+  if (c.kind == kCpWide) {
+    const size_t lds = ((size_t)2 * NP * nfp::kWRS + 3 * nfp::kWDT + (size_t)nfp::kWDT * nfp::kWRS) * sizeof(float);
+    return launch("cpw_bwd_maps", nfp::cpw_bwd_maps, grid, dim3(nfp::kWT), lds, st, k, NP, npt);
+  }
+  return with_np(c, [&](auto np) {
+    constexpr int kNP = decltype(np)::value;
+    if (c.kind == kCpPool) return launch("cpool_bwd_maps", nfp::cpool_bwd_maps<kNP>, grid, dim3(nfp::kCpT), 0, st, k, npt);
+    return with_act(c, [&](auto relu, auto nhwc) {
+      constexpr bool kNhwc = decltype(nhwc)::value;
+      return launch(kNhwc ? "cproj_bwd_maps_nhwc" : "cproj_bwd_maps", nfp::cproj_bwd_maps<kNP, decltype(relu)::value, kNhwc>, grid,
+                    dim3(nfp::kCpT), 0, st, k, npt);
+    });
+  });
+}
+
+// ---- a call on one rank's own statistics (nfp_cpool_*, nfp_cpool_wide_*, nfp_cproj_*) ----
 int cp_forward(const CpCall& c) {
-  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
   if (int rc = cp_check(c, c.out)) return rc;
   if ((c.rm_w == nullptr) != (c.rv_w == nullptr) || (!c.training && c.rm_w == nullptr))
     return fail(NFP_E_INVALID, "%s: running_mean and running_var come together (eval needs both)", c.what);
@@ -2001,33 +472,15 @@ int cp_forward(const CpCall& c) {
     if (int rc = cp_check_scratch(c, 0)) return rc;
   }
   if (c.B == 0) return NFP_OK;
-  nfp::CpK k = cp_k(c);
-  const bool wide = c.kind == kCpWide;
-  const int NP = wide ? cpw_np(c.N) : cpool_np(c.N);
-  k.mom = c.momentum;
-  if (proj)
-    k.outv = c.out;
-  else
-    k.out = (float*)c.out;
-  hipStream_t st = (hipStream_t)c.stream;
+  nfp::CpK k = cp_fwd_k(c);
   cp_variant(c, "fwd");
-  int rc = NFP_OK;
-  if (c.training) {
-    k.part_w = c.scratch, k.part = c.scratch, k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
-    rc = wide ? cpw_launch_stats(k, NP, c.scratch, st) : launch_stats(k, NP, st);
-  } else {
-    k.rm = c.rm_w, k.rv = c.rv_w;
-  }
-  if (proj)   // (cproj_fwd's own chunks)
-    k.CH = cproj_fwd_chunk(NP, c.B, c.P, c.D), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
-  if (rc == NFP_OK)
-    rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_fwd(k, NP, st) : cpool_by_np<LFwd>(NP, k, st);
+  int rc = c.training ? cp_local_stats(c, k) : NFP_OK;
+  if (rc == NFP_OK) rc = cp_main_forward(c, k);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
 
 int cp_backward(const CpCall& c) {
-  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
   if (int rc = cp_check(c, c.go)) return rc;
   if (!c.training && (c.rm == nullptr || c.rv == nullptr))
     return fail(NFP_E_INVALID, "%s: eval needs running_mean and running_var", c.what);
@@ -2041,33 +494,11 @@ int cp_backward(const CpCall& c) {
   if (sums)
     if (int rc = cp_check_scratch(c, 1)) return rc;
   if (c.B == 0) return NFP_OK;
-  nfp::CpK k = cp_k(c);
-  const bool wide = c.kind == kCpWide;
-  const int NP = wide ? cpw_np(c.N) : cpool_np(c.N);
-  if (proj) {
-    k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                   // cproj_bwd_part's passes
-    k.ipw = cproj_upw(c.B, c.P, c.D), k.S = cproj_slices(c.B, c.P, c.D);     // ... and how many of them a workgroup takes
-  }
-  if (proj)
-    k.gov = c.go;
-  else
-    k.go = (const float*)c.go;
-  k.stats = c.saved;
-  if (!c.training) k.rm = c.rm, k.rv = c.rv;
-  k.gm = c.gm, k.gw = c.gw, k.gg = c.gg, k.gb = c.gb;
-  hipStream_t st = (hipStream_t)c.stream;
+  nfp::CpK k = cp_bwd_k(c);
+  cp_slices(c, k, c.kind == kCpProj);
   cp_variant(c, "bwd");
-  int rc = NFP_OK;
-  if (sums) {
-    k.part_w = c.scratch, k.part = c.scratch;
-    k.kq_w = c.scratch + (int64_t)k.S * c.D * (c.N + 1), k.kq = k.kq_w;
-    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_part(k, NP, st) : cpool_by_np<LPart>(NP, k, st);
-    if (rc == NFP_OK)
-      rc = wide ? cpw_launch_reduce(k, st) : proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
-                : launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
-  }
-  if (rc == NFP_OK && c.gm != nullptr)
-    rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : wide ? cpw_launch_maps(k, NP, st) : cpool_by_np<LMaps>(NP, k, st);
+  int rc = sums ? cp_sums(c, k) : NFP_OK;
+  if (rc == NFP_OK && c.gm != nullptr) rc = cp_grad_maps(c, k);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
@@ -2112,30 +543,31 @@ void cps_variant(const CpCall& c, const char* stage) {
   snprintf(g_variant, sizeof(g_variant), "cpsync_%s<%s,%s%s>", stage, c.kind == kCpPool ? "pool" : c.relu ? "proj,relu" : "proj,lin",
            c.dtype == NFP_BF16 ? "bf16" : "f32", c.kind == kCpProj && c.layout == NFP_ACT_NHWC ? ",nhwc" : "");
 }
+// The CpCall of nfp_cpsync_forward / _reduce / _maps: training mode with `sync` set; the pooled kind is always NCHW with
+// the ReLU, whatever the entry was handed
+CpCall cps_call(const char* what, int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t relu,
+                int32_t layout, const void* maps, const float* w, const float* gamma, const float* beta) {
+  const bool proj = kind == NFP_CP_PROJ;
+  CpCall c = cp_call(what, proj ? kCpProj : kCpPool, B, N, P, D, dtype, 1, maps, w, gamma, beta);
+  if (proj) c.relu = relu, c.layout = layout;
+  c.sync = 1;
+  return c;
+}
 
 int cps_moments(const CpCall& c, double* record, int64_t record_doubles) {
   if (int rc = cpool_args(c.what, c.B, c.N, c.P, 1, c.dtype, 0)) return rc;
   if (c.B > 0 && c.maps == nullptr) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
   if (int rc = cps_rows(c.what, "record", record, 1, record_doubles, cps_record_len(c.N), sizeof(double))) return rc;
   if (int rc = cp_check_scratch(c, 0)) return rc;
-  nfp::CpK k = cpool_k(c.B, c.N, c.P, 1, c.dtype, 1);
-  k.maps = c.maps, k.part_w = c.scratch, k.part = c.scratch;
-  hipStream_t st = (hipStream_t)c.stream;
+  nfp::CpK k = cp_fwd_k(c);
   snprintf(g_variant, sizeof(g_variant), "cpsync_moments<%s>", c.dtype == NFP_BF16 ? "bf16" : "f32");
-  const int NP = cpool_np(c.N);
-  int rc = NFP_OK;
-  if (c.B > 0) {
-    const size_t lds = ((size_t)NP * k.CHs + NP + std::max(NP * NP, nfp::kCpMT)) * sizeof(float);
-    rc = launch("cpool_moments", nfp::cpool_moments, dim3((unsigned)((long long)k.B * k.nc)), dim3(nfp::kCpMT), lds, st, k, NP);
-  }
-  if (rc == NFP_OK) rc = launch("cps_record", nfp::cps_record, dim3(1), dim3(nfp::kCpFT), 0, st, k, record);
+  const int rc = cps_rank_record(c, k, record);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
 
 int cps_forward(const CpCall& c, int32_t kind, const double* records, int32_t world, int64_t records_doubles,
                 int64_t global_count) {
-  const bool proj = c.kind == kCpProj;
   if (int rc = cps_check(c, kind, c.out, c.saved_w)) return rc;
   if ((c.rm_w == nullptr) != (c.rv_w == nullptr))
     return fail(NFP_E_INVALID, "%s: running_mean and running_var come together", c.what);
@@ -2145,78 +577,39 @@ int cps_forward(const CpCall& c, int32_t kind, const double* records, int32_t wo
   if (global_count == 1 || (global_count > 0 && global_count < (int64_t)c.B * c.P))
     return fail(NFP_E_UNSUPPORTED, "%s: train-mode statistics need 2 values per channel over all ranks and no fewer than this "
                 "rank's %lld, got global_count = %lld", c.what, (long long)c.B * (long long)c.P, (long long)global_count);
-  nfp::CpK k = cp_k(c);
-  const int NP = cpool_np(c.N);
-  k.mom = c.momentum;
-  k.stats_w = c.saved_w, k.stats = c.saved_w, k.rm_w = c.rm_w, k.rv_w = c.rv_w;
-  if (proj)
-    k.outv = c.out;
-  else
-    k.out = (float*)c.out;
-  hipStream_t st = (hipStream_t)c.stream;
+  nfp::CpK k = cp_fwd_k(c);
   cps_variant(c, "fwd");
-  int rc = launch("cps_finish", nfp::cps_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0, st, k,
-                  records, (int)world);
-  if (proj && c.B > 0)   // (cproj_fwd's own chunks)
-    k.CH = cproj_fwd_chunk(NP, c.B, c.P, c.D), k.CHs = cpool_stride(k.CH), k.nc = (int)((c.P + k.CH - 1) / k.CH);
-  if (rc == NFP_OK && c.B > 0)
-    rc = proj ? cproj_by_np<JFwd>(NP, c.relu != 0, c.layout == NFP_ACT_NHWC, k, st) : cpool_by_np<LFwd>(NP, k, st);
+  int rc = cps_joined_stats(c, k, records, world);
+  if (rc == NFP_OK && c.B > 0) rc = cp_main_forward(c, k);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
 
 int cps_reduce(const CpCall& c, int32_t kind, float* kq_row, int64_t kq_floats) {
-  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
   if (int rc = cps_check(c, kind, c.go, c.saved)) return rc;
   if (int rc = cps_rows(c.what, "kq_row", kq_row, 1, kq_floats, cps_row_len(c.N), sizeof(float))) return rc;
   if (int rc = cp_check_scratch(c, 1)) return rc;
-  nfp::CpK k = cp_k(c);
-  const int NP = cpool_np(c.N);
-  k.stats = c.saved, k.gw = c.gw, k.gg = c.gg, k.gb = c.gb;
-  hipStream_t st = (hipStream_t)c.stream;
+  nfp::CpK k = cp_bwd_k(c);
   cps_variant(c, "bwd_reduce");
-  int rc;
-  if (c.B == 0) {
-    const long long n = std::max<long long>((long long)c.D * c.N, cps_row_len(c.N));
-    rc = launch("cps_zero", nfp::cps_zero, dim3((unsigned)std::min<long long>(1024, (n + nfp::kCpMT - 1) / nfp::kCpMT)),
-                dim3(nfp::kCpMT), 0, st, k, kq_row);
-  } else {
-    if (proj) {
-      k.CH = nfp::kCjSP, k.CHs = nfp::kCjSS;                                   // cproj_bwd_part's passes
-      k.ipw = cproj_upw(c.B, c.P, c.D), k.S = cproj_slices(c.B, c.P, c.D);     // ... and how many of them a workgroup takes
-      k.gov = c.go;
-    } else {
-      k.go = (const float*)c.go;
-    }
-    k.part_w = c.scratch, k.part = c.scratch;
-    k.kq_w = c.scratch + (int64_t)k.S * c.D * (c.N + 1), k.kq = k.kq_w;
-    rc = proj ? cproj_by_np<JPart>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LPart>(NP, k, st);
-    if (rc == NFP_OK)
-      rc = proj ? launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<true, true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k)
-                : launch("cpool_bwd_reduce", nfp::cpool_bwd_reduce<false, true>, dim3((unsigned)k.ntr), dim3(nfp::kCpMT), 0, st, k);
-    if (rc == NFP_OK) rc = launch("cps_kq_row", nfp::cps_kq_row, dim3(1), dim3(nfp::kCpMT), 0, st, k, kq_row);
+  int rc = NFP_OK;
+  if (c.B > 0) {
+    cp_slices(c, k, c.kind == kCpProj);
+    rc = cp_sums(c, k);
   }
+  if (rc == NFP_OK) rc = cps_rank_row(c, k, kq_row);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
 
 int cps_maps(const CpCall& c, int32_t kind, const float* kq_rows, int32_t world, int64_t kq_floats) {
-  const bool proj = c.kind == kCpProj, nhwc = c.layout == NFP_ACT_NHWC;
   if (int rc = cps_check(c, kind, c.go, c.saved)) return rc;
   if (int rc = cps_rows(c.what, "kq_rows", kq_rows, world, kq_floats, cps_row_len(c.N), sizeof(float))) return rc;
   if (c.B > 0 && c.gm == nullptr) return fail(NFP_E_INVALID, "%s: null tensor pointer", c.what);
   if (c.B == 0) return NFP_OK;
-  nfp::CpK k = cp_k(c);
-  const int NP = cpool_np(c.N);
-  k.stats = c.saved, k.gm = c.gm;
-  if (proj)
-    k.gov = c.go;
-  else
-    k.go = (const float*)c.go;
+  nfp::CpK k = cp_bwd_k(c);
   k.kq = kq_rows, k.ntr = world;   // (the ranks' rows, summed in rank order where the workgroups' shares are)
-  hipStream_t st = (hipStream_t)c.stream;
   cps_variant(c, "bwd_maps");
-  const int rc = proj ? cproj_by_np<JMaps>(NP, c.relu != 0, nhwc, k, st) : cpool_by_np<LMaps>(NP, k, st);
+  const int rc = cp_grad_maps(c, k);
   if (rc == NFP_OK) publish_variant();
   return rc;
 }
@@ -2235,27 +628,28 @@ int64_t nfp_cpool_saved_floats(int32_t N, int32_t D) {
 
 int64_t nfp_cpool_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
   if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
-  return std::max<int64_t>(1, backward ? cpool_bwd_scratch(B, N, D) : cpool_fwd_scratch(B, N, P));
+  return cp_scratch_floats(kCpPool, B, N, P, D, backward);
 }
 
 int64_t nfp_cpool_wide_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
   if (B < 1 || N < 1 || N > nfp::kWMaxN || P < 1 || D < 1) return 1;
-  return std::max<int64_t>(1, backward ? cpw_bwd_scratch(B, N, D) : cpw_fwd_scratch(B, N, P));
+  return cp_scratch_floats(kCpWide, B, N, P, D, backward);
 }
 
 int64_t nfp_cproj_scratch_floats(int32_t B, int32_t N, int64_t P, int32_t D, int32_t backward) {
   if (B < 1 || N < 1 || N > nfp::kCpMaxN || P < 1 || D < 1) return 1;
-  return std::max<int64_t>(1, backward ? cproj_bwd_scratch(B, N, P, D) : cpool_fwd_scratch(B, N, P));
+  return cp_scratch_floats(kCpProj, B, N, P, D, backward);
 }
 
-// The eight entries: a CpCall of the leading fields, in order, and cp_forward / cp_backward with the direction's own.
+// The eight entries of one rank's call: cp_call of the leading arguments, cp_buffers, and cp_forward / cp_backward with the
+// direction's own.
 
 int nfp_cpool_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype, int32_t training, const void* maps,
                       const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
                       double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
                       int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cpool_forward", kCpPool, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cpool_forward", kCpPool, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
@@ -2264,8 +658,8 @@ int nfp_cpool_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        const float* running_var, double eps, const float* saved, int64_t saved_floats, const float* grad_out,
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cpool_backward", kCpPool, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cpool_backward", kCpPool, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
@@ -2273,8 +667,8 @@ int nfp_cpool_wide_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t d
                            const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
                            double momentum, double eps, float* out, float* saved, int64_t saved_floats, float* scratch,
                            int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cpool_wide_forward", kCpWide, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cpool_wide_forward", kCpWide, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
@@ -2283,8 +677,8 @@ int nfp_cpool_wide_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t 
                             const float* running_var, double eps, const float* saved, int64_t saved_floats,
                             const float* grad_out, void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta,
                             float* scratch, int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cpool_wide_backward", kCpWide, NFP_ACT_NCHW, 1, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cpool_wide_backward", kCpWide, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
@@ -2292,8 +686,9 @@ int nfp_cproj_forward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dt
                           const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
                           float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
                           float* scratch, int64_t scratch_floats, void* hip_stream, int32_t out_layout) {
-  const CpCall c{"nfp_cproj_forward_fmt", kCpProj, out_layout, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cproj_forward_fmt", kCpProj, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  c.relu = relu, c.layout = out_layout;
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
@@ -2302,8 +697,9 @@ int nfp_cproj_backward_fmt(int32_t B, int32_t N, int64_t P, int32_t D, int32_t d
                            const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
                            void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                            int64_t scratch_floats, void* hip_stream, int32_t grad_out_layout) {
-  const CpCall c{"nfp_cproj_backward_fmt", kCpProj, grad_out_layout, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cproj_backward_fmt", kCpProj, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  c.relu = relu, c.layout = grad_out_layout;
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
@@ -2312,8 +708,9 @@ int nfp_cproj_forward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype,
                       const void* maps, const float* w, const float* gamma, const float* beta, float* running_mean,
                       float* running_var, double momentum, double eps, void* out, float* saved, int64_t saved_floats,
                       float* scratch, int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cproj_forward", kCpProj, NFP_ACT_NCHW, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cproj_forward", kCpProj, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  c.relu = relu;
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_forward(c, running_mean, running_var, momentum, out, saved);
 }
 
@@ -2322,12 +719,13 @@ int nfp_cproj_backward(int32_t B, int32_t N, int64_t P, int32_t D, int32_t dtype
                        const float* running_var, double eps, const float* saved, int64_t saved_floats, const void* grad_out,
                        void* grad_maps, float* grad_w, float* grad_gamma, float* grad_beta, float* scratch,
                        int64_t scratch_floats, void* hip_stream) {
-  const CpCall c{"nfp_cproj_backward", kCpProj, NFP_ACT_NCHW, relu, B, N, P, D, dtype, training, maps, w, gamma, beta, eps,
-                 saved_floats, scratch, scratch_floats, hip_stream};
+  CpCall c = cp_call("nfp_cproj_backward", kCpProj, B, N, P, D, dtype, training, maps, w, gamma, beta);
+  c.relu = relu;
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
   return cp_backward(c, running_mean, running_var, saved, grad_out, grad_maps, grad_w, grad_gamma, grad_beta);
 }
 
-// ---- nfp_cpsync_*: a CpCall in training mode with `sync` set; the pooled kind is always NCHW with the ReLU ----
+// ---- nfp_cpsync_*: the four staged entries, cps_call of the leading arguments ----
 
 int64_t nfp_cpsync_record_doubles(int32_t N) { return N < 1 ? 1 : cps_record_len(N); }
 int64_t nfp_cpsync_kq_floats(int32_t N) { return N < 1 ? 1 : cps_row_len(N); }
@@ -2338,9 +736,8 @@ int64_t nfp_cpsync_saved_floats(int32_t N, int32_t D) {
 
 int nfp_cpsync_moments(int32_t B, int32_t N, int64_t P, int32_t dtype, const void* maps, double* record, int64_t record_doubles,
                        float* scratch, int64_t scratch_floats, void* hip_stream) {
-  CpCall c{"nfp_cpsync_moments", kCpPool, NFP_ACT_NCHW, 1, B, N, P, 1, dtype, 1, maps, nullptr, nullptr, nullptr, 0.0, 0, scratch,
-           scratch_floats, hip_stream};
-  c.sync = 1;
+  CpCall c = cps_call("nfp_cpsync_moments", NFP_CP_POOL, B, N, P, 1, dtype, 1, NFP_ACT_NCHW, maps, nullptr, nullptr, nullptr);
+  cp_buffers(c, 0.0, 0, scratch, scratch_floats, hip_stream);
   return cps_moments(c, record, record_doubles);
 }
 
@@ -2349,10 +746,9 @@ int nfp_cpsync_forward(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D,
                        double momentum, double eps, const double* records, int32_t world, int64_t records_doubles,
                        int64_t global_count, void* out, float* saved, int64_t saved_floats, void* hip_stream,
                        int32_t out_layout) {
-  const bool proj = kind == NFP_CP_PROJ;
-  CpCall c{"nfp_cpsync_forward", proj ? kCpProj : kCpPool, proj ? out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype, 1,
-           maps, w, gamma, beta, eps, saved_floats, nullptr, 0, hip_stream};
-  c.sync = 1, c.rm_w = running_mean, c.rv_w = running_var, c.momentum = momentum, c.out = out, c.saved_w = saved;
+  CpCall c = cps_call("nfp_cpsync_forward", kind, B, N, P, D, dtype, relu, out_layout, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, nullptr, 0, hip_stream);
+  c.rm_w = running_mean, c.rv_w = running_var, c.momentum = momentum, c.out = out, c.saved_w = saved;
   return cps_forward(c, kind, records, world, records_doubles, global_count);
 }
 
@@ -2361,10 +757,9 @@ int nfp_cpsync_reduce(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, 
                       int64_t saved_floats, const void* grad_out, float* grad_w, float* grad_gamma, float* grad_beta,
                       float* kq_row, int64_t kq_floats, float* scratch, int64_t scratch_floats, void* hip_stream,
                       int32_t grad_out_layout) {
-  const bool proj = kind == NFP_CP_PROJ;
-  CpCall c{"nfp_cpsync_reduce", proj ? kCpProj : kCpPool, proj ? grad_out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype,
-           1, maps, w, gamma, beta, eps, saved_floats, scratch, scratch_floats, hip_stream};
-  c.sync = 1, c.saved = saved, c.go = grad_out, c.gw = grad_w, c.gg = grad_gamma, c.gb = grad_beta;
+  CpCall c = cps_call("nfp_cpsync_reduce", kind, B, N, P, D, dtype, relu, grad_out_layout, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, scratch, scratch_floats, hip_stream);
+  c.saved = saved, c.go = grad_out, c.gw = grad_w, c.gg = grad_gamma, c.gb = grad_beta;
   return cps_reduce(c, kind, kq_row, kq_floats);
 }
 
@@ -2372,10 +767,9 @@ int nfp_cpsync_maps(int32_t kind, int32_t B, int32_t N, int64_t P, int32_t D, in
                     const float* w, const float* gamma, const float* beta, double eps, const float* saved, int64_t saved_floats,
                     const void* grad_out, const float* kq_rows, int32_t world, int64_t kq_floats, void* grad_maps,
                     void* hip_stream, int32_t grad_out_layout) {
-  const bool proj = kind == NFP_CP_PROJ;
-  CpCall c{"nfp_cpsync_maps", proj ? kCpProj : kCpPool, proj ? grad_out_layout : NFP_ACT_NCHW, proj ? relu : 1, B, N, P, D, dtype, 1,
-           maps, w, gamma, beta, eps, saved_floats, nullptr, 0, hip_stream};
-  c.sync = 1, c.saved = saved, c.go = grad_out, c.gm = grad_maps;
+  CpCall c = cps_call("nfp_cpsync_maps", kind, B, N, P, D, dtype, relu, grad_out_layout, maps, w, gamma, beta);
+  cp_buffers(c, eps, saved_floats, nullptr, 0, hip_stream);
+  c.saved = saved, c.go = grad_out, c.gm = grad_maps;
   return cps_maps(c, kind, kq_rows, world, kq_floats);
 }
 }  // extern "C"

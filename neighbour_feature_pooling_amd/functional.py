@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _abi
-from ._host import attention_pool_host, compress_map_host, compress_pool_host, nfp_host
+from ._host import attention_pool_host, compress_conv, compress_finish, compress_map_host, compress_pool_host, nfp_host
 
 
 @dataclass(frozen=True)
@@ -1068,9 +1068,9 @@ def nfp_valid(x, cfg):
 
 # ---- the heads' compress-BN-ReLU-GAP tail — include/nfp.h: nfp_cpool_* (csrc/nfp_cpool.hip) — and the same projection
 # ---- with the map kept — nfp_cproj_* (the cproj kernels): one call path, one autograd node and one set of checks for both
-CPOOL_MAX_MAPS = 32     # csrc/nfp_cpool.hip: kCpMaxN (a lane keeps two weight rows in registers)
+CPOOL_MAX_MAPS = 32     # csrc/nfp_cp_kernels.h: kCpMaxN (a lane keeps two weight rows in registers)
 CPOOL_ROUTED_MAPS = 8   # what cpool_hip_serves takes by default: the maps counts that measured faster than the composition
-CPOOL_WIDE_MAX_MAPS = 96    # csrc/nfp_cpool.hip: kWMaxN (the cpw kernels: rows and maps in LDS, a tile of outputs per lane)
+CPOOL_WIDE_MAX_MAPS = 96    # csrc/nfp_cp_kernels.h: kWMaxN (the cpw kernels: rows and maps in LDS, a tile of outputs per lane)
 # What cpool_wide_serves takes by default: the (maps, B * P) classes scripts/bench_heads.py measured faster than the
 # composition beyond the run-to-run spread on an MI355X ("The wide form") — none: [64,48,7,7] 0.35x, [256,48,7,7]
 # 0.60x, [256,80,7,7] 0.42x, [64,48,14,14] 0.49x (-> 512, train-mode forward + backward, graph-timed), so 33 to 96 maps reach
@@ -1082,57 +1082,93 @@ _CP_ENTRIES = {"pool": ("nfp_cpool_forward", "nfp_cpool_backward", "nfp_cpool_sc
                "proj": ("nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt", "nfp_cproj_scratch_floats")}
 
 
-def _cpool_sizes(maps, w):
+# ---- what every call of the family is assembled from, on one rank's statistics or across ranks ----
+def _cp_sizes(maps, D, empty_rank=False):
+    """(B, N, P, D) of maps [B,N,...]; empty_rank (the nfp_cpsync_* entries): a rank without a value is B = 0 with one pixel."""
     B, N = maps.shape[:2]
-    return B, N, maps.numel() // max(B * N, 1), w.shape[0]
+    P = maps.shape[2:].numel()
+    if empty_rank:
+        return (B, N, P, D) if P > 0 else (0, N, 1, D)
+    return B, N, (P if B * N else 0), D
 
 
 def _ptr(t):
-    return t.data_ptr() if t is not None else None
+    """The pointer the library is handed for `t`: NULL for None and for a tensor without an element."""
+    return (t.data_ptr() or None) if t is not None else None
+
+
+def _cp_in_format(y, channels_last):
+    return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+
+
+def _cp_out(kind, maps, D, channels_last=False):
+    """The result of one call, uninitialised: [B,D] float32, or for "proj" [B,D,...] in the maps' dtype and the asked layout."""
+    if kind != "proj":
+        return torch.empty(maps.shape[0], D, dtype=torch.float32, device=maps.device)
+    return torch.empty((maps.shape[0], D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=maps.device,
+                       memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+
+
+def _cp_grad_out(kind, maps, grad_out):
+    """(grad_out as the library reads it, whether that is channels-last): dense float32, or for "proj" the maps' dtype in
+    the layout it arrives in (cproj_backward_call)."""
+    if kind != "proj":
+        return grad_out.contiguous().float(), False
+    go = grad_out.to(maps.dtype)        # (preserve_format: a dense tensor keeps its layout)
+    nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
+    return (go if nhwc else go.contiguous()), nhwc
+
+
+def _cp_grads(maps, D, want):
+    """(grad_maps like the maps, grad_w [D,N], grad_gamma [D], grad_beta [D]), uninitialised — None for each `want` leaves out."""
+    dev = maps.device
+    return (torch.empty_like(maps) if want[0] else None,
+            torch.empty(D, maps.shape[1], dtype=torch.float32, device=dev) if want[1] else None,
+            torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None,
+            torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None)
+
+
+def _cp_scratch(kind, sizes, backward, need, device):
+    """(scratch, its length) as the length query of `kind` sizes it; (None, 0) where the call needs none."""
+    n = int(getattr(_abi.load(), _CP_ENTRIES[kind][2])(*sizes, int(backward))) if need else 0
+    return (torch.empty(n, dtype=torch.float32, device=device) if n else None), n
 
 
 def _cp_invoke(kind, backward, maps, w, gamma, beta, use_batch_stats, relu, nhwc, need_scratch, middle):
     """One call of a _CP_ENTRIES function, on the maps' device — the one place its argument list is built: the sizes, dtype
     and mode (proj: relu), the maps and parameters, `middle` (the direction's own arguments), the scratch with its length,
     the stream (proj: the layout of out / grad_out)."""
-    L = _abi.load()
-    B, N, P, D = _cpool_sizes(maps, w)
+    sizes = _cp_sizes(maps, w.shape[0])
     proj = kind == "proj"
-    nscr = int(getattr(L, _CP_ENTRIES[kind][2])(B, N, P, D, int(backward))) if need_scratch else 0
-    scratch = torch.empty(nscr, dtype=torch.float32, device=maps.device) if nscr else None
-    args = [B, N, P, D, _DTYPES[maps.dtype], int(bool(use_batch_stats))] + ([int(bool(relu))] if proj else [])
-    args += [maps.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *middle, _ptr(scratch), nscr,
-             _raw_stream(maps.device)]
+    scratch, nscr = _cp_scratch(kind, sizes, backward, need_scratch, maps.device)
+    args = [*sizes, _DTYPES[maps.dtype], int(bool(use_batch_stats))] + ([int(bool(relu))] if proj else [])
+    args += [_ptr(maps), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *middle, _ptr(scratch), nscr, _raw_stream(maps.device)]
     args += [_abi.ACT_NHWC if nhwc else _abi.ACT_NCHW] if proj else []
-    _abi.check(getattr(L, _CP_ENTRIES[kind][int(backward)])(*args))
+    _abi.check(getattr(_abi.load(), _CP_ENTRIES[kind][int(backward)])(*args))
 
 
-def _cp_forward_call(kind, out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu=True, nhwc=False):
-    """The forward of `kind` into `out`; returns `saved`, the O(N*N + D) state the backward reads (None in eval)."""
-    _, N, _, D = _cpool_sizes(maps, w)
+def _cp_forward_call(kind, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu=True, nhwc=False):
+    """(out, saved) of the forward of `kind`; saved: the O(N*N + D) state the backward reads (None in eval)."""
+    N, D = maps.shape[1], w.shape[0]
     with _on_device(maps.device):
+        out = _cp_out(kind, maps, D, nhwc)
         ns = int(_abi.load().nfp_cpool_saved_floats(N, D)) if use_batch_stats else 0
         saved = torch.empty(ns, dtype=torch.float32, device=maps.device) if ns else None
         _cp_invoke(kind, False, maps, w, gamma, beta, use_batch_stats, relu, nhwc, use_batch_stats,
-                   [_ptr(rm), _ptr(rv), float(momentum), float(eps), out.data_ptr(), _ptr(saved), ns])
-    return saved
+                   [_ptr(rm), _ptr(rv), float(momentum), float(eps), _ptr(out), _ptr(saved), ns])
+    return out, saved
 
 
-def _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, go, want, relu=True, nhwc=False):
-    """(grad_maps, grad_w, grad_gamma, grad_beta) of `kind` under the dense grad_out `go` — None for each gradient `want`
-    (four flags) leaves out: a NULL pointer in the library, neither computed nor written."""
-    _, N, _, D = _cpool_sizes(maps, w)
-    dev = maps.device
-    with _on_device(dev):
-        gm = torch.empty_like(maps) if want[0] else None
-        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[1] else None
-        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
-        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[3] else None
+def _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want, relu=True):
+    """(grad_maps, grad_w, grad_gamma, grad_beta) of `kind` (_cp_grads) under grad_out (_cp_grad_out)."""
+    go, nhwc = _cp_grad_out(kind, maps, grad_out)
+    with _on_device(maps.device):
+        grads = _cp_grads(maps, w.shape[0], want)
         sums = use_batch_stats or want[1] or want[2] or want[3]
         _cp_invoke(kind, True, maps, w, gamma, beta, use_batch_stats, relu, nhwc, sums,
                    [None if use_batch_stats else _ptr(rm), None if use_batch_stats else _ptr(rv), float(eps), _ptr(saved),
-                    saved.numel() if saved is not None else 0, go.data_ptr(), _ptr(gm), _ptr(gw), _ptr(gg), _ptr(gb)])
-    return gm, gw, gg, gb
+                    saved.numel() if saved is not None else 0, _ptr(go), *map(_ptr, grads)])
+    return grads
 
 
 def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, kind="pool"):
@@ -1140,16 +1176,14 @@ def cpool_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, 
     use_batch_stats: train-mode statistics, the running ones (float32 [D], or both None) updated by the same call; `saved`
     is then the O(N*N + D) state the backward reads (None in eval, where rm / rv stand for the statistics).
     kind="wide": nfp_cpool_wide_forward (up to 96 maps), the same arguments and `saved`."""
-    with _on_device(maps.device):
-        out = torch.empty(maps.shape[0], w.shape[0], dtype=torch.float32, device=maps.device)
-    return out, _cp_forward_call(kind, out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps)
+    return _cp_forward_call(kind, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps)
 
 
 def cpool_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want, kind="pool"):
     """(grad_maps in the maps' dtype, grad_w [D,N], grad_gamma [D], grad_beta [D]) from nfp_cpool_backward — None for each
     gradient `want` (four flags) leaves out: a NULL pointer in the library, neither computed nor written.  kind="wide":
     nfp_cpool_wide_backward, on the `saved` of a wide forward."""
-    return _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out.contiguous().float(), want)
+    return _cp_backward_call(kind, maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want)
 
 
 class _CpHip(torch.autograd.Function):
@@ -1207,13 +1241,13 @@ def _cp_check_args(name, maps, weight, use_batch_stats, running_mean, running_va
         raise RuntimeError(f"{name}: without batch statistics the running mean and variance are required")
 
 
-def _cp_prepare(maps, weight, gamma, beta, rm, rv, use_batch_stats):
+def _cp_prepare(maps, weight, gamma, beta, rm, rv, own_stats):
     """What a served call hands its node: float32, contiguous (w [D,N], gamma, beta) — or None where the running statistics
-    are not float32 and contiguous, which is the host composition's.  ValueError as F.batch_norm raises it for a single
-    value per channel in training."""
+    are not float32 and contiguous, which is the host composition's.  own_stats (batch statistics of this rank alone):
+    ValueError as F.batch_norm raises it for a single value per channel in training."""
     B, N = maps.shape[:2]
     D = weight.shape[0]
-    if use_batch_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
+    if own_stats and maps.numel() // N == 1:     # torch/nn/functional.py::_verify_batch_size, on the conv's output
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D, 1, 1])}")
     if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
         return None
@@ -1347,10 +1381,7 @@ def cproj_forward_call(maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, 
     """(out [B,D,...] in the maps' dtype, saved) from nfp_cproj_forward_fmt on dense CUDA maps [B,N,...] and float32 w
     [D,N], gamma, beta [D] — cpool_forward_call's arguments and `saved`, plus `relu`; channels_last: `out` [B,D,H,W] is
     written channels-last (the maps stay NCHW)."""
-    with _on_device(maps.device):
-        out = torch.empty((maps.shape[0], w.shape[0]) + tuple(maps.shape[2:]), dtype=maps.dtype, device=maps.device,
-                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    return out, _cp_forward_call("proj", out, maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu, channels_last)
+    return _cp_forward_call("proj", maps, w, gamma, beta, rm, rv, use_batch_stats, momentum, eps, relu, channels_last)
 
 
 def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, relu, grad_out, want):
@@ -1359,11 +1390,7 @@ def cproj_backward_call(maps, w, gamma, beta, rm, rv, saved, use_batch_stats, ep
     neither computed nor written.  The layout grad_out arrives in selects the kernels, whatever the forward wrote: NCHW-dense
     (also where H = W = 1 or D = 1 make it both) the NCHW ones, channels-last-dense the channels-last ones, neither a
     copy; anything else is made NCHW-dense first."""
-    go = grad_out.to(maps.dtype)        # (preserve_format: a dense tensor keeps its layout)
-    nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
-    if not nhwc:
-        go = go.contiguous()
-    return _cp_backward_call("proj", maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, go, want, relu, nhwc)
+    return _cp_backward_call("proj", maps, w, gamma, beta, rm, rv, saved, use_batch_stats, eps, grad_out, want, relu)
 
 
 class _CProjHip(_CpHip):
@@ -1439,7 +1466,7 @@ def nfp_compress_map_tensors(maps, weight, gamma, beta, running_mean, running_va
                 and _cp_prepare(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats))
     if not prepared:
         y = compress_map_host(maps, weight, gamma, beta, running_mean, running_var, use_batch_stats, momentum, eps, relu)
-        return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+        return _cp_in_format(y, channels_last)
     return _CProjHip.apply(maps, *prepared, (running_mean, running_var), bool(use_batch_stats), float(momentum), float(eps),
                            bool(relu), need_grad, channels_last)
 
@@ -1459,7 +1486,7 @@ def nfp_compress_map(maps, weight, bn, relu=True, training=None, *, memory_forma
     use_batch_stats, rm, rv, factor = _bn_call_mode(bn, training)
     if factor is not None:
         y = compress_map_host(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, factor, bn.eps, relu)
-        return y.contiguous(memory_format=torch.channels_last) if channels_last else y
+        return _cp_in_format(y, channels_last)
     return nfp_compress_map_tensors(maps, weight, bn.weight, bn.bias, rm, rv, use_batch_stats, float(bn.momentum), bn.eps, relu,
                                     memory_format=memory_format)
 
@@ -1503,36 +1530,22 @@ def cp_sync_serves(kind, maps, gamma, beta, momentum):
     return 1 <= maps.shape[1] <= (CPOOL_MAX_MAPS if env == "0" else CPOOL_ROUTED_MAPS)
 
 
-def _cps_sizes(maps, D):
-    """(B, N, P, D) of a rank's maps [B,N,...]; a rank without a value is B = 0 with one pixel."""
-    B, N = maps.shape[:2]
-    P = 1
-    for s in maps.shape[2:]:
-        P *= s
-    return (B, N, P, D) if P > 0 else (0, N, 1, D)
-
-
 def _cps_head(kind, maps, w, gamma, beta, relu):
-    B, N, P, D = _cps_sizes(maps, w.shape[0])
-    return [_abi.CP_PROJ if kind == "proj" else _abi.CP_POOL, B, N, P, D, _DTYPES[maps.dtype], int(bool(relu)), _ptr(maps),
-            w.data_ptr(), gamma.data_ptr(), beta.data_ptr()]
-
-
-def _ptr0(t):
-    return (t.data_ptr() or None) if t is not None else None
+    """The leading arguments of nfp_cpsync_forward / _reduce / _maps."""
+    return [_abi.CP_PROJ if kind == "proj" else _abi.CP_POOL, *_cp_sizes(maps, w.shape[0], True), _DTYPES[maps.dtype],
+            int(bool(relu)), _ptr(maps), w.data_ptr(), gamma.data_ptr(), beta.data_ptr()]
 
 
 def cp_sync_moments_call(maps):
     """A rank's record from nfp_cpsync_moments: float64 [1 + N + N*N] — count, mean and scatter of its dense CUDA maps
     [B,N,...], B = 0 included."""
     L = _abi.load()
-    B, N, P, _ = _cps_sizes(maps, 1)
+    B, N, P, _ = sizes = _cp_sizes(maps, 1, True)
     with _on_device(maps.device):
         nr = int(L.nfp_cpsync_record_doubles(N))
         record = torch.empty(nr, dtype=torch.float64, device=maps.device)
-        ns = int(L.nfp_cpool_scratch_floats(B, N, P, 1, 0)) if B else 0
-        scratch = torch.empty(ns, dtype=torch.float32, device=maps.device) if ns else None
-        _abi.check(L.nfp_cpsync_moments(B, N, P, _DTYPES[maps.dtype], _ptr0(maps), record.data_ptr(), nr, _ptr(scratch), ns,
+        scratch, ns = _cp_scratch("pool", sizes, False, B, maps.device)
+        _abi.check(L.nfp_cpsync_moments(B, N, P, _DTYPES[maps.dtype], _ptr(maps), record.data_ptr(), nr, _ptr(scratch), ns,
                                         _raw_stream(maps.device)))
     return record
 
@@ -1543,64 +1556,47 @@ def cp_sync_forward_call(kind, maps, w, gamma, beta, rm, rv, momentum, eps, reco
     maps' dtype for "proj" — under the statistics joined from `records` [world, 1 + N + N*N] (float64, row r rank r's),
     and the state the backward reads.  rm / rv: the running statistics (float32 [D], or both None), updated in place."""
     L = _abi.load()
-    B, N, P, D = _cps_sizes(maps, w.shape[0])
     dev = maps.device
     with _on_device(dev):
-        if kind == "proj":
-            out = torch.empty((maps.shape[0], D) + tuple(maps.shape[2:]), dtype=maps.dtype, device=dev,
-                              memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-        else:
-            out = torch.empty(maps.shape[0], D, dtype=torch.float32, device=dev)
-        ns = int(L.nfp_cpsync_saved_floats(N, D))
+        out = _cp_out(kind, maps, w.shape[0], channels_last)
+        ns = int(L.nfp_cpsync_saved_floats(maps.shape[1], w.shape[0]))
         saved = torch.empty(ns, dtype=torch.float32, device=dev)
         records = records.contiguous()
         _abi.check(L.nfp_cpsync_forward(*_cps_head(kind, maps, w, gamma, beta, relu), _ptr(rm), _ptr(rv), float(momentum),
                                         float(eps), records.data_ptr(), records.shape[0], records.numel(), int(global_count),
-                                        _ptr0(out), saved.data_ptr(), ns, _raw_stream(dev),
+                                        _ptr(out), saved.data_ptr(), ns, _raw_stream(dev),
                                         _abi.ACT_NHWC if channels_last else _abi.ACT_NCHW))
     return out, saved
-
-
-def _cps_grad_out(kind, maps, grad_out):
-    """(grad_out as the library reads it, whether that is channels-last): cpool_backward_call's / cproj_backward_call's."""
-    if kind != "proj":
-        return grad_out.contiguous().float(), False
-    go = grad_out.to(maps.dtype)
-    nhwc = not go.is_contiguous() and go.dim() == 4 and go.is_contiguous(memory_format=torch.channels_last)
-    return (go if nhwc else go.contiguous()), nhwc
 
 
 def cp_sync_reduce_call(kind, maps, w, gamma, beta, saved, eps, grad_out, want=(True, True, True), relu=True):
     """(grad_w [D,N], grad_gamma [D], grad_beta [D], row) from nfp_cpsync_reduce: the rank's parameter gradients — None for
     each `want` leaves out; their sum over the ranks is the batch's — and its row [N + N*N] of k and Q."""
     L = _abi.load()
-    B, N, P, D = _cps_sizes(maps, w.shape[0])
+    sizes = _cp_sizes(maps, w.shape[0], True)
     dev = maps.device
-    go, nhwc = _cps_grad_out(kind, maps, grad_out)
+    go, nhwc = _cp_grad_out(kind, maps, grad_out)
     with _on_device(dev):
-        gw = torch.empty(D, N, dtype=torch.float32, device=dev) if want[0] else None
-        gg = torch.empty(D, dtype=torch.float32, device=dev) if want[1] else None
-        gb = torch.empty(D, dtype=torch.float32, device=dev) if want[2] else None
-        nk = int(L.nfp_cpsync_kq_floats(N))
+        grads = _cp_grads(maps, w.shape[0], (False, *want))[1:]
+        nk = int(L.nfp_cpsync_kq_floats(maps.shape[1]))
         row = torch.empty(nk, dtype=torch.float32, device=dev)
-        ns = int(getattr(L, _CP_ENTRIES[kind][2])(B, N, P, D, 1)) if B else 0
-        scratch = torch.empty(ns, dtype=torch.float32, device=dev) if ns else None
+        scratch, ns = _cp_scratch(kind, sizes, True, sizes[0], dev)
         _abi.check(L.nfp_cpsync_reduce(*_cps_head(kind, maps, w, gamma, beta, relu), float(eps), saved.data_ptr(), saved.numel(),
-                                       _ptr0(go), _ptr(gw), _ptr(gg), _ptr(gb), row.data_ptr(), nk, _ptr(scratch), ns,
-                                       _raw_stream(dev), _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
-    return gw, gg, gb, row
+                                       _ptr(go), *map(_ptr, grads), row.data_ptr(), nk, _ptr(scratch), ns, _raw_stream(dev),
+                                       _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
+    return (*grads, row)
 
 
 def cp_sync_maps_call(kind, maps, w, gamma, beta, saved, eps, grad_out, rows, relu=True):
     """grad_maps of the rank, in the maps' dtype, from nfp_cpsync_maps under `rows` [world, N + N*N] (row r rank r's)."""
     L = _abi.load()
     dev = maps.device
-    go, nhwc = _cps_grad_out(kind, maps, grad_out)
+    go, nhwc = _cp_grad_out(kind, maps, grad_out)
     with _on_device(dev):
         gm = torch.empty_like(maps)
         rows = rows.contiguous()
         _abi.check(L.nfp_cpsync_maps(*_cps_head(kind, maps, w, gamma, beta, relu), float(eps), saved.data_ptr(), saved.numel(),
-                                     _ptr0(go), rows.data_ptr(), rows.shape[0], rows.numel(), _ptr0(gm), _raw_stream(dev),
+                                     _ptr(go), rows.data_ptr(), rows.shape[0], rows.numel(), _ptr(gm), _raw_stream(dev),
                                      _abi.ACT_NHWC if nhwc else _abi.ACT_NCHW))
     return gm
 
@@ -1617,7 +1613,7 @@ def _cps_gather(row, group):
     return buf
 
 
-class _CpSyncHip(torch.autograd.Function):
+class _CpSyncHip(_CpHip):
     """_CPoolHip / _CProjHip in training mode with the statistics of every rank of `group`: moments -> gather -> finish and
     the main forward; part and reduce -> gather -> grad_maps.  Both gathers are entered by every rank, whatever its batch
     and whichever gradients it needs.  Saved: the maps, the parameters and the O(N*N + D) statistics."""
@@ -1628,47 +1624,36 @@ class _CpSyncHip(torch.autograd.Function):
         out, saved = cp_sync_forward_call(kind, maps, w, gamma, beta, stats[0], stats[1], momentum, eps, records, relu,
                                           channels_last)
         if need_grad:
-            ctx.save_for_backward(maps, w, gamma, beta, saved)
-            ctx.eps, ctx.relu, ctx.kind, ctx.group = eps, relu, kind, group
+            _CpHip._save(ctx, maps, w, gamma, beta, saved, stats, True, eps)
+            ctx.relu, ctx.kind, ctx.group = relu, kind, group
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        maps, w, gamma, beta, saved = ctx.saved_tensors
-        gw, gg, gb, row = cp_sync_reduce_call(ctx.kind, maps, w, gamma, beta, saved, ctx.eps, grad_out,
-                                              ctx.needs_input_grad[1:4], ctx.relu)
+        maps, w, gamma, beta, _, _, saved, _, eps = _CpHip._state(ctx)
+        gw, gg, gb, row = cp_sync_reduce_call(ctx.kind, maps, w, gamma, beta, saved, eps, grad_out, ctx.needs_input_grad[1:4],
+                                              ctx.relu)
         rows = _cps_gather(row, ctx.group)
         gm = None
         if ctx.needs_input_grad[0]:
-            gm = cp_sync_maps_call(ctx.kind, maps, w, gamma, beta, saved, ctx.eps, grad_out, rows, ctx.relu)
+            gm = cp_sync_maps_call(ctx.kind, maps, w, gamma, beta, saved, eps, grad_out, rows, ctx.relu)
         return (gm, gw, gg, gb, None, None, None, None, None, None, None, None)
 
 
 def _cp_sync_node_call(kind, maps, weight, gamma, beta, rm, rv, momentum, eps, group, relu, channels_last):
     """The sync node on what cp_sync_serves took, or None where the running statistics are not float32 and contiguous."""
-    if rm is not None and (rm.dtype != torch.float32 or rv.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous()):
+    prepared = _cp_prepare(maps, weight, gamma, beta, rm, rv, False)
+    if prepared is None:
         return None
-    N, D = maps.shape[1], weight.shape[0]
-    f32 = lambda t: t if t.dtype == torch.float32 else t.float()     # noqa: E731
     need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (maps, weight, gamma, beta))
-    out = _CpSyncHip.apply(maps.contiguous(), f32(weight).reshape(D, N).contiguous(), f32(gamma).contiguous(),
-                           f32(beta).contiguous(), (rm, rv), float(momentum), float(eps), bool(relu), need_grad, kind,
+    out = _CpSyncHip.apply(maps.contiguous(), *prepared, (rm, rv), float(momentum), float(eps), bool(relu), need_grad, kind,
                            channels_last, group)
     return out if out.dtype == maps.dtype else out.to(maps.dtype)
 
 
 def _cp_sync_finish_composition(kind, y, maps, relu, channels_last):
-    y = torch.relu(y) if relu else y
-    if kind == "pool":
-        return y.mean((2, 3))
-    y = y if maps.dim() == 4 else y.reshape(maps.shape[0], y.shape[1], *maps.shape[2:])
-    return y.contiguous(memory_format=torch.channels_last) if channels_last else y
-
-
-def _cp_conv(maps, weight):
-    B, N = maps.shape[:2]
-    return torch.nn.functional.conv2d(maps if maps.dim() == 4 else maps.reshape(B, N, -1, 1), weight.reshape(weight.shape[0], N, 1, 1))
+    return _cp_in_format(compress_finish(y, maps, relu, kind == "pool"), channels_last and kind != "pool")
 
 
 def _cp_sync_module_call(kind, maps, weight, bn, training, group, relu=True, channels_last=False):
@@ -1684,7 +1669,7 @@ def _cp_sync_module_call(kind, maps, weight, bn, training, group, relu=True, cha
     was = bn.training
     bn.training = training
     try:
-        y = bn(_cp_conv(maps, weight))
+        y = bn(compress_conv(maps, weight))
     finally:
         bn.training = was
     return _cp_sync_finish_composition(kind, y, maps, relu, channels_last)
@@ -1700,6 +1685,6 @@ def _cp_sync_tensors_call(kind, maps, weight, gamma, beta, rm, rv, momentum, eps
     if not maps.is_cuda:
         raise ValueError("SyncBatchNorm expected input tensor to be on GPU or privateuseone")
     from torch.nn.modules._functions import SyncBatchNorm as sync_batch_norm
-    y = sync_batch_norm.apply(_cp_conv(maps, weight), gamma, beta, rm, rv, eps, momentum, group,
+    y = sync_batch_norm.apply(compress_conv(maps, weight), gamma, beta, rm, rv, eps, momentum, group,
                               torch.distributed.get_world_size(group))
     return _cp_sync_finish_composition(kind, y, maps, relu, channels_last)
