@@ -284,6 +284,28 @@ int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, c
                        int64_t saved_floats, void* grad_x, void* hip_stream);
 
 /*
+ * The L1 family of the valid-map kernels: Norm p = 1 on the difference weights (diff_weights = 1) — the reference's
+ * NFPPooling() with no keywords (measure='norm', p=1, padding=0, R=1), the layer NFPInsert builds — and EMD, which the
+ * library turns into exactly that descriptor (the same sum of |centre - neighbour| and the same sign gradient, 0 at 0;
+ * its p and diff_weights fields are ignored).  Entry points of their own because their contract is smaller: the backward
+ * needs neither `out` nor a saved statistic (a pair's coefficient is -+ grad_out), so there is no `saved` and the caller
+ * may overwrite `out` before the backward.  grad_x[c][r] = sum_j W[j][r] sgn(x[c][r] - x[c][r + d_j]), sgn(0) = 0.
+ *   nfp_valid_abs_supported(d)  1: both calls below will launch (a host-only dry run; 4 KiB-aligned buffers assumed);
+ *                               changes neither nfp_launch_count, nfp_last_variant nor nfp_last_error
+ * Served: NFP_NORM with p == 1 and diff_weights = 1, NFP_EMD, either `similarity`; geometry, types and layouts exactly
+ * those of nfp_valid_* above (pad 0, stride 1, dilation 1, R = 1 or 2, 2R+1 <= W <= 128, NCHW with any C and any batch
+ * stride or 16-byte-aligned channels-last with C % 4 == 0 (float32) / C % 8 == 0 (bf16), map_f32 = 0, inner_R = 0).
+ * NFP_E_UNSUPPORTED, launching nothing: every other measure, Norm with p != 1, 'Norm' on the pure-neighbour weights
+ * (diff_weights = 0), and what the geometry and layout rules exclude.  A null tensor is NFP_E_INVALID; B = 0 returns
+ * NFP_OK without a launch.  One launch each way, no workspace, no atomics, the same bands and channel blocks as
+ * nfp_valid_*: two runs agree bitwise and image b's results do not depend on B.
+ * nfp_last_variant names fwd_valid<R,l1,f32|bf16,nchw|nhwc> / bwd_valid<R,l1,...>.  Additive to ABI 7.
+ */
+int nfp_valid_abs_supported(const nfp_desc* d);
+int nfp_valid_abs_forward(const nfp_desc* d, const void* x, void* out, void* hip_stream);
+int nfp_valid_abs_backward(const nfp_desc* d, const void* x, const void* grad_out, void* grad_x, void* hip_stream);
+
+/*
  * The tail the three trained heads of models/nfp_heads.py share behind their NFP maps (NFPHead nfp_heads.py:28-32,42-43,
  * MultiRadiusNFPHead 98-102,114-115, AdaptiveFusionNFP 301-305,323-324):
  *   compress = Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU        out [B,D] = GAP(compress(maps))

@@ -25,6 +25,7 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward",
            "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
+           "nfp_valid_abs_supported", "nfp_valid_abs_forward", "nfp_valid_abs_backward",
            "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
            "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward",
            "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt",
@@ -115,6 +116,10 @@ def load():
         L.nfp_valid_saved_floats.restype = i64
         L.nfp_valid_forward.argtypes = [dp, vp, vp, vp, i64, vp]
         L.nfp_valid_backward.argtypes = [dp, vp, vp, vp, vp, i64, vp, vp]
+    if hasattr(L, "nfp_valid_abs_forward"):     # (absent only from an older library loaded for an A/B run)
+        L.nfp_valid_abs_supported.argtypes = [dp]
+        L.nfp_valid_abs_forward.argtypes = [dp, vp, vp, vp]
+        L.nfp_valid_abs_backward.argtypes = [dp, vp, vp, vp, vp]
     if hasattr(L, "nfp_cpool_forward"):         # (absent only from an older library loaded for an A/B run)
         i32, f64 = ctypes.c_int32, ctypes.c_double
         L.nfp_cpool_saved_floats.argtypes = [i32, i32]

@@ -656,6 +656,39 @@ int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, c
   return finish(valid_backward(g, x, grad_out, out, saved, grad_x, (hipStream_t)hip_stream), "nfp_valid_backward");
 }
 
+// ... and their L1 family: Norm p = 1 on the difference weights and EMD (make_kp: the same descriptor), x alone on the way back
+int nfp_valid_abs_supported(const nfp_desc* d) {
+  KP g;
+  const DryRun dry;
+  void* const fake = kStandIn;
+  return make_kp(d, &g) == NFP_OK && valid_abs_refusal(g) == nullptr &&
+                 (g.B == 0 || (valid_abs_forward(g, fake, fake, nullptr) == NFP_OK &&
+                               valid_abs_backward(g, fake, fake, fake, nullptr) == NFP_OK))
+             ? 1 : 0;
+}
+
+static int valid_abs_kp(const nfp_desc* d, KP* g) {
+  if (int rc = make_kp(d, g)) return rc;
+  if (const char* why = valid_abs_refusal(*g)) return fail(NFP_E_UNSUPPORTED, "valid L1 maps: %s", why);
+  return NFP_OK;
+}
+
+int nfp_valid_abs_forward(const nfp_desc* d, const void* x, void* out, void* hip_stream) {
+  KP g;
+  if (int rc = valid_abs_kp(d, &g)) return rc;
+  if (g.B > 0 && (!x || !out)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (g.B == 0) return NFP_OK;
+  return finish(valid_abs_forward(g, x, out, (hipStream_t)hip_stream), "nfp_valid_abs_forward");
+}
+
+int nfp_valid_abs_backward(const nfp_desc* d, const void* x, const void* grad_out, void* grad_x, void* hip_stream) {
+  KP g;
+  if (int rc = valid_abs_kp(d, &g)) return rc;
+  if (g.B > 0 && (!x || !grad_out || !grad_x)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (g.B == 0) return NFP_OK;
+  return finish(valid_abs_backward(g, x, grad_out, grad_x, (hipStream_t)hip_stream), "nfp_valid_abs_backward");
+}
+
 // ---- ABI 7: NFPPooling(bias=True) — nfp_bias.hip ---------------------------------------------------------------------
 // The descriptor's own measure: make_kp serves EMD as Norm p = 1 on the difference weights, which a bias on the
 // neighbour side breaks (|(a + bc) - (x_n + beta)| is not |(a - x_n) + beta|).  The difference weights are applied by the

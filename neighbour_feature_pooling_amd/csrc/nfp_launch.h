@@ -168,7 +168,8 @@ struct DryFlag {
   ~DryFlag() { t_dry = was_dry; }
 };
 // ... and the calling thread's variant, plan and error strings put back: a question about a descriptor ("would both
-// launchers launch?" — nfp_pool_supported, nfp_gap_supported, nfp_valid_supported and their saved_floats) leaves no trace
+// launchers launch?" — nfp_pool_supported, nfp_gap_supported, nfp_valid_supported, nfp_valid_abs_supported and their
+// saved_floats) leaves no trace
 struct DryRun : DryFlag {
   char variant[sizeof(g_variant)], plan[sizeof(t_plan)], err[sizeof(g_err)];
   DryRun() {
@@ -447,5 +448,10 @@ int bias_backward(const KP& g, int dw, const void* x, const float* bc, const flo
 const char* valid_refusal(const KP& g);
 int valid_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st);
 int valid_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st);
+// ... and their L1 family (include/nfp.h: nfp_valid_abs_*): Norm p = 1 on the difference weights (EMD arrives as it: make_kp)
+// under the same geometry and layout rules; neither `out` nor a saved statistic on the way back.
+const char* valid_abs_refusal(const KP& g);
+int valid_abs_forward(const KP& g, const void* x, void* out, hipStream_t st);
+int valid_abs_backward(const KP& g, const void* x, const void* go, void* gx, hipStream_t st);
 
 }  // namespace nfp_host

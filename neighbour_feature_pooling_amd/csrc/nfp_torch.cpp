@@ -3,7 +3,7 @@
 // The reference's NFP is a chain of ATen ops whose autograd graph PyTorch builds (nfp.py:132-159); here one
 // forward and one backward kernel stand for it, and these torch::autograd::Function classes are the graph
 // nodes.  They do what functional.py's Python autograd.Functions do — allocate out / saved / grad_x, take torch's
-// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_* / nfp_valid_*) — without the Python
+// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_* / nfp_valid_* / nfp_valid_abs_*) — without the Python
 // interpreter on the launch path: eager host cost per forward + backward drops from ~75 us to the autograd
 // engine's own (scripts/host_overhead.py).  No device code in this file; plain pointers go across the ABI.
 //
@@ -162,11 +162,37 @@ struct NfpValidNode : torch::autograd::Function<NfpValidNode> {
   }
 };
 
+// ... and their L1 family (nfp_valid_abs_forward / nfp_valid_abs_backward: Norm p = 1 on the difference weights, EMD): the
+// backward reads x and grad_out alone, so x is all the node saves and the maps may be modified in place by the caller.
+struct NfpValidAbsNode : torch::autograd::Function<NfpValidAbsNode> {
+  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, bool nhwc, bool need_grad) {
+    c10::DeviceGuard guard(x.device());
+    Tensor out = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
+    check(nfp_valid_abs_forward(desc_of(desc), x.data_ptr(), out.data_ptr(), stream_of(x)));
+    if (need_grad) ctx->save_for_backward({x, desc});
+    ctx->saved_data["nhwc"] = nhwc;
+    return out;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto sv = ctx->get_saved_variables();
+    const Tensor &x = sv[0], &desc = sv[1];
+    c10::DeviceGuard guard(x.device());
+    Tensor go = grads[0].contiguous();
+    if (go.scalar_type() != x.scalar_type()) go = go.to(x.scalar_type());
+    Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
+    check(nfp_valid_abs_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), gx.data_ptr(), stream_of(x)));
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 Tensor nfp_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return NfpNode::apply(x, desc, oshape, ns, nhwc);
 }
 Tensor nfp_valid_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return NfpValidNode::apply(x, desc, oshape, ns, nhwc);
+}
+Tensor nfp_valid_abs_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, bool nhwc, bool need_grad) {
+  return NfpValidAbsNode::apply(x, desc, oshape, nhwc, need_grad);
 }
 std::vector<Tensor> nfp_pool_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc, bool want_gap,
                                    bool need_grad) {
@@ -184,5 +210,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nfp_pool_apply", &nfp_pool_apply, "the fused nfp_pooling tail as one autograd node (nfp_pool_forward / _backward)");
   m.def("nfp_gap_apply", &nfp_gap_apply, "GAP(x) beside the full maps as one autograd node (nfp_gap_forward / _backward)");
   m.def("nfp_valid_apply", &nfp_valid_apply, "an unpadded layer's maps as one autograd node (nfp_valid_forward / _backward)");
+  m.def("nfp_valid_abs_apply", &nfp_valid_abs_apply,
+        "an unpadded L1 layer's maps as one autograd node that saves x alone (nfp_valid_abs_forward / _backward)");
   m.attr("desc_bytes") = (int64_t)sizeof(nfp_desc);
 }

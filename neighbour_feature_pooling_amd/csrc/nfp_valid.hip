@@ -24,6 +24,14 @@
 // of every staged chunk (input rows [r0 - R, r0 + rb + R) clipped to the image).  Channels-last maps put grp along the
 // lanes, so that a lane stores 4 adjacent channels and neighbouring lanes neighbouring quads.
 // No atomics, every sum in a fixed order: two runs agree bitwise and image b's results do not depend on B.
+//
+// The L1 family (include/nfp.h: nfp_valid_abs_* — Norm p = 1 on the difference weights, the reference's default layer, and
+// EMD, which make_kp turns into it): fwd_valid<R, 2, ...> sums |x_u - x_t| over the same half stencil and finishes it as
+// -+ the sum; no norm, nothing saved.  bwd_valid<R, 3, ...>: the pair's coefficient is -+ grad_out alone, so phase A reads
+// grad_out under the two predicates and nothing else (no out, no saved, no diagonal), and phase B is
+//   grad_x[c][r] = sum_j Wt[j][r] sgn(x[c][r] - x[c][r + d_j])                   sgn(0) = 0 (torch's abs backward)
+// formed as bwd_tile's kNormP1 instantiation forms it: sgn3 (a compare, a select and a sign copy) under one fma.  Same
+// sizing, bands, chunks, channel blocks, lane maps and stores as the other families.
 #include "nfp_launch.h"
 #include "nfp_measures.h"
 
@@ -120,6 +128,7 @@ __device__ __forceinline__ void stage_rows(const KP& g, const VP& v, const void*
 // the finished map value of a pair sum (wave-uniform switch on the descriptor's measure)
 template <int PROD>
 __device__ __forceinline__ float valid_fin(const KP& g, float acc, float n2p, float n2q) {
+  if (PROD == 2) return g.similarity ? -acc : acc;   // (Norm p = 1: the sum of |a - t| itself)
   if (PROD) {
     if (g.measure == NFP_COSINE) {
       // ONE correctly rounded division by the product of the clamped norms (not acc * (1 / m_p) * (1 / m_q)): the same
@@ -147,6 +156,7 @@ __device__ __forceinline__ Coef valid_coef(const KP& g, float go, float ov, floa
 }
 
 // grid = (bands, B).  Dynamic LDS (floats): max(Cc * S, G * (NH + 1) * npix) — the slab, then the groups' partial sums.
+// PROD: 0 squared differences, 1 products (and |x_u|^2), 2 absolute differences (the L1 family: `saved` is never written)
 template <int R, int PROD, int BF, int NHWC>
 __global__ void __launch_bounds__(kValidFwdT) fwd_valid(KP g, VP v, const void* __restrict__ x, void* __restrict__ out,
                                                         float* __restrict__ saved) {
@@ -180,12 +190,14 @@ __global__ void __launch_bounds__(kValidFwdT) fwd_valid(KP g, VP v, const void* 
       for (int c = grp; c < cc; c += v.G) {
         const float* xc = vlds + c * v.S + u;
         const float a = xc[0];
-        if (PROD) n2 = fmaf(a, a, n2);
+        if (PROD == 1) n2 = fmaf(a, a, n2);
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
           const float t = xc[off[h]];
-          if (PROD) {
+          if (PROD == 1) {
             acc[h] = fmaf(a, t, acc[h]);
+          } else if (PROD == 2) {
+            acc[h] += fabsf(a - t);
           } else {
             const float d = a - t;
             acc[h] = fmaf(d, d, acc[h]);
@@ -215,7 +227,7 @@ __global__ void __launch_bounds__(kValidFwdT) fwd_valid(KP g, VP v, const void* 
   const float* pr = vlds;
   const float* n2s = vlds + NH * v.npix;
   // |x| per input pixel for the backward: a band owns the rows of its centres, the first and the last band the border rows
-  if (PROD && g.measure != NFP_DOT && saved != nullptr) {
+  if (PROD == 1 && g.measure != NFP_DOT && saved != nullptr) {
     const bool first = blockIdx.x == 0, last = blockIdx.x == gridDim.x - 1;
     float* sv = saved + (long long)b * g.P + (long long)i0 * W;
     for (int p = tid; p < npix; p += T) {
@@ -246,7 +258,8 @@ __global__ void __launch_bounds__(kValidFwdT) fwd_valid(KP g, VP v, const void* 
 // grid = (bands, B, channel blocks).  Dynamic LDS (floats): wt[N * npix], dg[npix], then the slab xs[round4(Cc) * S].
 // A channel's gradient depends on the slots and on that channel of x alone: every channel block repeats phase A and the
 // blocks' results are those of one workgroup walking all channels, bit for bit.
-// FAM: 0 distances, 1 products in the gather form above (dot, gfc), 2 cosine in the PROJECTED form
+// FAM: 0 distances, 1 products in the gather form above (dot, gfc), 3 the L1 family (slots of -+ grad_out alone, signs of
+// the differences in phase B; `outm` and `saved` are never read), 2 cosine in the PROJECTED form
 //   grad_x[c][r] = (1 / m_r) sum_j G[j][r] (xn[c][r + d_j] - s[j][r] rho_r xn[c][r])      xn = x / m, m = max(|x|, eps)
 // G the pair's grad_out (both orientations added), s its cosine, rho_r = m_r / |x_r| (0 at |x_r| = 0).  The gather form
 // takes the cosine's gradient as the difference of two sums of size |grad_out| / |x_r|; where pixel and neighbour are
@@ -264,7 +277,7 @@ __global__ void __launch_bounds__(kValidBwdT) bwd_valid(KP g, VP v, const void* 
   const int b = blockIdx.y, r0 = blockIdx.x * v.rb;   // first input row of the band
   const int rb = min(v.rb, H - r0), npix = rb * W;
   const int y0 = max(r0 - R, 0), y1 = min(r0 + rb + R, H), rows = y1 - y0;
-  constexpr int PROD = FAM != 0 ? 1 : 0;
+  constexpr int PROD = (FAM == 1 || FAM == 2) ? 1 : 0;
   constexpr int NW = FAM == 2 ? 2 * N : N;   // slots per pixel: cosine keeps the pair's cosine beside its weight
   float* wt = vlds;
   float* sv = wt + N * v.npix;               // (FAM == 2 only)
@@ -303,6 +316,9 @@ __global__ void __launch_bounds__(kValidBwdT) bwd_valid(KP g, VP v, const void* 
         }
         w = g.similarity ? gsum : -gsum;
         sv[j * v.npix + r] = g.similarity ? sj : 1.f - sj;
+      } else if (FAM == 3) {
+        if (in_r) w += dist_sign(g, ldv<BF>(go, mbase + (long long)j * g.O + o_r));
+        if (in_t) w += dist_sign(g, ldv<BF>(go, mbase + (long long)(N - 1 - j) * g.O + (y2 - R) * g.Wo + (x2 - R)));
       } else if (in_r || in_t) {   // (then (y2, x2) is a pixel of the image)
         const float n_t = stats ? nrm[y2 * W + x2] : 0.f;
         if (in_r) {
@@ -383,7 +399,8 @@ __global__ void __launch_bounds__(kValidBwdT) bwd_valid(KP g, VP v, const void* 
           s *= ir;
         } else {
 #pragma unroll
-          for (int j = 0; j < N; ++j) s = PROD ? fmaf(wr[j], xc[off[j]], s) : fmaf(wr[j], a - xc[off[j]], s);
+          for (int j = 0; j < N; ++j)
+            s = PROD ? fmaf(wr[j], xc[off[j]], s) : fmaf(wr[j], FAM == 3 ? sgn3(a - xc[off[j]]) : a - xc[off[j]], s);
         }
         a4[k] = s;
       }
@@ -442,9 +459,8 @@ int valid_even_chunk(int C, int cap, int mult) {
 
 }  // namespace
 
-const char* valid_refusal(const KP& g) {
-  if (!hot_measure(g)) return "cosine / dot / gfc / L2 (norm p=2) / rmse only";
-  if (!hot_product(g) && !g.diff) return "a distance on the pure-neighbour weights";
+// geometry and layout: what both sets of entry points ask beside their measures
+static const char* valid_shape_refusal(const KP& g) {
   if (g.rs == 12) return "one radius per call (inner_R = 0)";
   if (mixed_maps(g)) return "maps in the storage type (map_f32 = 0)";
   if (g.pad != 0 || g.stride != 1 || g.dil != 1 || (g.R != 1 && g.R != 2)) return "stride 1, dilation 1, padding 0, R = 1 or 2";
@@ -453,6 +469,18 @@ const char* valid_refusal(const KP& g) {
   if (!valid_nchw(g) && g.C % valid_ve(g) != 0) return "channels-last maps with C % 4 (float32) / C % 8 (bf16) != 0";
   if (!valid_nchw(g) && (g.sB % valid_ve(g) != 0 || g.gB % valid_ve(g) != 0)) return "channels-last images off 16-byte boundaries";
   return nullptr;
+}
+
+const char* valid_refusal(const KP& g) {
+  if (!hot_measure(g)) return "cosine / dot / gfc / L2 (norm p=2) / rmse only";
+  if (!hot_product(g) && !g.diff) return "a distance on the pure-neighbour weights";
+  return valid_shape_refusal(g);
+}
+
+const char* valid_abs_refusal(const KP& g) {
+  if (!hot_l1(g)) return "Norm p=1 / EMD only";
+  if (!g.diff) return "a distance on the pure-neighbour weights";
+  return valid_shape_refusal(g);
 }
 
 template <int R, int PROD>
@@ -473,7 +501,7 @@ static int valid_forward_rp(const KP& g, const void* x, void* out, float* saved,
   v.Cc = valid_even_chunk(g.C, kValidLdsFloats / v.S, 8);
   v.vec = (!nhwc && g.W % ve == 0 && g.sB % ve == 0 && aligned16(x)) ? 1 : 0;
   const size_t lds = sizeof(float) * (size_t)std::max(v.Cc * v.S, v.G * (NH + 1) * v.npix);
-  snprintf(g_variant, sizeof(g_variant), "fwd_valid<%d,%s,%s,%s>", R, PROD ? "prod" : "dist", bf ? "bf16" : "f32",
+  snprintf(g_variant, sizeof(g_variant), "fwd_valid<%d,%s,%s,%s>", R, PROD == 2 ? "l1" : (PROD ? "prod" : "dist"), bf ? "bf16" : "f32",
            nhwc ? "nhwc" : "nchw");
   const dim3 grid((unsigned)bands, (unsigned)g.B), block(T);
   return with_storage(g, [&](auto bf_, auto nhwc_) {   // (valid_nchw is g.contig: make_kp)
@@ -497,7 +525,7 @@ static int valid_backward_rp(const KP& g, const void* x, const void* go, const v
   v.npix = v.rb * g.W;
   const int rows = std::min(g.H, v.rb + 2 * R);
   v.S = (rows * g.W) | 1;
-  constexpr int PROD = FAM != 0 ? 1 : 0;
+  constexpr int PROD = (FAM == 1 || FAM == 2) ? 1 : 0;
   const int head = (((FAM == 2 ? 2 * N : N) + 1) * v.npix + 3) & ~3;   // wt (cosine: and the pairs' cosines) and dg in front of the slab
   // channel blocks along grid.z where bands and batch leave CUs idle: at least 32 channels each
   const int nz0 = std::max(1, std::min(ceil_div(512, bands * g.B), g.C / 32));
@@ -508,7 +536,7 @@ static int valid_backward_rp(const KP& g, const void* x, const void* go, const v
   const int T = std::min(kValidBwdT, (v.G * v.npix + 63) & ~63);
   v.vec = (!nhwc && g.W % ve == 0 && g.sB % ve == 0 && aligned16(x)) ? 1 : 0;
   const size_t lds = sizeof(float) * (size_t)(head + round4(v.Cc) * v.S);
-  snprintf(g_variant, sizeof(g_variant), "bwd_valid<%d,%s,%s,%s>", R, PROD ? "prod" : "dist", bf ? "bf16" : "f32",
+  snprintf(g_variant, sizeof(g_variant), "bwd_valid<%d,%s,%s,%s>", R, FAM == 3 ? "l1" : (PROD ? "prod" : "dist"), bf ? "bf16" : "f32",
            nhwc ? "nhwc" : "nchw");
   const dim3 grid((unsigned)bands, (unsigned)g.B, (unsigned)nz), block(T);
   return with_storage(g, [&](auto bf_, auto nhwc_) {
@@ -537,6 +565,17 @@ int valid_backward(const KP& g, const void* x, const void* go, const void* out, 
         return valid_backward_rp<R, 0>(g, x, go, out, saved, gx, st);
     });
   });
+}
+
+// the L1 family: no `out`, no `saved` (null to the kernels, which never read them)
+int valid_abs_forward(const KP& g, const void* x, void* out, hipStream_t st) {
+  if (const char* why = valid_abs_refusal(g)) return fail(NFP_E_UNSUPPORTED, "valid L1 maps: %s", why);
+  return with_radius(g, [&](auto r) { return valid_forward_rp<decltype(r)::value, 2>(g, x, out, nullptr, st); });
+}
+
+int valid_abs_backward(const KP& g, const void* x, const void* go, void* gx, hipStream_t st) {
+  if (const char* why = valid_abs_refusal(g)) return fail(NFP_E_UNSUPPORTED, "valid L1 maps: %s", why);
+  return with_radius(g, [&](auto r) { return valid_backward_rp<decltype(r)::value, 3>(g, x, go, nullptr, nullptr, gx, st); });
 }
 
 }  // namespace nfp_host

@@ -978,19 +978,22 @@ def _valid_plan(x, layout, cfg):
     return plan
 
 
-def _valid_layout(x, cfg):
+def _valid_layout(x, cfg, family="valid"):
     """The layout in which fwd_valid / bwd_valid read this call in place, or None where `nfp` serves it: NFP_VALID_OFF=1
     (read at call time), torch.compile, a CPU tensor, another dtype, images that are not dense, or a descriptor
-    nfp_valid_supported refuses (another measure, rows above 128 pixels, channels-last maps off the alignment rule)."""
+    nfp_valid_supported refuses (another measure, rows above 128 pixels, channels-last maps off the alignment rule).
+    family="valid_abs": the same question to nfp_valid_abs_supported (Norm p=1 on the difference weights, EMD), whose plan
+    has a cache key of its own."""
     if (torch.compiler.is_compiling() or not (x.is_cuda and x.dtype in _DTYPES) or cfg.inner_R or cfg.map_f32
             or os.environ.get("NFP_VALID_OFF") == "1"):
         return None
-    if not hasattr(_abi.load(), "nfp_valid_forward"):      # (an older library loaded for an A/B run)
+    if not hasattr(_abi.load(), f"nfp_{family}_forward"):  # (an older library loaded for an A/B run)
         return None
     layout = _in_place_layout(x.shape, x.stride(), x.element_size(), x.data_ptr())
-    if layout is None or not _valid_plan(x, layout, cfg).ask("nfp_valid_supported"):
+    if layout is None:
         return None
-    return layout
+    plan = _valid_plan(x, layout, cfg) if family == "valid" else _valid_abs_plan(x, layout, cfg)
+    return layout if plan.ask(f"nfp_{family}_supported") else None
 
 
 def valid_forward_call(x, layout, cfg, need_grad):
@@ -1036,13 +1039,73 @@ class _NfpValidHip(torch.autograd.Function):
         return valid_backward_call(x, ctx.plan, out, saved, grad_out), None, None, None
 
 
+def _valid_abs_plan(x, layout, cfg):
+    """The _Plan of a call on the valid-map kernels' L1 family (nfp_valid_abs_*): the descriptor of `_valid_plan`, cached
+    under a key of its own."""
+    key = ("valid_abs", tuple(x.shape), x.stride(0), layout, x.dtype, cfg, x.device.index)
+    plan = _plans_get(key)
+    if plan is None:
+        plan = _Plan(make_desc(x, cfg, layout), layout)
+        _plans_put(key, plan)
+    return plan
+
+
+def valid_abs_forward_call(x, layout, cfg):
+    """(out, plan) from nfp_valid_abs_forward on a call `_valid_layout(..., "valid_abs")` accepted: nothing is saved."""
+    L = _abi.load()
+    plan = _valid_abs_plan(x, layout, cfg)
+    with _on_device(x.device):
+        out = torch.empty(plan.oshape, dtype=x.dtype, device=x.device)
+        _abi.check(L.nfp_valid_abs_forward(ctypes.byref(plan.desc), x.data_ptr(), out.data_ptr(), _raw_stream(x.device)))
+    return out, plan
+
+
+def valid_abs_backward_call(x, plan, grad_out):
+    """grad_x from nfp_valid_abs_backward — of x and grad_out alone: dense, in x's inner layout."""
+    L = _abi.load()
+    go = _grad_out_as(grad_out, x.dtype)
+    with _on_device(x.device):
+        gx = _empty_grad_x(x, plan.nhwc)
+        _abi.check(L.nfp_valid_abs_backward(ctypes.byref(plan.desc), x.data_ptr(), go.data_ptr(), gx.data_ptr(),
+                                            _raw_stream(x.device)))
+    return gx
+
+
+class _NfpValidAbsHip(torch.autograd.Function):
+    """The maps of an unpadded L1 layer: one fwd_valid<..l1..> launch, one bwd_valid<..l1..> launch.  Saves x alone — the
+    pair coefficient of a sum of |a - b| is -+ grad_out — so the maps it returns may be modified in place."""
+
+    @staticmethod
+    def forward(ctx, x, layout, cfg, need_grad):
+        out, ctx.plan = valid_abs_forward_call(x, layout, cfg)
+        if need_grad:
+            ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        return valid_abs_backward_call(x, ctx.plan, grad_out), None, None, None
+
+
+def _measure_is_abs(cfg):
+    """Norm p=1 on the difference weights, or EMD: what nfp_valid_abs_* serves and nfp_valid_* refuses by its measure."""
+    return cfg.measure == "emd" or (cfg.measure == "norm" and cfg.p == 1 and cfg.diff_weights)
+
+
 def nfp_valid(x, cfg):
     """`nfp(x, cfg)` for an unpadded layer — cfg.padding == 0, stride 1, dilation 1 (ValueError otherwise): [B,C,H,W] ->
     [B, k*k-1, H-2R, W-2R], as models/nfp_heads.py::NFPBottleneck runs it inside every block.  A CUDA call that
     nfp_valid_supported accepts (cosine / dot / gfc / Norm p=2 / rmse, float32 or bfloat16, rows of at most 128 pixels,
-    NCHW or aligned channels-last images) runs the valid-map kernels, one launch each way; everything else — CPU tensors,
-    other measures, refused shapes, torch.compile, NFP_VALID_OFF=1 in the environment (read at call time) — is `nfp(x, cfg)`
-    unchanged.  Under torch.autocast, and for float16 / float64, the float32 upcast of `_amp_input`, as the fused callers."""
+    NCHW or aligned channels-last images) runs the valid-map kernels, one launch each way.  So does one that
+    nfp_valid_abs_supported accepts: Norm p=1 on the difference weights — the reference's default layer, NFPInsert's — and
+    EMD, under the same shape rules (fwd_valid<..l1..> / bwd_valid<..l1..>).  Everything else — CPU tensors, other
+    measures, refused shapes, torch.compile, NFP_VALID_OFF=1 in the environment (read at call time) — is `nfp(x, cfg)`
+    unchanged.  Under torch.autocast, and for float16 / float64, the float32 upcast of `_amp_input`, as the fused callers.
+
+    The L1 node saves x ALONE (its backward reads neither the maps nor a statistic): the returned maps may be modified in
+    place before the backward.  The maps of the other measures are saved for the backward and must not be."""
     if cfg.padding != 0 or cfg.stride != 1 or cfg.dilation != 1:
         raise ValueError(f"nfp_valid: padding 0, stride 1, dilation 1 only (got padding={cfg.padding}, "
                          f"stride={cfg.stride}, dilation={cfg.dilation}); use nfp")
@@ -1054,6 +1117,15 @@ def nfp_valid(x, cfg):
             out = nfp_valid(xin, cfg)
         return out if cast is None else out.to(cast)
     layout = _valid_layout(x, cfg)
+    if layout is None and _measure_is_abs(cfg):
+        layout = _valid_layout(x, cfg, "valid_abs")
+        if layout is not None:
+            need_grad = bool(x.requires_grad and torch.is_grad_enabled())
+            apply = getattr(_cpp_nodes() or None, "nfp_valid_abs_apply", None)
+            if apply is not None and x.shape[0] > 0:
+                plan = _valid_abs_plan(x, layout, cfg)
+                return _cpp_call(apply, x, plan.desc_tensor, list(plan.oshape), plan.nhwc, need_grad)
+            return _NfpValidAbsHip.apply(x, layout, cfg, need_grad)
     if layout is None:
         return nfp(x, cfg)
     need_grad = bool(x.requires_grad and torch.is_grad_enabled())

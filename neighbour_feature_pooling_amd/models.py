@@ -298,19 +298,21 @@ class NFPInsertNet(nn.Module):
     112 / 160 / 960 channels — an NFPInsert (NFPPooling(**nfp_kwargs), then a 1x1 conv + BN + ReLU back to the stage's
     channel count) replaces the feature map; the rest of the trunk follows, then the 960 -> 1280 head conv + Hardswish, GAP
     and fc.  With the class defaults (padding 0) the map shrinks by 2R at the insert.  memory_format (keyword only) is the
-    insert's: the layout its projected map is written in (NFPInsert)."""
+    insert's: the layout its projected map is written in (NFPInsert); so is valid_layer (default False): the insert's
+    unpadded layer on the valid-map kernels."""
     BLOCK_ENDS = (3, 5, 8, 12, 14, 17, 20)            # indices into backbone.features
     BLOCK_CHANNELS = (16, 24, 40, 80, 112, 160, 960)
 
     def __init__(self, num_classes=10, num_input_channels=3, nfp_insert_idx=1, nfp_kwargs=None, head_width=1280, *,
-                 memory_format=torch.contiguous_format):
+                 memory_format=torch.contiguous_format, valid_layer=False):
         super().__init__()
         from .nfp import NFPInsert
         if isinstance(nfp_insert_idx, bool) or not isinstance(nfp_insert_idx, int) or not 0 <= nfp_insert_idx <= 6:
             raise ValueError(f"nfp_insert_idx must be between 0 and 6 (inclusive), got {nfp_insert_idx!r}")
         self.nfp_insert_idx = nfp_insert_idx
         self.backbone = MobileNetV3LargeFeatures(in_chans=num_input_channels)
-        self.insert = NFPInsert(self.BLOCK_CHANNELS[nfp_insert_idx], memory_format=memory_format, **(nfp_kwargs or {}))
+        self.insert = NFPInsert(self.BLOCK_CHANNELS[nfp_insert_idx], memory_format=memory_format, valid_layer=valid_layer,
+                                **(nfp_kwargs or {}))
         self.conv_head = nn.Sequential(nn.Conv2d(960, head_width, 1), nn.Hardswish(inplace=True))   # timm: conv_head + act2
         self.fc = nn.Linear(head_width, num_classes)
 

@@ -343,14 +343,20 @@ class NFPInsert(nn.Module):
     functional.nfp_compress_map behind the layer: on the GPU, where it serves, the projected map is stored once and nothing
     of its size is saved for the backward.
     memory_format (keyword only): the layout of the result — torch.contiguous_format, torch.channels_last, or
-    torch.preserve_format: channels-last exactly when x is (dense in it and not also NCHW-dense)."""
+    torch.preserve_format: channels-last exactly when x is (dense in it and not also NCHW-dense).
+    valid_layer (keyword only, default False: `self.nfp(x)` as before): an unbiased layer with padding 0, stride 1 and
+    dilation 1 — the class defaults — runs as functional.nfp_valid(x, self.nfp.config): on the GPU the valid-map kernels, one
+    launch each way (for the default Norm p = 1 their L1 family, which saves x alone), where they serve; every other layer
+    keeps `self.nfp(x)`.  Parameters, state dict, RNG order and CPU results do not depend on it."""
 
-    def __init__(self, in_channels, out_channels=None, *, memory_format=torch.contiguous_format, **nfp_kwargs):
+    def __init__(self, in_channels, out_channels=None, *, memory_format=torch.contiguous_format, valid_layer=False,
+                 **nfp_kwargs):
         super().__init__()
         if memory_format not in _MODULE_FORMATS:
             raise ValueError(f"NFPInsert: memory_format must be torch.contiguous_format, torch.channels_last or "
                              f"torch.preserve_format, got {memory_format!r}")
         self.memory_format = memory_format
+        self.valid_layer = bool(valid_layer)
         from .heads import _reference_layer_draws
         out_channels = int(in_channels if out_channels is None else out_channels)
         self.nfp = NFPPooling(in_channels=in_channels, **nfp_kwargs)
@@ -360,6 +366,13 @@ class NFPInsert(nn.Module):
                                       nn.BatchNorm2d(out_channels), nn.ReLU(inplace=True))
         self.in_channels, self.out_channels = int(in_channels), out_channels
 
+    def _layer(self, x):
+        cfg = self.nfp.config
+        if (self.valid_layer and not self.nfp.bias and cfg.padding == 0 and cfg.stride == 1 and cfg.dilation == 1
+                and x.dim() == 4 and x.shape[1] == self.nfp.in_channels):
+            return nfp_valid(x, cfg)
+        return self.nfp(x)      # (and the layer's own complaint about any other input)
+
     def forward(self, x):
-        return nfp_compress_map(self.nfp(x), self.nfp_proj[0].weight, self.nfp_proj[1],
+        return nfp_compress_map(self._layer(x), self.nfp_proj[0].weight, self.nfp_proj[1],
                                 memory_format=_module_memory_format(self.memory_format, x))

@@ -8,6 +8,10 @@ One JSON line per (shape, mode): per arm the three times in us per fwd+bwd step,
 spread (max - min) of the `off` arm's three runs.  Then one NFPBottleneck(64, 256) train step at [64,64,56,56], both arms.
 
     python scripts/bench_valid.py [--out FILE] [--trace]      (--trace: a few steps per arm and shape, for a kernel trace)
+
+--l1: the same for the L1 layer — NFPPooling's class defaults, Norm p = 1, which nfp_valid serves on fwd_valid<..l1..> /
+bwd_valid<..l1..> — at the maps NFPInsertNet hands its insert, arms `valid` and `off` (NFP_VALID_OFF=1: fwd_pairs /
+bwd_gather), then one NFPInsertNet train step at [64,3,224,224] with nfp_insert_idx 0 and 1, valid_layer on and off.
 """
 import argparse
 import dataclasses
@@ -25,6 +29,11 @@ SHAPES = [((256, 16, 56, 56), torch.float32, False), ((256, 32, 28, 28), torch.f
           ((256, 64, 14, 14), torch.float32, False), ((256, 128, 7, 7), torch.float32, False),
           ((256, 64, 14, 14), torch.bfloat16, True), ((64, 512, 7, 7), torch.float32, False)]
 ARMS = ("valid", "off", "crop")
+L1_SHAPES = [((64, 16, 112, 112), torch.float32, False), ((64, 24, 56, 56), torch.float32, False),
+             ((64, 40, 28, 28), torch.float32, False), ((64, 80, 14, 14), torch.float32, False),
+             ((64, 960, 7, 7), torch.float32, False), ((256, 16, 56, 56), torch.float32, False),
+             ((64, 24, 56, 56), torch.bfloat16, True)]
+L1_ARMS = ("valid", "off")
 GRAPH_STEPS = 20
 
 
@@ -63,9 +72,9 @@ def time_us(fn, iters):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def bench_shape(shape, dtype, nhwc, trace):
+def bench_shape(shape, dtype, nhwc, trace, measure="cosine", ARMS=ARMS):
     dev = torch.device("cuda:0")
-    cfg = NFPPooling(shape[1], R=1, measure="cosine", padding=0).config
+    cfg = NFPPooling(shape[1], R=1, measure=measure, padding=0).config
     x = torch.randn(shape, device=dev).to(dtype)
     if nhwc:
         x = x.contiguous(memory_format=torch.channels_last)
@@ -110,8 +119,10 @@ def bench_shape(shape, dtype, nhwc, trace):
         recs.append(dict(shape=list(shape), dtype=str(dtype).split(".")[1], layout="nhwc" if nhwc else "nchw", mode=mode,
                          us={a: [round(v, 2) for v in t] for a, t in times.items()},
                          median_us={a: round(v, 2) for a, v in med.items()}, margin_us=round(margin, 2),
-                         beats_off=bool(med["off"] - med["valid"] > margin), beats_crop=bool(med["crop"] > med["valid"]),
-                         bwd_variant=variants))
+                         beats_off=bool(med["off"] - med["valid"] > margin),
+                         beats_crop=bool(med["crop"] > med["valid"]) if "crop" in med else None, bwd_variant=variants))
+        if measure != "cosine":
+            recs[-1]["measure"] = measure
     return recs
 
 
@@ -144,20 +155,64 @@ def bench_block(trace):
                  margin_us=round(max(times["off"]) - min(times["off"]), 1))]
 
 
+def bench_insert_net(idx, trace):
+    """One NFPInsertNet train step at [64,3,224,224] (the class-default L1 insert behind block `idx`): valid_layer on / off."""
+    from neighbour_feature_pooling_amd.models import NFPInsertNet
+    dev = torch.device("cuda:0")
+    x = torch.randn(64, 3, 224, 224, device=dev)
+    y = torch.randint(0, 10, (64,), device=dev)
+    steps = {}
+    for arm, on in (("valid", True), ("off", False)):
+        torch.manual_seed(0)
+        m = NFPInsertNet(num_classes=10, nfp_insert_idx=idx, valid_layer=on).to(dev)
+        opt = torch.optim.SGD(m.parameters(), lr=0.01)
+
+        def step(m=m, opt=opt):
+            opt.zero_grad(set_to_none=True)
+            torch.nn.functional.cross_entropy(m(x), y).backward()
+            opt.step()
+        steps[arm] = step
+        for _ in range(3):
+            step()
+    torch.cuda.synchronize()
+    if trace:
+        return []
+    times = {a: [] for a in steps}
+    for _ in range(3):
+        for arm in steps:
+            times[arm].append(time_us(steps[arm], 5))
+    med = {a: statistics.median(t) for a, t in times.items()}
+    margin = max(times["off"]) - min(times["off"])
+    return [dict(block=f"NFPInsertNet(nfp_insert_idx={idx}) train step [64,3,224,224] f32", mode="eager",
+                 us={a: [round(v, 1) for v in t] for a, t in times.items()},
+                 median_us={a: round(v, 1) for a, v in med.items()}, margin_us=round(margin, 1),
+                 beats_off=bool(med["off"] - med["valid"] > margin))]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--l1", action="store_true", help="the L1 layer (Norm p = 1) and the NFPInsertNet step instead")
     args = ap.parse_args()
     recs = []
-    for shape, dtype, nhwc in SHAPES:
-        recs += bench_shape(shape, dtype, nhwc, args.trace)
-    recs += bench_block(args.trace)
-    text = "\n".join(json.dumps(r) for r in recs)
-    print(text)
+
+    def emit(new):      # (a line as soon as it is measured)
+        for r in new:
+            print(json.dumps(r), flush=True)
+        recs.extend(new)
+    if args.l1:
+        for shape, dtype, nhwc in L1_SHAPES:
+            emit(bench_shape(shape, dtype, nhwc, args.trace, measure="norm", ARMS=L1_ARMS))
+        for idx in (0, 1):
+            emit(bench_insert_net(idx, args.trace))
+    else:
+        for shape, dtype, nhwc in SHAPES:
+            emit(bench_shape(shape, dtype, nhwc, args.trace))
+        emit(bench_block(args.trace))
     if args.out:
         with open(args.out, "w") as f:
-            f.write(text + "\n")
+            f.write("\n".join(json.dumps(r) for r in recs) + "\n")
 
 
 if __name__ == "__main__":
