@@ -65,7 +65,9 @@ def _pool_saved_bound(shape, dtype, cfg):
 @torch.library.custom_op("nfp_amd::nfp", mutates_args=(), device_types="cuda", schema=f"(Tensor x, {_CFG_SCHEMA}, bool need_grad) -> (Tensor, Tensor)")
 def nfp_op(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R, need_grad):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    return F.nfp_forward_call(x, cfg, need_grad, _saved_floats(tuple(x.shape), x.dtype, cfg, need_grad))[:2]
+    xd, plan = F._planned(x, cfg)
+    bound = _saved_floats(tuple(x.shape), x.dtype, cfg, need_grad)   # (what the fake implementation states)
+    return F.maps_forward_call(F.NFP, xd, plan, F._scratch_len(F.maps_saved_len(F.NFP, plan, cfg, x.dtype, need_grad), bound))
 
 
 @nfp_op.register_fake
@@ -82,7 +84,7 @@ def _(x, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps
 def nfp_backward_op(x, out, saved, grad_out, R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs,
                     diff_weights, inner_R):
     cfg = _cfg(R, measure, p, stride, padding, dilation, padding_mode, similarity, eps, q_scs, diff_weights, inner_R)
-    return F.nfp_backward_call(*F._planned(x, cfg), out, saved, grad_out)
+    return F.maps_backward_call(F.NFP, *F._planned(x, cfg), out, saved, grad_out)
 
 
 @nfp_backward_op.register_fake

@@ -40,28 +40,70 @@ const nfp_desc* desc_of(const Tensor& desc) {
   return (const nfp_desc*)desc.data_ptr();
 }
 
-struct NfpNode : torch::autograd::Function<NfpNode> {
-  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+// what the nodes share: float32 options like x; grad_out contiguous in the wanted type; NULL for a `saved` without an element
+at::TensorOptions f32_like(const Tensor& x) {
+  return x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous);
+}
+
+Tensor grad_as(const Tensor& g, at::ScalarType type) {
+  Tensor c = g.contiguous();
+  return c.scalar_type() == type ? c : c.to(type);
+}
+
+float* saved_ptr(const Tensor& saved) { return saved.defined() && saved.numel() ? saved.data_ptr<float>() : nullptr; }
+
+// The three "x -> maps" families (functional.py: NFP, VALID, VALID_ABS): their entry points behind one argument list, and
+// whether the backward reads the maps and `saved` at all.
+struct NfpCalls {       // nfp_forward / nfp_backward: `saved` goes without its length
+  static constexpr bool reads_maps = true;
+  static int fwd(const nfp_desc* d, const void* x, void* out, float* saved, int64_t, void* s) {
+    return nfp_forward(d, x, out, saved, s);
+  }
+  static int bwd(const nfp_desc* d, const void* x, const void* go, const void* out, const float* saved, int64_t, void* gx, void* s) {
+    return nfp_backward(d, x, go, out, saved, gx, s);
+  }
+};
+struct ValidCalls {     // an unpadded layer on the valid-map kernels: `saved` with its length; ns = 0: no backward will follow
+  static constexpr bool reads_maps = true;
+  static int fwd(const nfp_desc* d, const void* x, void* out, float* saved, int64_t ns, void* s) {
+    return nfp_valid_forward(d, x, out, saved, ns, s);
+  }
+  static int bwd(const nfp_desc* d, const void* x, const void* go, const void* out, const float* saved, int64_t ns, void* gx, void* s) {
+    return nfp_valid_backward(d, x, go, out, saved, ns, gx, s);
+  }
+};
+struct ValidAbsCalls {  // ... and their L1 family (Norm p = 1 on the difference weights, EMD): the backward reads x and grad_out
+  static constexpr bool reads_maps = false;   // alone, so x is all the node saves and the maps may be modified in place
+  static int fwd(const nfp_desc* d, const void* x, void* out, float*, int64_t, void* s) { return nfp_valid_abs_forward(d, x, out, s); }
+  static int bwd(const nfp_desc* d, const void* x, const void* go, const void*, const float*, int64_t, void* gx, void* s) {
+    return nfp_valid_abs_backward(d, x, go, gx, s);
+  }
+};
+
+template <class F>
+struct MapsNode : torch::autograd::Function<MapsNode<F>> {
+  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc,
+                        bool need_grad) {
     c10::DeviceGuard guard(x.device());
     const nfp_desc* d = desc_of(desc);
     // (d->map_f32: bf16 x with float32 maps — the torch.autocast call, include/nfp.h)
-    Tensor out = torch::empty(oshape, (d->map_f32 ? x.options().dtype(torch::kFloat32) : x.options()).memory_format(at::MemoryFormat::Contiguous));
-    Tensor saved = torch::empty({ns}, x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous));
-    check(nfp_forward(d, x.data_ptr(), out.data_ptr(), ns > 0 ? saved.data_ptr<float>() : nullptr, stream_of(x)));
-    ctx->save_for_backward({x, out, saved, desc});
+    Tensor out = torch::empty(oshape, d->map_f32 ? f32_like(x) : x.options().memory_format(at::MemoryFormat::Contiguous));
+    Tensor saved = F::reads_maps ? torch::empty({ns}, f32_like(x)) : Tensor();
+    check(F::fwd(d, x.data_ptr(), out.data_ptr(), saved_ptr(saved), ns, stream_of(x)));
+    if (need_grad) ctx->save_for_backward(F::reads_maps ? variable_list{x, desc, out, saved} : variable_list{x, desc});
     ctx->saved_data["nhwc"] = nhwc;
     return out;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     const auto sv = ctx->get_saved_variables();
-    const Tensor &x = sv[0], &out = sv[1], &saved = sv[2], &desc = sv[3];
+    const Tensor &x = sv[0], &desc = sv[1];
+    const Tensor out = F::reads_maps ? sv[2] : Tensor(), saved = F::reads_maps ? sv[3] : Tensor();
     c10::DeviceGuard guard(x.device());
-    Tensor go = grads[0].contiguous();
-    if (go.scalar_type() != out.scalar_type()) go = go.to(out.scalar_type());   // (grad_out in the maps' type: x's, or float32)
+    Tensor go = grad_as(grads[0], F::reads_maps ? out.scalar_type() : x.scalar_type());   // (the maps' type: x's, or float32)
     Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
-    check(nfp_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
-                       saved.numel() ? saved.data_ptr<float>() : nullptr, gx.data_ptr(), stream_of(x)));
-    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
+    check(F::bwd(desc_of(desc), x.data_ptr(), go.data_ptr(), F::reads_maps ? out.data_ptr() : nullptr, saved_ptr(saved),
+                 saved.defined() ? saved.numel() : 0, gx.data_ptr(), stream_of(x)));
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
 
@@ -71,14 +113,13 @@ struct NfpPoolNode : torch::autograd::Function<NfpPoolNode> {
   static variable_list forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns,
                                bool nhwc, bool want_gap, bool need_grad) {
     c10::DeviceGuard guard(x.device());
-    const nfp_desc* d = desc_of(desc);
-    const auto f32 = x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous);
+    const auto f32 = f32_like(x);
     Tensor gap = torch::empty({want_gap ? oshape[0] : 0, x.size(1)}, f32), nfpm = torch::empty({oshape[0], oshape[1]}, f32);
     Tensor omap = need_grad ? torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous))
                             : torch::empty({0}, x.options());
     Tensor saved = torch::empty({ns}, f32);
-    check(nfp_pool_forward(d, x.data_ptr(), want_gap ? gap.data_ptr<float>() : nullptr, nfpm.data_ptr<float>(),
-                           need_grad ? omap.data_ptr() : nullptr, ns > 0 ? saved.data_ptr<float>() : nullptr, stream_of(x)));
+    check(nfp_pool_forward(desc_of(desc), x.data_ptr(), want_gap ? gap.data_ptr<float>() : nullptr, nfpm.data_ptr<float>(),
+                           need_grad ? omap.data_ptr() : nullptr, saved_ptr(saved), stream_of(x)));
     ctx->save_for_backward({x, omap, saved, desc});
     ctx->saved_data["nhwc"] = nhwc;
     ctx->saved_data["want_gap"] = want_gap;
@@ -88,16 +129,14 @@ struct NfpPoolNode : torch::autograd::Function<NfpPoolNode> {
     const auto sv = ctx->get_saved_variables();
     const Tensor &x = sv[0], &omap = sv[1], &saved = sv[2], &desc = sv[3];
     c10::DeviceGuard guard(x.device());
-    const auto f32 = x.options().dtype(torch::kFloat32);
     // a pooled output that took no part in the loss arrives undefined: its gradient is zero
     // (grad_gap = NULL: GAP(x) was not produced, or took no part in the loss — no adjoint of the mean, include/nfp.h)
     const bool has_gap = ctx->saved_data["want_gap"].toBool() && grads[0].defined();
-    Tensor ggap = has_gap ? grads[0].contiguous().to(torch::kFloat32) : Tensor();
-    Tensor gnfp = grads[1].defined() ? grads[1].contiguous().to(torch::kFloat32)
-                                     : torch::zeros({omap.size(0), omap.size(1)}, f32);
+    Tensor ggap = has_gap ? grad_as(grads[0], torch::kFloat32) : Tensor();
+    Tensor gnfp = grads[1].defined() ? grad_as(grads[1], torch::kFloat32) : torch::zeros({omap.size(0), omap.size(1)}, f32_like(x));
     Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
     check(nfp_pool_backward(desc_of(desc), x.data_ptr(), has_gap ? ggap.data_ptr<float>() : nullptr, gnfp.data_ptr<float>(),
-                            omap.data_ptr(), saved.numel() ? saved.data_ptr<float>() : nullptr, gx.data_ptr(), stream_of(x)));
+                            omap.data_ptr(), saved_ptr(saved), gx.data_ptr(), stream_of(x)));
     return {gx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
@@ -108,13 +147,11 @@ struct NfpPoolNode : torch::autograd::Function<NfpPoolNode> {
 struct NfpGapNode : torch::autograd::Function<NfpGapNode> {
   static variable_list forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
     c10::DeviceGuard guard(x.device());
-    const nfp_desc* d = desc_of(desc);
-    const auto f32 = x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous);
-    Tensor gap = torch::empty({x.size(0), x.size(1)}, f32);
+    Tensor gap = torch::empty({x.size(0), x.size(1)}, f32_like(x));
     Tensor maps = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
-    Tensor saved = torch::empty({ns > 0 ? ns : 1}, f32);
-    check(nfp_gap_forward(d, x.data_ptr(), gap.data_ptr<float>(), maps.data_ptr(), saved.data_ptr<float>(), saved.numel(),
-                          stream_of(x)));
+    Tensor saved = torch::empty({ns > 0 ? ns : 1}, f32_like(x));
+    check(nfp_gap_forward(desc_of(desc), x.data_ptr(), gap.data_ptr<float>(), maps.data_ptr(), saved.data_ptr<float>(),
+                          saved.numel(), stream_of(x)));
     ctx->set_materialize_grads(false);
     ctx->save_for_backward({x, maps, saved, desc});
     ctx->saved_data["nhwc"] = nhwc;
@@ -126,9 +163,8 @@ struct NfpGapNode : torch::autograd::Function<NfpGapNode> {
     const Tensor &x = sv[0], &maps = sv[1], &saved = sv[2], &desc = sv[3];
     c10::DeviceGuard guard(x.device());
     const bool has_gap = grads[0].defined();
-    Tensor ggap = has_gap ? grads[0].contiguous().to(torch::kFloat32) : Tensor();
-    Tensor go = grads[1].defined() ? grads[1].contiguous() : torch::zeros_like(maps);
-    if (go.scalar_type() != x.scalar_type()) go = go.to(x.scalar_type());
+    Tensor ggap = has_gap ? grad_as(grads[0], torch::kFloat32) : Tensor();
+    Tensor go = grads[1].defined() ? grad_as(grads[1], x.scalar_type()) : torch::zeros_like(maps);
     Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
     check(nfp_gap_backward(desc_of(desc), x.data_ptr(), has_gap ? ggap.data_ptr<float>() : nullptr, go.data_ptr(),
                            maps.data_ptr(), saved.data_ptr<float>(), saved.numel(), gx.data_ptr(), stream_of(x)));
@@ -136,69 +172,19 @@ struct NfpGapNode : torch::autograd::Function<NfpGapNode> {
   }
 };
 
-// The maps of an unpadded layer on the valid-map kernels (nfp_valid_forward / nfp_valid_backward): NfpNode with the length
-// convention of those calls.  ns = 0: no backward will follow (nothing is saved, `saved` goes over as NULL).
-struct NfpValidNode : torch::autograd::Function<NfpValidNode> {
-  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
-    c10::DeviceGuard guard(x.device());
-    Tensor out = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
-    Tensor saved = torch::empty({ns}, x.options().dtype(torch::kFloat32).memory_format(at::MemoryFormat::Contiguous));
-    check(nfp_valid_forward(desc_of(desc), x.data_ptr(), out.data_ptr(), ns > 0 ? saved.data_ptr<float>() : nullptr, ns,
-                            stream_of(x)));
-    ctx->save_for_backward({x, out, saved, desc});
-    ctx->saved_data["nhwc"] = nhwc;
-    return out;
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto sv = ctx->get_saved_variables();
-    const Tensor &x = sv[0], &out = sv[1], &saved = sv[2], &desc = sv[3];
-    c10::DeviceGuard guard(x.device());
-    Tensor go = grads[0].contiguous();
-    if (go.scalar_type() != out.scalar_type()) go = go.to(out.scalar_type());
-    Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
-    check(nfp_valid_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), out.data_ptr(),
-                             saved.numel() ? saved.data_ptr<float>() : nullptr, saved.numel(), gx.data_ptr(), stream_of(x)));
-    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
-// ... and their L1 family (nfp_valid_abs_forward / nfp_valid_abs_backward: Norm p = 1 on the difference weights, EMD): the
-// backward reads x and grad_out alone, so x is all the node saves and the maps may be modified in place by the caller.
-struct NfpValidAbsNode : torch::autograd::Function<NfpValidAbsNode> {
-  static Tensor forward(AutogradContext* ctx, Tensor x, Tensor desc, std::vector<int64_t> oshape, bool nhwc, bool need_grad) {
-    c10::DeviceGuard guard(x.device());
-    Tensor out = torch::empty(oshape, x.options().memory_format(at::MemoryFormat::Contiguous));
-    check(nfp_valid_abs_forward(desc_of(desc), x.data_ptr(), out.data_ptr(), stream_of(x)));
-    if (need_grad) ctx->save_for_backward({x, desc});
-    ctx->saved_data["nhwc"] = nhwc;
-    return out;
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto sv = ctx->get_saved_variables();
-    const Tensor &x = sv[0], &desc = sv[1];
-    c10::DeviceGuard guard(x.device());
-    Tensor go = grads[0].contiguous();
-    if (go.scalar_type() != x.scalar_type()) go = go.to(x.scalar_type());
-    Tensor gx = empty_like_layout(x, ctx->saved_data["nhwc"].toBool());
-    check(nfp_valid_abs_backward(desc_of(desc), x.data_ptr(), go.data_ptr(), gx.data_ptr(), stream_of(x)));
-    return {gx, Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
 Tensor nfp_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
-  return NfpNode::apply(x, desc, oshape, ns, nhwc);
+  return MapsNode<NfpCalls>::apply(x, desc, oshape, ns, nhwc, true);
 }
 Tensor nfp_valid_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
-  return NfpValidNode::apply(x, desc, oshape, ns, nhwc);
+  return MapsNode<ValidCalls>::apply(x, desc, oshape, ns, nhwc, true);
 }
 Tensor nfp_valid_abs_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, bool nhwc, bool need_grad) {
-  return NfpValidAbsNode::apply(x, desc, oshape, nhwc, need_grad);
+  return MapsNode<ValidAbsCalls>::apply(x, desc, oshape, (int64_t)0, nhwc, need_grad);
 }
 std::vector<Tensor> nfp_pool_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc, bool want_gap,
                                    bool need_grad) {
   return NfpPoolNode::apply(x, desc, oshape, ns, nhwc, want_gap, need_grad);
 }
-
 std::vector<Tensor> nfp_gap_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return NfpGapNode::apply(x, desc, oshape, ns, nhwc);
 }

@@ -1,13 +1,30 @@
 #!/usr/bin/env python3
-"""Where does the eager host time of one NFP forward + backward go?  (cProfile over 3000 steps.)"""
-import cProfile, pstats, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+"""Where does the eager host time of one NFP forward + backward go?  (cProfile over 3000 steps.)
+
+--op     which call: nfp (the default: NFPPooling, cosine, padding 1), valid / valid_abs (functional.nfp_valid, padding 0:
+         cosine / Norm p = 1) or with_gap (functional.nfp_with_gap, cosine, padding 1) — all on a [64, 512, 7, 7] input
+--root   the tree whose package is imported (default: this script's own): the same script times another checkout
+NFP_PY_NODES=1 in the environment selects the Python autograd nodes."""
+import argparse, cProfile, pstats, os, sys, time
+ap = argparse.ArgumentParser()
+ap.add_argument("--op", choices=["nfp", "valid", "valid_abs", "with_gap"], default="nfp")
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
 import torch
-from neighbour_feature_pooling_amd import NFPPooling
-m = NFPPooling(512, R=1, measure="cosine", padding=1)
+from neighbour_feature_pooling_amd import NFPPooling, NfpConfig, nfp_valid, nfp_with_gap
 x = torch.randn(64, 512, 7, 7, device="cuda", requires_grad=True)
-go = torch.randn(64, 8, 7, 7, device="cuda")
+if args.op == "nfp":
+    m = NFPPooling(512, R=1, measure="cosine", padding=1)
+elif args.op == "with_gap":
+    cfg = NfpConfig(R=1, measure="cosine", padding=1, diff_weights=False)
+    m = lambda t: nfp_with_gap(t, cfg)[1]
+else:
+    cfg = NfpConfig(R=1, measure="cosine", padding=0, diff_weights=False) if args.op == "valid" else \
+        NfpConfig(R=1, measure="norm", p=1, padding=0, diff_weights=True)
+    m = lambda t: nfp_valid(t, cfg)
+with torch.no_grad():
+    go = torch.randn_like(m(x))
 
 
 def step():

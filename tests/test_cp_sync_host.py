@@ -1,5 +1,5 @@
 """SyncBatchNorm in the fused compress tails, on the host: the nfp_cpsync_* declarations, their length queries and their
-refusals (all before any HIP call), the group rule and the route predicate of functional.py, and a converted head without
+refusals (all before any HIP call), the group rule and the route predicate of compress.py, and a converted head without
 a process group.  No GPU needed."""
 import copy
 import os
@@ -11,6 +11,7 @@ import torch
 
 from conftest import ROOT
 from neighbour_feature_pooling_amd import NFPHead, _abi
+from neighbour_feature_pooling_amd import compress
 from neighbour_feature_pooling_amd import functional as Fn
 
 NEW_EXPORTS = {"nfp_cpsync_record_doubles", "nfp_cpsync_kq_floats", "nfp_cpsync_saved_floats", "nfp_cpsync_moments",
@@ -180,7 +181,7 @@ def test_the_route_does_not_depend_on_the_local_batch(monkeypatch):
     # the predicates of the rank-local path are as they were: the projection's still by pixel count, none under compile / autocast
     big, small, w = _dense((64, 8, 54, 54)), _dense((4, 8, 7, 7)), torch.zeros(16, 8, 1, 1)
     local = [lambda m: Fn.cpool_hip_serves(m, g, b, 0.1), lambda m: Fn.cproj_hip_serves(m, w, g, b, 0.1),
-             lambda m: Fn._cp_can_serve(m, g, b, 0.1)]
+             lambda m: compress._cp_can_serve(m, g, b, 0.1)]
     assert [f(big) for f in local] == [True] * 3 and [f(small) for f in local] == [True, False, True]
     monkeypatch.setenv("NFP_CPOOL_TORCH", "0")
     assert Fn.cpool_wide_serves(_dense((4, 48, 7, 7)), g, b, 0.1)

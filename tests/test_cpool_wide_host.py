@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import cases_heads_wide as KW
-from neighbour_feature_pooling_amd import _abi, functional
+from neighbour_feature_pooling_amd import _abi, compress, functional
 from test_heads_host import _Fake, fixture_errors, head_module, run_head
 
 INVALID, UNSUPPORTED = -1, -2
@@ -128,7 +128,7 @@ def test_the_entries_are_declared_exported_and_additive(lib):
     assert int(re.search(r"#define NFP_ABI_VERSION (\d+)", src).group(1)) == _abi.ABI_VERSION == 7
     for n in WIDE_EXPORTS:
         assert hasattr(lib, n), n
-    assert functional._CP_ENTRIES["wide"] == ("nfp_cpool_wide_forward", "nfp_cpool_wide_backward",
+    assert compress._CP_ENTRIES["wide"] == ("nfp_cpool_wide_forward", "nfp_cpool_wide_backward",
                                               "nfp_cpool_wide_scratch_floats")
 
 
@@ -161,7 +161,7 @@ def test_cpool_wide_serves(monkeypatch):
 
 
 def test_routing_under_the_switches(monkeypatch):
-    kind = functional._cpool_kind
+    kind = compress._cpool_kind
     g = torch.ones(4)
     f = lambda N: _Fake(shape=(4, N, 7, 7))      # noqa: E731
     monkeypatch.delenv("NFP_CPOOL_WIDE", raising=False)
@@ -183,7 +183,7 @@ def test_routing_under_the_switches(monkeypatch):
     # a routed class, were one measured: (min maps, max maps, min B * P)
     monkeypatch.delenv("NFP_CPOOL_TORCH")
     monkeypatch.delenv("NFP_CPOOL_WIDE")
-    monkeypatch.setattr(functional, "CPOOL_WIDE_ROUTED_CLASSES", ((33, 48, 4 * 49),))
+    monkeypatch.setattr(compress, "CPOOL_WIDE_ROUTED_CLASSES", ((33, 48, 4 * 49),))
     assert [kind(f(N), g, g, 0.1) for N in (32, 33, 48, 49)] == [None, "wide", "wide", None]
     assert kind(_Fake(shape=(3, 48, 7, 7)), g, g, 0.1) is None
 

@@ -200,7 +200,7 @@ def test_short_buffers_are_refused_before_any_launch(dev):
     L = _lib()
     cfg = NfpConfig(R=1, measure="cosine", padding=1, diff_weights=False)
     x = torch.randn(2, 4, 6, 5, device=dev)
-    plan = functional._bias_plan(x, "nchw", cfg)
+    plan = functional._plan(x, "nchw", cfg, tables=False)
     d, oshape, ns, nsc = plan.desc, plan.oshape, plan.ask("nfp_bias_saved_floats"), plan.ask("nfp_bias_scratch_floats")
     assert ns > 0 and nsc > 0
     bc, nb = torch.zeros(4, device=dev), torch.zeros(32, device=dev)

@@ -384,7 +384,7 @@ def _abi_call(dev, measure):
     cfg = NfpConfig(R=1, measure=measure, padding=1, diff_weights=False)
     g = torch.Generator(device=dev).manual_seed(101)
     x = torch.rand(4, 16, 12, 12, generator=g, device=dev)
-    plan = functional._bias_plan(x, "nchw", cfg)
+    plan = functional._plan(x, "nchw", cfg, tables=False)
     d, oshape, ns = plan.desc, plan.oshape, plan.ask("nfp_bias_saved_floats")
     bc, nb = torch.randn(16, generator=g, device=dev), torch.randn(128, generator=g, device=dev)
     stream = functional._raw_stream(x.device)

@@ -1,4 +1,4 @@
-"""SyncBatchNorm in the fused compress tails on the MI355X (include/nfp.h nfp_cpsync_*, functional.py "SyncBatchNorm in the
+"""SyncBatchNorm in the fused compress tails on the MI355X (include/nfp.h nfp_cpsync_*, compress.py "SyncBatchNorm in the
 two tails"), on one GPU:
 
   * emulated ranks — the staged call functions driven shard by shard, the records / rows joined with torch.cat (which is
@@ -248,7 +248,7 @@ def _module_step(fn, maps, w, bn, go, **kw):
 
 @pytest.mark.parametrize("kind", ["pool", "proj"])
 def test_one_rank_group_takes_todays_path(kind, dev, one_rank_group, monkeypatch):
-    from neighbour_feature_pooling_amd import nfp_compress_map, nfp_compress_pool
+    from neighbour_feature_pooling_amd import compress, nfp_compress_map, nfp_compress_pool
     from neighbour_feature_pooling_amd import functional as Fn
     monkeypatch.setenv("NFP_CPROJ_TORCH", "0")
     case, ins, _ = case_ref("pool_r1" if kind == "pool" else "proj_relu")
@@ -267,7 +267,7 @@ def test_one_rank_group_takes_todays_path(kind, dev, one_rank_group, monkeypatch
          d[2].clone().requires_grad_(True), d[3].clone().requires_grad_(True)]
     rm, rv = d[4].clone(), d[5].clone()
     n0 = _count()
-    out = Fn._CpSyncHip.apply(*t, (rm, rv), MOM, EPS, True, True, kind, False, one_rank_group)
+    out = compress._CpSyncHip.apply(*t, (rm, rv), MOM, EPS, True, True, kind, False, one_rank_group)
     n1 = _count()
     grads = torch.autograd.grad(out, t, d[6])
     torch.cuda.synchronize()
