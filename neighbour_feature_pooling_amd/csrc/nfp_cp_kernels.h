@@ -9,7 +9,7 @@
 namespace nfp {
 namespace {
 
-constexpr int kCpT = 512;         // threads of cpool_fwd / cpool_bwd_part / cpool_bwd_maps: 8 wavefronts
+constexpr int kCpT = 512;         // threads of cpool_fwd / cpool_bwd_part / cp_bwd_maps: 8 wavefronts
 constexpr int kCpW = kCpT / 64;
 constexpr int kCpDT = 128;        // channels of D per workgroup: 64 lanes x 2
 constexpr int kCpBudget = 8192;   // floats of maps per chunk (32 KiB): with the join buffers a workgroup stays near 50 KiB
@@ -17,7 +17,7 @@ constexpr int kCpMaxN = 32;
 constexpr int kCpRT = 32;         // channels of D per workgroup of cpool_bwd_reduce
 constexpr int kCpMT = 256;        // threads of cpool_moments / cpool_bwd_reduce
 constexpr int kCpFT = 1024;       // threads of cpool_finish
-constexpr int kCpMB = 128;        // channels of D per LDS block of cpool_bwd_maps
+constexpr int kCpMB = 128;        // channels of D per LDS block of cp_bwd_maps
 
 struct CpK {
   int B, N, P, CH, CHs, D, bf16, eval, S, ipw, nc, ntr;
@@ -51,44 +51,58 @@ __device__ __forceinline__ float cj_load(const CpK& k, const void* p, long long 
   return k.bf16 ? bf16_to_f32(((const uint16_t*)p)[j]) : ((const float*)p)[j];
 }
 
+// ... and v stored there
+__device__ __forceinline__ void cj_store(const CpK& k, void* p, long long j, float v) {
+  if (k.bf16)
+    ((uint16_t*)p)[j] = f32_to_bf16(v);
+  else
+    ((float*)p)[j] = v;
+}
+
+// element j of the maps, of map n: centred about mu, which the statistics hold as two floats
+__device__ __forceinline__ float cp_map(const CpK& k, int n, long long j, bool centre) {
+  float v = cj_load(k, k.maps, j);
+  if (centre) v = (v - k.stats[n]) - k.stats[k.N + n];
+  return v;
+}
+
 // The chunk [p0, p0 + ch) of image b into sm[NP][CHs] as centred float32; rows n >= N and pixels >= ch are zero.
 __device__ __forceinline__ void cp_stage(const CpK& k, int NP, float* sm, int b, int p0, int ch, bool centre) {
   const long long base = (long long)b * k.N * k.P + p0;
   const int total = NP * k.CHs;
   for (int i = threadIdx.x; i < total; i += blockDim.x) {
     const int n = i / k.CHs, pl = i - n * k.CHs;
-    float v = 0.f;
-    if (n < k.N && pl < ch) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
-      if (centre) v = (v - k.stats[n]) - k.stats[k.N + n];
-    }
-    sm[i] = v;
+    sm[i] = (n < k.N && pl < ch) ? cp_map(k, n, base + (long long)n * k.P + pl, centre) : 0.f;
+  }
+}
+
+// dst[i] = the sum over the k.ntr rows [k (N), Q (N * N)] that k.kq names, in row order: the workgroups' shares of
+// cpool_bwd_reduce, or the ranks' rows.  T: the threads of the workgroup.
+template <int T>
+__device__ __forceinline__ void cp_kq_sum(const CpK& k, float* dst) {
+  const int L = k.N + k.N * k.N;
+  for (int i = threadIdx.x; i < L; i += T) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * L + i];
+    dst[i] = s;
   }
 }
 
 // ---- moments ---------------------------------------------------------------------------------------------------------------
-// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP], red[max(NP * NP, 256)].
-// part_w: per chunk [a (N), r (N), Gram (N * N)].
-__global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* anchor = sm + NP * k.CHs;
-  float* red = anchor + NP;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kCpMT >> 6;
-  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int N = k.N, NN = NP * NP;
-  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
-  cp_stage(k, NP, sm, b, p0, ch, false);
-  __syncthreads();
-  for (int n = wv; n < NP; n += nw) {
+// The first passes over a staged chunk sm[.][CHs] of ch pixels, by 256 threads: the mean of map n as a float32 anchor
+// a_n, then the map centred about it in place and the mean r_n of what is left; outp takes [a (N), r (N)].  Rows n >= N
+// and pixels >= ch stay zero.  Ends behind a barrier.
+__device__ __forceinline__ void cp_anchor_centre(const CpK& k, float* sm, float* anchor, int ch, float* outp) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = kCpMT >> 6, N = k.N;
+  for (int n = wv; n < N; n += nw) {
     float s = 0.f;
     for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
     s = cp_wave_sum(s);
     if (lane == 0) anchor[n] = s / (float)ch;
   }
   __syncthreads();
-  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
+  for (int n = wv; n < N; n += nw) {
     const float an = anchor[n];
     float s = 0.f;
     for (int pl = lane; pl < ch; pl += 64) {
@@ -103,6 +117,23 @@ __global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
     }
   }
   __syncthreads();
+}
+
+// grid = B * nc chunks, block = 256.  LDS: sm[NP * CHs], anchor[NP], red[max(NP * NP, 256)].
+// part_w: per chunk [a (N), r (N), Gram (N * N)].
+__global__ void __launch_bounds__(kCpMT) cpool_moments(CpK k, int NP) {
+  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
+  float* sm = cp_lds;
+  float* anchor = sm + NP * k.CHs;
+  float* red = anchor + NP;
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
+  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
+  const int N = k.N, NN = NP * NP;
+  float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
+  cp_stage(k, NP, sm, b, p0, ch, false);
+  __syncthreads();
+  cp_anchor_centre(k, sm, anchor, ch, outp);
   // Gram about the anchor: pair (n, n2) per thread, the pixels in quads; with fewer pairs than threads the quads are dealt
   // to T / NN slices and joined in slice order
   const int nq = (ch + 3) >> 2;
@@ -306,15 +337,7 @@ __global__ void __launch_bounds__(kCpFT) cps_finish(CpK k, const double* recs, i
 
 // A rank's row [k (N), Q (N * N)]: the shares of cpool_bwd_reduce's workgroups, summed in workgroup order as the *_bwd_maps
 // kernels sum them.  Those kernels then read the ranks' rows where they read the workgroups' shares.  grid = 1, block = 256.
-__global__ void __launch_bounds__(kCpMT) cps_kq_row(CpK k, float* row) {
-  const int L = k.N + k.N * k.N;
-  for (int i = threadIdx.x; i < L; i += kCpMT) {
-    float s = 0.f;
-#pragma unroll 8
-    for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * L + i];
-    row[i] = s;
-  }
-}
+__global__ void __launch_bounds__(kCpMT) cps_kq_row(CpK k, float* row) { cp_kq_sum<kCpMT>(k, row); }
 
 // What a rank without an image contributes backward: a zero row and zero parameter gradients (those that are asked for).
 // grid-stride, block = 256.
@@ -342,7 +365,7 @@ __device__ __forceinline__ void cp_rows(const CpK& k, int tile, int lane, float 
     for (int n = 0; n < NP; ++n) ws[j][n] = (d < k.D && n < k.N) ? k.w[(long long)d * k.N + n] * scale : 0.f;
   }
 }
-// a of the lane's two channels at the four pixels of quad q: the shift first, then the maps in order (cpool_bwd_maps forms
+// a of the lane's two channels at the four pixels of quad q: the shift first, then the maps in order (cp_bwd_maps forms
 // the same chain: the same bits, the same mask)
 template <int NP>
 __device__ __forceinline__ void cp_preact(const float* sm, int CHs, int q, const float (&ws)[2][NP], const float (&sh)[2],
@@ -403,15 +426,61 @@ __global__ void __launch_bounds__(kCpT) cpool_fwd(CpK k) {
   }
 }
 
-// grid = (S, ceil(D / 128)), block = cp_part_threads: images [s * ipw, (s + 1) * ipw) of the batch.  LDS: sm[NP * CHs],
-// red[128 * (NP + 1)].  part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
-// A lane keeps 2 * NP scaled weights and 2 * NP sums: above 24 maps that passes the 256 registers two wavefronts per SIMD
-// leave each (92 spilled at 512 threads), so those run four wavefronts, one per SIMD, with the whole file.
+// The threads of the *_bwd_part kernels.  A lane keeps 2 * NP scaled weights and 2 * NP sums: above 24 maps that passes the
+// 256 registers two wavefronts per SIMD leave each (92 spilled at 512 threads), so those run four wavefronts, one per
+// SIMD, with the whole file.
 template <int NP>
 constexpr int cp_part_threads() { return NP > 24 ? 256 : kCpT; }
+
+// What cpool_bwd_part and cproj_bwd_part share behind their ga.
+// T_dn += ga c_n of the lane's two channels over the four pixels of quad q, the pixels in order
+template <int NP>
+__device__ __forceinline__ void cp_part_sum(const float* sm, int CHs, int q, const float (&ga)[2][4], float (&T)[2][NP]) {
+#pragma unroll
+  for (int n = 0; n < NP; ++n) {
+    const float4 c = ((const float4*)(sm + n * CHs))[q];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      float t = T[j][n];
+      t = fmaf(ga[j][0], c.x, t);
+      t = fmaf(ga[j][1], c.y, t);
+      t = fmaf(ga[j][2], c.z, t);
+      t = fmaf(ga[j][3], c.w, t);
+      T[j][n] = t;
+    }
+  }
+}
+// The wavefronts' sums joined in wavefront order into red[dl][NP + 1] (every lane its own words), then slice sl's rows of
+// part_w.  The caller has a barrier behind the last read of what red overlays.
+template <int NP>
+__device__ __forceinline__ void cp_part_join(const CpK& k, float* red, int sl, int tile, const float (&T)[2][NP],
+                                             const float (&gbs)[2]) {
+  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int w = 0; w < kW; ++w) {
+    if (wv == w) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float* r = red + (lane + 64 * j) * (NP + 1);
+#pragma unroll
+        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
+        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
+      }
+    }
+    __syncthreads();
+  }
+  const int N1 = k.N + 1;
+  for (int i = tid; i < kCpDT * N1; i += kT) {
+    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
+    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
+  }
+}
+
+// grid = (S, ceil(D / 128)), block = cp_part_threads: images [s * ipw, (s + 1) * ipw) of the batch.  LDS: sm[NP * CHs],
+// red[128 * (NP + 1)].  part_w: [S][D][N + 1] — T_dn of the slice, then grad_beta_d.
 template <int NP>
 __global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
-  constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
+  constexpr int kW = cp_part_threads<NP>() / 64;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   float* sm = cp_lds;
   float* red = sm + NP * k.CHs;
@@ -447,53 +516,90 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cpool_bwd_part(CpK k) {
             a[j][i] = (i < nv && a[j][i] > 0.f) ? gs[j] : 0.f;   // ga
             gbs[j] += a[j][i];
           }
-#pragma unroll
-        for (int n = 0; n < NP; ++n) {
-          const float4 c = ((const float4*)(sm + n * k.CHs))[q];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            float t = T[j][n];
-            t = fmaf(a[j][0], c.x, t);
-            t = fmaf(a[j][1], c.y, t);
-            t = fmaf(a[j][2], c.z, t);
-            t = fmaf(a[j][3], c.w, t);
-            T[j][n] = t;
-          }
+        cp_part_sum<NP>(sm, k.CHs, q, a, T);
+      }
+    }
+  }
+  cp_part_join<NP>(k, red, sl, tile, T, gbs);
+}
+
+// What both reduce kernels do once the slices are joined, by 256 threads behind a barrier: Tl[dl * ts + n] holds T_dn of
+// the workgroup's 32 channels from d0 = 32 blockIdx.x, with grad_beta_d at n = ts - 1; wl[dl * ws + n] their weights
+// (zero beyond D); sg[N * N] Sigma (training).  Per channel inv, s_d, grad_gamma and e, f; then grad_w; then this
+// workgroup's share [k (N), Q (N * N)] of kq_w (training).
+// SYNC (nfp_cpsync_reduce): e and f divide by the count over all ranks, which cps_finish left behind inv in stats, and
+// Sigma w comes from both of Sigma's floats.
+template <bool SYNC>
+__device__ __forceinline__ void cp_reduce_tail(const CpK& k, const float* Tl, int ts, const float* wl, int ws, const float* sg) {
+  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
+  const int tid = threadIdx.x, N = k.N, NN = N * N, d0 = blockIdx.x * kCpRT;
+  if (tid < kCpRT) {
+    const int d = d0 + tid;
+    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
+    if (d < k.D) {
+      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
+      c1 = k.gamma[d] * inv;
+      const float gb = Tl[tid * ts + ts - 1];
+      float dot = 0.f;
+      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * ws + n], Tl[tid * ts + n], dot);
+      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
+      if (!k.eval) {
+        const float M = SYNC ? cp_inv(k)[k.D] : (float)k.M;
+        e = c1 * (gb / M);
+        f = c1 * (gg * inv / M);
+      }
+      if (k.gg != nullptr) k.gg[d] = gg;
+      if (k.gb != nullptr) k.gb[d] = gb;
+    }
+    el[tid] = e;
+    fl[tid] = f;
+    ggl[tid] = gg;
+    c1l[tid] = c1;
+    invl[tid] = inv;
+  }
+  __syncthreads();
+  if (k.gw != nullptr)
+    for (int i = tid; i < kCpRT * N; i += kCpMT) {
+      const int dl = i / N, n = i - dl * N, d = d0 + dl;
+      if (d >= k.D) continue;
+      float t = Tl[dl * ts + n];
+      if (!k.eval) {
+        float sw = 0.f;
+        if constexpr (SYNC) {   // Sigma as cps_finish left it, two floats an entry, summed in float64
+          const float* lo = cp_inv(k) + k.D + 1;
+          double s64 = 0.0;
+          for (int n2 = 0; n2 < N; ++n2) s64 += ((double)sg[n * N + n2] + (double)lo[n * N + n2]) * (double)wl[dl * ws + n2];
+          sw = (float)s64;
+        } else {
+          for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * ws + n2], sw);
         }
+        t -= ggl[dl] * invl[dl] * sw;
       }
+      k.gw[(long long)d * N + n] = c1l[dl] * t;
     }
-  }
-  // the eight wavefronts in order into red[dl][NP + 1] (every lane its own words)
-  for (int w = 0; w < kW; ++w) {
-    if (wv == w) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float* r = red + (lane + 64 * j) * (NP + 1);
-#pragma unroll
-        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
-        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
-      }
+  if (k.eval || k.kq_w == nullptr) return;
+  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
+  for (int i = tid; i < N + NN; i += kCpMT) {
+    float s = 0.f;
+    if (i < N) {
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * ws + i], el[dl], s);
+    } else {
+      const int n = (i - N) / N, n2 = (i - N) - n * N;
+      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * ws + n], wl[dl * ws + n2], s);
     }
-    __syncthreads();
-  }
-  const int N1 = k.N + 1;
-  for (int i = tid; i < kCpDT * N1; i += kT) {
-    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
-    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
+    kq[i] = s;
   }
 }
 
 // grid = ceil(D / 32), block = 256.  kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
 // LIVE (the cproj backward, whose S reaches 512): loads are issued only from the element rounds and lanes that hold an
 // element; the sums and their order are the same in both forms.
-// SYNC (nfp_cpsync_reduce): the slices are one rank's, and e and f divide by the count over all ranks, which cps_finish
-// left behind inv in stats.
+// SYNC: the slices are one rank's (cp_reduce_tail).
 template <bool LIVE, bool SYNC = false>
 __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
   __shared__ float Tl[kCpRT * (kCpMaxN + 1)];
   __shared__ float wl[kCpRT * kCpMaxN];
   __shared__ float sg[kCpMaxN * kCpMaxN];
-  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
   const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
   {
     // a thread's elements (at most 5 of the 32 * (N + 1)) side by side, the slices in order: their loads are independent, so
@@ -556,127 +662,103 @@ __global__ void __launch_bounds__(kCpMT) cpool_bwd_reduce(CpK k) {
   if (!k.eval)
     for (int i = tid; i < NN; i += kCpMT) sg[i] = k.stats[2 * N + i];
   __syncthreads();
-  if (tid < kCpRT) {
-    const int d = d0 + tid;
-    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
-    if (d < k.D) {
-      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
-      c1 = k.gamma[d] * inv;
-      const float gb = Tl[tid * (kCpMaxN + 1) + kCpMaxN];
-      float dot = 0.f;
-      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * kCpMaxN + n], Tl[tid * (kCpMaxN + 1) + n], dot);
-      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
-      if (!k.eval) {
-        const float M = SYNC ? cp_inv(k)[k.D] : (float)k.M;
-        e = c1 * (gb / M);
-        f = c1 * (gg * inv / M);
-      }
-      if (k.gg != nullptr) k.gg[d] = gg;
-      if (k.gb != nullptr) k.gb[d] = gb;
-    }
-    el[tid] = e;
-    fl[tid] = f;
-    ggl[tid] = gg;
-    c1l[tid] = c1;
-    invl[tid] = inv;
-  }
-  __syncthreads();
-  if (k.gw != nullptr)
-    for (int i = tid; i < kCpRT * N; i += kCpMT) {
-      const int dl = i / N, n = i - dl * N, d = d0 + dl;
-      if (d >= k.D) continue;
-      float t = Tl[dl * (kCpMaxN + 1) + n];
-      if (!k.eval) {
-        float sw = 0.f;
-        if constexpr (SYNC) {   // Sigma as cps_finish left it, two floats an entry, summed in float64
-          const float* lo = cp_inv(k) + k.D + 1;
-          double s64 = 0.0;
-          for (int n2 = 0; n2 < N; ++n2) s64 += ((double)sg[n * N + n2] + (double)lo[n * N + n2]) * (double)wl[dl * kCpMaxN + n2];
-          sw = (float)s64;
-        } else {
-          for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * kCpMaxN + n2], sw);
-        }
-        t -= ggl[dl] * invl[dl] * sw;
-      }
-      k.gw[(long long)d * N + n] = c1l[dl] * t;
-    }
-  if (k.eval || k.kq_w == nullptr) return;
-  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
-  for (int i = tid; i < N + NN; i += kCpMT) {
-    float s = 0.f;
-    if (i < N) {
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * kCpMaxN + i], el[dl], s);
-    } else {
-      const int n = (i - N) / N, n2 = (i - N) - n * N;
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * kCpMaxN + n], wl[dl * kCpMaxN + n2], s);
-    }
-    kq[i] = s;
-  }
+  cp_reduce_tail<SYNC>(k, Tl, kCpMaxN + 1, wl, kCpMaxN, sg);
 }
 
 // ---- lanes along p -----------------------------------------------------------------------------------------------------------
+// Where the factor t_bdp of channel d at a lane's pixel comes from, in grad_m_bnp = sum_d s_d w_dn t_bdp [a_bdp > 0]:
+//   kCpGradPooled  G_bd / P of the pooled tail: divided once per channel when the block's table is filled, and kept in
+//                  the channel's row of it
+//   kCpGradNchw    the projection's grad_out [b][d][p]: a lane's own loads, four channels' in flight
+//   kCpGradNhwc    the projection's grad_out [b][p][d], where a lane's own loads would be D elements apart: the block's
+//                  [64 pixels][<= 128 d] tile comes through LDS instead — gt[pl * 129 + dl], written with d fastest across
+//                  the lanes (whole segments of global memory, consecutive banks) and read by every lane from its own
+//                  pixel's row (an odd stride: 32 banks)
+enum CpGrad { kCpGradPooled, kCpGradNchw, kCpGradNhwc };
+
 // grid = B * ceil(P / 64), block = 512: the 64 pixels from pt * 64 of image b.  LDS: red[NP * 64], kql[N + N * N], the table
-// of a block of channels tb[128][NP + 4].
-template <int NP>
-__global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
-  constexpr int kTS = NP + 4;   // floats per channel of the block's table: the row, the shift, G_bd / P (16-byte rows)
+// of a block of channels tb[128][NP + 4] — a channel's scaled row, then its shift (pooled: then G_bd / P) in 16-byte rows;
+// gt for kCpGradNhwc alone.  RELU: the pooled tail always has it.  The sums and their order are the same for every source.
+template <int NP, CpGrad SRC, bool RELU>
+__global__ void __launch_bounds__(kCpT) cp_bwd_maps(CpK k, int npt) {
+  static_assert(RELU || SRC != kCpGradPooled, "the pooled tail has the ReLU");
+  constexpr int kTS = NP + 4;
+  constexpr int kCS = SRC == kCpGradPooled ? 4 : 1;   // floats between two channels' scales in cf
+  constexpr int kU = SRC == kCpGradPooled ? 1 : 4;    // channels of a wavefront whose t is fetched together
+  constexpr int kGS = kCpMB + 1;
   __shared__ float red[NP * 64];
   __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
   __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
-  __shared__ float cf[kCpMB * 4];
+  __shared__ float cf[kCpMB * kCS];
+  __shared__ float gt[SRC == kCpGradNhwc ? 64 * kGS : 1];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
+  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N;
   const bool live = p < k.P;
-  if (!k.eval)
-    for (int i = tid; i < N + NN; i += kCpT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
+  if (!k.eval) cp_kq_sum<kCpT>(k, kql);
   float c[NP], g[NP];
   const long long base = (long long)b * N * k.P + p;
 #pragma unroll
   for (int n = 0; n < NP; ++n) {
-    float v = 0.f;
-    if (n < N && live) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    c[n] = v;
+    c[n] = (n < N && live) ? cp_map(k, n, base + (long long)n * k.P, !k.eval) : 0.f;
     g[n] = 0.f;
   }
-  // D in blocks of 128 channels: the block's rows s_d w_d, shifts and G_bd / P go to LDS with coalesced, independent loads
-  // first (fetched per channel inside the loop they were a chain of dependent global loads: 0.6 us per channel, measured),
-  // then every wavefront walks its channels of the block reading them as broadcasts
+  const long long gbase = (long long)b * k.D * k.P + p;
+  // D in blocks of 128 channels: the block's rows s_d w_d and shifts go to LDS with coalesced, independent loads first
+  // (fetched per channel inside the loop they were a chain of dependent global loads: 0.6 us per channel, measured), then
+  // every wavefront walks its channels of the block, dl = wv, wv + 8, ..., reading them as broadcasts
   for (int dB = 0; dB < k.D; dB += kCpMB) {
     const int nd = min(kCpMB, k.D - dB);
     if (dB > 0) __syncthreads();   // (the previous block has been read)
+    if constexpr (SRC == kCpGradNhwc) {
+      const int lg = nd <= 1 ? 0 : 32 - __clz(nd - 1);   // lanes cover nd rounded up to a power of two
+      for (int i = tid; i < 64 << lg; i += kCpT) {
+        const int dl = i & ((1 << lg) - 1), pl = i >> lg, pp = pt * 64 + pl;
+        if (dl < nd) gt[pl * kGS + dl] = pp < k.P ? cj_load(k, k.gov, ((long long)b * k.P + pp) * k.D + dB + dl) : 0.f;
+      }
+    }
     if (tid < nd) {
       float scale, shift;
       cp_coef(k, dB + tid, scale, shift);
-      cf[tid * 4] = scale;
+      cf[tid * kCS] = scale;
       tb[tid * kTS + NP] = shift;
-      tb[tid * kTS + NP + 1] = k.go[(long long)b * k.D + dB + tid] / (float)k.P;
+      if constexpr (SRC == kCpGradPooled) tb[tid * kTS + NP + 1] = k.go[(long long)b * k.D + dB + tid] / (float)k.P;
     }
     __syncthreads();
     for (int i = tid; i < nd * NP; i += kCpT) {
       const int dl = i / NP, n = i - dl * NP;
-      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl * 4] : 0.f;
+      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl * kCS] : 0.f;
     }
     __syncthreads();
-    for (int dl = wv; dl < nd; dl += kCpW) {
-      const float* row = tb + dl * kTS;
-      float wsn[NP];
-      float a = row[NP];
+    for (int dl0 = wv; dl0 < nd; dl0 += kU * kCpW) {   // kU channels' t together, used in channel order
+      float t[kU];
 #pragma unroll
-      for (int n = 0; n < NP; ++n) {
-        wsn[n] = row[n];
-        a = fmaf(wsn[n], c[n], a);
+      for (int u = 0; u < kU; ++u) {
+        const int dl = dl0 + u * kCpW;
+        if constexpr (SRC == kCpGradPooled)
+          t[u] = tb[dl * kTS + NP + 1];
+        else if constexpr (SRC == kCpGradNhwc)
+          t[u] = dl < nd ? gt[lane * kGS + dl] : 0.f;   // (zero beyond P)
+        else
+          t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
       }
-      const float t = a > 0.f ? row[NP + 1] : 0.f;
 #pragma unroll
-      for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], t, g[n]);
+      for (int u = 0; u < kU; ++u) {
+        const int dl = dl0 + u * kCpW;
+        if (dl >= nd) break;   // (the same in every lane)
+        const float* row = tb + dl * kTS;
+        float wsn[NP];
+#pragma unroll
+        for (int n = 0; n < NP; ++n) wsn[n] = row[n];
+        float tu = t[u];
+        if (RELU) {
+          float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain, the same bits, the same mask
+#pragma unroll
+          for (int n = 0; n < NP; ++n) a = fmaf(wsn[n], c[n], a);
+          tu = a > 0.f ? tu : 0.f;
+        }
+#pragma unroll
+        for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], tu, g[n]);
+      }
     }
   }
   for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
@@ -696,11 +778,7 @@ __global__ void __launch_bounds__(kCpT) cpool_bwd_maps(CpK k, int npt) {
         if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
       v -= qc;
     }
-    const long long j = base + (long long)n * k.P;
-    if (k.bf16)
-      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
-    else
-      ((float*)k.gm)[j] = v;
+    cj_store(k, k.gm, base + (long long)n * k.P, v);
   }
 }
 
@@ -710,58 +788,34 @@ constexpr int kCjDT = 64;    // channels of D per workgroup of cproj_fwd
 constexpr int kCjSP = 64;    // pixels per pass of cproj_bwd_part
 constexpr int kCjSS = 68;    // floats between two rows of a pass in LDS: 16-byte rows, an odd number of 16-byte slots
 
-// grid = B * nc * tiles (the tile fastest), block = 256; k.CH / k.CHs / k.nc are this kernel's own chunks (cproj_fwd_chunk).
-// LDS: sm[NP * CHs], tb[64][NP + 1] — the scaled row of a channel, then its shift.
+// out of one channel at pixel pl of the staged maps sm (rows CHs apart): row = the channel's scaled weights, then its shift.
+// The shift first, then the maps in order: cp_preact's chain.
 template <int NP, bool RELU>
-__global__ void __launch_bounds__(kCjT) cproj_fwd(CpK k, int tiles) {
-  constexpr int kTS = NP + 1;
-  extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  float* sm = cp_lds;
-  float* tb = sm + NP * k.CHs;
-  const int tid = threadIdx.x;
-  const int bj = blockIdx.x / tiles, tile = blockIdx.x - bj * tiles;
-  const int b = bj / k.nc, j = bj - b * k.nc;
-  const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
-  const int d0 = tile * kCjDT, nd = min(kCjDT, k.D - d0);
-  cp_stage(k, NP, sm, b, p0, ch, !k.eval);
-  for (int i = tid; i < nd * kTS; i += kCjT) {
-    const int dl = i / kTS, n = i - dl * kTS;
-    float scale, shift;
-    cp_coef(k, d0 + dl, scale, shift);
-    tb[i] = n == NP ? shift : (n < k.N ? k.w[(long long)(d0 + dl) * k.N + n] * scale : 0.f);
-  }
-  __syncthreads();
-  // element e = dl * ch + pl of the chunk's [nd][ch] range; a thread's next one is 256 further on
-  const int total = nd * ch, qT = kCjT / ch, rT = kCjT - qT * ch;
-  int dl = tid / ch, pl = tid - dl * ch;
-  const long long obase = ((long long)b * k.D + d0) * k.P + p0;
-  for (int e = tid; e < total; e += kCjT) {
-    const float* row = tb + dl * kTS;
-    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
+__device__ __forceinline__ float cj_act(const float* row, const float* sm, int CHs, int pl) {
+  float a = row[NP];
 #pragma unroll
-    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * k.CHs + pl], a);
-    if (RELU) a = a < 0.f ? 0.f : a;
-    const long long o = obase + (long long)dl * k.P + pl;
-    if (k.bf16)
-      ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
-    else
-      ((float*)k.outv)[o] = a;
-    pl += rT, dl += qT;
-    if (pl >= ch) pl -= ch, ++dl;
-  }
+  for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * CHs + pl], a);
+  if (RELU) a = a < 0.f ? 0.f : a;
+  return a;
 }
 
-// cproj_fwd for a channels-last out, [b][p][d]: the same grid, LDS and per-element chain — only who owns an element
-// changes.  The tile's share of the chunk is [ch][nd] with the channel fastest: element e = pl * nd + dl at
-// obase + pl * D + dl, so where the tile is all of D the chunk is one span of ch * D elements, and otherwise ch segments
-// of nd channels.  Lanes run along e: a wavefront's store covers whole segments (several pixels where D is small), the
-// rows of tb are read at an odd stride and the maps as broadcasts.
-// PAIR (bf16, out 4-byte aligned, and a single tile or an even D): a lane holds the two elements of an aligned dword and
-// stores them together.  With a single tile the pairs are laid over the span from its even address down (s: the span
-// starts on an odd element), so they may straddle two pixels' rows and the span's first and last element may stand
+// grid = B * nc * tiles (the tile fastest), block = 256; k.CH / k.CHs / k.nc are this kernel's own chunks (cproj_fwd_chunk).
+// LDS: sm[NP * CHs], tb[64][NP + 1] — the scaled row of a channel, then its shift.
+// The tile's share of the chunk is a [slow][fast] range that lanes walk flat, element e = slow * fast-extent + fast, a
+// thread's next one 256 further on.  NCHW out, [b][d][p]: [nd][ch], the pixel fastest, at obase + dl * P + pl.
+// NHWC out, [b][p][d]: [ch][nd], the channel fastest, at obase + pl * D + dl — so where the tile is all of D the chunk is
+// one span of ch * D elements, and otherwise ch segments of nd channels; a wavefront's store covers whole segments
+// (several pixels where D is small), the rows of tb are read at an odd stride and the maps as broadcasts.
+// Prologue, chain (cj_act) and store are shared; each layout keeps its own walk, and hands cj_act the maps the way its
+// loop always has (NCHW: the pixel's column; NHWC: the maps and the pixel).  As one walk over a fast extent of ch or nd
+// the NCHW eval forward measured 0.2 us (1 %) over its time at [64,8,54,54] -> 24 and [64,8,5,5] -> 160.
+// PAIR (NHWC only: bf16, out 4-byte aligned, and a single tile or an even D): a lane holds the two elements of an aligned
+// dword and stores them together.  With a single tile the pairs are laid over the span from its even address down (s: the
+// span starts on an odd element), so they may straddle two pixels' rows and the span's first and last element may stand
 // alone; with an even D every segment starts and ends on a pair.
-template <int NP, bool RELU, bool PAIR>
-__global__ void __launch_bounds__(kCjT) cproj_fwd_nhwc(CpK k, int tiles) {
+template <int NP, bool RELU, bool NHWC, bool PAIR = false>
+__global__ void __launch_bounds__(kCjT) cproj_fwd(CpK k, int tiles) {
+  static_assert(NHWC || !PAIR, "pairs are laid along d");
   constexpr int kTS = NP + 1;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   float* sm = cp_lds;
@@ -780,26 +834,27 @@ __global__ void __launch_bounds__(kCjT) cproj_fwd_nhwc(CpK k, int tiles) {
   }
   __syncthreads();
   const int CHs = k.CHs;
-  auto act = [&](int pl, int dl) {
-    const float* row = tb + dl * kTS;
-    float a = row[NP];   // the shift first, then the maps in order: cp_preact's chain
-#pragma unroll
-    for (int n = 0; n < NP; ++n) a = fmaf(row[n], sm[n * CHs + pl], a);
-    if (RELU) a = a < 0.f ? 0.f : a;
-    return a;
-  };
+  auto act = [&](int pl, int dl) { return cj_act<NP, RELU>(tb + dl * kTS, sm, CHs, pl); };
   const int total = nd * ch;
+  if constexpr (!NHWC) {
+    const int qT = kCjT / ch, rT = kCjT - qT * ch;
+    int dl = tid / ch, pl = tid - dl * ch;
+    const long long obase = ((long long)b * k.D + d0) * k.P + p0;
+    for (int e = tid; e < total; e += kCjT) {
+      const float a = cj_act<NP, RELU>(tb + dl * kTS, sm + pl, k.CHs, 0);
+      cj_store(k, k.outv, obase + (long long)dl * k.P + pl, a);
+      pl += rT, dl += qT;
+      if (pl >= ch) pl -= ch, ++dl;
+    }
+    return;
+  }
   const long long obase = ((long long)b * k.P + p0) * k.D + d0;
   if (!PAIR) {
-    const int qT = kCjT / nd, rT = kCjT - qT * nd;   // a thread's next element is 256 further on
+    const int qT = kCjT / nd, rT = kCjT - qT * nd;
     int pl = tid / nd, dl = tid - pl * nd;
     for (int e = tid; e < total; e += kCjT) {
       const float a = act(pl, dl);
-      const long long o = obase + (long long)pl * k.D + dl;
-      if (k.bf16)
-        ((uint16_t*)k.outv)[o] = f32_to_bf16(a);
-      else
-        ((float*)k.outv)[o] = a;
+      cj_store(k, k.outv, obase + (long long)pl * k.D + dl, a);
       dl += rT, pl += qT;
       if (dl >= nd) dl -= nd, ++pl;
     }
@@ -834,14 +889,13 @@ __global__ void __launch_bounds__(kCjT) cproj_fwd_nhwc(CpK k, int tiles) {
 // stores them as one 16-byte row piece.  ds_write_b128 is served eight lanes at a time; eight neighbouring channels are
 // 8 * 68 floats apart, banks 4 * dl + {0..3} (mod 32): all 32 different.  (One pixel per lane, a dword each, puts the 32
 // lanes of a half on eight banks.)  Lanes cover the nd channels of the tile rounded up to a power of two, 8 at the
-// least; the rows beyond that are zeroed once.  Everything behind the staging is the NCHW kernel's, sum for sum.
+// least; the rows beyond that are zeroed once.  Everything behind the staging is the same code for both layouts.
 template <int NP, bool RELU, bool NHWC = false>
 __global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, int nsub, int upw) {
   constexpr int kT = cp_part_threads<NP>(), kW = kT / 64;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   float* sm = cp_lds;
   float* gl = sm + NP * kCjSS;
-  float* red = gl;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int sl = blockIdx.x, tile = blockIdx.y;
   float ws[2][NP], sh[2], T[2][NP], gbs[2] = {0.f, 0.f};
@@ -896,154 +950,11 @@ __global__ void __launch_bounds__(cp_part_threads<NP>()) cproj_bwd_part(CpK k, i
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) gbs[j] += ga[j][i];
-#pragma unroll
-      for (int n = 0; n < NP; ++n) {
-        const float4 c = ((const float4*)(sm + n * kCjSS))[q];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          float t = T[j][n];
-          t = fmaf(ga[j][0], c.x, t);
-          t = fmaf(ga[j][1], c.y, t);
-          t = fmaf(ga[j][2], c.z, t);
-          t = fmaf(ga[j][3], c.w, t);
-          T[j][n] = t;
-        }
-      }
+      cp_part_sum<NP>(sm, kCjSS, q, ga, T);
     }
   }
   __syncthreads();   // (gl has been read: red takes its place)
-  for (int w = 0; w < kW; ++w) {   // the wavefronts in order into red[dl][NP + 1] (every lane its own words)
-    if (wv == w) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float* r = red + (lane + 64 * j) * (NP + 1);
-#pragma unroll
-        for (int n = 0; n < NP; ++n) r[n] = w == 0 ? T[j][n] : r[n] + T[j][n];
-        r[NP] = w == 0 ? gbs[j] : r[NP] + gbs[j];
-      }
-    }
-    __syncthreads();
-  }
-  const int N1 = k.N + 1;
-  for (int i = tid; i < kCpDT * N1; i += kT) {
-    const int dl = i / N1, j = i - dl * N1, d = tile * kCpDT + dl;
-    if (d < k.D) k.part_w[((long long)sl * k.D + d) * N1 + j] = red[dl * (NP + 1) + (j < k.N ? j : NP)];
-  }
-}
-
-// grid = B * ceil(P / 64), block = 512: cpool_bwd_maps with grad_out read per (channel, pixel).  LDS: red[NP * 64],
-// kql[N + N * N], tb[128][NP + 4] — a channel's scaled row, then its shift.
-// NHWC: grad_out is [b][p][d], where a lane's own loads would be D elements apart.  The block's [64 pixels][<= 128 d] tile
-// comes through LDS instead — gt[pl * 129 + dl], written with d fastest across the lanes (whole segments of global
-// memory, consecutive banks) and read by every lane from its own pixel's row (an odd stride: 32 banks).  The sums are the
-// NCHW kernel's, in its order.
-template <int NP, bool RELU, bool NHWC = false>
-__global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
-  constexpr int kTS = NP + 4;
-  constexpr int kGS = kCpMB + 1;
-  __shared__ float red[NP * 64];
-  __shared__ float kql[kCpMaxN + kCpMaxN * kCpMaxN];
-  __shared__ __attribute__((aligned(16))) float tb[kCpMB * kTS];
-  __shared__ float cf[kCpMB];
-  __shared__ float gt[NHWC ? 64 * kGS : 1];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p = pt * 64 + lane, N = k.N, NN = N * N;
-  const bool live = p < k.P;
-  if (!k.eval)
-    for (int i = tid; i < N + NN; i += kCpT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
-  float c[NP], g[NP];
-  const long long base = (long long)b * N * k.P + p;
-#pragma unroll
-  for (int n = 0; n < NP; ++n) {
-    float v = 0.f;
-    if (n < N && live) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    c[n] = v;
-    g[n] = 0.f;
-  }
-  const long long gbase = (long long)b * k.D * k.P + p;
-  for (int dB = 0; dB < k.D; dB += kCpMB) {
-    const int nd = min(kCpMB, k.D - dB);
-    if (dB > 0) __syncthreads();   // (the previous block has been read)
-    if constexpr (NHWC) {
-      const int lg = nd <= 1 ? 0 : 32 - __clz(nd - 1);   // lanes cover nd rounded up to a power of two
-      for (int i = tid; i < 64 << lg; i += kCpT) {
-        const int dl = i & ((1 << lg) - 1), pl = i >> lg, pp = pt * 64 + pl;
-        if (dl < nd) gt[pl * kGS + dl] = pp < k.P ? cj_load(k, k.gov, ((long long)b * k.P + pp) * k.D + dB + dl) : 0.f;
-      }
-    }
-    if (tid < nd) {
-      float scale, shift;
-      cp_coef(k, dB + tid, scale, shift);
-      cf[tid] = scale;
-      tb[tid * kTS + NP] = shift;
-    }
-    __syncthreads();
-    for (int i = tid; i < nd * NP; i += kCpT) {
-      const int dl = i / NP, n = i - dl * NP;
-      tb[dl * kTS + n] = n < N ? k.w[(long long)(dB + dl) * N + n] * cf[dl] : 0.f;
-    }
-    __syncthreads();
-    for (int dl0 = wv; dl0 < nd; dl0 += 4 * kCpW) {   // four channels' grad_out loads together, used in channel order
-      float t[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int dl = dl0 + u * kCpW;
-        if constexpr (NHWC)
-          t[u] = dl < nd ? gt[lane * kGS + dl] : 0.f;   // (zero beyond P)
-        else
-          t[u] = (dl < nd && live) ? cj_load(k, k.gov, gbase + (long long)(dB + dl) * k.P) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int dl = dl0 + u * kCpW;
-        if (dl >= nd) break;   // (the same in every lane)
-        const float* row = tb + dl * kTS;
-        float wsn[NP];
-#pragma unroll
-        for (int n = 0; n < NP; ++n) wsn[n] = row[n];
-        float tu = t[u];
-        if (RELU) {
-          float a = row[NP];
-#pragma unroll
-          for (int n = 0; n < NP; ++n) a = fmaf(wsn[n], c[n], a);
-          tu = a > 0.f ? tu : 0.f;
-        }
-#pragma unroll
-        for (int n = 0; n < NP; ++n) g[n] = fmaf(wsn[n], tu, g[n]);
-      }
-    }
-  }
-  for (int w = 0; w < kCpW; ++w) {   // the eight wavefronts in order
-    if (wv == w) {
-#pragma unroll
-      for (int n = 0; n < NP; ++n) red[n * 64 + lane] = w == 0 ? g[n] : red[n * 64 + lane] + g[n];
-    }
-    __syncthreads();
-  }
-  if (!live) return;
-  for (int n = wv; n < N; n += kCpW) {
-    float v = red[n * 64 + lane];
-    if (!k.eval) {
-      float qc = kql[n];
-#pragma unroll
-      for (int n2 = 0; n2 < NP; ++n2)
-        if (n2 < N) qc = fmaf(kql[N + n * N + n2], c[n2], qc);
-      v -= qc;
-    }
-    const long long j = base + (long long)n * k.P;
-    if (k.bf16)
-      ((uint16_t*)k.gm)[j] = f32_to_bf16(v);
-    else
-      ((float*)k.gm)[j] = v;
-  }
+  cp_part_join<NP>(k, gl, sl, tile, T, gbs);
 }
 
 // ---- the wide form: 1 <= N <= 96 maps (nfp_cpool_wide_*) --------------------------------------------------------------------
@@ -1051,7 +962,8 @@ __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
 // 32 maps.  Here the rows of a block of 64 channels and the chunk's centred maps both sit in LDS, and a lane owns a small
 // tile of outputs: nothing in registers grows with N beyond N' / 16 <= 6 accumulators per owned row (N' = N rounded up to 16).
 // The formulas, the saved state (2N + N^2 + D floats) and the layouts of the partial sums are the ones above.
-//   cpw_moments     cpool_moments with the Gram as 4 x 4 register tiles of (n, n2) pairs, each pair's sum in pixel order
+//   cpw_moments     cpool_moments' anchor and centring passes (cp_anchor_centre), then the Gram as 4 x 4 register tiles of
+//                   (n, n2) pairs, each pair's sum in pixel order
 //   cpw_mu          one workgroup: mu in float64 from the chunks' anchors (eight slices of consecutive chunks, in order)
 //   cpw_sigma       one workgroup per 64 (n, n2) pairs: cpool_finish's join of the chunks in float64, four slices in order
 //   cpw_var         one workgroup per 16 channels: w_d^T Sigma w_d in float64, the rows of Sigma dealt to sixteen slices
@@ -1061,7 +973,7 @@ __global__ void __launch_bounds__(kCpT) cproj_bwd_maps(CpK k, int npt) {
 //                   slots joined in order
 //   cpw_bwd_part    the same pre-activations over a slice of the batch, ga written to LDS as [p][d]; then T_dn as a second
 //                   product, a lane owning 4 channels x N'/16 maps, summed over the pixels in order (no join)
-//   cpw_bwd_reduce  cpool_bwd_reduce with its tables sized by N
+//   cpw_bwd_reduce  the slices joined into tables sized by N, then cpool_bwd_reduce's tail (cp_reduce_tail)
 //   cpw_bwd_maps    one workgroup per 64 pixels of an image: per block of 64 channels the pre-activations as in cpw_fwd, the
 //                   masked G_bd / P to LDS as [d][p]; then sum_d s_d w_dn ga_dp, a lane owning 4 pixels x N'/16 maps, summed
 //                   over d in order; then - k - Q c from LDS
@@ -1117,35 +1029,14 @@ __global__ void __launch_bounds__(kWT) cpw_moments(CpK k, int NP) {
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   float* sm = cp_lds;
   float* anchor = sm + NP * k.CHs;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = kWT >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x / k.nc, j = blockIdx.x - b * k.nc;
   const int p0 = j * k.CH, ch = min(k.CH, k.P - p0);
   const int N = k.N;
   float* outp = k.part_w + (long long)blockIdx.x * (2 * N + N * N);
   cp_stage(k, NP, sm, b, p0, ch, false);
   __syncthreads();
-  for (int n = wv; n < N; n += nw) {
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) s += sm[n * k.CHs + pl];
-    s = cp_wave_sum(s);
-    if (lane == 0) anchor[n] = s / (float)ch;
-  }
-  __syncthreads();
-  for (int n = wv; n < N; n += nw) {   // (rows n >= N and pixels >= ch stay zero)
-    const float an = anchor[n];
-    float s = 0.f;
-    for (int pl = lane; pl < ch; pl += 64) {
-      const float c = sm[n * k.CHs + pl] - an;
-      sm[n * k.CHs + pl] = c;
-      s += c;
-    }
-    s = cp_wave_sum(s);
-    if (lane == 0) {
-      outp[n] = an;
-      outp[N + n] = s / (float)ch;
-    }
-  }
-  __syncthreads();
+  cp_anchor_centre(k, sm, anchor, ch, outp);
   const int nq = (ch + 3) >> 2, NT = NP >> 2;
   for (int t = tid; t < NT * NT; t += kWT) {
     const int tn = t / NT, tm = t - tn * NT;
@@ -1406,9 +1297,9 @@ __global__ void __launch_bounds__(kWT) cpw_bwd_part(CpK k, int NP) {
 
 // grid = ceil(D / 32), block = 256.  LDS: Tl[32 * (N + 1)], wl[32 * N], sg[N * N].
 // kq_w: per workgroup [k (N), Q (N * N)] of its 32 channels (training).
+static_assert(kWT == kCpMT, "cp_reduce_tail and cp_anchor_centre walk with 256 threads");
 __global__ void __launch_bounds__(kWT) cpw_bwd_reduce(CpK k) {
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
-  __shared__ float el[kCpRT], fl[kCpRT], ggl[kCpRT], c1l[kCpRT], invl[kCpRT];
   const int tid = threadIdx.x, N = k.N, N1 = N + 1, NN = N * N, d0 = blockIdx.x * kCpRT;
   float* Tl = cp_lds;
   float* wl = Tl + kCpRT * N1;
@@ -1437,54 +1328,7 @@ __global__ void __launch_bounds__(kWT) cpw_bwd_reduce(CpK k) {
   if (!k.eval)
     for (int i = tid; i < NN; i += kWT) sg[i] = k.stats[2 * N + i];
   __syncthreads();
-  if (tid < kCpRT) {
-    const int d = d0 + tid;
-    float e = 0.f, f = 0.f, gg = 0.f, c1 = 0.f, inv = 0.f;
-    if (d < k.D) {
-      inv = k.eval ? 1.f / sqrtf(k.rv[d] + k.eps) : cp_inv(k)[d];
-      c1 = k.gamma[d] * inv;
-      const float gb = Tl[tid * N1 + N];
-      float dot = 0.f;
-      for (int n = 0; n < N; ++n) dot = fmaf(wl[tid * N + n], Tl[tid * N1 + n], dot);
-      gg = k.eval ? inv * (dot - k.rm[d] * gb) : inv * dot;
-      if (!k.eval) {
-        e = c1 * (gb / (float)k.M);
-        f = c1 * (gg * inv / (float)k.M);
-      }
-      if (k.gg != nullptr) k.gg[d] = gg;
-      if (k.gb != nullptr) k.gb[d] = gb;
-    }
-    el[tid] = e;
-    fl[tid] = f;
-    ggl[tid] = gg;
-    c1l[tid] = c1;
-    invl[tid] = inv;
-  }
-  __syncthreads();
-  if (k.gw != nullptr)
-    for (int i = tid; i < kCpRT * N; i += kWT) {
-      const int dl = i / N, n = i - dl * N, d = d0 + dl;
-      if (d >= k.D) continue;
-      float t = Tl[dl * N1 + n];
-      if (!k.eval) {
-        float sw = 0.f;
-        for (int n2 = 0; n2 < N; ++n2) sw = fmaf(sg[n * N + n2], wl[dl * N + n2], sw);
-        t -= ggl[dl] * invl[dl] * sw;
-      }
-      k.gw[(long long)d * N + n] = c1l[dl] * t;
-    }
-  if (k.eval || k.kq_w == nullptr) return;
-  float* kq = k.kq_w + (long long)blockIdx.x * (N + NN);
-  for (int i = tid; i < N + NN; i += kWT) {
-    float s = 0.f;
-    if (i < N) {
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(wl[dl * N + i], el[dl], s);
-    } else {
-      const int n = (i - N) / N, n2 = (i - N) - n * N;
-      for (int dl = 0; dl < kCpRT; ++dl) s = fmaf(fl[dl] * wl[dl * N + n], wl[dl * N + n2], s);
-    }
-    kq[i] = s;
-  }
+  cp_reduce_tail<false>(k, Tl, N1, wl, N, sg);
 }
 
 // grid = B * ceil(P / 64), block = 256: the 64 pixels from pt * 64 of image b.  Thread (dg = tid % 16, q = tid / 16) for
@@ -1502,17 +1346,12 @@ __global__ void __launch_bounds__(kWT) cpw_bwd_maps(CpK k, int NP, int npt) {
   float* tt = tb + NP * kWRS;
   float* kql = tb;
   const int tid = threadIdx.x, dg = tid & 15, q = tid >> 4, pq = dg, ns = q, nj = NP >> 4;
-  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p0 = pt * 64, N = k.N, NN = N * N;
+  const int b = blockIdx.x / npt, pt = blockIdx.x - b * npt, p0 = pt * 64, N = k.N;
   const int npx = min(64, k.P - p0);
   const long long base = (long long)b * N * k.P + p0;
   for (int i = tid; i < NP * 64; i += kWT) {
     const int n = i >> 6, pl = i & 63;
-    float v = 0.f;
-    if (n < N && pl < npx) {
-      v = cj_load(k, k.maps, base + (long long)n * k.P + pl);
-      if (!k.eval) v = (v - k.stats[n]) - k.stats[N + n];
-    }
-    cl[n * kWRS + pl] = v;
+    cl[n * kWRS + pl] = (n < N && pl < npx) ? cp_map(k, n, base + (long long)n * k.P + pl, !k.eval) : 0.f;
   }
   float g[4][kWJ];   // [pixel][map]
 #pragma unroll
@@ -1562,12 +1401,7 @@ __global__ void __launch_bounds__(kWT) cpw_bwd_maps(CpK k, int NP, int npt) {
   }
   if (!k.eval) {
     __syncthreads();   // (tb and tt have been read: k and Q take their place)
-    for (int i = tid; i < N + NN; i += kWT) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < k.ntr; ++t) s += k.kq[(long long)t * (N + NN) + i];
-      kql[i] = s;
-    }
+    cp_kq_sum<kWT>(k, kql);
     __syncthreads();
   }
 #pragma unroll
@@ -1591,11 +1425,7 @@ __global__ void __launch_bounds__(kWT) cpw_bwd_maps(CpK k, int NP, int npt) {
 #pragma unroll
     for (int px = 0; px < 4; ++px) {
       if (4 * pq + px >= npx) continue;
-      const long long o = base + (long long)n * k.P + 4 * pq + px;
-      if (k.bf16)
-        ((uint16_t*)k.gm)[o] = f32_to_bf16(v[px]);
-      else
-        ((float*)k.gm)[o] = v[px];
+      cj_store(k, k.gm, base + (long long)n * k.P + 4 * pq + px, v[px]);
     }
   }
 }

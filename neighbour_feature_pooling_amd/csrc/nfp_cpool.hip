@@ -25,8 +25,10 @@
 //                   ds_read_b128 along p (four pixels of one map per read, eight FMAs); the eight wavefronts split the pixels
 //   cpool_bwd_part  the same walk over a slice of the batch: T and grad_beta of the slice for the workgroup's channels
 //   cpool_bwd_reduce  one workgroup per 32 channels: the slices in order, the parameter gradients, this tile's share of k, Q
-//   cpool_bwd_maps  lanes along 64 pixels (their c_n in registers); D in blocks of 128 channels whose scaled rows are staged in
-//                   LDS and dealt to the wavefronts, joined in wave order through LDS; then - k - Q c
+//   cp_bwd_maps     lanes along 64 pixels (their c_n in registers); D in blocks of 128 channels whose scaled rows are staged in
+//                   LDS and dealt to the wavefronts, joined in wave order through LDS; then - k - Q c.  One template over
+//                   where a channel's factor comes from (CpGrad): here G_bd / P from the block's table — launched as
+//                   "cpool_bwd_maps"
 //
 // The same projection with the map kept — nfp_cproj_* (NFPInsert's nfp_proj, models/mobilenetv3.py:346-350; NFPBottleneck's
 // bn2(conv2(.)), nfp_heads.py:270-272): out_bdp = [relu](a_bdp) stored as [B,D,P] in the maps' dtype, and a backward given
@@ -38,12 +40,14 @@
 //                   store adjacent pixels of a channel (or run on into the next channel where the chunk is the whole image)
 //   cproj_bwd_part  cpool_bwd_part's lanes along d, over a slice of the batch's 64-pixel passes: the pass's maps and the
 //                   [128 channels][64 pixels] tile of grad_out go to LDS with lanes along p (whole lines), and are read back
-//                   as a float4 per channel
-//   cproj_bwd_maps  cpool_bwd_maps with grad_out read per (channel, pixel), lanes along p, four channels' loads in flight
+//                   as a float4 per channel; the sums into T, the join and part_w are cpool_bwd_part's (cp_part_sum,
+//                   cp_part_join)
+//   cp_bwd_maps     with grad_out read per (channel, pixel), lanes along p, four channels' loads in flight — launched as
+//                   "cproj_bwd_maps"
 // Channels-last out / grad_out, [b][p][d] (nfp_cproj_*_fmt, NFP_ACT_NHWC; the maps stay [B,N,P], the statistics kernels are
-// the same launches): cproj_fwd_nhwc — the same chain per element, lanes along the chunk's [p][d] range — and the NHWC
-// instantiations of cproj_bwd_part / cproj_bwd_maps, which bring their grad_out tile into LDS with d fastest and are the
-// NCHW kernels behind that: the same sums in the same order.
+// the same launches): cproj_fwd's NHWC instantiations — the same kernel, lanes along the chunk's [p][d] range, launched as
+// "cproj_fwd_nhwc" — and those of cproj_bwd_part / cp_bwd_maps ("cproj_bwd_part_nhwc", "cproj_bwd_maps_nhwc"), which bring
+// their grad_out tile into LDS with d fastest: the same sums in the same order.
 //
 // Statistics over the batches of several ranks (nn.SyncBatchNorm) — nfp_cpsync_*: the same step in four stages around two
 // gathers the caller makes.  The main forward, *_bwd_part and *_bwd_maps kernels above serve unchanged; what is added:
@@ -357,7 +361,7 @@ int cps_joined_stats(const CpCall& c, const nfp::CpK& k, const double* records, 
   return launch("cps_finish", nfp::cps_finish, dim3((unsigned)((k.D + nfp::kCpFT - 1) / nfp::kCpFT)), dim3(nfp::kCpFT), 0,
                 cp_stream(c), k, records, (int)world);
 }
-// The main forward under the statistics k names: cpool_fwd, cpw_fwd, or cproj_fwd / cproj_fwd_nhwc over chunks of their own
+// The main forward under the statistics k names: cpool_fwd, cpw_fwd, or cproj_fwd (either layout) over chunks of its own
 int cp_main_forward(const CpCall& c, nfp::CpK& k) {
   const int NP = cp_np(c);
   hipStream_t st = cp_stream(c);
@@ -376,18 +380,18 @@ int cp_main_forward(const CpCall& c, nfp::CpK& k) {
   const int tiles = (k.D + nfp::kCjDT - 1) / nfp::kCjDT;
   const size_t lds = ((size_t)NP * k.CHs + (size_t)nfp::kCjDT * (NP + 1)) * sizeof(float);
   const dim3 grid((unsigned)((long long)k.B * k.nc * tiles));
-  // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd_nhwc)
+  // two bf16 elements per lane where every pair is an aligned dword of one tile (cproj_fwd's PAIR)
   const bool pair = k.bf16 && ((uintptr_t)k.outv & 3) == 0 && (tiles == 1 || (k.D & 1) == 0);
   return with_np(c, [&](auto np) {
     return with_act(c, [&](auto relu, auto nhwc) {
       constexpr int kNP = decltype(np)::value;
       constexpr bool kRelu = decltype(relu)::value;
       if constexpr (!decltype(nhwc)::value)
-        return launch("cproj_fwd", nfp::cproj_fwd<kNP, kRelu>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+        return launch("cproj_fwd", nfp::cproj_fwd<kNP, kRelu, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
       else if (pair)
-        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<kNP, kRelu, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+        return launch("cproj_fwd_nhwc", nfp::cproj_fwd<kNP, kRelu, true, true>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
       else
-        return launch("cproj_fwd_nhwc", nfp::cproj_fwd_nhwc<kNP, kRelu, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
+        return launch("cproj_fwd_nhwc", nfp::cproj_fwd<kNP, kRelu, true, false>, grid, dim3(nfp::kCjT), lds, st, k, tiles);
     });
   });
 }
@@ -449,11 +453,12 @@ int cp_grad_maps(const CpCall& c, const nfp::CpK& k) {
   }
   return with_np(c, [&](auto np) {
     constexpr int kNP = decltype(np)::value;
-    if (c.kind == kCpPool) return launch("cpool_bwd_maps", nfp::cpool_bwd_maps<kNP>, grid, dim3(nfp::kCpT), 0, st, k, npt);
+    if (c.kind == kCpPool)
+      return launch("cpool_bwd_maps", nfp::cp_bwd_maps<kNP, nfp::kCpGradPooled, true>, grid, dim3(nfp::kCpT), 0, st, k, npt);
     return with_act(c, [&](auto relu, auto nhwc) {
-      constexpr bool kNhwc = decltype(nhwc)::value;
-      return launch(kNhwc ? "cproj_bwd_maps_nhwc" : "cproj_bwd_maps", nfp::cproj_bwd_maps<kNP, decltype(relu)::value, kNhwc>, grid,
-                    dim3(nfp::kCpT), 0, st, k, npt);
+      constexpr nfp::CpGrad kSrc = decltype(nhwc)::value ? nfp::kCpGradNhwc : nfp::kCpGradNchw;
+      return launch(kSrc == nfp::kCpGradNhwc ? "cproj_bwd_maps_nhwc" : "cproj_bwd_maps",
+                    nfp::cp_bwd_maps<kNP, kSrc, decltype(relu)::value>, grid, dim3(nfp::kCpT), 0, st, k, npt);
     });
   });
 }

@@ -35,6 +35,7 @@ CASES = {
     "one_image": ((1, 8, 7, 7), 32, 0, "B = 1"),
     "zero_row": ((4, 8, 7, 7), 32, 2, "an all-zero weight row: var = 0, a = beta"),
     "offset": ((4, 8, 7, 7), 32, 0, "maps = 10 + 0.1 randn"),
+    "n12": ((3, 12, 6, 5), 70, 1, "12 maps: the NP = 16 instantiations"),
 }
 
 

@@ -36,6 +36,7 @@ CASES = {
     "zero_row": ((4, 8, 7, 7), 32, 2, "an all-zero weight row: var = 0, a = beta"),
     "offset": ((4, 8, 7, 7), 32, 0, "maps = 10 + 0.1 randn"),
     "tiny_d": ((2, 8, 9, 9), 5, 0, "D smaller than any tile"),
+    "n12": ((3, 12, 6, 5), 70, 1, "12 maps: the NP = 16 instantiations"),
 }
 BF16_CASES = ("common", "n32_nonsquare")
 
