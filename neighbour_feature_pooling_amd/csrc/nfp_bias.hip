@@ -126,38 +126,16 @@ __global__ void __launch_bounds__(kBiasT) bias_fwd(const KP g, int dw, int OT, i
   }
 }
 
-template <int M> struct NCoefB { static constexpr int v = 1; };
-template <> struct NCoefB<NFP_COSINE> { static constexpr int v = 3; };
-template <> struct NCoefB<NFP_GFC> { static constexpr int v = 3; };
-template <> struct NCoefB<NFP_SMITH> { static constexpr int v = 3; };
-template <> struct NCoefB<NFP_PEARSON> { static constexpr int v = 5; };
-
 template <int M>
 __global__ void __launch_bounds__(kBiasT) bias_coef(const KP g, const void* __restrict__ go, const void* __restrict__ out,
                                                     const float* __restrict__ saved, float* __restrict__ cf) {
-  constexpr int NS = Meas<M>::NSTAT, NC = NCoefB<M>::v;
+  constexpr int NS = Meas<M>::NSTAT;
   const long long BNO = (long long)g.B * g.N * g.O;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < BNO; i += (long long)gridDim.x * blockDim.x) {
     const float sp0 = NS > 0 ? saved[i] : 0.f, sp1 = NS > 1 ? saved[BNO + i] : 0.f;
     const float sq0 = NS > 0 ? saved[NS * BNO + i] : 0.f, sq1 = NS > 1 ? saved[(NS + 1) * BNO + i] : 0.f;
-    const Coef c = Meas<M>::coef(ldx(go, i, g.godtype), ldx(out, i, g.odtype), sp0, sp1, sq0, sq1, g);
-    cf[i] = c.k0;
-    if (NC > 1) cf[BNO + i] = c.k1;
-    if (NC > 2) cf[2 * BNO + i] = c.k2;
-    if (NC > 3) cf[3 * BNO + i] = c.k3;
-    if (NC > 4) cf[4 * BNO + i] = c.k4;
+    store_coef<M>(cf, BNO, i, Meas<M>::coef(ldx(go, i, g.godtype), ldx(out, i, g.odtype), sp0, sp1, sq0, sq1, g));
   }
-}
-
-template <int M>
-__device__ __forceinline__ Coef load_coef_b(const float* cf, long long BNO, long long i) {
-  constexpr int NC = NCoefB<M>::v;
-  Coef c = {cf[i], 0.f, 0.f, 0.f, 0.f};
-  if (NC > 1) c.k1 = cf[BNO + i];
-  if (NC > 2) c.k2 = cf[2 * BNO + i];
-  if (NC > 3) c.k3 = cf[3 * BNO + i];
-  if (NC > 4) c.k4 = cf[4 * BNO + i];
-  return c;
 }
 
 // output coordinate oa that reads unpadded coordinate tc through tap d along an axis of `no` outputs, or -1
@@ -222,7 +200,7 @@ __global__ void __launch_bounds__(kBiasT) bias_gx(const KP g, int dw, const void
                                      ? ldx(x, cbase + (long long)qy * g.sH + (long long)qx * g.sW, g.dtype) : 0.f;
                 const float v = (dw ? xr - xq : xq) + beta[c * g.N + n];
                 float da, db;
-                Meas<M>::grad(a, v, load_coef_b<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
+                Meas<M>::grad(a, v, load_coef<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
                 acc += dw ? da + db : da;
               }
             } else {  // r is neighbour n of output o
@@ -232,7 +210,7 @@ __global__ void __launch_bounds__(kBiasT) bias_gx(const KP g, int dw, const void
                                    ? ldx(x, cbase + (long long)cy * g.sH + (long long)cx * g.sW, g.dtype) : 0.f;
               const float v = (dw ? xa - xr : xr) + beta[c * g.N + n];
               float da, db;
-              Meas<M>::grad(xa + bcc, v, load_coef_b<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
+              Meas<M>::grad(xa + bcc, v, load_coef<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
               acc += dw ? -db : db;
             }
           }
@@ -285,7 +263,7 @@ __global__ void __launch_bounds__(kBiasT) bias_part(const KP g, int dw, const vo
                              ? ldx(x, cbase + (long long)qy * g.sH + (long long)qx * g.sW, g.dtype) : 0.f;
         const float v = (dw ? xa - xq : xq) + bn;
         float da, db;
-        Meas<M>::grad(xa + bcc, v, load_coef_b<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
+        Meas<M>::grad(xa + bcc, v, load_coef<M>(cf, BNO, ((long long)b * g.N + n) * g.O + o), g, da, db);
         sdb += db;
         sda += da;
       }

@@ -12,50 +12,61 @@
 //   * "neighbour role": for every (o, n) whose neighbour tap lands on r:
 //                       d out[n,o] / d b   with a = x[c][centre(o)],  b = x[c][r]
 // The adjoint of pad / stride / dilation is an inverse index map.  It depends on the geometry only and is
-// separable, so each workgroup inverts it analytically into one short reader list per ROW and per COLUMN in LDS;
-// the readers of pixel (ry, rx) are the product of the two lists, walked in a fixed order.  Next to them sits a
-// table of the per-pair backward scalars Meas<M>::coef (grad_out, saved output and saved per-pixel stats enter only
-// here).  Thread (pixel, 16 channels) then accumulates grad_x in registers — one ds_read_b128 serves four
-// pair-gradients, nothing is scattered — and stores it directly.  The LDS-atomic kernel
-// (nfp_generic.h::bwd_generic) stays as the last resort (circular / over-padded maps beyond the LDS tables).
+// separable, so each workgroup inverts it analytically (axis_reader_raw) into one short reader list per ROW and per
+// COLUMN in LDS (pack_reader); the readers of pixel (ry, rx) are the product of the two lists, walked in a fixed
+// order.  Next to them sits a table of the per-pair backward scalars Meas<M>::coef (gather_pair_tables: grad_out,
+// saved output and saved per-pixel stats enter only here).  Thread (pixel, 16 channels) then accumulates grad_x in
+// registers — one ds_read_b128 serves four pair-gradients, nothing is scattered — and stores it directly
+// (gather_channels over gather_item).
+// Both kernels are that one structure over a BAND: rows ra .. ra+nr-1 of grad_x, the Ol outputs from output row oya
+// on that read them (local pair index j' = n*Ol + o'), and the window of np pixels of x from row w0 on that those
+// pairs pair the band with.  bwd_gather is the band (0, H) with (Ol, oya) = (O, 0) and (w0, np) = (0, P); what the two
+// kernels keep apart is scheduling: how the slots are compacted into lists and when the first slab is staged.
+// nfp_direct.h::bwd_direct stays as the last resort (maps beyond the LDS tables of both).
 #pragma once
 #include "nfp_measures.h"
 
 namespace nfp {
 
-// floats of Coef that Meas<M>::grad reads
-template <int M> struct NCoef { static constexpr int v = 1; };
-template <> struct NCoef<NFP_COSINE> { static constexpr int v = 3; };
-template <> struct NCoef<NFP_GFC> { static constexpr int v = 3; };
-template <> struct NCoef<NFP_SMITH> { static constexpr int v = 3; };
-template <> struct NCoef<NFP_PEARSON> { static constexpr int v = 5; };
-
-// LDS word offsets of the tables (host: launch_bwd_gather in nfp_generic.hip)
+// LDS word offsets of the tables (host: gather_layout in nfp_generic.hip).  bwd_gather: RB = H, ONm = O * N,
+// PSm = P + 1.
 struct GatherLds {
-  int ON;          // O * N pairs
-  int cf;          // float [NC][ON]  coefficient k of pair j = n*O + o at cf + k*ON + j
-  int nbq;         // u16   [ON]      neighbour pixel of pair j (P = zero padding: the slab's zero pixel)
-  int yl, xl;      // uint2 [H][capY] / [W][capX]  per-row / per-column reader lists (see axis_reader)
-  int yc, xc;      // u32   [H] / [W]              their lengths | number of leading centre-tap readers << 16
+  int RB;          // input rows per band
+  int ONm;         // bound on the band's N * Ol pairs
+  int cf;          // float [NC][ON]  coefficient k of pair j = n*Ol + o at cf + k*ON + j
+  int nbq;         // u16   [ON]      neighbour pixel of pair j in the window (np = zero padding: the slab's zero pixel)
+  int yl, xl;      // uint2 [RB][capY] / [W][capX]  per-row / per-column reader lists (see pack_reader)
+  int yc, xc;      // u32   [RB] / [W]              their lengths | number of leading centre-tap readers << 16
   int capY, capX;
-  int sl;          // uint2 [(H + W)][(2*pad + 1)*k]  uncompacted reader slots
-  int Ts;          // threads (whole wavefronts) that stage the first slab while the others build the tables
-  int xs;          // float4 slab [Cq][P + 1] (word offset, multiple of 4); pixel P of every quad is 0
+  int mm;          // banded: int [4] min / max output row reading the band, min / max x row needed
+  int sl;          // bwd_gather: uint2 [(H + W)][(2*pad + 1)*k] uncompacted reader slots (banded: in the slab area,
+                   // until the first slab is staged)
+  int Ts;          // bwd_gather: threads (whole wavefronts) that stage the first slab while the others build the tables
+  int xs;          // float4 slab [Cq][PSm] (word offset, multiple of 4); the last pixel of every quad's window is 0
+  int PSm;         // bound on window pixels + 1
   int Cq;          // channel quads per slab
   int Qwg;         // channel quads per workgroup
+};
+
+// the tables of a workgroup
+struct GatherTabs {
+  float* cf;
+  unsigned short* nbq;
+  uint2 *yl, *xl;
+  unsigned *yc, *xc;
+  float4* xs;
+  __device__ __forceinline__ GatherTabs(float* lds, const GatherLds& L)
+      : cf(lds + L.cf), nbq((unsigned short*)(lds + L.nbq)), yl((uint2*)(lds + L.yl)), xl((uint2*)(lds + L.xl)),
+        yc((unsigned*)(lds + L.yc)), xc((unsigned*)(lds + L.xc)), xs((float4*)(lds + L.xs)) {}
 };
 
 constexpr unsigned kNoCentre = 0x10000u;  // added to a centre-pixel part: the sum then exceeds every pixel index
 
 // The inverse of pad -> strided, dilated taps is separable.  Along one axis of size n (no outputs), slot
 // (ic, d) of coordinate i asks: does tap d of some output oa read i through padded coordinate tc(ic)?
-// tc(0) = i, then the left and right margins.  A reader is stored as the two addends the channel loop
-// needs, so that a (row reader, column reader) pair costs a handful of integer instructions:
-//   .x  part of the pair index j = n*O + o:      rows d*k*O + oa*Wo,       columns d*O + oa
-//   .y  part of the centre pixel of output o:    rows ca*W,  columns ca    (kNoCentre: zero padding)
-//       | part of the tap index << 20:           rows d*k,   columns d
-// (j still needs "- O if tap > centre tap", the centre itself is not a neighbour).
-__device__ __forceinline__ uint2 axis_reader(const KP& g, int i, int n, int no, int ic, int d, bool rows) {
+// tc(0) = i, then the left and right margins.  The raw hit is {d | oa << 8, ca} or {0xFFFFFFFF, -}; ca is the
+// centre coordinate of output oa, -1: in zero padding.
+__device__ __forceinline__ uint2 axis_reader_raw(const KP& g, int i, int n, int no, int ic, int d) {
   uint2 e = make_uint2(0xFFFFFFFFu, 0u);
   const int tc = ic == 0 ? i : (ic <= g.pad ? -ic : n - 1 + (ic - g.pad));
   if (ic > 0 && map_index(tc, n, g.mode) != i) return e;
@@ -63,12 +74,30 @@ __device__ __forceinline__ uint2 axis_reader(const KP& g, int i, int n, int no, 
   if (nn < 0) return e;
   const int oa = g.stride == 1 ? nn : fdivi(nn, g.stride);
   if (oa * g.stride != nn || oa >= no) return e;
-  const int ca = map_index(oa * g.stride + g.R * g.dil - g.pad, n, g.mode);
-  e.x = rows ? (unsigned)(d * g.k * g.O + oa * g.Wo) : (unsigned)(d * g.O + oa);
-  e.y = (ca < 0 ? kNoCentre : (unsigned)(rows ? ca * g.W : ca)) | ((unsigned)(rows ? d * g.k : d) << 20);
+  e.x = (unsigned)d | ((unsigned)oa << 8);
+  e.y = (unsigned)map_index(oa * g.stride + g.R * g.dil - g.pad, n, g.mode);
   return e;
 }
-
+// raw hit of slot s of the slot table [rows ra .. ra+nr-1, then every column][(2*pad + 1)*k]; rows: which axis
+__device__ __forceinline__ uint2 slot_reader(const KP& g, int s, int nslot, int ra, int nr, bool& rows) {
+  const int i = fdivi(s, nslot), w = s - i * nslot, ic = fdivi(w, g.k), d = w - ic * g.k;
+  rows = i < nr;
+  return rows ? axis_reader_raw(g, ra + i, g.H, g.Ho, ic, d) : axis_reader_raw(g, i - nr, g.W, g.Wo, ic, d);
+}
+// A list entry is a raw hit as the two addends the channel loop needs, so that a (row reader, column reader) pair
+// costs a handful of integer instructions; for the band of Ol outputs from output row oya, window from row w0:
+//   .x  part of the pair index j = n*Ol + o:     rows d*k*Ol + (oa - oya)*Wo,  columns d*Ol + oa
+//   .y  part of the centre pixel of output o:    rows (ca - w0)*W,  columns ca    (kNoCentre: zero padding)
+//       | part of the tap index << 20:           rows d*k,          columns d
+// (j still needs "- Ol if tap > centre tap", the centre itself is not a neighbour).
+__device__ __forceinline__ uint2 pack_reader(const KP& g, uint2 e, bool rows, int Ol, int oya, int w0) {
+  const unsigned d = e.x & 0xFFu;
+  const int oa = (int)(e.x >> 8), ca = (int)e.y;
+  if (rows)
+    return make_uint2((unsigned)((int)d * g.k * Ol + (oa - oya) * g.Wo),
+                      (ca < 0 ? kNoCentre : (unsigned)((ca - w0) * g.W)) | ((d * (unsigned)g.k) << 20));
+  return make_uint2((unsigned)((int)d * Ol + oa), (ca < 0 ? kNoCentre : (unsigned)ca) | (d << 20));
+}
 
 // x[b, 4*qc0 : 4*(qc0+cqn), pixels p0 .. p0+np-1] -> LDS float4[cq][np + 1] (local pixel np of every quad is
 // the zero a zero-padded tap reads); any strides, f32 or bf16; channels past C are 0.  With a pivot table the slab
@@ -197,18 +226,6 @@ __device__ __forceinline__ void stage_quads(float4* xs, const void* x, const KP&
     stage_quads_t<true>(xs, x, g, b, qc0, cqn, piv, p0, np, t, T);
 }
 
-template <int M>
-__device__ __forceinline__ Coef load_coef(const float* cf, int ON, int j) {
-  constexpr int NC = NCoef<M>::v;
-  Coef c = {0.f, 0.f, 0.f, 0.f, 0.f};
-  c.k0 = cf[j];
-  if (NC > 1) c.k1 = cf[ON + j];
-  if (NC > 2) c.k2 = cf[2 * ON + j];
-  if (NC > 3) c.k3 = cf[3 * ON + j];
-  if (NC > 4) c.k4 = cf[4 * ON + j];
-  return c;
-}
-
 // grad_x of one (pixel, QB channel quads) item: centre role + neighbour role over the pixel's reader lists.
 // Two pairs are in flight per step (index -> coefficient / slab reads -> arithmetic is a chain of LDS latencies;
 // N = k*k - 1 is a multiple of 8, so the centre loop needs no remainder).
@@ -297,6 +314,85 @@ __device__ __forceinline__ void gather_item(const KP& g, const float4* const (&s
   }
 }
 
+// cf / nbq of this image's pairs j = n*Ol + o', o' = o - o_base, for the window of np pixels from pixel p0; threads
+// tt of TT.  A neighbour outside the window (read only for outputs centred in the band, whose neighbours are inside
+// it by construction) or in zero padding -> the zero pixel np.
+template <int M>
+__device__ __forceinline__ void gather_pair_tables(const KP& g, int b, const void* go, const void* out,
+                                                   const float* saved, float* cf, unsigned short* nbq, int o_base,
+                                                   int Ol, int p0, int np, int tt, int TT) {
+  const float* sv = (Meas<M>::NSTAT > 0) ? saved + (long long)b * Meas<M>::NSTAT * g.P : nullptr;
+  const int ON = Ol * g.N;
+  for (int j = tt; j < ON; j += TT) {
+    const int n = fdivi(j, Ol), o = o_base + (j - n * Ol);
+    const int q = nbr_pixel(g, o, n), pc = tap_pixel(g, o, g.R, g.R);
+    const long long oi = ((long long)b * g.N + n) * g.O + o;
+    const float sp0 = (Meas<M>::NSTAT > 0 && pc >= 0) ? sv[pc] : 0.f;
+    const float sp1 = (Meas<M>::NSTAT > 1 && pc >= 0) ? sv[g.P + pc] : 0.f;
+    const float sq0 = (Meas<M>::NSTAT > 0 && q >= 0) ? sv[q] : 0.f;
+    const float sq1 = (Meas<M>::NSTAT > 1 && q >= 0) ? sv[g.P + q] : 0.f;
+    store_coef<M>(cf, ON, j, Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, sq0, sq1, g));
+    const int ql = q - p0;
+    nbq[j] = (unsigned short)((q < 0 || ql < 0 || ql >= np) ? np : ql);
+  }
+}
+
+// the up to four channels c .. c+3 of a quad of grad_x, channel c at element `base`
+__device__ __forceinline__ void store_quad(void* gx, const KP& g, long long base, int c, const float4& v) {
+  stx(gx, base, v.x, g.dtype);
+  if (c + 1 < g.C) stx(gx, base + g.sC, v.y, g.dtype);
+  if (c + 2 < g.C) stx(gx, base + 2 * g.sC, v.z, g.dtype);
+  if (c + 3 < g.C) stx(gx, base + 3 * g.sC, v.w, g.dtype);
+}
+
+// The channel loop over quads [q_begin, q_end): slab by slab, stage the window (np pixels from row w0) and let thread
+// (band pixel, QB quads) gather its grad_x from the band's tables (rows ra .. ra+nr-1, Ol local outputs).  staged:
+// the caller has staged the first slab already.
+template <int M, int QB>
+__device__ __forceinline__ void gather_channels(const KP& g, const GatherLds& L, const GatherTabs& tb, const void* x,
+                                                void* gx, int q_begin, int q_end, int ra, int nr, int w0, int np,
+                                                int Ol, bool staged) {
+  const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
+  const int ON = Ol * g.N, PS = np + 1, nbp = nr * g.W;  // pairs, slab pitch, band pixels
+  const unsigned mid = (unsigned)((g.k * g.k) >> 1);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  NFP_STAMP_INIT();
+  for (int qc0 = q_begin; qc0 < q_end; qc0 += L.Cq) {
+    const int cqn = min(L.Cq, q_end - qc0);
+    const bool first = staged && qc0 == q_begin;
+    __syncthreads();  // tables (and first slab) complete, slots consumed / previous slab consumed
+    if (first) NFP_STAMP(4);
+    if (!first) {
+      stage_quads(tb.xs, x, g, b, qc0, cqn, nullptr, w0 * g.W, np, t, T);
+      __syncthreads();
+    }
+    if (first) NFP_STAMP(5);
+    const int nqb = (cqn + QB - 1) / QB;
+    for (int i = t; i < nqb * nbp; i += T) {
+      const int qb = fdivi(i, nbp), rl = i - qb * nbp;
+      const int ryl = fdivi(rl, g.W), rx = rl - ryl * g.W, ry = ra + ryl;
+      const int r = (ry - w0) * g.W + rx;  // window pixel of this band pixel
+      const float4* slab[QB];
+      float4 a[QB], acc[QB];
+#pragma unroll
+      for (int u = 0; u < QB; ++u) {
+        slab[u] = tb.xs + min(qb * QB + u, cqn - 1) * PS;  // clamped: the surplus quad is computed, never stored
+        a[u] = slab[u][r];
+        acc[u] = zero4;
+      }
+      gather_item<M, QB>(g, slab, a, acc, tb.yl + ryl * L.capY, tb.xl + rx * L.capX, tb.yc[ryl], tb.xc[rx], tb.cf, ON,
+                         tb.nbq, Ol, (unsigned)np, mid);
+#pragma unroll
+      for (int u = 0; u < QB; ++u) {
+        const int cq = qb * QB + u, c = 4 * (qc0 + cq);
+        if (cq < cqn)
+          store_quad(gx, g, (long long)b * g.gB + (long long)c * g.sC + (long long)ry * g.sH + (long long)rx * g.sW, c,
+                     acc[u]);
+      }
+    }
+  }
+}
+
 #ifndef NFP_GATHER_T
 #define NFP_GATHER_T 512
 #endif
@@ -305,53 +401,30 @@ __global__ void __launch_bounds__(NFP_GATHER_T) bwd_gather(const KP g, const Gat
                                                   const void* __restrict__ go, const void* __restrict__ out,
                                                   const float* __restrict__ saved, void* __restrict__ gx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int NC = NCoef<M>::v;
-  float* cf = lds + L.cf;
-  unsigned short* nbq = (unsigned short*)(lds + L.nbq);
-  uint2* yl = (uint2*)(lds + L.yl);
-  uint2* xl = (uint2*)(lds + L.xl);
-  unsigned* yc = (unsigned*)(lds + L.yc);
-  unsigned* xc = (unsigned*)(lds + L.xc);
-  float4* xs = (float4*)(lds + L.xs);
+  const GatherTabs tb(lds, L);
   const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
-  const int ON = L.ON, PS = g.P + 1;
-  const float* sv = (Meas<M>::NSTAT > 0) ? saved + (long long)b * Meas<M>::NSTAT * g.P : nullptr;
   NFP_STAMP_INIT();
   NFP_STAMP(0);
 
   // The first L.Ts threads stage the first slab; the others build the tables meanwhile.  Each part is one or two
   // passes of dependent work (index arithmetic; global load -> arithmetic -> LDS), i.e. latency, not throughput:
   // side by side they cost the longer of the two instead of the sum.
-  const int Q = (g.C + 3) >> 2;
-  const int q_begin = blockIdx.y * L.Qwg, q_end = min(Q, q_begin + L.Qwg);
+  const int q_begin = blockIdx.y * L.Qwg, q_end = min((g.C + 3) >> 2, q_begin + L.Qwg);
   const int nslot = (2 * g.pad + 1) * g.k;
   uint2* slots = (uint2*)(lds + L.sl);
-  if (t < L.Ts) {
-    stage_quads(xs, x, g, b, q_begin, min(L.Cq, q_end - q_begin), nullptr, 0, g.P, t, L.Ts);
+  const int Ts = L.Ts;  // one read: stage_quads is compiled knowing its thread count exceeds a thread index, so is > 0
+  if (t < Ts) {
+    stage_quads(tb.xs, x, g, b, q_begin, min(L.Cq, q_end - q_begin), nullptr, 0, g.P, t, Ts);
   } else {
-    const int tt = t - L.Ts, TT = T - L.Ts;
-    // ---- tables: reader slots of every row and column (geometry only), one slot per thread ---------------
+    const int tt = t - Ts, TT = T - Ts;
+    // ---- tables: reader slots of every row and column (geometry only), one slot per thread, packed here ----
     for (int s = tt; s < (g.H + g.W) * nslot; s += TT) {
-      const int i = fdivi(s, nslot), w = s - i * nslot, ic = fdivi(w, g.k), d = w - ic * g.k;
-      slots[s] = i < g.H ? axis_reader(g, i, g.H, g.Ho, ic, d, true) : axis_reader(g, i - g.H, g.W, g.Wo, ic, d, false);
+      bool rows;
+      const uint2 e = slot_reader(g, s, nslot, 0, g.H, rows);
+      slots[s] = e.x == 0xFFFFFFFFu ? e : pack_reader(g, e, rows, g.O, 0, 0);
     }
     // ---- tables: per-pair coefficients and neighbour pixels (this image) ----------------------------------
-    for (int j = tt; j < ON; j += TT) {
-      const int n = fdivi(j, g.O), o = j - n * g.O;
-      const int q = nbr_pixel(g, o, n), pc = tap_pixel(g, o, g.R, g.R);
-      const long long oi = ((long long)b * g.N + n) * g.O + o;
-      const float sp0 = (Meas<M>::NSTAT > 0 && pc >= 0) ? sv[pc] : 0.f;
-      const float sp1 = (Meas<M>::NSTAT > 1 && pc >= 0) ? sv[g.P + pc] : 0.f;
-      const float sq0 = (Meas<M>::NSTAT > 0 && q >= 0) ? sv[q] : 0.f;
-      const float sq1 = (Meas<M>::NSTAT > 1 && q >= 0) ? sv[g.P + q] : 0.f;
-      const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, sq0, sq1, g);
-      cf[j] = c.k0;
-      if (NC > 1) cf[ON + j] = c.k1;
-      if (NC > 2) cf[2 * ON + j] = c.k2;
-      if (NC > 3) cf[3 * ON + j] = c.k3;
-      if (NC > 4) cf[4 * ON + j] = c.k4;
-      nbq[j] = (unsigned short)(q < 0 ? g.P : q);
-    }
+    gather_pair_tables<M>(g, b, go, out, saved, tb.cf, tb.nbq, 0, g.O, 0, g.P, tt, TT);
   }
   NFP_STAMP(2);
   __syncthreads();
@@ -359,7 +432,7 @@ __global__ void __launch_bounds__(NFP_GATHER_T) bwd_gather(const KP g, const Gat
   // pair of two of them makes this pixel the centre of an output), then the others, each in slot order.
   // One wavefront per list: lane = slot, position = running count + popcount of the ballot below the lane.
   for (int i = t >> 6; i < g.H + g.W; i += T >> 6) {
-    uint2* list = i < g.H ? yl + i * L.capY : xl + (i - g.H) * L.capX;
+    uint2* list = i < g.H ? tb.yl + i * L.capY : tb.xl + (i - g.H) * L.capX;
     const unsigned ctap = (unsigned)(i < g.H ? g.R * g.k : g.R);
     const int lane = t & 63;
     unsigned cnt = 0, ncentre = 0;
@@ -377,54 +450,13 @@ __global__ void __launch_bounds__(NFP_GATHER_T) bwd_gather(const KP g, const Gat
     }
     if (lane == 0) {
       if (i < g.H)
-        yc[i] = cnt | (ncentre << 16);
+        tb.yc[i] = cnt | (ncentre << 16);
       else
-        xc[i - g.H] = cnt | (ncentre << 16);
+        tb.xc[i - g.H] = cnt | (ncentre << 16);
     }
   }
   NFP_STAMP(3);
-
-  // ---- channel loop ------------------------------------------------------------------------------------
-  const unsigned mid = (unsigned)((g.k * g.k) >> 1);
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int qc0 = q_begin; qc0 < q_end; qc0 += L.Cq) {
-    const int cqn = min(L.Cq, q_end - qc0);
-    __syncthreads();  // tables and first slab complete / previous slab consumed
-    if (qc0 == q_begin) NFP_STAMP(4);
-    if (qc0 != q_begin) {
-      stage_quads(xs, x, g, b, qc0, cqn, nullptr, 0, g.P, t, T);
-      __syncthreads();
-    }
-    if (qc0 == q_begin) NFP_STAMP(5);
-    const int nqb = (cqn + QB - 1) / QB;
-    for (int i = t; i < nqb * g.P; i += T) {
-      const int qb = fdivi(i, g.P), r = i - qb * g.P;
-      const int ry = fdivi(r, g.W), rx = r - ry * g.W;
-      const float4* slab[QB];
-      float4 a[QB], acc[QB];
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        slab[u] = xs + min(qb * QB + u, cqn - 1) * PS;  // clamped: the surplus quad is computed, never stored
-        a[u] = slab[u][r];
-        acc[u] = zero4;
-      }
-      const uint2* yrow = yl + ry * L.capY;
-      const uint2* xrow = xl + rx * L.capX;
-      gather_item<M, QB>(g, slab, a, acc, yrow, xrow, yc[ry], xc[rx], cf, ON, nbq, g.O, (unsigned)g.P, mid);
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        const int cq = qb * QB + u;
-        if (cq < cqn) {
-          const int c = 4 * (qc0 + cq);
-          const long long base = (long long)b * g.gB + (long long)c * g.sC + (long long)ry * g.sH + (long long)rx * g.sW;
-          stx(gx, base, acc[u].x, g.dtype);
-          if (c + 1 < g.C) stx(gx, base + g.sC, acc[u].y, g.dtype);
-          if (c + 2 < g.C) stx(gx, base + 2 * g.sC, acc[u].z, g.dtype);
-          if (c + 3 < g.C) stx(gx, base + 3 * g.sC, acc[u].w, g.dtype);
-        }
-      }
-    }
-  }
+  gather_channels<M, QB>(g, L, tb, x, gx, q_begin, q_end, 0, g.H, 0, g.P, g.O, true);
   NFP_STAMP(6);
 }
 
@@ -436,48 +468,16 @@ __global__ void __launch_bounds__(NFP_GATHER_T) bwd_gather(const KP g, const Gat
 // over the lists and over the pairs), the launcher only bounds them: for non-circular padding with
 // pad <= R*dilation an output reads rows within R*dilation of its centre and padding folds back inside that
 // window, so oyb - oya + 1 <= (RB - 1 + 2*R*dil)/stride + 2 and w1 - w0 + 1 <= RB + 2*R*dil.
-struct BandLds {
-  int RB;          // input rows per band
-  int ONm;         // bound on N * O'
-  int cf, nbq;     // as GatherLds, sized for ONm
-  int yl, xl, yc, xc, capY, capX;  // row lists for RB rows, column lists for W columns
-  int mm;          // int [4]: min / max output row reading the band, min / max x row needed
-  int xs;          // float4 slab [Cq][PSm]; the raw reader slots live here until the first slab is staged
-  int PSm;         // bound on window pixels + 1
-  int Cq, Qwg;
-};
-
-// raw reader of axis coordinate i: {d | oa << 8, ca} or {0xFFFFFFFF, -}; ca = -1: centre in zero padding
-__device__ __forceinline__ uint2 axis_reader_raw(const KP& g, int i, int n, int no, int ic, int d) {
-  uint2 e = make_uint2(0xFFFFFFFFu, 0u);
-  const int tc = ic == 0 ? i : (ic <= g.pad ? -ic : n - 1 + (ic - g.pad));
-  if (ic > 0 && map_index(tc, n, g.mode) != i) return e;
-  const int nn = tc + g.pad - d * g.dil;
-  if (nn < 0) return e;
-  const int oa = g.stride == 1 ? nn : fdivi(nn, g.stride);
-  if (oa * g.stride != nn || oa >= no) return e;
-  e.x = (unsigned)d | ((unsigned)oa << 8);
-  e.y = (unsigned)map_index(oa * g.stride + g.R * g.dil - g.pad, n, g.mode);
-  return e;
-}
-
 template <int M, int QB>
-__global__ void __launch_bounds__(512) bwd_gather_banded(const KP g, const BandLds L, const void* __restrict__ x,
+__global__ void __launch_bounds__(512) bwd_gather_banded(const KP g, const GatherLds L, const void* __restrict__ x,
                                                          const void* __restrict__ go, const void* __restrict__ out,
                                                          const float* __restrict__ saved, void* __restrict__ gx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int NC = NCoef<M>::v;
-  float* cf = lds + L.cf;
-  unsigned short* nbq = (unsigned short*)(lds + L.nbq);
-  uint2* yl = (uint2*)(lds + L.yl);
-  uint2* xl = (uint2*)(lds + L.xl);
-  unsigned* yc = (unsigned*)(lds + L.yc);
-  unsigned* xc = (unsigned*)(lds + L.xc);
+  const GatherTabs tb(lds, L);
   int* mm = (int*)(lds + L.mm);
-  float4* xs = (float4*)(lds + L.xs);
   const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
   const int ra = blockIdx.z * L.RB, rb = min(g.H, ra + L.RB), nr = rb - ra;  // this band's rows
-  const float* sv = (Meas<M>::NSTAT > 0) ? saved + (long long)b * Meas<M>::NSTAT * g.P : nullptr;
+  const int q_begin = blockIdx.y * L.Qwg, q_end = min((g.C + 3) >> 2, q_begin + L.Qwg);
 
   if (t == 0) {
     mm[0] = g.Ho;
@@ -488,23 +488,18 @@ __global__ void __launch_bounds__(512) bwd_gather_banded(const KP g, const BandL
   __syncthreads();
   // ---- raw reader slots of the band's rows and of every column; which output rows read the band? --------
   const int nslot = (2 * g.pad + 1) * g.k;
-  uint2* slots = (uint2*)xs;
+  uint2* slots = (uint2*)tb.xs;
   for (int s = t; s < (nr + g.W) * nslot; s += T) {
-    const int i = fdivi(s, nslot), w = s - i * nslot, ic = fdivi(w, g.k), d = w - ic * g.k;
-    uint2 e;
-    if (i < nr) {
-      e = axis_reader_raw(g, ra + i, g.H, g.Ho, ic, d);
-      if (e.x != 0xFFFFFFFFu) {
-        const int oa = (int)(e.x >> 8), ca = (int)e.y;
-        atomicMin(&mm[0], oa);
-        atomicMax(&mm[1], oa);
-        if (ca >= 0) {  // the centre row of an output that reads the band
-          atomicMin(&mm[2], ca);
-          atomicMax(&mm[3], ca);
-        }
+    bool rows;
+    const uint2 e = slot_reader(g, s, nslot, ra, nr, rows);
+    if (rows && e.x != 0xFFFFFFFFu) {
+      const int oa = (int)(e.x >> 8), ca = (int)e.y;
+      atomicMin(&mm[0], oa);
+      atomicMax(&mm[1], oa);
+      if (ca >= 0) {  // the centre row of an output that reads the band
+        atomicMin(&mm[2], ca);
+        atomicMax(&mm[3], ca);
       }
-    } else {
-      e = axis_reader_raw(g, i - nr, g.W, g.Wo, ic, d);
     }
     slots[s] = e;
   }
@@ -526,109 +521,37 @@ __global__ void __launch_bounds__(512) bwd_gather_banded(const KP g, const BandL
   }
   __syncthreads();
   const int w0 = mm[2], w1 = mm[3];
-  const int p0 = w0 * g.W, np = (w1 - w0 + 1) * g.W, PS = np + 1;  // window pixels (np + 1 <= L.PSm)
-  if (ON > L.ONm || PS > L.PSm) {
+  const int p0 = w0 * g.W, np = (w1 - w0 + 1) * g.W;  // window pixels (np + 1 <= L.PSm)
+  if (ON > L.ONm || np + 1 > L.PSm) {
     // cannot happen if the launcher's bounds hold; never write past LDS: poison this band's gradient instead
-    const int Q0 = (g.C + 3) >> 2, qa = blockIdx.y * L.Qwg, qe = min(Q0, qa + L.Qwg);
-    for (int i = t; i < (qe - qa) * 4 * nr * g.W; i += T) {
-      const int c = 4 * qa + i / (nr * g.W), rl = i % (nr * g.W);
+    for (int i = t; i < (q_end - q_begin) * 4 * nr * g.W; i += T) {
+      const int c = 4 * q_begin + i / (nr * g.W), rl = i % (nr * g.W);
       if (c < g.C)
         stx(gx, (long long)b * g.gB + (long long)c * g.sC + (long long)(ra + rl / g.W) * g.sH +
                 (long long)(rl % g.W) * g.sW, __builtin_nanf(""), g.dtype);
     }
     return;
   }
-  // ---- final tables -------------------------------------------------------------------------------------------
+  // ---- final tables: one thread per list, packed here (the band's ranges are known only now) -------------------
   for (int i = t; i < nr + g.W; i += T) {
     const bool rows = i < nr;
-    uint2* list = rows ? yl + i * L.capY : xl + (i - nr) * L.capX;
-    const unsigned cd = (unsigned)g.R;
+    uint2* list = rows ? tb.yl + i * L.capY : tb.xl + (i - nr) * L.capX;
     unsigned cnt = 0, ncentre = 0;
     for (int pass = 0; pass < 2; ++pass) {  // readers through the centre tap first, then the others, in slot order
       for (int w = 0; w < nslot; ++w) {
         const uint2 e = slots[i * nslot + w];
-        if (e.x == 0xFFFFFFFFu) continue;
-        const unsigned d = e.x & 0xFFu;
-        if ((d == cd) != (pass == 0)) continue;
-        const int oa = (int)(e.x >> 8), ca = (int)e.y;
-        uint2 f;
-        if (rows) {
-          f.x = (unsigned)((int)d * g.k * Ol + (oa - oya) * g.Wo);
-          f.y = (ca < 0 ? kNoCentre : (unsigned)((ca - w0) * g.W)) | ((d * (unsigned)g.k) << 20);
-        } else {
-          f.x = (unsigned)((int)d * Ol + oa);
-          f.y = (ca < 0 ? kNoCentre : (unsigned)ca) | (d << 20);
-        }
-        list[cnt++] = f;
+        if (e.x == 0xFFFFFFFFu || ((e.x & 0xFFu) == (unsigned)g.R) != (pass == 0)) continue;
+        list[cnt++] = pack_reader(g, e, rows, Ol, oya, w0);
       }
       if (pass == 0) ncentre = cnt;
     }
     if (rows)
-      yc[i] = cnt | (ncentre << 16);
+      tb.yc[i] = cnt | (ncentre << 16);
     else
-      xc[i - nr] = cnt | (ncentre << 16);
+      tb.xc[i - nr] = cnt | (ncentre << 16);
   }
-  for (int j = t; j < ON; j += T) {
-    const int n = fdivi(j, Ol), o = o_base + (j - n * Ol);
-    const int q = nbr_pixel(g, o, n), pc = tap_pixel(g, o, g.R, g.R);
-    const long long oi = ((long long)b * g.N + n) * g.O + o;
-    const float sp0 = (Meas<M>::NSTAT > 0 && pc >= 0) ? sv[pc] : 0.f;
-    const float sp1 = (Meas<M>::NSTAT > 1 && pc >= 0) ? sv[g.P + pc] : 0.f;
-    const float sq0 = (Meas<M>::NSTAT > 0 && q >= 0) ? sv[q] : 0.f;
-    const float sq1 = (Meas<M>::NSTAT > 1 && q >= 0) ? sv[g.P + q] : 0.f;
-    const Coef c = Meas<M>::coef(ldx(go, oi, g.godtype), ldx(out, oi, g.odtype), sp0, sp1, sq0, sq1, g);
-    cf[j] = c.k0;
-    if (NC > 1) cf[ON + j] = c.k1;
-    if (NC > 2) cf[2 * ON + j] = c.k2;
-    if (NC > 3) cf[3 * ON + j] = c.k3;
-    if (NC > 4) cf[4 * ON + j] = c.k4;
-    // neighbour pixel in window coordinates; read only for outputs centred in the band, whose neighbours are
-    // inside the window by construction (anything else, and zero padding, -> the zero pixel)
-    const int ql = q - p0;
-    nbq[j] = (unsigned short)((q < 0 || ql < 0 || ql >= np) ? np : ql);
-  }
-
-  // ---- channel loop ------------------------------------------------------------------------------------
-  const int Q = (g.C + 3) >> 2;
-  const int q_begin = blockIdx.y * L.Qwg, q_end = min(Q, q_begin + L.Qwg);
-  const unsigned mid = (unsigned)((g.k * g.k) >> 1);
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int nbp = nr * g.W;  // band pixels
-  for (int qc0 = q_begin; qc0 < q_end; qc0 += L.Cq) {
-    const int cqn = min(L.Cq, q_end - qc0);
-    __syncthreads();  // tables complete, slots consumed / previous slab consumed
-    stage_quads(xs, x, g, b, qc0, cqn, nullptr, p0, np, t, T);
-    __syncthreads();
-    const int nqb = (cqn + QB - 1) / QB;
-    for (int i = t; i < nqb * nbp; i += T) {
-      const int qb = fdivi(i, nbp), rl = i - qb * nbp;
-      const int ryl = fdivi(rl, g.W), rx = rl - ryl * g.W, ry = ra + ryl;
-      const int r = (ry - w0) * g.W + rx;  // window pixel of this band pixel
-      const float4* slab[QB];
-      float4 a[QB], acc[QB];
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        slab[u] = xs + min(qb * QB + u, cqn - 1) * PS;
-        a[u] = slab[u][r];
-        acc[u] = zero4;
-      }
-      const uint2* yrow = yl + ryl * L.capY;
-      const uint2* xrow = xl + rx * L.capX;
-      gather_item<M, QB>(g, slab, a, acc, yrow, xrow, yc[ryl], xc[rx], cf, ON, nbq, Ol, (unsigned)np, mid);
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        const int cq = qb * QB + u;
-        if (cq < cqn) {
-          const int c = 4 * (qc0 + cq);
-          const long long base = (long long)b * g.gB + (long long)c * g.sC + (long long)ry * g.sH + (long long)rx * g.sW;
-          stx(gx, base, acc[u].x, g.dtype);
-          if (c + 1 < g.C) stx(gx, base + g.sC, acc[u].y, g.dtype);
-          if (c + 2 < g.C) stx(gx, base + 2 * g.sC, acc[u].z, g.dtype);
-          if (c + 3 < g.C) stx(gx, base + 3 * g.sC, acc[u].w, g.dtype);
-        }
-      }
-    }
-  }
+  gather_pair_tables<M>(g, b, go, out, saved, tb.cf, tb.nbq, o_base, Ol, p0, np, t, T);
+  gather_channels<M, QB>(g, L, tb, x, gx, q_begin, q_end, ra, nr, w0, np, Ol, false);
 }
 
 // ---- forward --------------------------------------------------------------------------------------------

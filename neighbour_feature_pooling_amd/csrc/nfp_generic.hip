@@ -90,8 +90,9 @@ int launch_fwd_generic(KP g, const void* x, void* out, float* saved, hipStream_t
                 0, st, g, x, out, saved);
 }
 
-// Gather-form backward (nfp_gather.h): tables + one slab of >= QB channel quads must fit in LDS and the
-// packed 16-bit indices must hold; otherwise the LDS-atomic kernel below serves the call.
+// Gather-form backward (nfp_gather.h): both kernels are one structure over bands of grad_x rows, bwd_gather with one
+// band.  The tables + one slab of >= QB channel quads must fit in LDS and the packed indices must hold; otherwise
+// nfp_direct.h::bwd_direct serves the call.
 bool force_atomic() { return g_sw.bwd_atomic.load(std::memory_order_relaxed) != 0; }
 // tests: NFP_BWD_BANDS=n sends every call through the banded kernel with >= n bands
 int force_bands() { return g_sw.bwd_bands.load(std::memory_order_relaxed); }
@@ -106,133 +107,116 @@ int force_bands() { return g_sw.bwd_bands.load(std::memory_order_relaxed); }
 #define NFP_GATHER_SLAB_KB 48
 #endif
 
-template <int M>
-int launch_bwd_gather(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st) {
-  constexpr int QB = NFP_GATHER_QB, NC = NCoef<M>::v;
-  const long long ON = (long long)g.O * g.N;
-  // index ranges the packed tables hold (nfp_gather.h)
-  if (force_atomic() || force_bands() > 0 || ON > 65535 || g.P > 65534 || g.k > 15 || g.pad > 8 || g.H >= 16383 ||
-      g.W >= 16383 || (long long)(g.H + g.W) * (2 * g.pad + 1) * g.k >= (1 << 20))
-    return kNotApplicable;
+// index ranges the packed reader entries hold, whatever the bands (nfp_gather.h::axis_reader_raw, pack_reader)
+bool gather_packs(const KP& g) {
+  return g.k <= 15 && g.pad <= 8 && g.H < 16383 && g.W < 16383 && (long long)(g.H + g.W) * (2 * g.pad + 1) * g.k < (1 << 20);
+}
+
+// What the two launchers share, for bands of RB rows of grad_x whose tables hold at most ONm pairs and whose window
+// holds at most PSm - 1 pixels: the reader-list capacities, the walk over the tables cf .. xc and the channel split;
+// grid = (B, channel blocks, bands).  Returns the word offset behind xc — the launcher appends its own tables, then
+// the slab — or -1 where the 16-bit pair / pixel indices do not hold.
+long long gather_layout(const KP& g, int NC, int RB, long long ONm, long long PSm, GatherLds& L, dim3& grid) {
+  constexpr int QB = NFP_GATHER_QB;
+  if (ONm > 65535 || PSm > 65535) return -1;
   auto folds = [&](int n) {  // padded coordinates that can fold onto one coordinate of an axis of size n
     if (g.pad == 0 || g.mode == NFP_PAD_ZEROS) return 1;
     if (g.mode == NFP_PAD_REPLICATE) return n == 1 ? 2 * g.pad + 1 : g.pad + 1;
     return 3;
   };
-  GatherLds L;
-  L.ON = (int)ON;
+  L.RB = RB;
+  L.ONm = (int)ONm;
+  L.PSm = (int)PSm;
   L.capY = g.k * folds(g.H);
   L.capX = g.k * folds(g.W);
   long long w = 0;
-  L.cf = (int)w;  w += (long long)NC * L.ON;
-  L.nbq = (int)w; w += (L.ON + 1) / 2;
+  L.cf = (int)w;  w += NC * ONm;
+  L.nbq = (int)w; w += (ONm + 1) / 2;
   w = (w + 1) & ~1LL;  // uint2 lists
-  L.yl = (int)w;  w += 2LL * g.H * L.capY;
+  L.yl = (int)w;  w += 2LL * RB * L.capY;
   L.xl = (int)w;  w += 2LL * g.W * L.capX;
-  L.yc = (int)w;  w += g.H;
+  L.yc = (int)w;  w += RB;
   L.xc = (int)w;  w += g.W;
+  // channel split: enough workgroups to fill the chip at small batch, whole QB blocks per workgroup
+  const int Q = (g.C + 3) / 4, bands = (g.H + RB - 1) / RB, maxS = (Q + QB - 1) / QB;
+  int S = (NFP_GATHER_WGS + g.B * bands - 1) / (g.B * bands);
+  if (S > maxS) S = maxS;
+  if (S < 1) S = 1;
+  L.Qwg = (((Q + S - 1) / S) + QB - 1) / QB * QB;
+  grid = dim3(g.B, (Q + L.Qwg - 1) / L.Qwg, bands);
+  return w;
+}
+
+// One band: the slots have a table of their own, a quarter of the threads stage the first slab under the table build,
+// and the slab is capped by a budget that keeps several workgroups per CU.
+template <int M>
+int launch_bwd_gather(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
+                      hipStream_t st) {
+  constexpr int QB = NFP_GATHER_QB;
+  if (force_bands() > 0 || !gather_packs(g)) return kNotApplicable;
+  GatherLds L{};
+  dim3 grid;
+  long long w = gather_layout(g, NCoef<M>::v, g.H, (long long)g.O * g.N, (long long)g.P + 1, L, grid);
+  if (w < 0) return kNotApplicable;
   w = (w + 1) & ~1LL;
   L.sl = (int)w;  w += 2LL * (g.H + g.W) * (2 * g.pad + 1) * g.k;
   w = (w + 3) & ~3LL;
   if (w * 4 > kLdsMax) return kNotApplicable;
   L.xs = (int)w;
-  L.Ts = NFP_GATHER_T / 4;  // a quarter of the threads stage
-  const size_t table_bytes = (size_t)w * 4, quad_bytes = (size_t)(g.P + 1) * 16;
+  L.Ts = NFP_GATHER_T / 4;
+  const size_t table_bytes = (size_t)w * 4, quad_bytes = (size_t)L.PSm * 16;
   if (table_bytes + QB * quad_bytes > (size_t)kLdsMax) return kNotApplicable;
-  const int Q = (g.C + 3) / 4;
-  // channel split: enough workgroups to fill the chip at small batch, whole QB blocks per workgroup
-  int S = (NFP_GATHER_WGS + g.B - 1) / g.B;
-  const int maxS = (Q + QB - 1) / QB;
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  L.Qwg = (((Q + S - 1) / S) + QB - 1) / QB * QB;
-  S = (Q + L.Qwg - 1) / L.Qwg;
-  // slab: what the workgroup needs, capped by a budget that keeps several workgroups per CU, then by LDS
   size_t budget = (size_t)NFP_GATHER_SLAB_KB * 1024;
   if (budget < QB * quad_bytes) budget = QB * quad_bytes;
   if (budget > (size_t)kLdsMax - table_bytes) budget = (size_t)kLdsMax - table_bytes;
-  int Cq = (int)(budget / quad_bytes) / QB * QB;
-  if (Cq > L.Qwg) Cq = L.Qwg;
-  L.Cq = Cq;
-  const size_t lds = table_bytes + (size_t)Cq * quad_bytes;
+  L.Cq = std::min((int)(budget / quad_bytes) / QB * QB, L.Qwg);
+  const size_t lds = table_bytes + (size_t)L.Cq * quad_bytes;
   snprintf(g_variant, sizeof(g_variant), "bwd_gather");
-  return launch("bwd_gather", bwd_gather<M, QB>, dim3(g.B, S), dim3(NFP_GATHER_T), lds, st, g, L, x, go, out, saved, gx);
+  return launch("bwd_gather", bwd_gather<M, QB>, grid, dim3(NFP_GATHER_T), lds, st, g, L, x, go, out, saved, gx);
 }
 
-// Banded variant for maps whose whole-image tables exceed LDS (nfp_gather.h::bwd_gather_banded).
+// Maps whose whole-image tables exceed LDS (nfp_gather.h::bwd_gather_banded): the fewest bands whose tables take at
+// most half of LDS; the rest is the slab (at least one block of QB quads), which holds the slots first.
 template <int M>
 int launch_bwd_gather_banded(const KP& g, const void* x, const void* go, const void* out, const float* saved,
                              void* gx, hipStream_t st) {
-  constexpr int QB = NFP_GATHER_QB, NC = NCoef<M>::v;
-  if (force_atomic() || g.k > 15 || g.pad > 8 || g.H >= 16383 || g.W >= 16383 ||
-      (long long)(g.H + g.W) * (2 * g.pad + 1) * g.k >= (1 << 20))
-    return kNotApplicable;
-  auto folds = [&](int n) {
-    if (g.pad == 0 || g.mode == NFP_PAD_ZEROS) return 1;
-    if (g.mode == NFP_PAD_REPLICATE) return n == 1 ? 2 * g.pad + 1 : g.pad + 1;
-    return 3;
-  };
+  constexpr int QB = NFP_GATHER_QB;
+  if (!gather_packs(g)) return kNotApplicable;
   const bool local = g.mode != NFP_PAD_CIRCULAR && g.pad <= g.R * g.dil;  // an output reads near its centre only
-  const int reach = 2 * g.R * g.dil, nslot = (2 * g.pad + 1) * g.k, Q = (g.C + 3) / 4;
-  BandLds L;
-  L.capY = g.k * folds(g.H);
-  L.capX = g.k * folds(g.W);
-  long long w = 0;
+  const int reach = 2 * g.R * g.dil, nslot = (2 * g.pad + 1) * g.k;
+  GatherLds L{};
+  dim3 grid;
   size_t table_bytes = 0, quad_bytes = 0, slot_bytes = 0;
-  int bands = 0;
+  bool found = false;
   const int nb0 = local ? std::min(std::max(force_bands(), 1), g.H) : 1;
-  for (int nb = nb0; nb <= g.H; nb = local ? nb + 1 : g.H + 1) {
+  for (int nb = nb0; nb <= g.H && !found; nb = local ? nb + 1 : g.H + 1) {
     const int RB = (g.H + nb - 1) / nb;
     const int orows = local ? std::min(g.Ho, (RB - 1 + reach) / g.stride + 2) : g.Ho;
     const int wrows = local ? std::min(g.H, RB + reach) : g.H;
-    const long long ONm = (long long)g.N * orows * g.Wo, PSm = (long long)wrows * g.W + 1;
-    if (PSm > 65535) continue;
-    w = 0;
-    L.cf = (int)w;  w += NC * ONm;
-    L.nbq = (int)w; w += (ONm + 1) / 2;
-    w = (w + 1) & ~1LL;
-    L.yl = (int)w;  w += 2LL * RB * L.capY;
-    L.xl = (int)w;  w += 2LL * g.W * L.capX;
-    L.yc = (int)w;  w += RB;
-    L.xc = (int)w;  w += g.W;
+    long long w = gather_layout(g, NCoef<M>::v, RB, (long long)g.N * orows * g.Wo, (long long)wrows * g.W + 1, L, grid);
+    if (w < 0) continue;
     L.mm = (int)w;  w += 4;
     w = (w + 3) & ~3LL;
+    L.xs = (int)w;
     table_bytes = (size_t)w * 4;
-    quad_bytes = (size_t)PSm * 16;
+    quad_bytes = (size_t)L.PSm * 16;
     slot_bytes = (size_t)(RB + g.W) * nslot * 8;
-    // tables may take half of LDS; the rest is the slab (at least one block of QB quads) or the slots
-    if (table_bytes <= (size_t)kLdsMax / 2 && table_bytes + std::max(QB * quad_bytes, slot_bytes) <= (size_t)kLdsMax) {
-      L.RB = RB;
-      L.ONm = (int)ONm;
-      L.PSm = (int)PSm;
-      L.xs = (int)w;
-      bands = (g.H + RB - 1) / RB;
-      break;
-    }
+    found = table_bytes <= (size_t)kLdsMax / 2 && table_bytes + std::max(QB * quad_bytes, slot_bytes) <= (size_t)kLdsMax;
   }
-  if (bands == 0) return kNotApplicable;
-  int S = (NFP_GATHER_WGS + g.B * bands - 1) / (g.B * bands);
-  const int maxS = (Q + QB - 1) / QB;
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  L.Qwg = (((Q + S - 1) / S) + QB - 1) / QB * QB;
-  S = (Q + L.Qwg - 1) / L.Qwg;
-  size_t room = (size_t)kLdsMax - table_bytes;
-  int Cq = (int)(room / quad_bytes) / QB * QB;
-  if (Cq > L.Qwg) Cq = L.Qwg;
-  L.Cq = Cq;
-  const size_t lds = table_bytes + std::max((size_t)Cq * quad_bytes, slot_bytes);
+  if (!found) return kNotApplicable;
+  L.Cq = std::min((int)(((size_t)kLdsMax - table_bytes) / quad_bytes) / QB * QB, L.Qwg);
+  const size_t lds = table_bytes + std::max((size_t)L.Cq * quad_bytes, slot_bytes);
   snprintf(g_variant, sizeof(g_variant), "bwd_gather_banded");
-  return launch("bwd_gather_banded", bwd_gather_banded<M, QB>, dim3(g.B, S, bands), dim3(512), lds, st, g, L, x, go, out,
-                saved, gx);
+  return launch("bwd_gather_banded", bwd_gather_banded<M, QB>, grid, dim3(512), lds, st, g, L, x, go, out, saved, gx);
 }
 
 template <int M>
 int launch_bwd_generic(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
                        hipStream_t st) {
-  if (int rc = launch_bwd_gather<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
-  if (int rc = launch_bwd_gather_banded<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
+  if (!force_atomic()) {
+    if (int rc = launch_bwd_gather<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
+    if (int rc = launch_bwd_gather_banded<M>(g, x, go, out, saved, gx, st); rc != kNotApplicable) return rc;
+  }
   // last resort (nfp_direct.h): no LDS tables, any map size, still one writer per element in a fixed order
   snprintf(g_variant, sizeof(g_variant), "bwd_direct");
   return launch("bwd_direct", bwd_direct<M>, dim3((unsigned)((g.P + 255) / 256), (g.C + kDirectCB - 1) / kDirectCB, g.B),

@@ -21,6 +21,36 @@ struct Coef {
 template <int M>
 struct Meas;
 
+// floats of Coef that Meas<M>::coef sets and Meas<M>::grad reads
+template <int M> struct NCoef { static constexpr int v = 1; };
+template <> struct NCoef<NFP_COSINE> { static constexpr int v = 3; };
+template <> struct NCoef<NFP_GFC> { static constexpr int v = 3; };
+template <> struct NCoef<NFP_SMITH> { static constexpr int v = 3; };
+template <> struct NCoef<NFP_PEARSON> { static constexpr int v = 5; };
+
+// A table of Coef is kept as NCoef<M> planes of floats: float k of entry i at cf[k * stride + i] (I: int in LDS,
+// long long in global memory).
+template <int M, typename I>
+__device__ __forceinline__ Coef load_coef(const float* cf, I stride, I i) {
+  constexpr int NC = NCoef<M>::v;
+  Coef c = {0.f, 0.f, 0.f, 0.f, 0.f};
+  c.k0 = cf[i];
+  if (NC > 1) c.k1 = cf[stride + i];
+  if (NC > 2) c.k2 = cf[2 * stride + i];
+  if (NC > 3) c.k3 = cf[3 * stride + i];
+  if (NC > 4) c.k4 = cf[4 * stride + i];
+  return c;
+}
+template <int M, typename I>
+__device__ __forceinline__ void store_coef(float* cf, I stride, I i, const Coef& c) {
+  constexpr int NC = NCoef<M>::v;
+  cf[i] = c.k0;
+  if (NC > 1) cf[stride + i] = c.k1;
+  if (NC > 2) cf[2 * stride + i] = c.k2;
+  if (NC > 3) cf[3 * stride + i] = c.k3;
+  if (NC > 4) cf[4 * stride + i] = c.k4;
+}
+
 // ---- Norm: -(sum |a-b|^p)^(1/p)   nfp.py:141-148 (weights nfp.py:74-80) -----------------
 // PK = 1 / 2: the order is known at compile time (the dispatcher picks these for p == 1, the reference's
 // default, and p == 2), so the per-channel code has no powf and no branch on p; PK = 0: any finite p > 0.
