@@ -230,10 +230,11 @@ __device__ __forceinline__ int nbr_pixel(const KP& g, int o, int n) {
 }
 
 // In-kernel phase stamps exist only in the diagnostic build (-DNFP_STAMPS, scripts/diag_stamps.py includes
-// nfp_diag.h); in the product build the two macros expand to nothing.
+// nfp_diag.h); in the product build the macros expand to nothing.
 #ifdef NFP_STAMPS
 #include "nfp_diag.h"
 #else
+#define NFP_STAMP_SETTER(unit)
 #define NFP_STAMP_INIT() do { } while (0)
 #define NFP_STAMP_ENTRY() do { } while (0)
 #define NFP_STAMP_INIT_ENTRY() do { } while (0)

@@ -4,6 +4,13 @@
 #pragma once
 // (included from inside namespace nfp)
 __constant__ unsigned long long* nfp_stamp_buf = nullptr;
+// Every translation unit whose kernels stamp has its own copy of that pointer, and (at file scope) exports a setter for it;
+// nfp_hip.hip::nfp_debug_set_stamp_buffer calls them all.
+#define NFP_STAMP_SETTER(unit)                                                                      \
+  extern "C" int nfp_debug_set_stamp_buffer_##unit(void* dev_ptr) {                                 \
+    unsigned long long* p = (unsigned long long*)dev_ptr;                                           \
+    return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3; \
+  }
 // The buffer pointer is read ONCE, by a scalar load (constant address space: its wait is on lgkmcnt and does not
 // cover vector loads in flight — fwd_band / bwd_fast read it BEHIND their first requests, below); a stamp is then one
 // s_memtime/s_memrealtime pair and two stores, with no vmcnt wait, so loads in flight stay in flight.

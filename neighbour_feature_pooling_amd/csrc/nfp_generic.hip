@@ -245,10 +245,4 @@ int attn_softmax_backward(const KP& g, const void* go, const void* out, float* g
 
 }  // namespace nfp_host
 
-#ifdef NFP_STAMPS
-// (every translation unit has its own copy of the device-side stamp pointer)
-extern "C" int nfp_debug_set_stamp_buffer_generic(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
-}
-#endif
+NFP_STAMP_SETTER(generic)

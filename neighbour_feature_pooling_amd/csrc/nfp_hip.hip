@@ -89,9 +89,7 @@ int make_kp(const nfp_desc* d, KP* g) {
   g->pool_gap = g->pool_map = 1;
   g->d2s = d->measure == NFP_RMSE ? 1.0f / (float)d->C : 1.0f;
   g->zero0 = d->measure == NFP_RMSE ? 0 : 1;
-  if (!(g->stride == 1 && g->dil == 1 && g->pad == g->R && g->mode != NFP_PAD_CIRCULAR && (g->R == 1 || g->R == 2) &&
-        g->P <= kBwdThreads && g->P >= 4))
-    g->ws = nullptr;   // (not a table geometry — nfp_launch.h::fast_geometry: its workspace holds the counters alone)
+  if (!fast_geometry(*g)) g->ws = nullptr;   // (not a table geometry: its workspace holds the counters alone)
   // index arithmetic of the general kernels: coordinates in 15 bits, pair indices in 31
   if (d->H > 32767 || d->W > 32767 || (int64_t)g->P > (1 << 26) || (int64_t)g->N * g->O >= (1LL << 31) || d->B > 65535)
     return fail(NFP_E_UNSUPPORTED, "feature map [%d,%d,%d,%d] with k = %d exceeds the index range of the kernels", d->B,
@@ -164,19 +162,36 @@ int finish(int rc, const char* what) {
   return rc;
 }
 
+// Checks the entry points share.  The ORDER in which an entry applies them is its own, and observable: where two checks
+// fail at once the caller sees the first (tests/test_entry_refusals_host.py).
+// One of `tensors` is null although required (the valid and biased entries: x / out only for B > 0)
+bool missing(std::initializer_list<const void*> tensors, bool required = true) {
+  for (const void* p : tensors)
+    if (required && !p) {
+      fail(NFP_E_INVALID, "null tensor pointer");
+      return true;
+    }
+  return false;
+}
+
+// a caller buffer shorter than its size query says.  `query`: "<size function> is", or what reads it
+int short_buffer(const char* what, int64_t have, const char* query, int64_t need) {
+  return fail(NFP_E_INVALID, "%s holds %lld floats, %s %lld", what, (long long)have, query, (long long)need);
+}
+
 // The hot-path forward of a plain single-radius map, or kNotApplicable: table kernels (matrix cores first for bf16), then the
 // row-band kernels.
 int hot_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st) {
   if (g_sw.tile_first.load(std::memory_order_relaxed))
-    if (int rc = tile_forward(g, x, out, saved, st, false, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = tile_forward(g, x, out, saved, st); rc != kNotApplicable) return rc;
   // (Geman / Canberra / Hellinger / Jeffrey / squared chord / chi-squared 1 share the kSymTerm instantiation)
   if (fast_ok(g, x, x, true)) {
     // (the matrix-core forward has the cosine and L2 forms alone)
-    if (int rc = table_fwd_gram(g, x, out, saved, st, nullptr, nullptr); rc != kNotApplicable) return rc;
-    if (int rc = table_fwd_band(g, x, out, saved, st, kPoolNone, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = table_fwd_gram(g, x, out, saved, st); rc != kNotApplicable) return rc;
+    if (int rc = table_fwd_band(g, x, out, saved, st); rc != kNotApplicable) return rc;
   }
   // maps above the table kernels' 512 pixels, or a descriptor without its tables: the row-band kernels (nfp_tile_fwd.hip)
-  if (int rc = tile_forward(g, x, out, saved, st, false, nullptr, nullptr, nullptr, nullptr); rc != kNotApplicable) return rc;
+  if (int rc = tile_forward(g, x, out, saved, st); rc != kNotApplicable) return rc;
   return kNotApplicable;
 }
 
@@ -202,20 +217,25 @@ int mixed_refused(const nfp_desc* d) {
   return NFP_OK;
 }
 
+// Radii (1, 2) from one pass (g.rs == 12): the table kernels' two-radius form or a refusal — `table` is its launcher,
+// `which` the direction its refusal names
+template <typename F>
+int multi_radius(const KP& g, const void* x, const void* gx, const char* which, F&& table) {
+  if (g.ws == nullptr || !fast_ok(g, x, gx))
+    return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
+                "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
+  const int rc = table();
+  return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path %s", which) : rc;
+}
+
 int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!x || !out) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, out})) return NFP_E_INVALID;
   if (int rc = mixed_refused(d)) return rc;
   if (g.B == 0) return NFP_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (g.rs == 12) {
-    if (g.ws == nullptr || !fast_ok(g, x, x))
-      return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
-                  "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = table_fwd_band(g, x, out, saved, st, kPoolNone, nullptr, nullptr, nullptr, nullptr);
-    return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path forward") : rc;
-  }
+  if (g.rs == 12) return multi_radius(g, x, x, "forward", [&] { return table_fwd_band(g, x, out, saved, st); });
   if (int rc = hot_forward(g, x, out, saved, st); rc != kNotApplicable) return rc;
   if (g.measure == NFP_ATTENTION) {
     // raw dots in f32: in `out` itself for float32 maps, in the caller's scratch (nfp_saved_floats) for bf16
@@ -242,20 +262,20 @@ int forward_impl(const nfp_desc* d, const void* x, void* out, float* saved, void
 int hot_backward(const KP& g, const void* x, const void* grad_out, const void* out, const float* saved, void* grad_x,
                  hipStream_t st) {
   if (g_sw.tile_first.load(std::memory_order_relaxed))
-    if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   // k = 5, float32 NCHW, maps of 14 x 14 and more: the row-band backward (window weights in registers, no 13-entry-per-pixel
   // gather phase) beats the table kernel — [256,192,14,14] L2 40.9 -> 35.7 us, cosine 41.1 -> 37.1, [256,256,14,14] 50.5 ->
   // 44.1 (profiles/r04_n_…; the FORWARD stays on the tables: 19 vs 28 us; channels-last and bf16 stay too).  Same saved
   // state (the map and |x| per pixel), so the two mix.
   if (g.R == 2 && g.rs != 12 && g.dtype == NFP_F32 && g.contig && g.P >= 196 && hot_measure(g))
-    if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   // The table kernels.  The kSymTerm measures only below 14 x 14: from there up the row-band backward is ahead ([256,192,14,14]
   // k = 5 97.5 vs 101.9 us, [256,64,20,20] 37.5 vs 41.4; at 7 x 7 the table kernel: [64,512,7,7] 10.1-12.3 vs 18.2-22.5 us —
   // profiles/r04_zd_…; the forward stays on the tables up to 512 pixels: 52.7 vs 66.8 us at [256,192,14,14])
   if (g.ws != nullptr && fast_ok(g, x, grad_x, true) && !(hot_sym(g) && !(NFP_SYM_TABLE_BWD && g.P < 196))) {
-    if (int rc = table_backward(g, x, grad_out, out, saved, grad_x, st, kPoolNone, nullptr, nullptr); rc != kNotApplicable) return rc;
+    if (int rc = table_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   }
-  if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st, false, nullptr, nullptr); rc != kNotApplicable) return rc;
+  if (int rc = tile_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   return kNotApplicable;
 }
 
@@ -263,18 +283,13 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
                   void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!x || !grad_out || !out || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, grad_out, out, grad_x})) return NFP_E_INVALID;
   if ((stats_of(g.measure) > 0 || g.measure == NFP_ATTENTION) && !saved) return fail(NFP_E_INVALID, "measure %d needs the saved state of nfp_forward", g.measure);
   if (int rc = mixed_refused(d)) return rc;
   if (g.B == 0) return NFP_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (g.rs == 12) {
-    if (g.ws == nullptr || !fast_ok(g, x, grad_x))
-      return fail(NFP_E_UNSUPPORTED, "multi-radius: cosine / dot / gfc / L2 / rmse / norm p=1 / emd on maps of at most %d pixels, "
-                  "C %% 4 == 0, dense layout, descriptor with a workspace", kBwdThreads);
-    const int rc = table_backward(g, x, grad_out, out, saved, grad_x, st, kPoolNone, nullptr, nullptr);
-    return rc == kNotApplicable ? fail(NFP_E_UNSUPPORTED, "multi-radius: the map does not fit the hot-path backward") : rc;
-  }
+  if (g.rs == 12)
+    return multi_radius(g, x, grad_x, "backward", [&] { return table_backward(g, x, grad_out, out, saved, grad_x, st); });
   if (int rc = hot_backward(g, x, grad_out, out, saved, grad_x, st); rc != kNotApplicable) return rc;
   if (g.measure == NFP_ATTENTION) {
     float* gd = const_cast<float*>(saved);  // scratch handed over by nfp_forward's caller (nfp_saved_floats)
@@ -294,87 +309,109 @@ int backward_impl(const nfp_desc* d, const void* x, const void* grad_out, const 
   return rc;
 }
 
-// Floats of scratch behind the per-pixel state in `saved` that the row-band pooled forward needs: every band's share of
-// the two pooled sums (nfp_tile.h::fwd_tile<POOL> -> pool_fold).  Set by pool_forward / gap_forward (also in plan mode).
-thread_local long long t_pool_scratch = 0;
-
-int pool_forward(const KP& g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm) {
-  t_pool_scratch = 0;
-  if (g.ws != nullptr && fast_ok(g, x, x)) {
-    // the matrix-core forward where it applies, as in nfp_forward (it declines float32 storage itself)
-    if (int rc = table_fwd_gram(g, x, out_map, saved, st, gap, nfpm); rc != kNotApplicable) return rc;
-    // row bands at small batches: each band's share of the pooled sums goes to the scratch behind the norms
-    float* part = saved != nullptr ? saved + (long long)stats_of(g.measure) * g.B * g.P : nullptr;
-    int nb = 1;
-    const int rc = table_fwd_band(g, x, out_map, saved, st, kPoolBoth, gap, nfpm, part, &nb);
-    if (rc == NFP_OK && nb > 1) {
-      t_pool_scratch = (long long)g.B * nb * (g.C + g.N);
-      if (g.tickets != nullptr) return rc;   // (the last band to arrive folded them inside the launch)
-      variant_suffix("+pool_fold");
-      return tile_pool_fold(g, part, gap, nfpm, nb, st);
-    }
-    if (rc != kNotApplicable) return rc;
-  }
-  if (!tile_ok(g, x, x)) return kNotApplicable;
-  // row bands (any map size): per-band partial sums into the scratch behind the norms, joined by pool_fold
-  if (saved == nullptr) return fail(NFP_E_INVALID, "fused pooling tail on this map needs the scratch of nfp_pool_saved_floats");
-  float* part = saved + (long long)stats_of(g.measure) * g.B * g.P;
-  int nb = 0;
-  if (int rc = tile_forward(g, x, out_map, saved, st, kPoolBoth, part, &nb, gap, nfpm); rc != NFP_OK) return rc;
-  t_pool_scratch = (long long)g.B * nb * (g.C + g.N);
-  if (g.tickets != nullptr) return NFP_OK;   // (single launch: the last band to arrive folds, nfp_common.h::pool_last_band)
-  variant_suffix("+pool_fold");
-  return tile_pool_fold(g, part, gap, nfpm, nb, st);
-}
-int pool_backward(const KP& g, const void* x, const void* out_map, const float* saved, void* gx, hipStream_t st,
-                     const float* ggap, const float* gnfpm) {
-  if (g.ws != nullptr && fast_ok(g, x, gx))
-    if (int rc = table_backward(g, x, nullptr, out_map, saved, gx, st, kPoolBoth, ggap, gnfpm); rc != kNotApplicable) return rc;
-  return tile_backward(g, x, nullptr, out_map, saved, gx, st, kPoolBoth, ggap, gnfpm);
-}
-
-// ---- GAP(x) beside the maps (nfp_gap_*): the pass of an NFP head (nfp_heads.py: gap(fmap) and nfp(fmap) of one feature map) ----
-// Forward: the pooled kernels' channel sums without their map sums (kPoolGap); several bands per image write rows of C
-// partial sums to the scratch behind the norms, joined in band order by pool_fold — never by the arrival counters (no
-// atomics on this path).  Backward: grad_out read as a map, ggap[b,c] / P added in the same store.
-// bf16: fwd_gram (its channel sums are a run-time option) and the matrix-core backwards serve this mode as well.
-// R = 12 (radii 1 and 2 from one pass, MultiRadiusNFPHead): the table kernels alone — the two-radius window has no
-// matrix-core and no row-band form, so bf16 runs on the vector kernels (as nfp_forward's) and maps above 512 pixels are
-// not served; one band per image (no counters on this path), so no pool_fold launch either.
-int gap_forward(KP g, const void* x, void* out_map, float* saved, hipStream_t st, float* gap) {
-  t_pool_scratch = 0;
-  g.tickets = nullptr;
-  g.pool_gap = g.pool_map = 1;
-  if (saved == nullptr) return fail(NFP_E_INVALID, "GAP beside the maps needs the scratch of nfp_gap_saved_floats");
-  float* part = saved + (long long)stats_of(g.measure) * g.B * g.P;
+// ---- the fused tails: nfp_pool_* (kPoolBoth: both pooled sums) and nfp_gap_* (kPoolGap: GAP(x) beside the full maps, the
+// pass of an NFP head — nfp_heads.py: gap(fmap) and nfp(fmap) of one feature map) ----
+// Forward: the table kernels (matrix cores first, as in nfp_forward: fwd_gram's sums are a run-time option and it declines
+// float32 storage itself), else the row bands.  One band per image writes its sums itself; several write rows of partial
+// sums to the scratch behind the per-pixel state in `saved` (nfp_tile.h::fwd_tile<POOL>), joined in band order by pool_fold —
+// or, in pool mode with the arrival counters, by the last band to arrive inside the same launch
+// (nfp_common.h::pool_last_band).  *scratch (if asked for): the floats of those rows; it is written on that route alone.
+// Radius 12 (radii 1 and 2 from one pass, MultiRadiusNFPHead; gap mode only: nfp_pool_* refuses it) has neither a
+// matrix-core nor a row-band form: table_fwd_gram declines it itself and tile_ok refuses it through tile_geometry, so the
+// vector table kernels serve bf16 too and maps above 512 pixels are not served.
+int fused_forward(KP g, int mode, const void* x, void* out_map, float* saved, hipStream_t st, float* gap, float* nfpm,
+                  long long* scratch = nullptr) {
+  // what differs between the two tails:
+  const bool gp = mode == kPoolGap;
+  if (gp) g.tickets = nullptr;              // gap: never the arrival counters (no atomics on this path)
+  if (gp) g.pool_gap = g.pool_map = 1;      //      both outputs always (pool: the entry's, NULL = not wanted)
+  const int width = gp ? g.C : g.C + g.N;   // floats of a scratch row: the channel sums, and pool's map sums behind them
   KP gfold = g;
-  gfold.N = 0;   // (rows of C floats: pool_fold joins the channel sums alone)
+  if (gp) gfold.N = 0;                      // (pool_fold then joins the channel sums alone)
+  // gap needs `saved` up front; pool only on the row-band route — without it the table route keeps one band (part = null)
+  if (gp && saved == nullptr) return fail(NFP_E_INVALID, "GAP beside the maps needs the scratch of nfp_gap_saved_floats");
+
+  float* part = saved != nullptr ? saved + (long long)stats_of(g.measure) * g.B * g.P : nullptr;
+  int nb = 1;
+  const FwdTail t{mode, gap, nfpm, part, &nb};
+  int rc = kNotApplicable;
   if (g.ws != nullptr && fast_ok(g, x, x)) {
-    if (g.rs != 12)
-      if (int rc = table_fwd_gram(g, x, out_map, saved, st, gap, nullptr); rc != kNotApplicable) return rc;
-    int nb = 1;
-    const int rc = table_fwd_band(g, x, out_map, saved, st, kPoolGap, gap, nullptr, part, &nb);
-    if (rc == NFP_OK && nb > 1) {
-      t_pool_scratch = (long long)g.B * nb * g.C;
-      variant_suffix("+pool_fold");
-      return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
-    }
-    if (rc != kNotApplicable) return rc;
+    if (int rcg = table_fwd_gram(g, x, out_map, saved, st, t); rcg != kNotApplicable) return rcg;
+    rc = table_fwd_band(g, x, out_map, saved, st, t);
+    if (rc != kNotApplicable && !(rc == NFP_OK && nb > 1)) return rc;
   }
-  if (g.rs == 12 || !tile_ok(g, x, x)) return kNotApplicable;
-  int nb = 0;
-  if (int rc = tile_forward(g, x, out_map, saved, st, kPoolGap, part, &nb, gap, nullptr); rc != NFP_OK) return rc;
-  t_pool_scratch = (long long)g.B * nb * g.C;
+  if (rc == kNotApplicable) {   // row bands (any map size): always partial sums, joined below
+    if (!tile_ok(g, x, x)) return kNotApplicable;
+    if (saved == nullptr) return fail(NFP_E_INVALID, "fused pooling tail on this map needs the scratch of nfp_pool_saved_floats");
+    if (rc = tile_forward(g, x, out_map, saved, st, t); rc != NFP_OK) return rc;
+  }
+  if (scratch) *scratch = (long long)g.B * nb * width;
+  if (g.tickets != nullptr) return NFP_OK;   // (the last band to arrive folded them inside the launch)
   variant_suffix("+pool_fold");
-  return tile_pool_fold(gfold, part, gap, nullptr, nb, st);
+  return tile_pool_fold(gfold, part, gap, nfpm, nb, st);
 }
-int gap_backward(KP g, const void* x, const void* go, const void* out_map, const float* saved, void* gx, hipStream_t st,
-                    const float* ggap) {
+
+// Backward: the table kernels, else the row bands (tile_backward refuses radius 12 itself: tile_ok).  pool: no grad_out
+// (go = null), both pooled gradients; gap: grad_out read as a map, ggap[b,c] / P added in the same store.
+int fused_backward(KP g, int mode, const void* x, const void* go, const void* out_map, const float* saved, void* gx,
+                   hipStream_t st, const float* ggap, const float* gnfpm) {
   g.pool_gap = ggap != nullptr ? 1 : 0;   // NULL: GAP(x) took no part in the loss — nothing is added, nothing is read
+  const BwdTail t{mode, ggap, gnfpm};
   if (g.ws != nullptr && fast_ok(g, x, gx))
-    if (int rc = table_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr); rc != kNotApplicable) return rc;
-  if (g.rs == 12) return kNotApplicable;
-  return tile_backward(g, x, go, out_map, saved, gx, st, kPoolGap, ggap, nullptr);
+    if (int rc = table_backward(g, x, go, out_map, saved, gx, st, t); rc != kNotApplicable) return rc;
+  return tile_backward(g, x, go, out_map, saved, gx, st, t);
+}
+
+// "Would both launchers launch?" — both run in plan mode, on kStandIn pointers (4 KiB-aligned, as nfp_plan's; nothing
+// touches the GPU), so the answer is exactly what the two entries would do, whatever the LDS sizing rules of the kernels
+// are this week (round 2 re-derived the backward's table size for the pooled tail and forgot the forward's slab: 576
+// descriptors with R = 2 and P >= 256 were promised and then refused — ADVICE round 2); nothing of the calling thread's
+// variant / plan / error strings changes.
+template <typename F, typename G>
+bool both_launch(F&& forward, G&& backward) {
+  const DryRun dry;
+  return forward() == NFP_OK && backward() == NFP_OK;
+}
+
+// The measures of the two fused tails.  The gap calls also take radii (1, 2) together (inner_R = 1: make_kp); Norm p = 1 /
+// EMD are outside hot_measure; map_f32 is nfp_forward's / nfp_backward's only.
+bool tail_measure_ok(const KP& g, int mode) { return (mode == kPoolGap || g.rs != 12) && hot_measure(g) && !mixed_maps(g); }
+int tail_refused(const KP& g, int mode) {
+  if (tail_measure_ok(g, mode)) return NFP_OK;
+  return fail(NFP_E_UNSUPPORTED, mode == kPoolGap ? "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse"
+                                                  : "fused pooling tail: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+}
+// the forward of a tail as its dry runs make it (gap: no map sums)
+int tail_try_forward(const KP& g, int mode, long long* scratch = nullptr) {
+  void* const p = kStandIn;
+  return fused_forward(g, mode, p, p, (float*)p, nullptr, (float*)p, mode == kPoolGap ? nullptr : (float*)p, scratch);
+}
+
+// nfp_pool_supported / nfp_gap_supported: cosine / L2 (and their riders) on "same" maps, either layout, float32 or bf16 — the
+// table kernels (<= 512 pixels, descriptor with its workspace) or the row-band kernels (any size).  Pointer alignment is the
+// caller's: channels-last maps need 16-byte aligned images (as nfp_forward's hot path).
+int tail_supported(const nfp_desc* d, int mode) {
+  KP g;
+  if (make_kp(d, &g) || !tail_measure_ok(g, mode)) return 0;
+  if (g.B == 0) return 1;
+  const bool gp = mode == kPoolGap;
+  return both_launch([&] { return tail_try_forward(g, mode); }, [&] {
+    void* const p = kStandIn;
+    const float* f = (const float*)p;
+    return fused_backward(g, mode, p, gp ? p : nullptr, p, f, p, nullptr, f, gp ? nullptr : f);
+  }) ? 1 : 0;
+}
+// ... and their saved_floats: the per-pixel state, and behind it the scratch rows the forward would write
+int64_t tail_saved_floats(const nfp_desc* d, int mode) {
+  KP g;
+  if (make_kp(d, &g)) return -1;
+  if (!tail_measure_ok(g, mode) || g.B == 0) return 0;
+  long long scratch = 0;
+  {
+    const DryRun dry;
+    if (tail_try_forward(g, mode, &scratch) != NFP_OK) return 0;
+  }
+  return (int64_t)stats_of(g.measure) * g.B * g.P + scratch;
 }
 
 }  // namespace
@@ -391,7 +428,7 @@ static int max_links(const KP& g) {
     if (g.mode == NFP_PAD_REPLICATE) return lo ? 0 : n - 1;
     return -1;
   };
-  const int K = g.k, R = g.R;
+  const int R = g.R;
   // per axis: cnt[a][b] = taps d in [-R, R] with fold(a + d) == b
   auto axis = [&](int n, int rad, std::vector<int>& cnt) {
     cnt.assign((size_t)n * n, 0);
@@ -420,18 +457,14 @@ static int max_links(const KP& g) {
             n += iy[(size_t)ry * g.H + ty] * ix[(size_t)rx * g.W + tx] + iy[(size_t)ty * g.H + ry] * ix[(size_t)tx * g.W + rx];
           best = std::max(best, n);
         }
-  (void)K;
   return best;
 }
 
 int64_t nfp_workspace_bytes(const nfp_desc* d) {
   KP g;
   if (make_kp(d, &g)) return -1;
-  if (!fast_geometry(g)) {
-    // no tables; "same" maps the row-band kernels serve still get the arrival counters of their fused pooling tail
-    return (g.stride == 1 && g.dil == 1 && g.pad == g.R && g.mode != NFP_PAD_CIRCULAR && (g.R == 1 || g.R == 2) && g.rs != 12)
-               ? (int64_t)kTicketBytes : 0;
-  }
+  // no tables; "same" maps the row-band kernels serve still get the arrival counters of their fused pooling tail
+  if (!fast_geometry(g)) return same_geometry(g) && g.rs != 12 ? (int64_t)kTicketBytes : 0;
   const WsLayout L = ws_layout(g.P, g.rs, g.mode);
   if (max_links(g) > L.LW) return 0;
   return (int64_t)kTicketBytes + (int64_t)L.bytes;
@@ -482,141 +515,72 @@ int nfp_plan(const nfp_desc* d, int32_t backward, char* buf, int32_t buflen) {
 }
 
 // ---- fused nfp_pooling tail (models/NFP_Pooling.py:27-31) ----------------------------------------------
-// Both launchers run in plan mode (nothing touches the GPU): the answer is exactly "nfp_pool_forward AND
-// nfp_pool_backward would launch", whatever the LDS sizing rules of the kernels are this week.  (Round 2 re-derived
-// the backward's table size here and forgot the forward's slab: 576 descriptors with R = 2 and P >= 256 were promised
-// and then refused — ADVICE round 2.)
-static int pool_plan(const KP& g, bool backward) {
-  const DryRun dry;
-  void* const fake = kStandIn;
-  const float* cf = (const float*)fake;
-  return backward ? pool_backward(g, fake, fake, cf, fake, nullptr, cf, cf)
-                  : pool_forward(g, fake, fake, (float*)fake, nullptr, (float*)fake, (float*)fake);
-}
-
-static bool pool_measure_ok(const KP& g) {
-  return g.rs != 12 && hot_measure(g) && !mixed_maps(g);   // (map_f32: nfp_forward / nfp_backward only)
-}
-
-int nfp_pool_supported(const nfp_desc* d) {
-  KP g;
-  if (make_kp(d, &g)) return 0;
-  // cosine / L2 on "same" maps, either layout, float32 or bf16: the table kernels (<= 512 pixels, descriptor with its
-  // workspace) or the row-band kernels (any size).  Pointer alignment is the caller's: channels-last maps need 16-byte
-  // aligned images (as nfp_forward's hot path).
-  if (!pool_measure_ok(g)) return 0;
-  if (g.B == 0) return 1;
-  return pool_plan(g, false) == NFP_OK && pool_plan(g, true) == NFP_OK ? 1 : 0;
-}
-
-int64_t nfp_pool_saved_floats(const nfp_desc* d) {
-  KP g;
-  if (make_kp(d, &g)) return -1;
-  if (!pool_measure_ok(g) || g.B == 0) return 0;
-  if (pool_plan(g, false) != NFP_OK) return 0;
-  return (int64_t)stats_of(g.measure) * g.B * g.P + t_pool_scratch;
-}
+int nfp_pool_supported(const nfp_desc* d) { return tail_supported(d, kPoolBoth); }
+int64_t nfp_pool_saved_floats(const nfp_desc* d) { return tail_saved_floats(d, kPoolBoth); }
 
 int nfp_pool_forward(const nfp_desc* d, const void* x, float* gap, float* nfpm, void* out_map, float* saved,
                      void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!x || !nfpm) return fail(NFP_E_INVALID, "null tensor pointer");
-  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "fused pooling tail: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (missing({x, nfpm})) return NFP_E_INVALID;
+  if (int rc = tail_refused(g, kPoolBoth)) return rc;
   if (g.B == 0) return NFP_OK;
   g.pool_gap = gap != nullptr ? 1 : 0;       // NULL: GAP(x) is not wanted (texture_pooling.py:251-252)
   g.pool_map = out_map != nullptr ? 1 : 0;   // NULL: no backward will follow, nobody reads the maps
-  hipStream_t st = (hipStream_t)hip_stream;
-  return finish(pool_forward(g, x, out_map, saved, st, gap, nfpm), "nfp_pool_forward");
+  return finish(fused_forward(g, kPoolBoth, x, out_map, saved, (hipStream_t)hip_stream, gap, nfpm), "nfp_pool_forward");
 }
 
+// (grad_gap NULL: GAP(x) took no part in the loss, or was never produced)
 int nfp_pool_backward(const nfp_desc* d, const void* x, const float* grad_gap, const float* grad_nfpm,
                       const void* out_map, const float* saved, void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!x || !grad_nfpm || !out_map || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
-  if (!pool_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "fused pooling tail: cosine / dot / gfc / L2 (norm p=2) / rmse, one radius");
+  if (missing({x, grad_nfpm, out_map, grad_x})) return NFP_E_INVALID;
+  if (int rc = tail_refused(g, kPoolBoth)) return rc;
   if (stats_of(g.measure) > 0 && !saved) return fail(NFP_E_INVALID, "missing saved state");
   if (g.B == 0) return NFP_OK;
-  g.pool_gap = grad_gap != nullptr ? 1 : 0;  // NULL: GAP(x) took no part in the loss (or was never produced)
-  hipStream_t st = (hipStream_t)hip_stream;
-  return finish(pool_backward(g, x, out_map, saved, grad_x, st, grad_gap, grad_nfpm), "nfp_pool_backward");
+  return finish(fused_backward(g, kPoolBoth, x, nullptr, out_map, saved, grad_x, (hipStream_t)hip_stream, grad_gap, grad_nfpm),
+                "nfp_pool_backward");
 }
 
 // ---- GAP(x) beside the full maps: the first step of an NFP head (nfp_heads.py) -------------------------------------------
-// As pool_plan: both launchers in plan mode, so that a 1 means nfp_gap_forward AND nfp_gap_backward will launch.
-static int gap_plan(const KP& g, bool backward) {
-  const DryRun dry;
-  void* const fake = kStandIn;
-  const float* cf = (const float*)fake;
-  return backward ? gap_backward(g, fake, fake, fake, cf, fake, nullptr, cf)
-                  : gap_forward(g, fake, fake, (float*)fake, nullptr, (float*)fake);
-}
-
-// The gap calls also take radii (1, 2) together (inner_R = 1: make_kp); Norm p = 1 / EMD are outside hot_measure.
-static bool gap_measure_ok(const KP& g) { return hot_measure(g) && !mixed_maps(g); }   // (map_f32: nfp_forward / nfp_backward only)
-
-int nfp_gap_supported(const nfp_desc* d) {
-  KP g;
-  if (make_kp(d, &g)) return 0;
-  if (!gap_measure_ok(g)) return 0;
-  if (g.B == 0) return 1;
-  return gap_plan(g, false) == NFP_OK && gap_plan(g, true) == NFP_OK ? 1 : 0;
-}
-
-int64_t nfp_gap_saved_floats(const nfp_desc* d) {
-  KP g;
-  if (make_kp(d, &g)) return -1;
-  if (!gap_measure_ok(g) || g.B == 0) return 0;
-  if (gap_plan(g, false) != NFP_OK) return 0;
-  return (int64_t)stats_of(g.measure) * g.B * g.P + t_pool_scratch;
-}
+int nfp_gap_supported(const nfp_desc* d) { return tail_supported(d, kPoolGap); }
+int64_t nfp_gap_saved_floats(const nfp_desc* d) { return tail_saved_floats(d, kPoolGap); }
 
 int nfp_gap_forward(const nfp_desc* d, const void* x, float* gap, void* out_map, float* saved, int64_t saved_floats,
                     void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!gap_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse");
+  if (int rc = tail_refused(g, kPoolGap)) return rc;
   if (g.B == 0) return NFP_OK;
-  if (!x || !gap || !out_map) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, gap, out_map})) return NFP_E_INVALID;
   const int64_t need = std::max<int64_t>(nfp_gap_saved_floats(d), 1);
-  if (saved == nullptr || saved_floats < need)
-    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_gap_saved_floats is %lld", (long long)(saved ? saved_floats : 0),
-                (long long)need);
-  hipStream_t st = (hipStream_t)hip_stream;
-  return finish(gap_forward(g, x, out_map, saved, st, gap), "nfp_gap_forward");
+  if (saved == nullptr || saved_floats < need) return short_buffer("saved", saved ? saved_floats : 0, "nfp_gap_saved_floats is", need);
+  return finish(fused_forward(g, kPoolGap, x, out_map, saved, (hipStream_t)hip_stream, gap, nullptr), "nfp_gap_forward");
 }
 
 int nfp_gap_backward(const nfp_desc* d, const void* x, const float* grad_gap, const void* grad_out, const void* out_map,
                      const float* saved, int64_t saved_floats, void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = make_kp(d, &g)) return rc;
-  if (!gap_measure_ok(g)) return fail(NFP_E_UNSUPPORTED, "GAP beside the maps: cosine / dot / gfc / L2 (norm p=2) / rmse");
+  if (int rc = tail_refused(g, kPoolGap)) return rc;
   if (g.B == 0) return NFP_OK;
-  if (!x || !grad_out || !out_map || !grad_x) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, grad_out, out_map, grad_x})) return NFP_E_INVALID;
   const int64_t need = (int64_t)stats_of(g.measure) * g.B * g.P;   // (the backward reads the per-pixel state alone)
   if (need > 0 && (saved == nullptr || saved_floats < need))
-    return fail(NFP_E_INVALID, "saved holds %lld floats, the backward reads %lld", (long long)(saved ? saved_floats : 0), (long long)need);
-  hipStream_t st = (hipStream_t)hip_stream;
-  return finish(gap_backward(g, x, grad_out, out_map, saved, grad_x, st, grad_gap), "nfp_gap_backward");
+    return short_buffer("saved", saved ? saved_floats : 0, "the backward reads", need);
+  return finish(fused_backward(g, kPoolGap, x, grad_out, out_map, saved, grad_x, (hipStream_t)hip_stream, grad_gap, nullptr),
+                "nfp_gap_backward");
 }
 
 // ---- valid maps (padding 0): nfp_valid.hip ---------------------------------------------------------------------------------
-// Both launchers in plan mode, so that a 1 means nfp_valid_forward AND nfp_valid_backward will launch (4 KiB-aligned
-// buffers assumed, as nfp_plan does); nothing of the calling thread's variant / plan / error strings changes.
-static int valid_plan(const KP& g, bool backward) {
-  const DryRun dry;
-  void* const fake = kStandIn;
-  return backward ? valid_backward(g, fake, fake, fake, (const float*)fake, fake, nullptr)
-                  : valid_forward(g, fake, fake, (float*)fake, nullptr);
-}
-
 int nfp_valid_supported(const nfp_desc* d) {
   KP g;
-  const DryRun dry;   // (make_kp and valid_refusal's callers write the error string too)
-  return make_kp(d, &g) == NFP_OK && valid_refusal(g) == nullptr &&
-                 (g.B == 0 || (valid_plan(g, false) == NFP_OK && valid_plan(g, true) == NFP_OK))
-             ? 1 : 0;
+  const DryRun dry;   // (make_kp writes the error string too)
+  void* const p = kStandIn;
+  if (make_kp(d, &g) != NFP_OK || valid_refusal(g) != nullptr) return 0;
+  return g.B == 0 || both_launch([&] { return valid_forward(g, p, p, (float*)p, nullptr); },
+                                 [&] { return valid_backward(g, p, p, p, (const float*)p, p, nullptr); });
 }
 
 int64_t nfp_valid_saved_floats(const nfp_desc* d) {
@@ -635,10 +599,9 @@ static int valid_kp(const nfp_desc* d, KP* g) {
 int nfp_valid_forward(const nfp_desc* d, const void* x, void* out, float* saved, int64_t saved_floats, void* hip_stream) {
   KP g;
   if (int rc = valid_kp(d, &g)) return rc;
-  if (g.B > 0 && (!x || !out)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, out}, g.B > 0)) return NFP_E_INVALID;
   const int64_t need = nfp_valid_saved_floats(d);
-  if (saved != nullptr && saved_floats < need)
-    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_valid_saved_floats is %lld", (long long)saved_floats, (long long)need);
+  if (saved != nullptr && saved_floats < need) return short_buffer("saved", saved_floats, "nfp_valid_saved_floats is", need);
   if (g.B == 0) return NFP_OK;
   return finish(valid_forward(g, x, out, saved, (hipStream_t)hip_stream), "nfp_valid_forward");
 }
@@ -647,11 +610,10 @@ int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, c
                        int64_t saved_floats, void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = valid_kp(d, &g)) return rc;
-  if (g.B > 0 && (!x || !grad_out || !out || !grad_x)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, grad_out, out, grad_x}, g.B > 0)) return NFP_E_INVALID;
   const int64_t need = nfp_valid_saved_floats(d);
   if (need > 0 && (saved == nullptr || saved_floats < need))
-    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_valid_saved_floats is %lld", (long long)(saved ? saved_floats : 0),
-                (long long)need);
+    return short_buffer("saved", saved ? saved_floats : 0, "nfp_valid_saved_floats is", need);
   if (g.B == 0) return NFP_OK;
   return finish(valid_backward(g, x, grad_out, out, saved, grad_x, (hipStream_t)hip_stream), "nfp_valid_backward");
 }
@@ -660,11 +622,10 @@ int nfp_valid_backward(const nfp_desc* d, const void* x, const void* grad_out, c
 int nfp_valid_abs_supported(const nfp_desc* d) {
   KP g;
   const DryRun dry;
-  void* const fake = kStandIn;
-  return make_kp(d, &g) == NFP_OK && valid_abs_refusal(g) == nullptr &&
-                 (g.B == 0 || (valid_abs_forward(g, fake, fake, nullptr) == NFP_OK &&
-                               valid_abs_backward(g, fake, fake, fake, nullptr) == NFP_OK))
-             ? 1 : 0;
+  void* const p = kStandIn;
+  if (make_kp(d, &g) != NFP_OK || valid_abs_refusal(g) != nullptr) return 0;
+  return g.B == 0 || both_launch([&] { return valid_abs_forward(g, p, p, nullptr); },
+                                 [&] { return valid_abs_backward(g, p, p, p, nullptr); });
 }
 
 static int valid_abs_kp(const nfp_desc* d, KP* g) {
@@ -676,7 +637,7 @@ static int valid_abs_kp(const nfp_desc* d, KP* g) {
 int nfp_valid_abs_forward(const nfp_desc* d, const void* x, void* out, void* hip_stream) {
   KP g;
   if (int rc = valid_abs_kp(d, &g)) return rc;
-  if (g.B > 0 && (!x || !out)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, out}, g.B > 0)) return NFP_E_INVALID;
   if (g.B == 0) return NFP_OK;
   return finish(valid_abs_forward(g, x, out, (hipStream_t)hip_stream), "nfp_valid_abs_forward");
 }
@@ -684,7 +645,7 @@ int nfp_valid_abs_forward(const nfp_desc* d, const void* x, void* out, void* hip
 int nfp_valid_abs_backward(const nfp_desc* d, const void* x, const void* grad_out, void* grad_x, void* hip_stream) {
   KP g;
   if (int rc = valid_abs_kp(d, &g)) return rc;
-  if (g.B > 0 && (!x || !grad_out || !grad_x)) return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, grad_out, grad_x}, g.B > 0)) return NFP_E_INVALID;
   if (g.B == 0) return NFP_OK;
   return finish(valid_abs_backward(g, x, grad_out, grad_x, (hipStream_t)hip_stream), "nfp_valid_abs_backward");
 }
@@ -731,11 +692,10 @@ int nfp_bias_forward(const nfp_desc* d, const void* x, const float* centre_bias,
   int dw;
   if (int rc = bias_kp(d, &g, &dw)) return rc;
   // (an empty batch: x and out hold no element, and torch hands such tensors over as NULL)
-  if ((g.B > 0 && (!x || !out)) || !neighbour_bias || (!centre_bias && !bias_no_centre(g)))
-    return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, out}, g.B > 0) || missing({neighbour_bias}) || missing({centre_bias}, !bias_no_centre(g))) return NFP_E_INVALID;
   const int64_t need = nfp_bias_saved_floats(d);
   if ((saved != nullptr || g.measure == NFP_ATTENTION) && need > 0 && (saved == nullptr || saved_floats < need))
-    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
+    return short_buffer("saved", saved_floats, "nfp_bias_saved_floats is", need);
   if (g.B == 0) return NFP_OK;
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.measure == NFP_ATTENTION) {
@@ -754,15 +714,13 @@ int nfp_bias_backward(const nfp_desc* d, const void* x, const float* centre_bias
   int dw;
   if (int rc = bias_kp(d, &g, &dw)) return rc;
   const bool nc = bias_no_centre(g);
-  if ((g.B > 0 && (!x || !grad_out || !out || !grad_x)) || !neighbour_bias || !grad_neighbour_bias ||
-      (!nc && (!centre_bias || !grad_centre_bias)))
-    return fail(NFP_E_INVALID, "null tensor pointer");
+  if (missing({x, grad_out, out, grad_x}, g.B > 0) || missing({neighbour_bias, grad_neighbour_bias}) ||
+      missing({centre_bias, grad_centre_bias}, !nc))
+    return NFP_E_INVALID;
   const int64_t need = nfp_bias_saved_floats(d), need_s = nfp_bias_scratch_floats(d);
-  if (need > 0 && (saved == nullptr || saved_floats < need))
-    return fail(NFP_E_INVALID, "saved holds %lld floats, nfp_bias_saved_floats is %lld", (long long)saved_floats, (long long)need);
+  if (need > 0 && (saved == nullptr || saved_floats < need)) return short_buffer("saved", saved_floats, "nfp_bias_saved_floats is", need);
   if ((need_s > 0 && scratch == nullptr) || scratch_floats < need_s)
-    return fail(NFP_E_INVALID, "scratch holds %lld floats, nfp_bias_scratch_floats is %lld", (long long)scratch_floats,
-                (long long)need_s);
+    return short_buffer("scratch", scratch_floats, "nfp_bias_scratch_floats is", need_s);
   hipStream_t st = (hipStream_t)hip_stream;
   if (g.measure == NFP_ATTENTION) {
     // gradient with respect to the dots behind the scratch's coefficient and partial-sum parts, then DotProduct's backward

@@ -253,13 +253,13 @@ inline bool force_generic() { return g_sw.force_generic.load(std::memory_order_r
 // the matrix-core kernels (nfp_mfma.h::fwd_gram, nfp_fast.h::bwd_gemm_phase): NFP_MFMA=0 turns them off
 inline bool mfma_enabled() { return g_sw.mfma.load(std::memory_order_relaxed) != 0; }
 
-// Geometry of the hot path: "same" maps (stride 1, dilation 1, pad = R) small enough for one workgroup per image.
-// These are the descriptors that have workspace tables (nfp_tables.h).
-inline bool fast_geometry(const KP& g) {
-  if (g.stride != 1 || g.dil != 1 || g.pad != g.R || g.mode == NFP_PAD_CIRCULAR) return false;
-  if (g.R != 1 && g.R != 2) return false;
-  return g.P <= kBwdThreads && g.P >= 4;
+// A "same" map: stride 1, dilation 1, pad = R, no circular padding, k = 3 or 5 — what every hot-path kernel is built for
+inline bool same_geometry(const KP& g) {
+  return g.stride == 1 && g.dil == 1 && g.pad == g.R && g.mode != NFP_PAD_CIRCULAR && (g.R == 1 || g.R == 2);
 }
+// Geometry of the table kernels: "same" maps small enough for one workgroup per image.
+// These are the descriptors that have workspace tables (nfp_tables.h).
+inline bool fast_geometry(const KP& g) { return same_geometry(g) && g.P <= kBwdThreads && g.P >= 4; }
 
 // Which calls the hot-path kernels serve; everything else runs on the generic kernels.
 // sym: also the five measures of nfp_measures.h::kSymTerm (plain single-radius maps only: their callers pass it)
@@ -279,8 +279,7 @@ inline bool fast_ok(const KP& g, const void* x, const void* gx, bool sym = false
 
 // ... and the row-band kernels (nfp_tile.h): "same" maps of any size, no tables
 inline bool tile_geometry(const KP& g) {
-  if (g.stride != 1 || g.dil != 1 || g.pad != g.R || g.mode == NFP_PAD_CIRCULAR || g.rs == 12) return false;
-  if (g.R != 1 && g.R != 2) return false;
+  if (!same_geometry(g) || g.rs == 12) return false;
   // one thread per padded position: the smallest band (R + 1 rows and its halo) must fit a workgroup
   if (g.W < 2 * g.R + 2 || g.H < g.R + 1) return false;
   return (g.W + 2 * g.R) * (3 * g.R + 1) <= 1024;
@@ -338,7 +337,21 @@ int with_hot(const KP& g, F&& f) {
   return hot_product(g) ? f(Int<NFP_COSINE>{}) : f(Int<NFP_NORM>{});
 }
 
-// the fused tail of the launch: none, nfp_pool_* (both pooled sums) or nfp_gap_* (GAP(x) beside the maps)
+// The fused tail of a launch as one value; default-constructed: plain maps, no tail.  mode: kPoolNone, kPoolBoth (nfp_pool_*:
+// both pooled sums) or kPoolGap (nfp_gap_*: GAP(x) beside the maps).  The launchers unpack it at their launch(...) call.
+struct FwdTail {
+  int mode = nfp::kPoolNone;
+  float* gap = nullptr;    // [B,C] channel means, or null
+  float* nfpm = nullptr;   // [B,N] map means (kPoolBoth), or null
+  float* part = nullptr;   // scratch for the bands' partial sums: rows of C + N floats (kPoolGap: C), or null (one band)
+  int* nb = nullptr;       // out: rows of `part` per image
+};
+struct BwdTail {
+  int mode = nfp::kPoolNone;
+  const float* ggap = nullptr;    // grad of gap [B,C], or null
+  const float* gnfpm = nullptr;   // grad of nfpm [B,N] (kPoolBoth), or null
+};
+// ... and its template argument
 template <typename F>
 int with_pool(int pool, F&& f) {
   if (pool == nfp::kPoolGap) return f(Int<nfp::kPoolGap>{});
@@ -407,28 +420,25 @@ int attn_softmax_backward(const KP& g, const void* go, const void* out, float* g
 
 // ---- the table kernels of nfp_mfma.h / nfp_band.h (nfp_table_fwd.hip) and nfp_fast.h (nfp_table_bwd.hip) ------------------
 // Each returns NFP_OK, kNotApplicable or an NFP_E_* code; g_variant names the launch.  The caller has asked fast_ok; the
-// radius (12: g.rs), the family (with_hot<true>) and the tail (pool, as below) select the instantiation.  Those that exist:
+// radius (12: g.rs), the family (with_hot<true>) and the tail (t.mode) select the instantiation.  Those that exist:
 // plain maps for every family, but not kSymTerm with radius 12; the pooled and gap tails for the cosine and L2 families
 // alone, and kPoolBoth not with radius 12.  fwd_gram and the matrix-core backward: cosine / L2, one radius (its tail is
 // a run-time option of fwd_gram: gap, nfpm or both null).
 template <int R, int M, int POOL>
 constexpr bool kHasTable = POOL == nfp::kPoolNone ? !(R == 12 && M == kSymTerm)
                                                   : (M == NFP_COSINE || M == NFP_NORM) && !(R == 12 && POOL == nfp::kPoolBoth);
-int table_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap, float* nfpm);
-int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* gap, float* nfpm,
-                   float* part, int* nb);
+int table_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t = {});
+int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t = {});
 // (the matrix-core form first where it exists and applies, else the vector form)
 int table_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                   int pool, const float* ggap, const float* gnfpm);
+                   const BwdTail& t = {});
 
 // ---- the row-band kernels of nfp_tile.h (nfp_tile_fwd.hip, nfp_tile_bwd.hip; shared sizing: nfp_tile_launch.h) ------------
 // Each returns NFP_OK, kNotApplicable (this descriptor is not theirs / does not fit) or an NFP_E_* code; g_variant names
-// the launch.  pool: nfp::kPoolNone / kPoolBoth (the fused nfp_pooling tail) / kPoolGap (GAP(x) beside the maps); part = scratch
-// for the bands' partial sums, rows of C + N floats (kPoolGap: C); *nb = rows per image.
-int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
-                 float* gap, float* nfpm);
+// the launch.  The tail: FwdTail / BwdTail above (a pooled forward always writes its sums to t.part, *t.nb rows per image).
+int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t = {});
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                  int pool, const float* ggap, const float* gnfpm);
+                  const BwdTail& t = {});
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st);
 
 // ---- NFPPooling(bias=True) (nfp_bias.hip, ABI 7) -------------------------------------------------------------------------

@@ -39,7 +39,7 @@ constexpr size_t kEarlyBudget = 96 * 1024;  // slab beside the pair values (comm
 
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
 int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
+                      hipStream_t st, const BwdTail& t) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
 #ifndef NFP_BWD_WGS
 #define NFP_BWD_WGS 256
@@ -97,20 +97,20 @@ int launch_bwd_fast_t(KP g, const void* x, const void* go, const void* out, cons
   if constexpr (R == 1 && !BF && !NHWC && POOL == kPoolNone && (M == NFP_COSINE || M == NFP_NORM)) {
     if (!satb && g.Cc >= g.Cwg && ceil_div(g.Cwg / 4, g.G) <= nfp::kRS && !g_sw.stage_blocks.load(std::memory_order_relaxed))
       return launch_staged(true, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, true>, dim3(g.B, S), dim3(T), lds, st, x, go, out,
-                           saved, g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+                           saved, g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, t.ggap, t.gnfpm, g);
   }
   if constexpr (!NHWC)
     return launch_staged(false, "bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
-                         g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+                         g.ws, hgeom, g.C, g.Cwg, g.Cc, gx, t.ggap, t.gnfpm, g);
   else
     return launch("bwd_fast", bwd_fast<R, M, BF, NHWC, POOL, 0, false, MF>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved, g.ws, hgeom,
-                  g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+                  g.C, g.Cwg, g.Cc, gx, t.ggap, t.gnfpm, g);
 }
 
 // Phase B of the backward on the matrix cores (nfp_fast.h::bwd_gemm_phase): bf16 storage, C a multiple of 32.
 template <int R, int M, bool NHWC, int POOL = kPoolNone>
 int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                      hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
+                      hipStream_t st, const BwdTail& t) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
   if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 31) || mixed_maps(g)) return kNotApplicable;
   if (NHWC && (((uintptr_t)x & 15) || ((g.sB * 2) & 15) || ((uintptr_t)gx & 15) || ((g.gB * 2) & 15)))
@@ -163,7 +163,7 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
       snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma2%s>", R, hot_name(g), NHWC ? "nhwc" : "nchw",
                pool_tag(POOL));
       return launch("bwd_fast_mfma2", bwd_fast<R, M, true, NHWC, POOL, 2>, dim3(g.B, S), dim3(T), lds3, st, x, go, out, saved,
-                    g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+                    g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, t.ggap, t.gnfpm, g);
     }
   }
   if (rt >= 2 && rt < nt) rt = (nt + ((nt + rt - 1) / rt) - 1) / ((nt + rt - 1) / rt);  // even rounds
@@ -176,7 +176,7 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
   snprintf(g_variant, sizeof(g_variant), "bwd_fast<R%d,%s,bf16,%s,mfma%s>", R, hot_name(g),
            NHWC ? "nhwc" : "nchw", pool_tag(POOL));
   return launch("bwd_fast_mfma", bwd_fast<R, M, true, NHWC, POOL, 1>, dim3(g.B, S), dim3(T), lds, st, x, go, out, saved,
-                g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, ggap, gnfpm, g);
+                g.ws, nfp::bwd_head_geom(g.P, g.mode, g.unit, g.G, T), g.C, g.Cwg, g.Cc, gx, t.ggap, t.gnfpm, g);
 }
 
 // The table backward: phase B on the matrix cores where that form exists (bf16 maps, one radius, cosine / L2) and applies,
@@ -184,23 +184,23 @@ int launch_bwd_gemm_t(KP g, const void* x, const void* go, const void* out, cons
 // matrix-core backward stages grad_out / out under an LDS budget sized for 2-byte values.)
 template <int R, int M, int POOL = kPoolNone>
 int launch_bwd_fast(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx,
-                    hipStream_t st, const float* ggap = nullptr, const float* gnfpm = nullptr) {
+                    hipStream_t st, const BwdTail& t) {
   return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
     if constexpr (bf() && !mf() && R != 12 && (M == NFP_COSINE || M == NFP_NORM))
-      if (int rc = launch_bwd_gemm_t<R, M, nhwc(), POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm); rc != kNotApplicable)
+      if (int rc = launch_bwd_gemm_t<R, M, nhwc(), POOL>(g, x, go, out, saved, gx, st, t); rc != kNotApplicable)
         return rc;
-    return launch_bwd_fast_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+    return launch_bwd_fast_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, t);
   });
 }
 
 }  // namespace
 
 int table_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                   int pool, const float* ggap, const float* gnfpm) {
-  return with_radius<true>(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+                   const BwdTail& t) {
+  return with_radius<true>(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
     if constexpr (kHasTable<R, M, POOL>)
-      return launch_bwd_fast<R, M, POOL>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+      return launch_bwd_fast<R, M, POOL>(g, x, go, out, saved, gx, st, t);
     else
       return kNotApplicable;
   }); }); });
@@ -208,10 +208,4 @@ int table_backward(const KP& g, const void* x, const void* go, const void* out, 
 
 }  // namespace nfp_host
 
-#ifdef NFP_STAMPS
-// (every translation unit has its own copy of the device-side stamp pointer)
-extern "C" int nfp_debug_set_stamp_buffer_table_bwd(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
-}
-#endif
+NFP_STAMP_SETTER(table_bwd)

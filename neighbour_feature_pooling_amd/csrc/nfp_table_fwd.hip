@@ -19,8 +19,7 @@ namespace {
 #define NFP_BAND_WGS 256
 #endif
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool MF = false>   // MF: float32 maps beside bf16 x
-int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                      float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
+int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
   constexpr int NF = Win<R>::NF;
   int nb = std::min(g.H, (NFP_BAND_WGS + g.B - 1) / g.B);   // bands per image so that >= NFP_BAND_WGS workgroups exist
   // two workgroups per CU overlap each other's load and sum phases — worth it while a band's R halo rows stay a small
@@ -36,7 +35,7 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
 #endif
   // Round 4: with the workspace's arrival counters the last band to finish folds them all inside the SAME launch
   // (nfp_common.h::pool_last_band): the bands come back.  Without counters: one band, as before.
-  if (POOL && (part == nullptr || !(NFP_POOL_BANDS || g.tickets != nullptr))) nb = 1;
+  if (POOL && (t.part == nullptr || !(NFP_POOL_BANDS || g.tickets != nullptr))) nb = 1;
   const int rb = (g.H + nb - 1) / nb;
   nb = (g.H + rb - 1) / rb;
   const int psm = std::min(g.P, (rb + g.R) * g.W);          // most pixels a band stages
@@ -80,7 +79,7 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   if (lds > (size_t)kLdsMax) return kNotApplicable;
   snprintf(g_variant, sizeof(g_variant), "fwd_band<R%s,%s,%s,%s%s>x%d", R == 12 ? "1+2" : (R == 1 ? "1" : "2"), hot_name(g),
            MF ? "mix" : (BF ? "bf16" : "f32"), NHWC ? "nhwc" : "nchw", pool_tag(POOL), nb);
-  if (nb_out) *nb_out = nb;
+  if (t.nb) *t.nb = nb;
   // the kernel's preloadable head (nfp_common.h): what stands in front of its first x request
   const uint32_t sB_lo = (uint32_t)((unsigned long long)g.sB & 0xFFFFFFFFull), sB_hi = (uint32_t)((unsigned long long)g.sB >> 32);
   const uint32_t hchunk = nfp::band_head_chunk(g.Cc, lg, g.R, T), hgeom = nfp::band_head_geom(g.H, g.W, rb);
@@ -89,12 +88,12 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
   auto go = [&](auto kernel) {
     if constexpr (NHWC)
       return launch("fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk, hgeom, out, saved,
-                    gap, nfpm, part, g);
+                    t.gap, t.nfpm, t.part, g);
     else
       return launch_staged(false, "fwd_band", kernel, dim3(g.B, nb), dim3(T), lds, st, x, g.ws, sB_lo, sB_hi, g.C, hchunk,
-                           hgeom, out, saved, gap, nfpm, part, g);
+                           hgeom, out, saved, t.gap, t.nfpm, t.part, g);
   };
-  // (pooled, several bands: the bands' partial sums go to `part`; the caller folds them — nfp_hip.hip::pool_forward)
+  // (pooled, several bands: the bands' partial sums go to t.part; the caller folds them — nfp_hip.hip::fused_forward)
   if constexpr (M != kSymTerm)
   if (g.unit || g.gfc || g.d2s != 1.f)   // DotProduct / GFC / RMSE: the finalize with the run-time constants
     return go(fwd_band<R, M, BF, NHWC, POOL, true, MF>);
@@ -102,18 +101,16 @@ int launch_fwd_band_t(KP g, const void* x, void* out, float* saved, hipStream_t 
 }
 
 template <int R, int M, int POOL = kPoolNone>
-int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                    float* nfpm = nullptr, float* part = nullptr, int* nb_out = nullptr) {
+int launch_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
   if (g.ws == nullptr) return kNotApplicable;
   return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
-    return launch_fwd_band_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, gap, nfpm, part, nb_out);
+    return launch_fwd_band_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, t);
   });
 }
 
-// Matrix-core forward (nfp_mfma.h): bf16, dense channels-last, C a multiple of 16.
+// Matrix-core forward (nfp_mfma.h): bf16, dense channels-last, C a multiple of 16.  Of the tail it takes the two outputs alone.
 template <int R, int M>
-int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap = nullptr,
-                    float* nfpm = nullptr) {
+int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap, float* nfpm) {
   if (!mfma_enabled() || g.dtype != NFP_BF16 || (g.C & 15) || g.P > 512) return kNotApplicable;
   if (mixed_maps(g)) return kNotApplicable;   // (the Gram-form L2 loses digits a float32 map would show: DESIGN §4)
   if (g.unit || g.gfc || g.d2s != 1.f) return kNotApplicable;   // (DotProduct / GFC / RMSE: the vector kernels' run-time constants)
@@ -142,22 +139,21 @@ int launch_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStre
 
 }  // namespace
 
-int table_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, float* gap, float* nfpm) {
+int table_fwd_gram(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
   return with_radius<true>(g, [&](auto r) { return with_hot<true>(g, [&](auto m) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value;
     if constexpr (R != 12 && (M == NFP_COSINE || M == NFP_NORM))   // the matrix-core forward has these two forms alone
-      return launch_fwd_gram<R, M>(g, x, out, saved, st, gap, nfpm);
+      return launch_fwd_gram<R, M>(g, x, out, saved, st, t.gap, t.nfpm);
     else
       return kNotApplicable;
   }); });
 }
 
-int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* gap, float* nfpm,
-                   float* part, int* nb) {
-  return with_radius<true>(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
+  return with_radius<true>(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
     if constexpr (kHasTable<R, M, POOL>)
-      return launch_fwd_band<R, M, POOL>(g, x, out, saved, st, gap, nfpm, part, nb);
+      return launch_fwd_band<R, M, POOL>(g, x, out, saved, st, t);
     else
       return kNotApplicable;
   }); }); });
@@ -165,10 +161,4 @@ int table_fwd_band(const KP& g, const void* x, void* out, float* saved, hipStrea
 
 }  // namespace nfp_host
 
-#ifdef NFP_STAMPS
-// (every translation unit has its own copy of the device-side stamp pointer)
-extern "C" int nfp_debug_set_stamp_buffer_table_fwd(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
-}
-#endif
+NFP_STAMP_SETTER(table_fwd)

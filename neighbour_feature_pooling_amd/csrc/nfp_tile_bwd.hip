@@ -9,7 +9,7 @@ namespace {
 
 template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone, bool MF = false>
 int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                      const float* ggap = nullptr, const float* gnfpm = nullptr) {
+                      const BwdTail& t) {
   constexpr int N = Win<R>::N, K2 = Win<R>::K2;
   const int Wu = g.W + 2 * R;
   for (int attempt = 0; attempt < 2; ++attempt) {
@@ -74,8 +74,8 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
         const void* os = (const char*)out + (long long)b0 * N * g.P * oes;
         const float* ss = saved ? saved + (long long)b0 * g.P : nullptr;
         void* gxs = (char*)gx + (long long)b0 * g.gB * es;
-        const float* ggs = ggap ? ggap + (long long)b0 * g.C : nullptr;
-        const float* gns = gnfpm ? gnfpm + (long long)b0 * N : nullptr;
+        const float* ggs = t.ggap ? t.ggap + (long long)b0 * g.C : nullptr;
+        const float* gns = t.gnfpm ? t.gnfpm + (long long)b0 * N : nullptr;
         auto go_ = [&](auto gfc, auto cstv) {
           return launch("bwd_tile", bwd_tile<R, M, BF, NHWC, POOL, decltype(gfc)::value, decltype(cstv)::value, MF>, grid, block, lds, st,
                         gs, tg, xs, gos, os, ss, gxs, ggs, gns);
@@ -103,13 +103,13 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
 }  // namespace
 
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
-                  int pool, const float* ggap, const float* gnfpm) {
+                  const BwdTail& t) {
   if (!tile_ok(g, x, gx)) return kNotApplicable;
-  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
     if constexpr (kHasTile<M, POOL>)   // (grad_out of kPoolGap is a map; grad(GAP) joins in the store)
       return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
-        return launch_bwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, ggap, gnfpm);
+        return launch_bwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, t);
       });
     else
       return kNotApplicable;
@@ -118,10 +118,4 @@ int tile_backward(const KP& g, const void* x, const void* go, const void* out, c
 
 }  // namespace nfp_host
 
-#ifdef NFP_STAMPS
-// (every translation unit has its own copy of the device-side stamp pointer)
-extern "C" int nfp_debug_set_stamp_buffer_tile_bwd(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
-}
-#endif
+NFP_STAMP_SETTER(tile_bwd)

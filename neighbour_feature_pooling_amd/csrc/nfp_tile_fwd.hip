@@ -9,8 +9,7 @@ namespace {
 
 // MF: float32 maps beside bf16 x (mixed_maps, nfp_launch.h) — the register-staged kernel, not the LDS-DMA one
 template <int R, int M, bool BF, bool NHWC, int POOL = nfp::kPoolNone, bool MF = false>
-int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t st, float* part = nullptr, int* nb_out = nullptr,
-                      float* gap = nullptr, float* nfpm = nullptr) {
+int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
   constexpr int NF = Win<R>::NF, N = Win<R>::N;
   constexpr int NP = POOL == nfp::kPoolBoth ? N : 0;   // map sums behind the channel sums of a scratch row
   const int Wu = g.W + 2 * R;
@@ -67,7 +66,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
         }
       }
       nfp::TileGeo tg = {nb, rows, Wu, ppb, 1, g.H / nb, g.H % nb, (int)(lds / 4)};
-      if (nb_out) *nb_out = POOL ? nb * nfp::kPoolSub : nb;   // (pooled: rows of partial sums per image)
+      if (t.nb) *t.nb = POOL ? nb * nfp::kPoolSub : nb;   // (pooled: rows of partial sums per image)
       snprintf(g_variant, sizeof(g_variant), "fwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"),
                NHWC ? "nhwc" : "nchw", dma ? ",dma" : "", pool_tag(POOL), nb);
       const dim3 block(G, Wu, rows);
@@ -80,9 +79,9 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
         const void* xs = (const char*)x + (long long)b0 * g.sB * es;
         void* os = (char*)out + (long long)b0 * N * g.P * oes;
         float* ss = saved ? saved + (long long)b0 * g.P : nullptr;
-        float* ps = part ? part + (long long)b0 * nb * nfp::kPoolSub * (g.C + NP) : nullptr;
-        float* gs_ = gap ? gap + (long long)b0 * g.C : nullptr;
-        float* ns_ = nfpm ? nfpm + (long long)b0 * N : nullptr;
+        float* ps = t.part ? t.part + (long long)b0 * nb * nfp::kPoolSub * (g.C + NP) : nullptr;
+        float* gs_ = t.gap ? t.gap + (long long)b0 * g.C : nullptr;
+        float* ns_ = t.nfpm ? t.nfpm + (long long)b0 * N : nullptr;
         int rc;
         if (M == NFP_COSINE && g.gfc) {
           rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, M == NFP_COSINE, false, MF>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
@@ -104,17 +103,16 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
 
 }  // namespace
 
-int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, int pool, float* part, int* nb,
-                 float* gap, float* nfpm) {
+int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
   if (!tile_ok(g, x, x)) return kNotApplicable;
   // (the symmetric-term measures below 14 x 14: the any-geometry forward spreads the same arithmetic over more threads:
   // [64,512,7,7] 9 vs 14 us; the backward wins at every size: 17.6-22.9 vs 20.9-28.6 us there — profiles/r04_zd_…)
   if (hot_sym(g) && g.P < 196) return kNotApplicable;
-  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(pool, [&](auto p) {
+  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
     if constexpr (kHasTile<M, POOL>)
       return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
-        return launch_fwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, part, nb, gap, nfpm);
+        return launch_fwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, t);
       });
     else
       return kNotApplicable;
@@ -129,10 +127,4 @@ int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int 
 
 }  // namespace nfp_host
 
-#ifdef NFP_STAMPS
-// (every translation unit has its own copy of the device-side stamp pointer)
-extern "C" int nfp_debug_set_stamp_buffer_tile_fwd(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(nfp::nfp_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -3;
-}
-#endif
+NFP_STAMP_SETTER(tile_fwd)

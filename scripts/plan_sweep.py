@@ -8,7 +8,7 @@
 Two builds decide alike when their outputs are equal byte for byte (a change to the host-side selection code is
 checked that way: the parent's library and the new one, every setting).  A line holds the descriptor, nfp_plan in both
 directions (return code, text, nfp_last_error() where refused), nfp_saved_floats / nfp_workspace_bytes /
-nfp_output_shape, the pool / gap / valid queries (with the stand-in workspace the descriptor is entitled to) and the
+nfp_output_shape, the pool / gap / valid / valid_abs queries (with the stand-in workspace the descriptor is entitled to) and the
 biased path's two sizes.
 
 Descriptors: the 3000 draws of tests/test_dispatch_plan.py's sweep (same generator and seed), the tables of
@@ -80,7 +80,8 @@ def line(L, d):
     cols.append(f"saved={L.nfp_saved_floats(ref)} ws={wsb} shape={rc}:{n.value},{ho.value},{wo.value}")
     d.ws = 0x1000 if wsb > 0 else None
     cols.append(f"pool={L.nfp_pool_supported(ref)}/{L.nfp_pool_saved_floats(ref)} gap={L.nfp_gap_supported(ref)}/"
-                f"{L.nfp_gap_saved_floats(ref)} valid={L.nfp_valid_supported(ref)}/{L.nfp_valid_saved_floats(ref)}")
+                f"{L.nfp_gap_saved_floats(ref)} valid={L.nfp_valid_supported(ref)}/{L.nfp_valid_saved_floats(ref)} "
+                f"valid_abs={L.nfp_valid_abs_supported(ref)}")
     cols.append(f"bias={L.nfp_bias_saved_floats(ref)}/{L.nfp_bias_scratch_floats(ref)}")
     return " | ".join(cols)
 
