@@ -62,6 +62,8 @@ struct KP {
 //   kPoolGap   nfp_gap_*: GAP(x) beside the full maps (an NFP head, nfp_heads.py: gap(fmap) and nfp(fmap) of one feature
 //              map) — no pooled map sums; the backward reads grad_out as a map and adds ggap[b,c] / P in the same store
 constexpr int kPoolNone = 0, kPoolBoth = 1, kPoolGap = 2;
+// threads of a bwd_tile<3,...> workgroup at most (nfp_tile.h: its launch bound; nfp_launch.h::tile_r3_geometry: what that admits)
+constexpr int kTileBwdCapR3 = 512;
 
 // ---- the preloadable HEAD of fwd_band (nfp_band.h) and bwd_fast (nfp_fast.h) ---------------------------------------------
 // A kernel's arguments lie in a block of memory the host (or the graph) wrote, which no earlier launch has read: whatever the

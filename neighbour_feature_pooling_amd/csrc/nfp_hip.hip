@@ -107,9 +107,12 @@ extern "C" int nfp_debug_set_stamp_buffer_table_fwd(void* dev_ptr);
 extern "C" int nfp_debug_set_stamp_buffer_table_bwd(void* dev_ptr);
 extern "C" int nfp_debug_set_stamp_buffer_tile_fwd(void* dev_ptr);
 extern "C" int nfp_debug_set_stamp_buffer_tile_bwd(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_tile_r3_fwd(void* dev_ptr);
+extern "C" int nfp_debug_set_stamp_buffer_tile_r3_bwd(void* dev_ptr);
 extern "C" int nfp_debug_set_stamp_buffer(void* dev_ptr) {
   for (auto set : {nfp_debug_set_stamp_buffer_generic, nfp_debug_set_stamp_buffer_table_fwd, nfp_debug_set_stamp_buffer_table_bwd,
-                   nfp_debug_set_stamp_buffer_tile_fwd, nfp_debug_set_stamp_buffer_tile_bwd})
+                   nfp_debug_set_stamp_buffer_tile_fwd, nfp_debug_set_stamp_buffer_tile_bwd,
+                   nfp_debug_set_stamp_buffer_tile_r3_fwd, nfp_debug_set_stamp_buffer_tile_r3_bwd})
     if (int rc = set(dev_ptr)) return rc;
   return NFP_OK;
 }

@@ -1,6 +1,6 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI and
 // dispatch; nfp_generic.hip: the any-geometry kernels; nfp_table_fwd.hip / nfp_table_bwd.hip: the table kernels;
-// nfp_tile_fwd.hip / nfp_tile_bwd.hip: the row-band kernels; nfp_bias.hip: NFPPooling(bias=True);
+// nfp_tile_fwd.hip / nfp_tile_bwd.hip: the row-band kernels (nfp_tile_r3_fwd.hip / nfp_tile_r3_bwd.hip: their radius 3); nfp_bias.hip: NFPPooling(bias=True);
 // nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_cpool.hip: the heads'
 // compress-BN-ReLU-GAP tail), and the interface of each unit's launchers to the dispatcher (below).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
@@ -62,6 +62,9 @@ struct Switches {
                                      // more per pixel (8 pieces per position: [256,128,28,28] 23.9 -> 18.8 us, [256,64,56,56] 44.2 ->
                                      // 42.2) — 0 = never, 1 = wherever it applies (float32 loses: 72 -> 121 us at
                                      // [256,16,112,112]; profiles/r04_h_…)
+  std::atomic<int> tile_r3{-1};      // radius-3 "same" maps (k = 7) on the row-band kernels of nfp_tile.h: -1 = the default routing
+                                     // (tile_r3_wanted below), 0 = never (fwd_pairs / bwd_gather, as before those instantiations
+                                     // existed: the A/B arm), 1 = wherever they can serve
   std::atomic<int> stage_blocks{0};  // A/B, tests: NCHW maps staged in 4 x 4 blocks also where bwd_fast's launcher would stage
                                      // them by pixel rows (nfp_fast.h: StagedRows) — the two forms agree bitwise
 };
@@ -89,6 +92,10 @@ inline void read_env() {
   {
     const char* e = getenv("NFP_TILE_DMA");
     g_sw.tile_dma = e ? (e[0] == '1' ? 1 : 0) : -1;
+  }
+  {
+    const char* e = getenv("NFP_TILE_R3");
+    g_sw.tile_r3 = e ? (e[0] == '1' ? 1 : 0) : -1;
   }
   g_sw.stage_blocks = flag("NFP_STAGE_BLOCKS", 0);
   g_sw.tile_first = flag("NFP_TILE_FIRST", 0);   // A/B: the row-band kernels of nfp_tile.h also for maps the table kernels serve
@@ -277,8 +284,31 @@ inline bool fast_ok(const KP& g, const void* x, const void* gx, bool sym = false
   return true;
 }
 
+// Radius 3 (k = 7) on the row-band kernels.  Both directions must serve what either serves, and the backward is the
+// narrower: bwd_tile<3,...> runs workgroups of at most kTileBwdCapR3 = 512 threads (its registers: nfp_tile.h), one per padded
+// position of a band of at least R + 1 = 4 rows and its 2R halo rows — (W + 6) * 10 <= 512, W <= 45 — and the bands, each at
+// most rb = 512 / (W + 6) - 6 rows and at least 4, must add up to H (any H >= 4 once rb >= 7; multiples of 4 below).
+// No W >= 2R + 2 rule here (it never guarded anything in these kernels), so 7 x 7 — W = 2R + 1 — is served.
+inline bool tile_r3_geometry(const KP& g) {
+  if (g.R != 3 || g.rs != 3 || g.stride != 1 || g.dil != 1 || g.pad != 3 || g.mode == NFP_PAD_CIRCULAR) return false;
+  if (g.W < 4 || g.H < 4) return false;   // (reflect padding of 3 needs 4 rows and columns: make_kp; the others keep the same floor)
+  const int rb = nfp::kTileBwdCapR3 / (g.W + 6) - 6;
+  return rb >= 4 && (rb >= 7 || (g.H + rb - 1) / rb <= g.H / 4);
+}
+// ... and whether the routing wants them there.  Unset (the default): batches of at least 12 544 pixels — [256,C,7,7],
+// [64,C,14,14], [16,C,28,28] — where they measured 1.57x to 12.4x faster than fwd_pairs + bwd_gather; below, at 7 x 7 with 512 channels, they
+// lose (a workgroup walks all its channels in series behind a phase A that reads 2 x 48 maps: [64,512,7,7] 86.4 vs 72.9 us,
+// [128,512,7,7] 107.7 vs 96.9, [192,512,7,7] 171.1 vs 168.9 — profiles/r13_a_r3_row_band_ab.txt) and larger
+// maps are not measured there: such batches keep the kernels they had.
+constexpr long long kTileR3MinPixels = 12544;
+inline bool tile_r3_wanted(const KP& g) {
+  const int sw = g_sw.tile_r3.load(std::memory_order_relaxed);
+  return sw < 0 ? (long long)g.B * g.P >= kTileR3MinPixels : sw != 0;
+}
+
 // ... and the row-band kernels (nfp_tile.h): "same" maps of any size, no tables
 inline bool tile_geometry(const KP& g) {
+  if (g.R == 3) return tile_r3_geometry(g) && tile_r3_wanted(g);
   if (!same_geometry(g) || g.rs == 12) return false;
   // one thread per padded position: the smallest band (R + 1 rows and its halo) must fit a workgroup
   if (g.W < 2 * g.R + 2 || g.H < g.R + 1) return false;
@@ -287,6 +317,7 @@ inline bool tile_geometry(const KP& g) {
 inline bool tile_ok(const KP& g, const void* x, const void* gx) {
   if (force_generic() || !tile_geometry(g) || (g.C & 3)) return false;
   if (!hot_measure(g) && !hot_l1(g) && !hot_sym(g)) return false;
+  if (g.R == 3 && (!hot_measure(g) || mixed_maps(g))) return false;   // (k = 7: no Norm p = 1, symmetric-term or map_f32 form)
   const bool nhwc = g.sC == 1 && g.sW == g.C && g.sH == (long long)g.W * g.C;
   if (!g.contig && !nhwc) return false;
   const int es = g.dtype == NFP_F32 ? 4 : 2;
@@ -394,10 +425,10 @@ int with_storage(const KP& g, F&& f) {
   if (g.dtype == NFP_BF16) return g.contig ? f(yes, no) : f(yes, yes);
   return g.contig ? f(no, no) : f(no, yes);
 }
-// MF kernels exist only for plain maps (no pooling), one radius and the COSINE / NORM instantiations (with their dot / gfc /
+// MF kernels exist only for plain maps (no pooling), one radius (1 or 2) and the COSINE / NORM instantiations (with their dot / gfc /
 // rmse riders); Norm p = 1 and the symmetric-term measures with float32 maps are the any-geometry kernels'
 template <int R, int M, int POOL>
-constexpr bool kHasMixed = POOL == nfp::kPoolNone && R != 12 && (M == NFP_COSINE || M == NFP_NORM);
+constexpr bool kHasMixed = POOL == nfp::kPoolNone && R != 12 && R != 3 && (M == NFP_COSINE || M == NFP_NORM);
 // ... and the launchers that serve mixed_maps descriptors: f(BF, NHWC, MF)
 template <int R, int M, int POOL, typename F>
 int with_storage_mixed(const KP& g, F&& f) {
@@ -440,6 +471,10 @@ int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                   const BwdTail& t = {});
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st);
+// ... and their radius-3 instantiations, units of their own (tile_forward / tile_backward hand g.R == 3 on)
+int tile_forward_r3(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t);
+int tile_backward_r3(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
+                     const BwdTail& t);
 
 // ---- NFPPooling(bias=True) (nfp_bias.hip, ABI 7) -------------------------------------------------------------------------
 // g.measure is the descriptor's own measure (Attention: its DotProduct form), g.diff = 0 and dw = the difference weights.

@@ -775,8 +775,10 @@ __global__ void __launch_bounds__(256) pool_fold(const float* __restrict__ part,
 // gradients travel through LDS.)
 // POOL = kPoolGap: grad_out IS a map, read as the plain backward reads it; ggap[b,c] / P joins in the same store.
 // MF: float32 grad_out / out beside bf16 x / grad_x (nfp_desc.map_f32).
+// k = 7: w[49], sv[48] and gov[48] are live together — 128 registers (what four wavefronts per SIMD leave) spill 152 of
+// them; workgroups of at most 512 threads, two per compute unit, get 256 (kTileBwdCapR3).
 template <int R, int M, bool BF, bool NHWC, int POOL = kPoolNone, bool GFC = false, bool CST = false, bool MF = false>
-__global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8) : 4)) bwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
+__global__ void __launch_bounds__((R == 3 ? kTileBwdCapR3 : 1024), (R == 3 ? 2 : (R == 1 && M != kSymTerm ? (CST ? 5 : 8) : 4))) bwd_tile(const KP g, const TileGeo tg, const void* __restrict__ x,
                                                 const void* __restrict__ go, const void* __restrict__ out,
                                                 const float* __restrict__ saved, void* __restrict__ gx,
                                                 const float* __restrict__ ggap, const float* __restrict__ gnfpm) {
@@ -951,6 +953,8 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
     // a bit mask of the valid (row, column) combinations, then one trip per VALID combination (an edge pixel has one,
     // a corner three) — wavefronts without a border pixel skip the loop
     constexpr int KK = 2 * R + 1;
+    // (a bit per combination: 25 at k = 5, 49 at k = 7 — there the mask takes 64 bits)
+    using Mask = std::conditional_t<(KK * KK > 32), unsigned long long, unsigned>;
     unsigned my = 1u, mx = 1u;
 #pragma unroll
     for (int i = 1; i < KK; ++i) {
@@ -959,12 +963,12 @@ __global__ void __launch_bounds__(1024, (R == 1 && M != kSymTerm ? (CST ? 5 : 8)
       my |= ((fo.y(ry, H) == ps.y && vyu >= 0 && vyu < bd.rows) ? 1u : 0u) << i;
       mx |= (fo.x(rx, W) == ps.x ? 1u : 0u) << i;
     }
-    unsigned mask = 0u;
+    Mask mask = 0;
 #pragma unroll
-    for (int c = 1; c < KK * KK; ++c) mask |= (((my >> (c / KK)) & (mx >> (c % KK)) & 1u)) << c;
-    while (mask != 0u) {
-      const int c = __builtin_ctz(mask);
-      mask &= mask - 1u;
+    for (int c = 1; c < KK * KK; ++c) mask |= (Mask)(((my >> (c / KK)) & (mx >> (c % KK)) & 1u)) << c;
+    while (mask != 0) {
+      const int c = sizeof(Mask) == 8 ? __builtin_ctzll(mask) : __builtin_ctz((unsigned)mask);
+      mask &= mask - 1;
       const int iy = fdivi(c, KK), ix = c - iy * KK;
       const int uy = iy == 0 ? ps.y : (iy <= R ? -iy : H - 1 + (iy - R));
       const int ux = ix == 0 ? ps.x : (ix <= R ? -ix : W - 1 + (ix - R));

@@ -1,5 +1,6 @@
 // nfp_tile_bwd.hip — the row-band backward of nfp_tile.h (bwd_tile) with its launcher (interface: nfp_launch.h::tile_backward;
 // sizing shared with the forward: nfp_tile_launch.h).
+// Compiled twice, as nfp_tile_fwd.hip: nfp_tile_r3_bwd.hip includes it with NFP_TILE_R3_UNIT for radius 3 (tile_backward_r3).
 #include "nfp_tile_launch.h"
 
 using namespace nfp;
@@ -14,8 +15,9 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
   const int Wu = g.W + 2 * R;
   for (int attempt = 0; attempt < 2; ++attempt) {
     // first choice: two workgroups per compute unit (k = 3: 64 registers, up to 1024 threads each; k = 5: 128, up to 512)
+    // k = 7: 512 threads either time — the kernel's launch bound (nfp_tile.h; nfp_launch.h::tile_r3_geometry admits what fits it)
     const size_t budget = attempt == 0 ? tile_lds() : (size_t)kLdsMax;
-    const int kCap = tile_cap((R == 1 || attempt == 1) ? 1024 : 512);
+    const int kCap = R == 3 ? std::min(tile_cap(nfp::kTileBwdCapR3), nfp::kTileBwdCapR3) : tile_cap((R == 1 || attempt == 1) ? 1024 : 512);
     for (int rb0 = tile_rows_wanted(g, kCap); rb0 >= 1; --rb0) {
       int nb = 1;
       const int rb = tile_bands(g, rb0, nb);
@@ -26,7 +28,7 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
       const size_t wr = 16 + (size_t)((rows * 2 * R + 2 * R * g.W) * K2 + 4 * K2) * 4;   // spare slot, ring rows (+ slack)
       if (fixed + pv > budget) continue;
       // channel blocks: enough workgroups to fill the chip when images x bands do not
-      int S = ceil_div(tile_wgs(), g.B * nb);
+      int S = ceil_div(tile_block_wgs(R), g.B * nb);
       if (S > g.C / 4) S = g.C / 4;
       if (S < 1) S = 1;
       g.Cwg = round4(ceil_div(g.C, S));
@@ -59,7 +61,8 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
 #ifndef NFP_TILE_CST_MINB
 #define NFP_TILE_CST_MINB (BF ? 80 : 256)
 #endif
-      const bool cst = NHWC && G == 1 && g.C * (BF ? 2 : 4) >= NFP_TILE_CST_MINB && npu <= 640;
+      // (k = 7: no dense form — the sizes that would take it are not among the measured ones)
+      const bool cst = R != 3 && NHWC && G == 1 && g.C * (BF ? 2 : 4) >= NFP_TILE_CST_MINB && npu <= 640;
       snprintf(g_variant, sizeof(g_variant), "bwd_tile<R%d,%s,%s,%s%s%s>x%d", R, hot_name(g), MF ? "mix" : (BF ? "bf16" : "f32"),
                NHWC ? "nhwc" : "nchw", cst ? ",dense" : "", pool_tag(POOL), nb);
       const std::true_type T_;
@@ -83,13 +86,13 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
         int rc;
         if (M == NFP_COSINE && g.gfc) {
           if constexpr (M == NFP_COSINE) {
-            if constexpr (NHWC) rc = cst ? go_(T_, T_) : go_(T_, F_);
+            if constexpr (NHWC && R != 3) rc = cst ? go_(T_, T_) : go_(T_, F_);
             else rc = go_(T_, F_);
           } else {
             rc = go_(F_, F_);
           }
         } else {
-          if constexpr (NHWC) rc = cst ? go_(F_, T_) : go_(F_, F_);
+          if constexpr (NHWC && R != 3) rc = cst ? go_(F_, T_) : go_(F_, F_);
           else rc = go_(F_, F_);
         }
         if (rc != NFP_OK) return rc;
@@ -102,12 +105,20 @@ int launch_bwd_tile_t(KP g, const void* x, const void* go, const void* out, cons
 
 }  // namespace
 
+#ifdef NFP_TILE_R3_UNIT
+int tile_backward_r3(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
+                     const BwdTail& t) {
+#else
 int tile_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st,
                   const BwdTail& t) {
+#endif
   if (!tile_ok(g, x, gx)) return kNotApplicable;
-  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
+#ifndef NFP_TILE_R3_UNIT
+  if (g.R == 3) return tile_backward_r3(g, x, go, out, saved, gx, st, t);
+#endif
+  return with_tile_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
-    if constexpr (kHasTile<M, POOL>)   // (grad_out of kPoolGap is a map; grad(GAP) joins in the store)
+    if constexpr (kHasTile<R, M, POOL>)   // (grad_out of kPoolGap is a map; grad(GAP) joins in the store)
       return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
         return launch_bwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, go, out, saved, gx, st, t);
       });
@@ -118,4 +129,8 @@ int tile_backward(const KP& g, const void* x, const void* go, const void* out, c
 
 }  // namespace nfp_host
 
+#ifdef NFP_TILE_R3_UNIT
+NFP_STAMP_SETTER(tile_r3_bwd)
+#else
 NFP_STAMP_SETTER(tile_bwd)
+#endif

@@ -1,5 +1,7 @@
 // nfp_tile_fwd.hip — the row-band forward of nfp_tile.h (fwd_tile, and pool_fold behind its pooled forms) with its launcher
 // (interface: nfp_launch.h::tile_forward / tile_pool_fold; sizing shared with the backward: nfp_tile_launch.h).
+// Compiled twice: as itself for radii 1 and 2, and — included by nfp_tile_r3_fwd.hip with NFP_TILE_R3_UNIT — for radius 3
+// (tile_forward_r3), so that the k = 7 instantiations compile beside the others and not behind them.
 #include "nfp_tile_launch.h"
 
 using namespace nfp;
@@ -49,7 +51,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
       bool dma = false;
       const int dma_sw = g_sw.tile_dma.load(std::memory_order_relaxed);
       const bool dma_auto = BF && (g.C * 2) % 128 == 0;   // (8 pieces per position and chunk: where it measured faster)
-      if (!MF && (dma_sw == 1 || (dma_sw < 0 && dma_auto)) && M != nfp::kSymTerm && NHWC && !POOL && G == 1 && !g.gfc && (g.C * (BF ? 2 : 4)) % 16 == 0 &&
+      if (!MF && R != 3 && (dma_sw == 1 || (dma_sw < 0 && dma_auto)) && M != nfp::kSymTerm && NHWC && !POOL && G == 1 && !g.gfc && (g.C * (BF ? 2 : 4)) % 16 == 0 &&
           !(((uintptr_t)x) & 15) && !((g.sB * (BF ? 2 : 4)) & 15)) {
         const int tp = g.C * (BF ? 2 : 4) / 16, npu64 = (npu + 63) & ~63;
         for (int lpc = 3; lpc >= 0; --lpc) {
@@ -86,7 +88,7 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
         if (M == NFP_COSINE && g.gfc) {
           rc = launch("fwd_tile", fwd_tile<R, M, BF, NHWC, POOL, M == NFP_COSINE, false, MF>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
         } else if (dma) {
-          if constexpr (NHWC && !POOL && !MF)
+          if constexpr (NHWC && !POOL && !MF && R != 3)   // (no LDS-DMA form at k = 7)
             rc = launch("fwd_tile_dma", fwd_tile<R, M, BF, true, false, false, true>, grid, block, lds, st, gs, tg, xs, os, ss, ps, gs_, ns_);
           else
             rc = kNotApplicable;
@@ -103,14 +105,21 @@ int launch_fwd_tile_t(KP g, const void* x, void* out, float* saved, hipStream_t 
 
 }  // namespace
 
+#ifdef NFP_TILE_R3_UNIT
+int tile_forward_r3(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
+#else
 int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st, const FwdTail& t) {
+#endif
   if (!tile_ok(g, x, x)) return kNotApplicable;
+#ifndef NFP_TILE_R3_UNIT
+  if (g.R == 3) return tile_forward_r3(g, x, out, saved, st, t);
+#endif
   // (the symmetric-term measures below 14 x 14: the any-geometry forward spreads the same arithmetic over more threads:
   // [64,512,7,7] 9 vs 14 us; the backward wins at every size: 17.6-22.9 vs 20.9-28.6 us there — profiles/r04_zd_…)
   if (hot_sym(g) && g.P < 196) return kNotApplicable;
-  return with_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
+  return with_tile_radius(g, [&](auto r) { return with_hot<true>(g, [&](auto m) { return with_pool(t.mode, [&](auto p) {
     constexpr int R = decltype(r)::value, M = decltype(m)::value, POOL = decltype(p)::value;
-    if constexpr (kHasTile<M, POOL>)
+    if constexpr (kHasTile<R, M, POOL>)
       return with_storage_mixed<R, M, POOL>(g, [&](auto bf, auto nhwc, auto mf) {
         return launch_fwd_tile_t<R, M, bf(), nhwc(), POOL, mf()>(g, x, out, saved, st, t);
       });
@@ -119,12 +128,18 @@ int tile_forward(const KP& g, const void* x, void* out, float* saved, hipStream_
   }); }); });
 }
 
+#ifndef NFP_TILE_R3_UNIT
 int tile_pool_fold(const KP& g, const float* part, float* gap, float* nfpm, int nb, hipStream_t st) {
   const long long n = (long long)g.B * (g.C + g.N);
   return launch("pool_fold", pool_fold<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, gap, nfpm, g.B, nb, g.C, g.N,
                 g.invP);
 }
+#endif
 
 }  // namespace nfp_host
 
+#ifdef NFP_TILE_R3_UNIT
+NFP_STAMP_SETTER(tile_r3_fwd)
+#else
 NFP_STAMP_SETTER(tile_fwd)
+#endif

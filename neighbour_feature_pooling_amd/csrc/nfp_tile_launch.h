@@ -17,6 +17,10 @@ namespace nfp_host {
 #define NFP_TILE_LDS_KB 78     // per workgroup, so that two share a compute unit
 #endif
 inline int tile_wgs() { return g_sw.tile_wgs > 0 ? (int)g_sw.tile_wgs : NFP_TILE_WGS; }
+#ifndef NFP_TILE_WGS_R3
+#define NFP_TILE_WGS_R3 256    // k = 7, the backward's channel blocks: every extra block repeats a phase A over 2 x 48 maps — half
+#endif                         // the target measured best at [64 / 128 / 192 / 256,512,7,7]: 86 / 108 / 171 / 151 us against 109 / 130 / 194 / 173
+inline int tile_block_wgs(int R) { return g_sw.tile_wgs > 0 ? (int)g_sw.tile_wgs : (R == 3 ? NFP_TILE_WGS_R3 : NFP_TILE_WGS); }
 inline size_t tile_lds() { return (size_t)(g_sw.tile_lds_kb > 0 ? (int)g_sw.tile_lds_kb : NFP_TILE_LDS_KB) * 1024; }
 inline int tile_max_grid() { return g_sw.tile_max_grid > 0 ? std::min((int)g_sw.tile_max_grid, nfp::kTileMaxGrid) : nfp::kTileMaxGrid; }
 inline int tile_cap(int dflt) { return g_sw.tile_cap > 0 ? std::min((int)g_sw.tile_cap, 1024) : dflt; }
@@ -46,8 +50,21 @@ inline int tile_groups(const KP& g, int nb, int npu, int cap, int cq) {
   return lg;
 }
 
-// Norm p = 1 (the class default, nfp.py:16; and EMD: make_kp) and the symmetric-term measures: plain maps only
-template <int M, int POOL>
-constexpr bool kHasTile = POOL == nfp::kPoolNone || M == NFP_COSINE || M == NFP_NORM;
+// Norm p = 1 (the class default, nfp.py:16; and EMD: make_kp) and the symmetric-term measures: plain maps only, and not
+// at radius 3 (k = 7: the product and squared-difference families alone — tile_ok asks hot_measure there)
+template <int R, int M, int POOL>
+constexpr bool kHasTile = (M == NFP_COSINE || M == NFP_NORM) || (POOL == nfp::kPoolNone && R != 3);
+
+// The radius of a row-band launch: 1 or 2 here; 3 in the units of its own (nfp_tile_r3_fwd.hip / nfp_tile_r3_bwd.hip, which
+// compile this unit's launcher with NFP_TILE_R3_UNIT).  with_radius itself is shared with the table launchers, which have
+// no k = 7 form.
+template <typename F>
+int with_tile_radius(const KP& g, F&& f) {
+#ifdef NFP_TILE_R3_UNIT
+  return f(Int<3>{});
+#else
+  return with_radius(g, f);
+#endif
+}
 
 }  // namespace nfp_host
