@@ -306,6 +306,33 @@ int nfp_valid_abs_forward(const nfp_desc* d, const void* x, void* out, void* hip
 int nfp_valid_abs_backward(const nfp_desc* d, const void* x, const void* grad_out, void* grad_x, void* hip_stream);
 
 /*
+ * NFP at STRIDE 2 to 4 — dilation 1, R = 1 or 2, pad = 0 or pad = R with zeros / reflect / replicate: the `--nfp_stride`
+ * layers of the reference's demo.py (RESNET18_NFP_AT_LAYER, *_NFP_CONV_ONLY / _CONV_MLP, MOBILENETV3_NFP_INSERT).  Kernels of
+ * their own (csrc/nfp_strided.hip: fwd_strided / bwd_strided) on the padded row band, one launch each way, no tables, no
+ * workspace, no atomics: two runs agree bitwise and image b's results do not depend on B.  out / grad_out are
+ * [B, N, Ho, Wo] contiguous in d->dtype, exactly what nfp_forward writes for the descriptor; grad_x is fully overwritten,
+ * with zeros at the pixels no window reaches.  Signatures and length convention of the nfp_valid_* quartet:
+ *   nfp_strided_supported(d)     1: both calls below will launch (a host-only dry run; 4 KiB-aligned buffers assumed)
+ *   nfp_strided_saved_floats(d)  floats of `saved` (|x| per input pixel for cosine / gfc, else 0); -1 for a malformed d
+ * Served: cosine / dot / gfc / Norm p = 2 / rmse (the distances on the difference weights), either `similarity`,
+ * 2 <= stride <= 4, float32 / bf16, H + 2 pad >= 2R + 1 (W likewise) and W + 2 pad <= 128; images dense in NCHW order (any
+ * C) or in channels-last order (C % 4 == 0 for float32, C % 8 == 0 for bf16, images on 16-byte boundaries), any batch
+ * stride.  The backward keeps the slots of a band of at least R + 1 image rows and its ring rows in LDS: R = 2 with
+ * pad = 2 is served up to W + 2 pad <= 64 at every height, wider where that band still fits (the query answers).
+ * NFP_E_UNSUPPORTED, launching nothing: stride 1 or above 4, dilation != 1, any other padding amount, circular padding,
+ * R >= 3, every other measure, wider rows, map_f32 = 1, inner_R != 0.  A null tensor or a `saved` shorter than
+ * nfp_strided_saved_floats(d) is NFP_E_INVALID and launches nothing (forward: `saved` may be NULL when no backward
+ * follows).  B = 0 returns NFP_OK without a launch.  nfp_forward / nfp_backward / nfp_plan keep strided descriptors on
+ * fwd_pairs / bwd_gather.  nfp_last_variant names fwd_strided<R,prod|dist,f32|bf16,nchw|nhwc> / bwd_strided<...>.
+ * Additive to ABI 7.
+ */
+int nfp_strided_supported(const nfp_desc* d);
+int64_t nfp_strided_saved_floats(const nfp_desc* d);
+int nfp_strided_forward(const nfp_desc* d, const void* x, void* out, float* saved, int64_t saved_floats, void* hip_stream);
+int nfp_strided_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out, const float* saved,
+                         int64_t saved_floats, void* grad_x, void* hip_stream);
+
+/*
  * The tail the three trained heads of models/nfp_heads.py share behind their NFP maps (NFPHead nfp_heads.py:28-32,42-43,
  * MultiRadiusNFPHead 98-102,114-115, AdaptiveFusionNFP 301-305,323-324):
  *   compress = Conv2d(N, D, 1, bias=False) -> BatchNorm2d(D) -> ReLU        out [B,D] = GAP(compress(maps))

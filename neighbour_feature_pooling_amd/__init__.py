@@ -11,6 +11,7 @@ Drop-in for the reference's NFP hot path:
     nfp_attention_pool               its tail (1x1 conv, softmax over the pixels, weighted sum) as one op
     NFPBottleneck                    <- models/nfp_heads.py::NFPBottleneck (a residual block around an unpadded cosine NFP layer)
     nfp_valid                        `nfp_op` for padding = 0 on the valid-map kernels (one launch each way)
+    nfp_strided                      `nfp_op` for stride 2 to 4 on the strided row-band kernels (one launch each way; opt-in)
     NFPHead, MultiRadiusNFPHead,     <- models/nfp_heads.py: the three heads the reference trains (GAP + compressed NFP maps,
     AdaptiveFusionNFP                   fused by an MLP or a gate)
     nfp_compress_pool                their shared tail GAP(relu(bn(conv1x1(maps)))) as one op, without the [B,D,H,W] activation
@@ -22,7 +23,8 @@ Drop-in for the reference's NFP hot path:
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
 """
 from .functional import (NfpConfig, nfp_attention_pool, nfp_compress_map, nfp_compress_map_tensors, nfp_compress_pool,
-                         nfp_compress_pool_tensors, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_valid, nfp_with_gap)
+                         nfp_compress_pool_tensors, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_strided, nfp_valid,
+                         nfp_with_gap)
 from .functional import nfp as nfp_op  # (`nfp` itself is the submodule holding NFPPooling)
 from .nfp import (EnhancedNFPPooling, MultiRadiusNFPPooling, NFPBottleneck, NFPInsert, NFPPooling, NFPWithGap,
                   SimilarityAwarePooling)
@@ -33,5 +35,5 @@ from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
 __all__ = ["NFPPooling", "EnhancedNFPPooling", "MultiRadiusNFPPooling", "nfp_pooling", "nfp_op", "nfp_pool", "nfp_pooled",
            "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool",
            "NFPBottleneck", "nfp_valid", "NFPHead", "MultiRadiusNFPHead", "AdaptiveFusionNFP", "nfp_compress_pool",
-           "nfp_compress_pool_tensors", "NFPInsert", "nfp_compress_map", "nfp_compress_map_tensors"]
+           "nfp_compress_pool_tensors", "NFPInsert", "nfp_compress_map", "nfp_compress_map_tensors", "nfp_strided"]
 __version__ = "0.4.0"

@@ -26,6 +26,7 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
            "nfp_valid_abs_supported", "nfp_valid_abs_forward", "nfp_valid_abs_backward",
+           "nfp_strided_supported", "nfp_strided_saved_floats", "nfp_strided_forward", "nfp_strided_backward",
            "nfp_cpool_saved_floats", "nfp_cpool_scratch_floats", "nfp_cpool_forward", "nfp_cpool_backward",
            "nfp_cproj_scratch_floats", "nfp_cproj_forward", "nfp_cproj_backward",
            "nfp_cproj_forward_fmt", "nfp_cproj_backward_fmt",
@@ -116,6 +117,12 @@ def load():
         L.nfp_valid_saved_floats.restype = i64
         L.nfp_valid_forward.argtypes = [dp, vp, vp, vp, i64, vp]
         L.nfp_valid_backward.argtypes = [dp, vp, vp, vp, vp, i64, vp, vp]
+    if hasattr(L, "nfp_strided_forward"):       # (absent only from an older library loaded for an A/B run)
+        L.nfp_strided_supported.argtypes = [dp]
+        L.nfp_strided_saved_floats.argtypes = [dp]
+        L.nfp_strided_saved_floats.restype = i64
+        L.nfp_strided_forward.argtypes = [dp, vp, vp, vp, i64, vp]
+        L.nfp_strided_backward.argtypes = [dp, vp, vp, vp, vp, i64, vp, vp]
     if hasattr(L, "nfp_valid_abs_forward"):     # (absent only from an older library loaded for an A/B run)
         L.nfp_valid_abs_supported.argtypes = [dp]
         L.nfp_valid_abs_forward.argtypes = [dp, vp, vp, vp]

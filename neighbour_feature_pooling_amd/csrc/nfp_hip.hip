@@ -653,6 +653,51 @@ int nfp_valid_abs_backward(const nfp_desc* d, const void* x, const void* grad_ou
   return finish(valid_abs_backward(g, x, grad_out, grad_x, (hipStream_t)hip_stream), "nfp_valid_abs_backward");
 }
 
+// ---- strided maps (stride 2 to 4): nfp_strided.hip — the valid-map quartet's signatures and length convention -------------
+int nfp_strided_supported(const nfp_desc* d) {
+  KP g;
+  const DryRun dry;
+  void* const p = kStandIn;
+  if (make_kp(d, &g) != NFP_OK || strided_refusal(g) != nullptr) return 0;
+  return g.B == 0 || both_launch([&] { return strided_forward(g, p, p, (float*)p, nullptr); },
+                                 [&] { return strided_backward(g, p, p, p, (const float*)p, p, nullptr); });
+}
+
+int64_t nfp_strided_saved_floats(const nfp_desc* d) {
+  KP g;
+  if (make_kp(d, &g)) return -1;
+  if (strided_refusal(g) != nullptr) return 0;
+  return (int64_t)stats_of(g.measure) * g.B * g.P;   // |x| per input pixel (cosine / gfc)
+}
+
+static int strided_kp(const nfp_desc* d, KP* g) {
+  if (int rc = make_kp(d, g)) return rc;
+  if (const char* why = strided_refusal(*g)) return fail(NFP_E_UNSUPPORTED, "strided maps: %s", why);
+  return NFP_OK;
+}
+
+int nfp_strided_forward(const nfp_desc* d, const void* x, void* out, float* saved, int64_t saved_floats, void* hip_stream) {
+  KP g;
+  if (int rc = strided_kp(d, &g)) return rc;
+  if (missing({x, out}, g.B > 0)) return NFP_E_INVALID;
+  const int64_t need = nfp_strided_saved_floats(d);
+  if (saved != nullptr && saved_floats < need) return short_buffer("saved", saved_floats, "nfp_strided_saved_floats is", need);
+  if (g.B == 0) return NFP_OK;
+  return finish(strided_forward(g, x, out, saved, (hipStream_t)hip_stream), "nfp_strided_forward");
+}
+
+int nfp_strided_backward(const nfp_desc* d, const void* x, const void* grad_out, const void* out, const float* saved,
+                         int64_t saved_floats, void* grad_x, void* hip_stream) {
+  KP g;
+  if (int rc = strided_kp(d, &g)) return rc;
+  if (missing({x, grad_out, out, grad_x}, g.B > 0)) return NFP_E_INVALID;
+  const int64_t need = nfp_strided_saved_floats(d);
+  if (need > 0 && (saved == nullptr || saved_floats < need))
+    return short_buffer("saved", saved ? saved_floats : 0, "nfp_strided_saved_floats is", need);
+  if (g.B == 0) return NFP_OK;
+  return finish(strided_backward(g, x, grad_out, out, saved, grad_x, (hipStream_t)hip_stream), "nfp_strided_backward");
+}
+
 // ---- ABI 7: NFPPooling(bias=True) — nfp_bias.hip ---------------------------------------------------------------------
 // The descriptor's own measure: make_kp serves EMD as Norm p = 1 on the difference weights, which a bias on the
 // neighbour side breaks (|(a + bc) - (x_n + beta)| is not |(a - x_n) + beta|).  The difference weights are applied by the

@@ -1,7 +1,7 @@
 // nfp_launch.h — host-side launch machinery shared by the translation units of libnfp_hip.so (nfp_hip.hip: C ABI and
 // dispatch; nfp_generic.hip: the any-geometry kernels; nfp_table_fwd.hip / nfp_table_bwd.hip: the table kernels;
 // nfp_tile_fwd.hip / nfp_tile_bwd.hip: the row-band kernels (nfp_tile_r3_fwd.hip / nfp_tile_r3_bwd.hip: their radius 3); nfp_bias.hip: NFPPooling(bias=True);
-// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_cpool.hip: the heads'
+// nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_strided.hip: stride 2-4; nfp_cpool.hip: the heads'
 // compress-BN-ReLU-GAP tail), and the interface of each unit's launchers to the dispatcher (below).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 //
@@ -498,5 +498,12 @@ int valid_backward(const KP& g, const void* x, const void* go, const void* out, 
 const char* valid_abs_refusal(const KP& g);
 int valid_abs_forward(const KP& g, const void* x, void* out, hipStream_t st);
 int valid_abs_backward(const KP& g, const void* x, const void* go, void* gx, hipStream_t st);
+
+// ---- strided maps: stride 2 to 4, dilation 1, padding 0 or R (nfp_strided.hip; include/nfp.h: nfp_strided_*) ---------------
+// As the valid-map trio: strided_refusal names what lies outside the kernels' set, or null; the launchers return NFP_OK or
+// an NFP_E_* code (NFP_E_UNSUPPORTED also for a band that does not fit a workgroup); g_variant names the launch.
+const char* strided_refusal(const KP& g);
+int strided_forward(const KP& g, const void* x, void* out, float* saved, hipStream_t st);
+int strided_backward(const KP& g, const void* x, const void* go, const void* out, const float* saved, void* gx, hipStream_t st);
 
 }  // namespace nfp_host

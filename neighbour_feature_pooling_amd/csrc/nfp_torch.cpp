@@ -3,7 +3,7 @@
 // The reference's NFP is a chain of ATen ops whose autograd graph PyTorch builds (nfp.py:132-159); here one
 // forward and one backward kernel stand for it, and these torch::autograd::Function classes are the graph
 // nodes.  They do what functional.py's Python autograd.Functions do — allocate out / saved / grad_x, take torch's
-// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_* / nfp_valid_* / nfp_valid_abs_*) — without the Python
+// current stream, call nfp_forward / nfp_backward (nfp_pool_* / nfp_gap_* / nfp_valid_* / nfp_strided_* / nfp_valid_abs_*) — without the Python
 // interpreter on the launch path: eager host cost per forward + backward drops from ~75 us to the autograd
 // engine's own (scripts/host_overhead.py).  No device code in this file; plain pointers go across the ABI.
 //
@@ -52,7 +52,7 @@ Tensor grad_as(const Tensor& g, at::ScalarType type) {
 
 float* saved_ptr(const Tensor& saved) { return saved.defined() && saved.numel() ? saved.data_ptr<float>() : nullptr; }
 
-// The three "x -> maps" families (functional.py: NFP, VALID, VALID_ABS): their entry points behind one argument list, and
+// The four "x -> maps" families (functional.py: NFP, VALID, STRIDED, VALID_ABS): their entry points behind one argument list, and
 // whether the backward reads the maps and `saved` at all.
 struct NfpCalls {       // nfp_forward / nfp_backward: `saved` goes without its length
   static constexpr bool reads_maps = true;
@@ -70,6 +70,15 @@ struct ValidCalls {     // an unpadded layer on the valid-map kernels: `saved` w
   }
   static int bwd(const nfp_desc* d, const void* x, const void* go, const void* out, const float* saved, int64_t ns, void* gx, void* s) {
     return nfp_valid_backward(d, x, go, out, saved, ns, gx, s);
+  }
+};
+struct StridedCalls {   // a stride 2-4 layer on the strided kernels: the valid-map contract
+  static constexpr bool reads_maps = true;
+  static int fwd(const nfp_desc* d, const void* x, void* out, float* saved, int64_t ns, void* s) {
+    return nfp_strided_forward(d, x, out, saved, ns, s);
+  }
+  static int bwd(const nfp_desc* d, const void* x, const void* go, const void* out, const float* saved, int64_t ns, void* gx, void* s) {
+    return nfp_strided_backward(d, x, go, out, saved, ns, gx, s);
   }
 };
 struct ValidAbsCalls {  // ... and their L1 family (Norm p = 1 on the difference weights, EMD): the backward reads x and grad_out
@@ -178,6 +187,9 @@ Tensor nfp_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns,
 Tensor nfp_valid_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
   return MapsNode<ValidCalls>::apply(x, desc, oshape, ns, nhwc, true);
 }
+Tensor nfp_strided_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, int64_t ns, bool nhwc) {
+  return MapsNode<StridedCalls>::apply(x, desc, oshape, ns, nhwc, true);
+}
 Tensor nfp_valid_abs_apply(Tensor x, Tensor desc, std::vector<int64_t> oshape, bool nhwc, bool need_grad) {
   return MapsNode<ValidAbsCalls>::apply(x, desc, oshape, (int64_t)0, nhwc, need_grad);
 }
@@ -196,6 +208,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nfp_pool_apply", &nfp_pool_apply, "the fused nfp_pooling tail as one autograd node (nfp_pool_forward / _backward)");
   m.def("nfp_gap_apply", &nfp_gap_apply, "GAP(x) beside the full maps as one autograd node (nfp_gap_forward / _backward)");
   m.def("nfp_valid_apply", &nfp_valid_apply, "an unpadded layer's maps as one autograd node (nfp_valid_forward / _backward)");
+  m.def("nfp_strided_apply", &nfp_strided_apply, "a stride 2-4 layer's maps as one autograd node (nfp_strided_forward / _backward)");
   m.def("nfp_valid_abs_apply", &nfp_valid_abs_apply,
         "an unpadded L1 layer's maps as one autograd node that saves x alone (nfp_valid_abs_forward / _backward)");
   m.attr("desc_bytes") = (int64_t)sizeof(nfp_desc);

@@ -32,13 +32,11 @@
 //   grad_x[c][r] = sum_j Wt[j][r] sgn(x[c][r] - x[c][r + d_j])                   sgn(0) = 0 (torch's abs backward)
 // formed as bwd_tile's kNormP1 instantiation forms it: sgn3 (a compare, a select and a sign copy) under one fma.  Same
 // sizing, bands, chunks, channel blocks, lane maps and stores as the other families.
-#include "nfp_launch.h"
-#include "nfp_measures.h"
+#include "nfp_valid.h"   // (ldv, tap_of, valid_fin, valid_coef and the layout predicates: shared with nfp_strided.hip)
 
 namespace nfp {
 namespace {
 
-constexpr int kValidLdsFloats = 20000;   // 80 000 bytes: two workgroups per CU out of 160 KiB
 constexpr int kValidFwdT = 1024, kValidBwdT = 512;
 
 struct VP {
@@ -50,20 +48,6 @@ struct VP {
   int vec;    // 16-byte global loads: rows and pointers allow them
   int Cz;     // backward: channels per workgroup along grid.z (a multiple of 8, or C)
 };
-
-template <int BF>
-__device__ __forceinline__ float ldv(const void* p, long long i) {
-  return BF ? bf16_to_f32(((const uint16_t*)p)[i]) : ((const float*)p)[i];
-}
-
-// tap n of the k x k window without its centre -> (dy, dx)
-template <int R>
-__device__ __forceinline__ void tap_of(int n, int& dy, int& dx) {
-  constexpr int K = 2 * R + 1;
-  const int t = n < (K * K) / 2 ? n : n + 1;
-  dy = t / K - R;
-  dx = t - (t / K) * K - R;
-}
 
 // rows [y0, y0 + rows) of image b, channels [c0, c0 + cc) -> xs[c * S + (y - y0) * W + x], float32
 template <int BF, int NHWC>
@@ -123,36 +107,6 @@ __device__ __forceinline__ void stage_rows(const KP& g, const VP& v, const void*
       xs[c * v.S + p] = ldv<BF>(x, base + (long long)c * g.sC + p);
     }
   }
-}
-
-// the finished map value of a pair sum (wave-uniform switch on the descriptor's measure)
-template <int PROD>
-__device__ __forceinline__ float valid_fin(const KP& g, float acc, float n2p, float n2q) {
-  if (PROD == 2) return g.similarity ? -acc : acc;   // (Norm p = 1: the sum of |a - t| itself)
-  if (PROD) {
-    if (g.measure == NFP_COSINE) {
-      // ONE correctly rounded division by the product of the clamped norms (not acc * (1 / m_p) * (1 / m_q)): the same
-      // value for both orientations of a pair, and exactly +-1 where the two pixels are parallel to rounding (C = 1:
-      // |fl(a b)| == fl(|a| |b|)) — which the backward's projected form relies on
-      const float s = acc / (fmaxf(sqrtf(n2p), g.eps) * fmaxf(sqrtf(n2q), g.eps));
-      return g.similarity ? s : 1.f - s;
-    }
-    if (g.measure == NFP_GFC) return Meas<NFP_GFC>::fin(acc, n2p, 0.f, n2q, 0.f, g);
-    return Meas<NFP_DOT>::fin(acc, 0.f, 0.f, 0.f, 0.f, g);
-  }
-  if (g.measure == NFP_RMSE) return Meas<NFP_RMSE>::fin(acc, 0.f, 0.f, 0.f, 0.f, g);
-  return Meas<kNormP2>::fin(acc, 0.f, 0.f, 0.f, 0.f, g);
-}
-// the backward scalars of a pair (centre norm np, neighbour norm nq)
-template <int PROD>
-__device__ __forceinline__ Coef valid_coef(const KP& g, float go, float ov, float np, float nq) {
-  if (PROD) {
-    if (g.measure == NFP_COSINE) return Meas<NFP_COSINE>::coef(go, ov, np, 0.f, nq, 0.f, g);
-    if (g.measure == NFP_GFC) return Meas<NFP_GFC>::coef(go, ov, np, 0.f, nq, 0.f, g);
-    return Meas<NFP_DOT>::coef(go, ov, 0.f, 0.f, 0.f, 0.f, g);
-  }
-  if (g.measure == NFP_RMSE) return Meas<NFP_RMSE>::coef(go, ov, 0.f, 0.f, 0.f, 0.f, g);
-  return Meas<kNormP2>::coef(go, ov, 0.f, 0.f, 0.f, 0.f, g);
 }
 
 // grid = (bands, B).  Dynamic LDS (floats): max(Cc * S, G * (NH + 1) * npix) — the slab, then the groups' partial sums.
@@ -439,23 +393,10 @@ namespace {
 
 constexpr int kValidMaxW = 128;
 
-// what the kernels read in place: images dense in NCHW or channels-last order (any batch stride)
-bool valid_nchw(const KP& g) { return g.sW == 1 && g.sH == g.W && g.sC == (long long)g.H * g.W; }
-bool valid_nhwc(const KP& g) { return g.sC == 1 && g.sW == g.C && g.sH == (long long)g.W * g.C; }
-int valid_ve(const KP& g) { return g.dtype == NFP_BF16 ? 8 : 4; }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // Bands of about 8 rows (a halo of 2R rows on top: a quarter / a half more staged than owned), fewer rows where the
 // threads or the LDS ask for it.  NOT a function of the batch: the band height sets the number of channel groups, and with
 // it the order of the sums — image b's results must not depend on B.
 int valid_bands(int rows, int rb_max) { return std::max(ceil_div(rows, rb_max), ceil_div(rows, 8)); }
-
-int valid_even_chunk(int C, int cap, int mult) {
-  cap = std::max(mult, cap / mult * mult);
-  const int nch = ceil_div(C, cap);
-  return std::min(cap, ceil_div(ceil_div(C, nch), mult) * mult);
-}
 
 }  // namespace
 

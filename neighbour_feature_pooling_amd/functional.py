@@ -418,6 +418,8 @@ VALID = _MapsFamily("nfp_valid_forward", "nfp_valid_backward", "nfp_valid_apply"
                     "nfp_valid_supported", "nfp_valid_saved_floats")
 VALID_ABS = _MapsFamily("nfp_valid_abs_forward", "nfp_valid_abs_backward", "nfp_valid_abs_apply", False, False, False,
                         "nfp_valid_abs_supported")
+STRIDED = _MapsFamily("nfp_strided_forward", "nfp_strided_backward", "nfp_strided_apply", False, True, True,
+                      "nfp_strided_supported", "nfp_strided_saved_floats")
 
 
 def maps_saved_len(fam, plan, cfg, dtype, need_grad):
@@ -461,7 +463,7 @@ def maps_backward_call(fam, x, plan, out, saved, grad_out):
 
 
 class _MapsHip(torch.autograd.Function):
-    """The Python node of the three families: one forward launch, one backward launch.  It holds its forward's plan and
+    """The Python node of the four families: one forward launch, one backward launch.  It holds its forward's plan and
     saves what its backward reads — nothing without a gradient to follow."""
 
     @staticmethod
@@ -1029,13 +1031,14 @@ def nfp_attention_pool(maps, weight, bias):
 
 
 # ---- valid maps: stride 1, dilation 1, padding 0 — include/nfp.h: nfp_valid_*, nfp_valid_abs_* (csrc/nfp_valid.hip) ---------
-def _valid_route(x, cfg, fam):
-    """The table-less plan on which the family's kernels (VALID: fwd_valid / bwd_valid; VALID_ABS: their l1 forms) read this
-    call in place, or None where `nfp` serves it: NFP_VALID_OFF=1 (read at call time), torch.compile, a CPU tensor, another
-    dtype, images that are not dense, or a descriptor the family's `supported` query refuses (another measure, rows above
-    128 pixels, channels-last maps off the alignment rule).  Both families ask the one plan of the signature."""
+def _valid_route(x, cfg, fam, off="NFP_VALID_OFF"):
+    """The table-less plan on which the family's kernels (VALID: fwd_valid / bwd_valid; VALID_ABS: their l1 forms; STRIDED:
+    fwd_strided / bwd_strided) read this call in place, or None where `nfp` serves it: `off`=1 in the environment (read at
+    call time), torch.compile, a CPU tensor, another dtype, images that are not dense, or a descriptor the family's
+    `supported` query refuses (another measure, rows above 128 pixels, channels-last maps off the alignment rule).  The
+    families ask the one plan of the signature."""
     if (torch.compiler.is_compiling() or not (x.is_cuda and x.dtype in _DTYPES) or cfg.inner_R or cfg.map_f32
-            or os.environ.get("NFP_VALID_OFF") == "1"):
+            or os.environ.get(off) == "1"):
         return None
     if not hasattr(_abi.load(), fam.forward):  # (an older library loaded for an A/B run)
         return None
@@ -1075,6 +1078,30 @@ def nfp_valid(x, cfg):
         plan = _valid_route(x, cfg, fam)
         if plan is not None:
             return _maps_node(fam, x, plan, cfg, _need_grad(x))
+    return nfp(x, cfg)
+
+
+# ---- strided maps: stride 2 to 4, dilation 1 — include/nfp.h: nfp_strided_* (csrc/nfp_strided.hip) --------------------------
+def nfp_strided(x, cfg):
+    """`nfp(x, cfg)` for a layer with cfg.stride >= 2 and dilation 1 (ValueError otherwise): the `--nfp_stride` layers of the
+    reference's demo.py.  A CUDA call that nfp_strided_supported accepts (cosine / dot / gfc / Norm p=2 / rmse, stride 2 to
+    4, R = 1 or 2, padding 0 or R with zeros / reflect / replicate, float32 or bfloat16, padded rows of at most 128
+    positions, NCHW or aligned channels-last images) runs the strided row-band kernels, one launch each way.  Everything
+    else — CPU tensors, other measures, refused shapes, torch.compile, NFP_STRIDED_OFF=1 in the environment (read at call
+    time: the A/B switch) — is `nfp(x, cfg)` unchanged: the any-geometry kernels.  Under torch.autocast, and for float16 /
+    float64, the float32 upcast of `_upcast`, as nfp_valid.  The maps are saved for the backward and must not be modified
+    in place."""
+    if cfg.stride < 2 or cfg.dilation != 1:
+        raise ValueError(f"nfp_strided: stride >= 2 and dilation 1 only (got stride={cfg.stride}, "
+                         f"dilation={cfg.dilation}); use nfp, or nfp_valid for an unpadded stride-1 layer")
+    if x.dim() != 4:
+        raise RuntimeError(f"NFP expects a 4-D [B,C,H,W] feature map, got {tuple(x.shape)}")
+    up = _upcast(nfp_strided, x, cfg)
+    if up is not None:
+        return up
+    plan = _valid_route(x, cfg, STRIDED, off="NFP_STRIDED_OFF")
+    if plan is not None:
+        return _maps_node(STRIDED, x, plan, cfg, _need_grad(x))
     return nfp(x, cfg)
 
 

@@ -299,12 +299,13 @@ class NFPInsertNet(nn.Module):
     channel count) replaces the feature map; the rest of the trunk follows, then the 960 -> 1280 head conv + Hardswish, GAP
     and fc.  With the class defaults (padding 0) the map shrinks by 2R at the insert.  memory_format (keyword only) is the
     insert's: the layout its projected map is written in (NFPInsert); so is valid_layer (default False): the insert's
-    unpadded layer on the valid-map kernels."""
+    unpadded layer on the valid-map kernels; and strided_layer (default False): the insert's stride >= 2 layer on the
+    strided row-band kernels."""
     BLOCK_ENDS = (3, 5, 8, 12, 14, 17, 20)            # indices into backbone.features
     BLOCK_CHANNELS = (16, 24, 40, 80, 112, 160, 960)
 
     def __init__(self, num_classes=10, num_input_channels=3, nfp_insert_idx=1, nfp_kwargs=None, head_width=1280, *,
-                 memory_format=torch.contiguous_format, valid_layer=False):
+                 memory_format=torch.contiguous_format, valid_layer=False, strided_layer=False):
         super().__init__()
         from .nfp import NFPInsert
         if isinstance(nfp_insert_idx, bool) or not isinstance(nfp_insert_idx, int) or not 0 <= nfp_insert_idx <= 6:
@@ -312,7 +313,7 @@ class NFPInsertNet(nn.Module):
         self.nfp_insert_idx = nfp_insert_idx
         self.backbone = MobileNetV3LargeFeatures(in_chans=num_input_channels)
         self.insert = NFPInsert(self.BLOCK_CHANNELS[nfp_insert_idx], memory_format=memory_format, valid_layer=valid_layer,
-                                **(nfp_kwargs or {}))
+                                strided_layer=strided_layer, **(nfp_kwargs or {}))
         self.conv_head = nn.Sequential(nn.Conv2d(960, head_width, 1), nn.Hardswish(inplace=True))   # timm: conv_head + act2
         self.fc = nn.Linear(head_width, num_classes)
 

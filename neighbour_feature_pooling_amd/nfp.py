@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _abi
 from .functional import (NfpConfig, gap_servable, multi_radius_config, nfp, nfp_attention_pool, nfp_biased,
-                         nfp_compress_map, nfp_multi_radius, nfp_valid, nfp_with_gap)
+                         nfp_compress_map, nfp_multi_radius, nfp_strided, nfp_valid, nfp_with_gap)
 
 _DISPATCH = set(_abi.MEASURES) | set(_abi.MEASURE_ALIASES)
 
@@ -347,16 +347,19 @@ class NFPInsert(nn.Module):
     valid_layer (keyword only, default False: `self.nfp(x)` as before): an unbiased layer with padding 0, stride 1 and
     dilation 1 — the class defaults — runs as functional.nfp_valid(x, self.nfp.config): on the GPU the valid-map kernels, one
     launch each way (for the default Norm p = 1 their L1 family, which saves x alone), where they serve; every other layer
-    keeps `self.nfp(x)`.  Parameters, state dict, RNG order and CPU results do not depend on it."""
+    keeps `self.nfp(x)`.  Parameters, state dict, RNG order and CPU results do not depend on it.
+    strided_layer (keyword only, default False): likewise, an unbiased layer with stride >= 2 and dilation 1 runs as
+    functional.nfp_strided(x, self.nfp.config) — on the GPU the strided row-band kernels where they serve."""
 
     def __init__(self, in_channels, out_channels=None, *, memory_format=torch.contiguous_format, valid_layer=False,
-                 **nfp_kwargs):
+                 strided_layer=False, **nfp_kwargs):
         super().__init__()
         if memory_format not in _MODULE_FORMATS:
             raise ValueError(f"NFPInsert: memory_format must be torch.contiguous_format, torch.channels_last or "
                              f"torch.preserve_format, got {memory_format!r}")
         self.memory_format = memory_format
         self.valid_layer = bool(valid_layer)
+        self.strided_layer = bool(strided_layer)
         from .heads import _reference_layer_draws
         out_channels = int(in_channels if out_channels is None else out_channels)
         self.nfp = NFPPooling(in_channels=in_channels, **nfp_kwargs)
@@ -371,6 +374,9 @@ class NFPInsert(nn.Module):
         if (self.valid_layer and not self.nfp.bias and cfg.padding == 0 and cfg.stride == 1 and cfg.dilation == 1
                 and x.dim() == 4 and x.shape[1] == self.nfp.in_channels):
             return nfp_valid(x, cfg)
+        if (self.strided_layer and not self.nfp.bias and cfg.stride >= 2 and cfg.dilation == 1
+                and x.dim() == 4 and x.shape[1] == self.nfp.in_channels):
+            return nfp_strided(x, cfg)
         return self.nfp(x)      # (and the layer's own complaint about any other input)
 
     def forward(self, x):
