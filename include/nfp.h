@@ -262,6 +262,41 @@ int nfp_attpool_backward(int32_t B, int32_t N, int64_t P, int32_t dtype, const v
                          int64_t scratch_floats, void* hip_stream);
 
 /*
+ * The encoding layer of the Deep-TEN baseline, models/deepten.py::DeepTENEncoding.forward (deepten.py:51-58), without its
+ * [B,N,K,D] residual tensor (csrc/nfp_deepten.hip).  x [B,D,H,W] read as N = H*W pixels of D channels, K codewords:
+ *   dist[b,n,k] = sum_d (x[b,n,d] - c[k,d])^2      A = softmax_k(-scale[k] * dist)      out[b,k,d] = sum_n A[b,n,k] (x[b,n,d] - c[k,d])
+ *   x          dtype = enum nfp_dtype; layout = enum nfp_act_layout: NFP_ACT_NCHW, element (n, d) of image b at
+ *              b*sxB + d*N + n, or NFP_ACT_NHWC (channels-last, a token sequence [B,N,D]), at b*sxB + n*D + d; sxB >= 0 in
+ *              elements (the class token in front of a ViT's patch tokens stays where it is)
+ *   codewords  [K,D], scale [K], saved, scratch, grad_out [B,K,D], grad_codewords [K,D], grad_scale [K]: float32 DEVICE
+ *              pointers; out [B,K,D] and grad_x (dense, in x's layout) in x's dtype, one rounding; all arithmetic is float32
+ *   saved      nfp_deepten_saved_floats(B, N, K) = 2*B*N*K floats (min 1): A, then dist.  Written by the forward for the
+ *              backward — and for the forward's own second launch, which reads A from it: it is required also when no
+ *              backward follows
+ *   scratch    nfp_deepten_scratch_floats(B, N, K, D, want_params) floats (min 1): w [B,N,K] and, with want_params (either
+ *              parameter gradient asked for), the per-image partials of grad_codewords [B,K,D] and the per-tile ones of
+ *              grad_scale
+ * Each of grad_x, grad_codewords, grad_scale may be NULL: it is then neither computed nor written.  No atomics: two runs
+ * agree bitwise, and image b's out / grad_x do not depend on B.
+ * The launch counter moves by 2 (forward: dten_assign, dten_aggregate); backward: dten_bwd_assign, then dten_bwd_x with
+ * grad_x or grad_codewords, then dten_reduce with either parameter gradient — 2 with grad_x alone, 3 with everything, 0
+ * with none.  nfp_last_variant names dten_fwd<f32|bf16,nchw|nhwc> / dten_bwd<f32|bf16,nchw|nhwc>.
+ * NFP_E_INVALID, launching nothing (checked before any HIP call): a NULL required pointer, B < 0, N < 1, K < 1, D < 1, an
+ * unknown dtype or layout, sxB < 0, a saved or scratch shorter than its query.  NFP_E_UNSUPPORTED: K > 64; N*D, N*K or K*D
+ * of 2^31 and more.  B = 0 returns NFP_OK without a launch (and writes nothing).  Additive to ABI 7: no descriptor, no
+ * workspace.
+ */
+int64_t nfp_deepten_saved_floats(int32_t B, int64_t N, int32_t K);
+int64_t nfp_deepten_scratch_floats(int32_t B, int64_t N, int32_t K, int32_t D, int32_t want_params);
+int nfp_deepten_forward(int32_t B, int64_t N, int32_t K, int32_t D, int32_t dtype, int32_t layout, int64_t sxB, const void* x,
+                        const float* codewords, const float* scale, void* out, float* saved, int64_t saved_floats,
+                        void* hip_stream);
+int nfp_deepten_backward(int32_t B, int64_t N, int32_t K, int32_t D, int32_t dtype, int32_t layout, int64_t sxB, const void* x,
+                         const float* codewords, const float* scale, const float* saved, int64_t saved_floats,
+                         const float* grad_out, void* grad_x, float* grad_codewords, float* grad_scale, float* scratch,
+                         int64_t scratch_floats, void* hip_stream);
+
+/*
  * NFP on VALID maps — stride 1, dilation 1, pad = 0, R = 1 or 2: the layer inside every block of
  * models/nfp_heads.py::NFPBottleneck (nfp_heads.py:234-278) and in front of SimilarityAwarePooling's softmax.  Kernels of
  * their own (csrc/nfp_valid.hip: fwd_valid / bwd_valid), one launch each way, no workspace, no atomics: two runs agree

@@ -21,19 +21,23 @@ Drop-in for the reference's NFP hot path:
                                      (both ops follow an nn.SyncBatchNorm across the ranks of its process group: README,
                                         "SyncBatchNorm in the fused tails")
     nfp_pooled                       <- F.adaptive_avg_pool2d(NFPPooling(feat), 1) of models/texture_pooling.py:251-252, 320-321
+    DeepTENEncoding                  <- models/deepten.py::DeepTENEncoding, the Deep-TEN baseline's encoding layer, without its
+    nfp_deepten_encode                  [B,N,K,D] residual tensor (models.DeepTENNet: the nets of texture_pooling.py:468-526)
 """
-from .functional import (NfpConfig, nfp_attention_pool, nfp_compress_map, nfp_compress_map_tensors, nfp_compress_pool,
+from .functional import (NfpConfig, nfp_attention_pool, nfp_deepten_encode, nfp_compress_map, nfp_compress_map_tensors, nfp_compress_pool,
                          nfp_compress_pool_tensors, nfp_multi_radius, nfp_pool, nfp_pooled, nfp_strided, nfp_valid,
                          nfp_with_gap)
 from .functional import nfp as nfp_op  # (`nfp` itself is the submodule holding NFPPooling)
 from .nfp import (EnhancedNFPPooling, MultiRadiusNFPPooling, NFPBottleneck, NFPInsert, NFPPooling, NFPWithGap,
                   SimilarityAwarePooling)
 from .pooling import nfp_pooling
+from .deepten import DeepTENEncoding
 from .heads import AdaptiveFusionNFP, MultiRadiusNFPHead, NFPHead
 from . import _ops  # registers torch.ops.nfp_amd.* (torch.compile support)
 
 __all__ = ["NFPPooling", "EnhancedNFPPooling", "MultiRadiusNFPPooling", "nfp_pooling", "nfp_op", "nfp_pool", "nfp_pooled",
            "nfp_multi_radius", "NfpConfig", "nfp_with_gap", "NFPWithGap", "SimilarityAwarePooling", "nfp_attention_pool",
            "NFPBottleneck", "nfp_valid", "NFPHead", "MultiRadiusNFPHead", "AdaptiveFusionNFP", "nfp_compress_pool",
-           "nfp_compress_pool_tensors", "NFPInsert", "nfp_compress_map", "nfp_compress_map_tensors", "nfp_strided"]
+           "nfp_compress_pool_tensors", "NFPInsert", "nfp_compress_map", "nfp_compress_map_tensors", "nfp_strided",
+           "DeepTENEncoding", "nfp_deepten_encode"]
 __version__ = "0.4.0"

@@ -24,6 +24,7 @@ EXPORTS = ["nfp_abi_version", "nfp_last_error", "nfp_output_shape", "nfp_saved_f
            "nfp_bias_saved_floats", "nfp_bias_scratch_floats", "nfp_bias_forward", "nfp_bias_backward",
            "nfp_gap_supported", "nfp_gap_saved_floats", "nfp_gap_forward", "nfp_gap_backward",
            "nfp_attpool_scratch_floats", "nfp_attpool_forward", "nfp_attpool_backward",
+           "nfp_deepten_saved_floats", "nfp_deepten_scratch_floats", "nfp_deepten_forward", "nfp_deepten_backward",
            "nfp_valid_supported", "nfp_valid_saved_floats", "nfp_valid_forward", "nfp_valid_backward",
            "nfp_valid_abs_supported", "nfp_valid_abs_forward", "nfp_valid_abs_backward",
            "nfp_strided_supported", "nfp_strided_saved_floats", "nfp_strided_forward", "nfp_strided_backward",
@@ -111,6 +112,14 @@ def load():
         L.nfp_attpool_scratch_floats.restype = i64
         L.nfp_attpool_forward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp]
         L.nfp_attpool_backward.argtypes = [i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    if hasattr(L, "nfp_deepten_forward"):       # (absent only from an older library loaded for an A/B run)
+        i32 = ctypes.c_int32
+        L.nfp_deepten_saved_floats.argtypes = [i32, i64, i32]
+        L.nfp_deepten_scratch_floats.argtypes = [i32, i64, i32, i32, i32]
+        L.nfp_deepten_saved_floats.restype = L.nfp_deepten_scratch_floats.restype = i64
+        head = [i32, i64, i32, i32, i32, i32, i64, vp, vp, vp]          # B, N, K, D, dtype, layout, sxB, x, codewords, scale
+        L.nfp_deepten_forward.argtypes = head + [vp, vp, i64, vp]
+        L.nfp_deepten_backward.argtypes = head + [vp, i64, vp, vp, vp, vp, vp, i64, vp]
     if hasattr(L, "nfp_valid_forward"):         # (absent only from an older library loaded for an A/B run)
         L.nfp_valid_supported.argtypes = [dp]
         L.nfp_valid_saved_floats.argtypes = [dp]

@@ -119,6 +119,22 @@ def attention_pool_host(maps, w, b):
     return (m * att.unsqueeze(1)).sum(-1)
 
 
+def deepten_host(x, codewords, scale):
+    """The Deep-TEN encoding layer (models/deepten.py::DeepTENEncoding.forward) in plain torch ops, any dtype, device and
+    strides: x [B,D,H,W], codewords [K,D], scale [K] -> [B, K*D].  The residuals pixel - codeword [B,N,K,D] are formed
+    twice, as the reference forms them — for the squared distances behind the softmax over the codewords, and for the
+    sum over the pixels under it.  Mixed dtypes promote as torch promotes them; outside torch.autocast the result is cast
+    to x's dtype.  Autograd differentiates."""
+    B, D = x.shape[:2]
+    K = codewords.shape[0]
+    pix = x.flatten(2).transpose(1, 2)                                              # [B,N,D]
+    dist = (pix.unsqueeze(2) - codewords.reshape(1, 1, K, D)).pow(2).sum(dim=3)      # [B,N,K]
+    assign = torch.softmax(-scale.reshape(1, 1, K) * dist, dim=2)
+    resid = pix.unsqueeze(1) - codewords.reshape(1, K, 1, D)                        # [B,K,N,D]
+    enc = (assign.transpose(1, 2).unsqueeze(3) * resid).sum(dim=2).reshape(B, K * D)
+    return enc if torch.is_autocast_enabled(x.device.type) else enc.to(x.dtype)
+
+
 def compress_conv(maps, weight):
     """The 1x1 conv of the two compositions below: maps [B,N,H,W] (or [B,N,P], taken as [B,N,P,1]) under weight [D,N,1,1] or
     [D,N] -> [B,D,H,W] ([B,D,P,1])."""

@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libnfp_hip.so")
 # longest compile first, so that the short ones fill the workers the long ones leave
 SOURCES = ["nfp_table_bwd.hip", "nfp_generic.hip", "nfp_tile_bwd.hip", "nfp_tile_r3_bwd.hip", "nfp_table_fwd.hip",
            "nfp_tile_fwd.hip", "nfp_tile_r3_fwd.hip", "nfp_cpool.hip", "nfp_valid.hip", "nfp_strided.hip", "nfp_bias.hip",
-           "nfp_hip.hip", "nfp_attpool.hip"]
+           "nfp_hip.hip", "nfp_attpool.hip", "nfp_deepten.hip"]
 # compile jobs per library: build_hip() runs the product and the LDS-poison build side by side, together 16
 MAX_JOBS = 8
 # -fno-slp-vectorize: left to itself hipcc packs adjacent scalar f32 FMAs of the channel loops into v_pk_fma_f32,

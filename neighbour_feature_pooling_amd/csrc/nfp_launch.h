@@ -2,7 +2,7 @@
 // dispatch; nfp_generic.hip: the any-geometry kernels; nfp_table_fwd.hip / nfp_table_bwd.hip: the table kernels;
 // nfp_tile_fwd.hip / nfp_tile_bwd.hip: the row-band kernels (nfp_tile_r3_fwd.hip / nfp_tile_r3_bwd.hip: their radius 3); nfp_bias.hip: NFPPooling(bias=True);
 // nfp_attpool.hip: SimilarityAwarePooling's softmax-pool tail; nfp_valid.hip: unpadded maps; nfp_strided.hip: stride 2-4; nfp_cpool.hip: the heads'
-// compress-BN-ReLU-GAP tail), and the interface of each unit's launchers to the dispatcher (below).  Separate
+// compress-BN-ReLU-GAP tail; nfp_deepten.hip: the Deep-TEN baseline's encoding layer), and the interface of each unit's launchers to the dispatcher (below).  Separate
 // units so that they compile in parallel; everything here is `inline` (one instance per shared library).
 //
 // Also the one home of "descriptor field -> kernel template argument": with_radius, with_hot, with_measure, with_storage and

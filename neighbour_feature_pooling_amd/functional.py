@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _abi
-from ._host import attention_pool_host, nfp_host
+from ._host import attention_pool_host, deepten_host, nfp_host
 
 
 @dataclass(frozen=True)
@@ -1028,6 +1028,102 @@ def nfp_attention_pool(maps, weight, bias):
     need_grad = _need_grad(maps, weight, bias)
     pooled = _AttPoolHip.apply(maps, weight.reshape(-1).float().contiguous(), bias.reshape(-1).float(), need_grad)
     return pooled if pooled.dtype == maps.dtype else pooled.to(maps.dtype)
+
+
+# ---- the Deep-TEN encoding layer — include/nfp.h: nfp_deepten_* (csrc/nfp_deepten.hip) -------------------------------------
+DEEPTEN_MAX_CODES = 64      # K the kernels serve (csrc/nfp_deepten.hip: kDtMaxK)
+
+
+def _deepten_geometry(x, codewords):
+    """(B, N, K, D, layout id, batch stride) of a [B,D,H,W] x whose images are dense in NCHW or channels-last order."""
+    B, D, H, W = x.shape
+    layout = _in_place_layout(x.shape, x.stride())
+    return (B, H * W, codewords.shape[0], D, _abi.ACT_NHWC if layout == "nhwc" else _abi.ACT_NCHW,
+            x.stride(0) if B > 1 else D * H * W)
+
+
+def deepten_forward_call(x, codewords, scale):
+    """(out [B,K*D] in x's dtype, saved: A and dist, 2*B*N*K float32) from nfp_deepten_forward on a CUDA x [B,D,H,W] of
+    dense images and float32 codewords [K,D], scale [K].  `saved` hands A from the first launch to the second, so it is
+    made also when no backward follows."""
+    L = _abi.load()
+    B, N, K, D, layout, sxB = _deepten_geometry(x, codewords)
+    with _on_device(x.device):
+        out = torch.empty(B, K * D, dtype=x.dtype, device=x.device)
+        ns = int(L.nfp_deepten_saved_floats(B, N, K))
+        saved = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_deepten_forward(B, N, K, D, _DTYPES[x.dtype], layout, sxB, x.data_ptr(), codewords.data_ptr(),
+                                         scale.data_ptr(), out.data_ptr(), saved.data_ptr(), ns, _raw_stream(x.device)))
+    return out, saved
+
+
+def deepten_backward_call(x, codewords, scale, saved, grad_out, want_x, want_c, want_s):
+    """(grad_x dense in x's layout and dtype, grad_codewords [K,D], grad_scale [K]) from nfp_deepten_backward — None for
+    each gradient nobody wants (a NULL pointer in the library: neither computed nor written)."""
+    L = _abi.load()
+    B, N, K, D, layout, sxB = _deepten_geometry(x, codewords)
+    go = grad_out.contiguous().float()
+    with _on_device(x.device):
+        gx = None
+        if want_x:
+            fmt = torch.channels_last if layout == _abi.ACT_NHWC else torch.contiguous_format
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device, memory_format=fmt)
+        gc = torch.empty(K, D, dtype=torch.float32, device=x.device) if want_c else None
+        gs = torch.empty(K, dtype=torch.float32, device=x.device) if want_s else None
+        ns = int(L.nfp_deepten_scratch_floats(B, N, K, D, int(want_c or want_s)))
+        scratch = torch.empty(ns, dtype=torch.float32, device=x.device)
+        _abi.check(L.nfp_deepten_backward(B, N, K, D, _DTYPES[x.dtype], layout, sxB, x.data_ptr(), codewords.data_ptr(),
+                                          scale.data_ptr(), saved.data_ptr(), saved.numel(), go.data_ptr(),
+                                          gx.data_ptr() if want_x else None, gc.data_ptr() if want_c else None,
+                                          gs.data_ptr() if want_s else None, scratch.data_ptr(), ns, _raw_stream(x.device)))
+    return gx, gc, gs
+
+
+class _DeepTenHip(torch.autograd.Function):
+    """out [B,K*D] of a CUDA x [B,D,H,W] of dense images and float32 (codewords [K,D], scale [K]): two kernels forward, two
+    to three backward.  need_grad: some input requires a gradient and grad mode is on, sampled by the caller."""
+
+    @staticmethod
+    def forward(ctx, x, codewords, scale, need_grad):
+        out, saved = deepten_forward_call(x, codewords, scale)
+        if need_grad:
+            ctx.save_for_backward(x, codewords, scale, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, codewords, scale, saved = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        gx, gc, gs = deepten_backward_call(x, codewords, scale, saved, grad_out, want[0], want[1], want[2])
+        return gx, gc, gs, None
+
+
+def _deepten_hip_serves(x, codewords):
+    """The kernels serve CUDA float32 / bfloat16 x of a non-empty batch whose images are dense in NCHW or channels-last
+    order (any batch stride that keeps them apart) and up to 64 codewords, outside torch.compile (where the layer is traced
+    as ATen ops), unless NFP_DEEPTEN_TORCH=1 (read at call time) asks for the torch formulation."""
+    return (not torch.compiler.is_compiling() and x.is_cuda and x.dtype in _DTYPES and x.shape[0] > 0 and x.numel() > 0
+            and codewords.shape[0] <= DEEPTEN_MAX_CODES and os.environ.get("NFP_DEEPTEN_TORCH") != "1"
+            and _in_place_layout(x.shape, x.stride()) is not None)
+
+
+def nfp_deepten_encode(x, codewords, scale):
+    """The Deep-TEN encoding layer (models/deepten.py::DeepTENEncoding.forward): x [B,D,H,W], codewords [K,D], scale [K] ->
+    [B, K*D], the residuals x - c summed over the pixels under softmax_k(-scale_k |x - c_k|^2).
+    CUDA float32 / bfloat16 x in a served layout runs the HIP kernels (include/nfp.h: nfp_deepten_*; float32 arithmetic, the
+    result and grad_x rounded once to x's dtype; a gradient for x, the codewords and the scale, each only where wanted),
+    which never form the [B,N,K,D] residual tensor.  Everything else — CPU, float16, float64, other strides, K > 64,
+    torch.compile, torch.autocast, NFP_DEEPTEN_TORCH=1 — runs the torch formulation `_host.deepten_host`."""
+    if x.dim() != 4:
+        raise RuntimeError(f"nfp_deepten_encode expects a 4-D [B,D,H,W] feature map, got {tuple(x.shape)}")
+    if codewords.dim() != 2 or codewords.shape[1] != x.shape[1] or scale.shape != codewords.shape[:1]:
+        raise RuntimeError(f"nfp_deepten_encode: x of {x.shape[1]} channels needs codewords [K,{x.shape[1]}] and scale [K], "
+                           f"got {tuple(codewords.shape)} and {tuple(scale.shape)}")
+    if (x.is_cuda and torch.is_autocast_enabled("cuda")) or not _deepten_hip_serves(x, codewords):
+        return deepten_host(x, codewords, scale)
+    need_grad = _need_grad(x, codewords, scale)
+    return _DeepTenHip.apply(x, codewords.float().contiguous(), scale.float().contiguous(), need_grad)
 
 
 # ---- valid maps: stride 1, dilation 1, padding 0 — include/nfp.h: nfp_valid_*, nfp_valid_abs_* (csrc/nfp_valid.hip) ---------

@@ -205,6 +205,29 @@ class NFPNet(nn.Module):
         return self.fc(x.view(x.size(0), -1))
 
 
+class DeepTENNet(nn.Module):
+    """texture_pooling.py::{ResNet18,MobileNetV3,ViTTiny}_DeepTENPooling (468-526) with a local backbone: the feature map
+    through the Deep-TEN encoding layer (deepten.DeepTENEncoding, K codewords), BatchNorm1d over its K*C values and the
+    classifier.  ViT tokens are handed over as a channels-last view of the token matrix (the reference's reshape copies)."""
+
+    def __init__(self, backbone="resnet18", num_classes=10, num_input_channels=3, num_codes=32, **backbone_kw):
+        super().__init__()
+        from .deepten import DeepTENEncoding
+        self.backbone = BACKBONES[backbone](in_chans=num_input_channels, **backbone_kw)
+        C = self.backbone.num_features
+        self.encoding = DeepTENEncoding(in_channels=C, num_codes=num_codes)
+        self.bn = nn.BatchNorm1d(num_codes * C)
+        self.fc = nn.Linear(num_codes * C, num_classes)
+
+    def forward(self, x):
+        feats = self.backbone.forward_features(x)
+        if feats.dim() == 3:  # ViT tokens -> grid, read in place (as NFPNet)
+            tok = feats[:, 1:]
+            H = W = int(math.isqrt(tok.shape[1]))
+            feats = tok.transpose(1, 2).unflatten(2, (H, W))
+        return self.fc(self.bn(self.encoding(feats)))
+
+
 class NFPHeadNet(nn.Module):
     """A backbone under an NFP head of the kind models/nfp_heads.py::NFPHead describes: the head consumes GAP(fmap) AND the
     full NFP maps of the same feature map — the maps through a trainable 1x1 compress conv, so gradients come back for both.

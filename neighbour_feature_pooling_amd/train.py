@@ -20,11 +20,21 @@ import torch.distributed as dist
 import torch.nn as nn
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from .models import MultiStageNFPNet, NFPNet
+from .models import DeepTENNet, MultiStageNFPNet, NFPNet
 from .nfp import NFPPooling
 
 
-def build(model="resnet18", num_classes=10, in_chans=3, image=224, nfp=None, device="cpu", dtype=torch.float32):
+def build(model="resnet18", num_classes=10, in_chans=3, image=224, nfp=None, device="cpu", dtype=torch.float32, pooling="nfp",
+          num_codes=32):
+    """pooling="deepten": the Deep-TEN baseline of the same backbone (models.DeepTENNet, num_codes codewords) instead of NFP."""
+    if pooling not in ("nfp", "deepten"):
+        raise ValueError(f"pooling must be 'nfp' or 'deepten', got {pooling!r}")
+    if pooling == "deepten":
+        if model == "mobilenetv3_multistage":
+            raise ValueError("pooling='deepten' needs a single-map backbone, not mobilenetv3_multistage")
+        kw = {"img_size": image} if model.startswith("vit") else {}
+        net = DeepTENNet(model, num_classes=num_classes, num_input_channels=in_chans, num_codes=num_codes, **kw)
+        return net.to(device=device, dtype=dtype)
     if model == "mobilenetv3_multistage":      # texture_pooling.py:211-268: NFP on all five stage outputs
         return MultiStageNFPNet(num_classes=num_classes, num_input_channels=in_chans).to(device=device, dtype=dtype)
     kw = {"img_size": image} if model.startswith("vit") else {}
@@ -66,6 +76,9 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--nfp-radius", type=int, default=1)
     ap.add_argument("--nfp-measure", default="cosine")
+    ap.add_argument("--pooling", choices=["nfp", "deepten"], default="nfp", help="deepten: the Deep-TEN encoding baseline "
+                    "(models.DeepTENNet) instead of the NFP layer")
+    ap.add_argument("--num-codes", type=int, default=32, help="--pooling deepten: codewords of the encoding layer")
     ap.add_argument("--channels-last", action="store_true", help="NHWC activations and weights: MIOpen's NHWC "
                     "convolutions, and NFP reads the channels-last feature map in place")
     ap.add_argument("--autotune", action="store_true", help="torch.backends.cudnn.benchmark: MIOpen find mode")
@@ -105,7 +118,8 @@ def main():
     ctor = dict(R=a.nfp_radius, measure=a.nfp_measure, padding=a.nfp_radius)
     if a.nfp_measure == "norm":
         ctor["p"] = 2
-    net = build(a.model, a.classes, a.in_chans, a.image, NFPPooling(C, **ctor), dev, dtype)
+    net = build(a.model, a.classes, a.in_chans, a.image, NFPPooling(C, **ctor) if a.pooling == "nfp" else None, dev, dtype,
+                pooling=a.pooling, num_codes=a.num_codes)
     torch.backends.cudnn.benchmark = bool(a.autotune)
     if a.channels_last:
         net = net.to(memory_format=torch.channels_last)
@@ -137,7 +151,7 @@ def main():
         print(json.dumps({"model": a.model, "n_gpus": world, "batch_per_gpu": a.batch, "image": a.image,
                           "dtype": a.dtype, "ms_per_step": round(dt * 1e3, 3),
                           "images_per_s": round(world * a.batch / dt, 1), "loss": round(float(loss), 4),
-                          "nfp": f"{a.nfp_measure} R={a.nfp_radius}",
+                          "nfp": f"{a.nfp_measure} R={a.nfp_radius}" if a.pooling == "nfp" else f"deepten K={a.num_codes}",
                           "layout": "channels_last" if a.channels_last else "nchw", "autotune": bool(a.autotune)}))
     if world > 1:
         dist.destroy_process_group()
